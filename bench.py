@@ -14,23 +14,29 @@ ONE RCCL gather of the band-integrated ffDTF to rank 0 (inside the timed region)
 `--shard windows` is the strong-scaling mode (secondary partitioning: C2 at 2 / 4 / 8 GPUs): ONE dyad,
 rank r uploads only the samples of its window range (read-only halo of one window) and computes those windows; same
 gather; `"scaling": "strong"`.
-Side measurements on the same line (N = 1, after the headline's timed region; `--no-side` skips them):
-`end_to_end` -- recordings streamed from pinned host memory through `Engine.stream_dyads` (H2D of dyad d+1 and D2H of
-the band-integrated result of dyad d-1 under the compute of dyad d), windows/s including PCIe both ways;
-`with_spectra` -- ffDTF and the spectra S = H V H^T of every window from one fit.
+A plain run sets up, warms up, times the K steps and prints the result line; nothing else runs.  `--full` adds what
+the headline does not need, all after the timed region:
+* checks: one extra step with the singularity check (both info arrays zero), every ffDTF row sums to one, the
+  in-kernel normalisation equals the separate K4 pass bit for bit on the whole output, and one window equals the
+  oracle (`checks_after_timed_region`; HYPERMVAR_BENCH_NOCHECK=1 skips them);
+* side measurements (N = 1; `--no-side` skips them): `end_to_end` -- recordings streamed from pinned host memory through
+  `Engine.stream_dyads` (H2D of dyad d+1 and D2H of the band-integrated result of dyad d-1 under the compute of dyad
+  d), windows/s including PCIe both ways; `with_spectra` -- ffDTF and the spectra S = H V H^T of every window from one
+  fit (`--with-spectra` asks for this one alone, with or without `--full`);
+* `cpu_baseline` (`--no-cpu-baseline` skips it): the NumPy port of the reference's loop structure,
+  oracle/mvar_oracle.py, on a bounded sample of the same windows, rank 0 only; the vectorised restatement and an
+  all-cores run are reported as sub-fields.
 
-    python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` for the dominant
-kernel (K3, timed with HIP events recorded by the library around its launch inside the timed region)
-and `cpu_baseline` (the NumPy port of the reference's loop structure, oracle/mvar_oracle.py, on a
-bounded sample of the same windows, rank 0 only; the vectorised restatement and an all-cores run are
-reported as sub-fields).  The timed steps run with check=False (the singularity check is a device
-synchronisation, not work); after the timed region one extra step is checked: both info arrays zero, every
-ffDTF row sums to one, the in-kernel normalisation equals the separate K4 pass bit for bit on the whole
-output, and one window equals the oracle.
+Prints ONE JSON line on rank 0: `value` windows/s over the K timed steps, `ms_per_step` the wall time of one timed
+step, and `roofline` for the dominant kernel (K3, timed with HIP events recorded by the library around its launch
+inside the timed steps, so it costs no run of its own).  The timed steps run with check=False (the singularity check
+is a device synchronisation, not work).  The synthetic recordings are generated with one BLAS thread, so the inputs
+are the same bits whatever the host's thread settings.
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step computed on rank 0 (see `dump_outputs`).
 """
 import argparse
 import json
@@ -40,6 +46,7 @@ import time
 
 import numpy as np
 import torch
+from threadpoolctl import threadpool_limits
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -67,7 +74,6 @@ def cpu_baseline(x_host, positions, w, p, freqs, fs, budget_s=12.0, max_windows=
     vectorised the same math with batched LAPACK calls, 1 process / 1 BLAS thread;
     all_cores  the vectorised restatement in one process per core (multiprocessing), 1 BLAS thread each."""
     from oracle import mvar_oracle as O      # the ONLY place bench.py touches oracle/
-    from threadpoolctl import threadpool_limits
     out = {}
     with threadpool_limits(limits=1):
         for key, fn, budget in (("loop", O.full_freq_dtf_loop, budget_s), ("vec", O.full_freq_dtf, budget_s / 3)):
@@ -104,12 +110,42 @@ def cpu_baseline(x_host, positions, w, p, freqs, fs, budget_s=12.0, max_windows=
             "all_cores": allc, "host_cores_visible": cores}
 
 
+DUMP_WINDOWS = 5                 # whole windows of the output written by --dump-outputs (8 MiB each at 64 ch, 256 freqs)
+DUMP_ELEMENTS = 1 << 19          # single values drawn from the whole output (4 MiB, and 4 MiB of their indices)
+DUMP_SEED = 20240601
+
+
+def dump_outputs(dirname, out):
+    """What the timed path hands its caller -- the ffDTF array out (items, m, m, F) float64, about 5 GB per dyad -- as a
+    fixed, seeded sample of at most 64 MB, float64:
+    ffdtf_windows.npy        (DUMP_WINDOWS, m, m, F) whole windows: the first, the last and seeded ones in between;
+    ffdtf_window_index.npy   their item indices;
+    ffdtf_sample.npy         DUMP_ELEMENTS values at seeded flat indices (sorted) across the whole array, so that
+                             every window is looked at;
+    ffdtf_sample_index.npy   those flat indices (exact in float64 below 2**53)."""
+    os.makedirs(dirname, exist_ok=True)
+    n = out.shape[0]
+    rng = np.random.default_rng(DUMP_SEED)
+    inner = np.arange(1, n - 1)
+    win = np.unique(np.r_[0, n - 1, rng.choice(inner, size=min(DUMP_WINDOWS - 2, inner.size), replace=False)])
+    flat = np.sort(rng.integers(0, out.numel(), size=DUMP_ELEMENTS, dtype=np.int64))
+    sample = out.reshape(-1)[torch.from_numpy(flat).to(out.device)]
+    np.save(os.path.join(dirname, "ffdtf_windows.npy"), out[torch.from_numpy(win).to(out.device)].cpu().numpy())
+    np.save(os.path.join(dirname, "ffdtf_window_index.npy"), win.astype(np.float64))
+    np.save(os.path.join(dirname, "ffdtf_sample.npy"), sample.cpu().numpy())
+    np.save(os.path.join(dirname, "ffdtf_sample_index.npy"), flat.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the checks, the side measurements and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of what the last timed step computed to DIR/*.npy (float64, < 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--minutes", type=float, default=10.0, help="recording length per dyad (default 10)")
     ap.add_argument("--dyads-per-gpu", type=int, default=1,
                     help="dyads per GPU (8 with --gpus 8 = BASELINE config 3: 64 dyads); one chunk per dyad")
@@ -126,13 +162,16 @@ def main():
     ap.add_argument("--shard", default="dyads", choices=("dyads", "windows"),
                     help="N > 1: dyads = weak scaling (one or D dyads per rank); windows = strong scaling (ONE dyad, every "
                          "rank a window range of it)")
-    ap.add_argument("--no-side", action="store_true", help="skip the side measurements (end_to_end, with_spectra)")
+    ap.add_argument("--no-side", action="store_true",
+                    help="with --full: skip the side measurements (end_to_end, with_spectra)")
     ap.add_argument("--stream-dyads", type=int, default=0,
                     help="recordings streamed in the end_to_end side measurement (default: max(4, dyads per GPU))")
     ap.add_argument("--backend", default="nccl", choices=("nccl", "gloo"),
                     help="process-group backend for N > 1 (nccl = RCCL; gloo only to rehearse the N > 1 code path "
                          "with several ranks on ONE GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -158,10 +197,16 @@ def main():
     strong = (args.shard == "windows")
     eng = Engine(device=dev, max_workspace_bytes=64 << 30)
     fdev = eng.to_device(freqs)
+
+    def recording(dyad):
+        # one BLAS thread: the recursion's mat-vecs round the same way whatever the host's thread settings
+        with threadpool_limits(limits=1):
+            return synthetic_var_dyad(dyad, m=m, p=p, T=T, fs=fs)
+
     if strong:
         # strong scaling: ONE dyad (index 0, the same on every rank); this rank uploads only its window range's samples
         assert D == 1, "--shard windows is one dyad"
-        x_hosts = [synthetic_var_dyad(0, m=m, p=p, T=T, fs=fs)]
+        x_hosts = [recording(0)]
         s_lo, s_hi, my_pos, (w_lo, w_hi) = hdist.shard_window_items(positions, w, world, rank)
         x = eng.to_device(np.ascontiguousarray(x_hosts[0][None, :, s_lo:s_hi]))
         item_rec, item_start = window_items(1, my_pos, dev)
@@ -169,7 +214,7 @@ def main():
         all_positions, positions = positions, my_pos
     else:
         # weak scaling: dyad index = rank * D + d
-        x_hosts = [synthetic_var_dyad(rank * D + d, m=m, p=p, T=T, fs=fs) for d in range(D)]
+        x_hosts = [recording(rank * D + d) for d in range(D)]
         x = eng.to_device(np.stack(x_hosts))                            # (D, 64, T) resident in HBM
         item_rec, item_start = window_items(D, positions, dev)
         n_items = D * n_windows
@@ -225,11 +270,14 @@ def main():
         if rank == 0:
             assert gathered.shape[0] == world and bool(torch.isfinite(gathered).all())
 
-    # ---- after the timed region: one checked step (diagnostic kernel variants may skip it)
+    if args.dump_outputs and rank == 0:                                 # what the last timed step left in `out`
+        dump_outputs(args.dump_outputs, out)
+
+    # ---- --full, after the timed region: one checked step (diagnostic kernel variants may skip it)
     checks = {}
-    if os.environ.get("HYPERMVAR_BENCH_NOCHECK"):
+    if args.full and os.environ.get("HYPERMVAR_BENCH_NOCHECK"):
         checks = {"skipped": True}
-    else:
+    elif args.full:
         _, _, _, (info_yw, info_tf) = step(check=True)                 # raises on any singular window
         checks["info_all_zero"] = not (bool(info_yw.any()) or bool(info_tf.any()))
         rowsum_err = float((out.sum(dim=(2, 3)) - 1.0).abs().max().item())
@@ -252,7 +300,7 @@ def main():
 
     # ---- side measurement: recordings streamed from (pinned) host memory, PCIe both ways inside the clock
     e2e_res = None
-    side = (world == 1 and not strong and not args.no_side)
+    side = (args.full and world == 1 and not strong and not args.no_side)
     if side:
         E = args.stream_dyads or max(16, D)
         feed_src = [torch.from_numpy(xh).pin_memory() for xh in x_hosts]          # what a loader would hand over
@@ -355,13 +403,15 @@ def main():
             "path_tflops": FLOP_WINDOW * value / world / 1e12,
             "path_frac_of_peak": FLOP_WINDOW * value / world / 1e12 / PEAK_F64_TFLOPS,
             "path_flops_are": "algorithmic (direct-form K1), not executed",
-            "checks_after_timed_region": checks,
+            "full": args.full,
         }
+        if args.full:
+            res["checks_after_timed_region"] = checks
         if spectra_res is not None:
             res["with_spectra"] = spectra_res
         if e2e_res is not None:
             res["end_to_end"] = e2e_res
-        if not args.no_cpu_baseline:           # rank 0's host cores, whatever N is
+        if args.full and not args.no_cpu_baseline:           # rank 0's host cores, whatever N is
             res["cpu_baseline"] = cpu_baseline(x_hosts[0], all_positions, w, p, freqs, fs)
         print(json.dumps(res))
     if world > 1:

@@ -3,6 +3,7 @@
 # usage (on the GPU box, repo root): bash tools/dbg/ab.sh <variant .so> [extra bench flags]
 set -eo pipefail
 L=$PWD/$1; shift
+set -- --full "$@"          # the checks after the timed steps are printed below
 HYPERMVAR_LIB=$L timeout -k 10 400 python -m pytest tests/test_gpu_parity.py -x -q -m gpu --deselect tests/test_gpu_parity.py::test_native_library_is_what_runs 2>&1 | tail -3
 python bench.py --steps 10 --warmup 3 --no-cpu-baseline "$@" > gpurun_out/ab_base.json
 HYPERMVAR_LIB=$L python bench.py --steps 10 --warmup 3 --no-cpu-baseline "$@" > gpurun_out/ab_var.json

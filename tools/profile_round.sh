@@ -3,7 +3,7 @@
 #     gpurun --timeout 900 -- 'bash tools/profile_round.sh r01'
 # Four separate rocprofv3 passes of the same bench command (kernel trace + stats; FETCH_SIZE;
 # WRITE_SIZE; SQ counters) -- counters never share a pass with each other's groups or with a
-# runtime trace -- then the plain bench line.  tools/summarise_profiles.py turns the raw output
+# runtime trace -- then the bench line with --full.  tools/summarise_profiles.py turns the raw output
 # under gpurun_out/ into the committed files under profiles/.
 set -eo pipefail
 TAG=${1:-r03}
@@ -27,7 +27,7 @@ rocprofv3 --pmc SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_IDX_
     -d "$OUT/sq2" -o run --output-format csv -- python3 $PMCB > "$OUT/sq2.log" 2>&1 || echo "sq2 pass failed (non-fatal)"
 echo "sq2 pass done"
 cd "$REPO"
-python3 bench.py --steps 5 --warmup 2 > "$OUT/bench.json" 2> "$OUT/bench.err"
+python3 bench.py --full --steps 5 --warmup 2 > "$OUT/bench.json" 2> "$OUT/bench.err"
 cat "$OUT/bench.json"
 # side measurement: the ffDTF + spectra path (kernel stats only)
 cd /tmp
