@@ -71,6 +71,10 @@ SIGNATURES = {
                                       c_int, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_int64, c_int64, c_double, c_int64, c_int64, c_int64, c_int64,
                                       c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hmv_fad_workspace_bytes": (c_int64, [c_int64, c_int]),
+    "hmv_fad_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int,
+                            c_double, c_double, c_int] + [c_void_p] * 17),
+    "hmv_fad_decompose_f64": (c_int, [c_void_p, c_int64, c_int, c_double, c_double, c_int] + [c_void_p] * 13),
 }
 
 # option bits of the fused entry points (include/hypermvar.h)

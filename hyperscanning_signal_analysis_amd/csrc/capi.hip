@@ -642,4 +642,52 @@ int hmv_sliding_ffdtf_spectra_f64(const double* x, int64_t rec_stride, int64_t l
                       stream, aux_stream);
 }
 
+int64_t hmv_fad_workspace_bytes(int64_t n_series, int pmax) {
+  return (n_series < 0 || pmax < 1 || pmax > HMV_MAX_ORDER) ? -1 : 0;
+}
+
+int hmv_fad_f64(const double* x, int64_t rec_stride, int64_t ld, const int64_t* item_rec, const int64_t* item_start,
+                int64_t n_items, int m, int n, int pmax, int order, int crit, double fs, double imag_tol,
+                int pair_conjugates, int32_t* order_out, double* crit_out, double* ar, double* noise_variance,
+                double* poles, double* C, double* alpha, double* freq, double* beta, double* bandwidth, double* phi,
+                double* B, uint8_t* osc_mask, int32_t* paired, int32_t* n_paired, int32_t* info, void* stream) {
+  if (m < 1 || m > HMV_MAX_CHANNELS) return fail(-1, "hmv_fad_f64: channel count must be in 1..64");
+  if (pmax < 1 || pmax > HMV_MAX_ORDER) return fail(-2, "hmv_fad_f64: maximum model order must be in 1..32");
+  if (n <= pmax) return fail(-3, "hmv_fad_f64: series shorter than the model order");
+  if (!x || !item_rec || !item_start || !order_out || !ar || !noise_variance || !poles || !C || !alpha || !freq ||
+      !beta || !bandwidth || !phi || !B || !osc_mask || !paired || !n_paired || !info || n_items < 0)
+    return fail(-4, "hmv_fad_f64: null pointer");
+  if (crit < 0 || crit > 2) return fail(-5, "hmv_fad_f64: criterion must be 0 (AIC), 1 (HQ) or 2 (SC)");
+  if (order < 0 || order > pmax) return fail(-6, "hmv_fad_f64: model order must be 0 (automatic) or in 1..pmax");
+  hmv::FadArgs a{};
+  a.from_fit = 1;
+  a.x = x; a.rec_stride = rec_stride; a.ld = ld;
+  a.item_rec = reinterpret_cast<const long long*>(item_rec);
+  a.item_start = reinterpret_cast<const long long*>(item_start);
+  a.n_series = n_items * m; a.m = m; a.n = n; a.pmax = pmax; a.order = order; a.crit = crit;
+  a.fs = fs; a.imag_tol = imag_tol; a.pair_conjugates = pair_conjugates != 0;
+  a.order_out = order_out; a.crit_out = crit_out; a.ar = ar; a.noise = noise_variance;
+  a.poles = poles; a.C = C; a.alpha = alpha; a.freq = freq; a.beta = beta; a.bw = bandwidth; a.phi = phi; a.B = B;
+  a.osc = osc_mask; a.paired = paired; a.n_paired = n_paired; a.info = info;
+  return hmv::launch_fad(a, S(stream));
+}
+
+int hmv_fad_decompose_f64(const double* ar, int64_t n_series, int p, double fs, double imag_tol, int pair_conjugates,
+                          double* poles, double* C, double* alpha, double* freq, double* beta, double* bandwidth,
+                          double* phi, double* B, uint8_t* osc_mask, int32_t* paired, int32_t* n_paired, int32_t* info,
+                          void* stream) {
+  if (p < 1 || p > HMV_MAX_ORDER) return fail(-2, "hmv_fad_decompose_f64: model order must be in 1..32");
+  if (!ar || !poles || !C || !alpha || !freq || !beta || !bandwidth || !phi || !B || !osc_mask || !paired ||
+      !n_paired || !info || n_series < 0)
+    return fail(-4, "hmv_fad_decompose_f64: null pointer");
+  hmv::FadArgs a{};
+  a.from_fit = 0;
+  a.n_series = n_series; a.pmax = p;
+  a.fs = fs; a.imag_tol = imag_tol; a.pair_conjugates = pair_conjugates != 0;
+  a.ar = const_cast<double*>(ar);
+  a.poles = poles; a.C = C; a.alpha = alpha; a.freq = freq; a.beta = beta; a.bw = bandwidth; a.phi = phi; a.B = B;
+  a.osc = osc_mask; a.paired = paired; a.n_paired = n_paired; a.info = info;
+  return hmv::launch_fad(a, S(stream));
+}
+
 }  // extern "C"

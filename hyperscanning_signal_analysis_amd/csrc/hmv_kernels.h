@@ -143,4 +143,34 @@ int launch_psd(const double* x, long long n_ch, long long n, long long ld, const
 long long dpss_workspace_bytes(long long M, int K, int sym);
 int launch_dpss(long long M, double NW, int K, int sym, double* tapers, double* ratios, void* workspace, hipStream_t st);
 
+// ---- FAD decomposition of univariate AR models (fad.hip) ------------------------------------------------------------
+struct FadArgs {
+  int from_fit;             // 1: fit from samples first (fad_fit_kernel), 0: decompose the given coefficients
+  // fit: series s = item * m + ch is channel ch of window `item` (addressing as LagcovArgs)
+  const double* x;
+  long long rec_stride, ld;
+  const long long* item_rec;
+  const long long* item_start;
+  long long n_series;
+  int m, n;
+  int pmax;                 // row length of every [series][pmax] array (decomposition only: the order p)
+  int order;                // fit: 0 = automatic (criterion `crit`: 0 AIC, 1 HQ, 2 SC), else the fixed order
+  int crit;
+  double fs, imag_tol;
+  int pair_conjugates;
+  int* order_out;           // [S] (fit only)
+  double* crit_out;         // [S][pmax] optional (fit only)
+  double* ar;               // [S][pmax]: written by the fit, read by the decomposition
+  double* noise;            // [S] (fit only)
+  double* poles;            // complex [S][pmax]
+  double* C;                // complex [S][pmax]
+  double* alpha;            // complex [S][pmax]
+  double* freq, *beta, *bw, *phi, *B;   // [S][pmax]
+  unsigned char* osc;       // [S][pmax]
+  int* paired;              // [S][pmax]
+  int* n_paired;            // [S]
+  int* info;                // [S]
+};
+int launch_fad(const FadArgs& a, hipStream_t st);
+
 }  // namespace hmv

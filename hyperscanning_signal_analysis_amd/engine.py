@@ -674,6 +674,70 @@ class Engine:
             self.raise_on_info(info_tf, "mvar_transfer_function (inverse of A(f))", per_item=F)
         return ff, torch.view_as_complex(S)
 
+    # ------------------------------------------------------------------ FAD (fad.hip)
+    FAD_CRIT = {"AIC": 0, "HQ": 1, "SC": 2}
+
+    def _fad_outputs(self, S: int, P: int):
+        e = self.empty
+        return dict(poles=e(S, P, 2), C=e(S, P, 2), alpha=e(S, P, 2), freq_hz=e(S, P), beta=e(S, P),
+                    bandwidth_hz=e(S, P), phi=e(S, P), B=e(S, P), osc_mask=e(S, P, dtype=torch.uint8),
+                    paired_index=e(S, P, dtype=torch.int32), n_paired=e(S, dtype=torch.int32),
+                    info=e(S, dtype=torch.int32))
+
+    @staticmethod
+    def _fad_finish(o: dict):
+        for k in ("poles", "C", "alpha"):
+            o[k] = torch.view_as_complex(o[k])
+        o["osc_mask"] = o["osc_mask"].bool()
+        return o
+
+    def fad(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, pmax: int, order: int = 0,
+            crit: int = 0, fs: float = 1.0, imag_tol: float = 1e-8, pair_conjugates: bool = True):
+        """FAD decomposition of every channel of every window (`hmv_fad_f64`).  x: (n_rec, m, T) float64 device tensor;
+        series s = item * m + ch.  order 0 = automatic (crit 0/1/2 = AIC/HQ/SC over 1..pmax).  Returns a dict of device
+        tensors with rows of pmax entries per series (NaN / False / -1 past the series' order): order, crit (automatic
+        mode), ar, noise_variance, poles / C / alpha (complex128), freq_hz, beta, bandwidth_hz, phi, B, osc_mask (bool),
+        paired_index (int32) + n_paired, info (bit 0 fit breakdown, bit 1 no convergence, bit 2 ambiguous grouping)."""
+        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
+        x = x if x.stride(2) == 1 else x.contiguous()
+        n_rec, m, T = x.shape
+        self.check_items(x, item_rec, item_start, n, pmax)
+        n_items = int(item_rec.numel())
+        S, P = n_items * m, int(pmax)
+        o = self._fad_outputs(S, P)
+        o["order"] = self.empty(S, dtype=torch.int32)
+        o["crit"] = self.empty(S, P) if int(order) == 0 else None
+        o["ar"] = self.empty(S, P)
+        o["noise_variance"] = self.empty(S)
+        with torch.cuda.device(self.device):
+            rc = self.lib.hmv_fad_f64(
+                x.data_ptr(), x.stride(0), x.stride(1), item_rec.data_ptr(), item_start.data_ptr(), n_items, m, int(n),
+                P, int(order), int(crit), float(fs), float(imag_tol), int(bool(pair_conjugates)),
+                o["order"].data_ptr(), _ptr(o["crit"]), o["ar"].data_ptr(), o["noise_variance"].data_ptr(),
+                o["poles"].data_ptr(), o["C"].data_ptr(), o["alpha"].data_ptr(), o["freq_hz"].data_ptr(),
+                o["beta"].data_ptr(), o["bandwidth_hz"].data_ptr(), o["phi"].data_ptr(), o["B"].data_ptr(),
+                o["osc_mask"].data_ptr(), o["paired_index"].data_ptr(), o["n_paired"].data_ptr(), o["info"].data_ptr(),
+                self.stream())
+        _lib.check(rc, "hmv_fad_f64")
+        return self._fad_finish(o)
+
+    def fad_decompose(self, ar: torch.Tensor, fs: float, imag_tol: float = 1e-8, pair_conjugates: bool = True):
+        """Poles, residues and FAD parameters of given AR coefficients ar (S, p) (`hmv_fad_decompose_f64`): the same
+        outputs as `fad` minus the fit (order, crit, ar, noise_variance)."""
+        ar = self.to_device(ar)
+        assert ar.dim() == 2
+        S, p = ar.shape
+        o = self._fad_outputs(S, p)
+        with torch.cuda.device(self.device):
+            rc = self.lib.hmv_fad_decompose_f64(
+                ar.data_ptr(), S, p, float(fs), float(imag_tol), int(bool(pair_conjugates)),
+                o["poles"].data_ptr(), o["C"].data_ptr(), o["alpha"].data_ptr(), o["freq_hz"].data_ptr(),
+                o["beta"].data_ptr(), o["bandwidth_hz"].data_ptr(), o["phi"].data_ptr(), o["B"].data_ptr(),
+                o["osc_mask"].data_ptr(), o["paired_index"].data_ptr(), o["n_paired"].data_ptr(), o["info"].data_ptr(),
+                self.stream())
+        _lib.check(rc, "hmv_fad_decompose_f64")
+        return self._fad_finish(o)
+
 
 _default = None
 

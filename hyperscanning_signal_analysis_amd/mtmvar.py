@@ -11,6 +11,10 @@ Differences that are deliberate and documented in DESIGN.md:
   * `multivariate_spectra` and `full_freq_dtf` share nothing in the reference (each refits the model);
     here each call still fits once, but `mvar_analysis()` returns both from a single fit.
 Supported sizes: 1..64 channels, model order 1..32.
+
+FAD (frequency-amplitude-damping) decomposition, mtmvar.py:607-845: `fad_decomposition` and `fad_components_table`
+with the reference's signatures, plus `fad_decomposition_batch` for many series in one pass (the fit, the roots and
+the residues run on the GPU; see DESIGN.md "FAD").
 """
 from __future__ import annotations
 
@@ -21,7 +25,7 @@ from .engine import Engine, SingularMatrixError, default_engine
 
 __all__ = ["count_corr", "ar_coeff", "mvar_transfer_function", "multivariate_spectra", "dtf_multivariate",
            "full_freq_dtf", "mvar_criterion", "mvar_analysis", "lag_covariances", "compute_and_plot_mvar",
-           "mvar_plot"]
+           "mvar_plot", "fad_decomposition", "fad_decomposition_batch", "fad_components_table"]
 
 
 # ----------------------------------------------------------------------------- internals
@@ -327,3 +331,207 @@ def compute_and_plot_mvar(ncdf_path, channel_subset=None, max_model_order=20, op
         plt.tight_layout()
         plt.show()
     return ff_dtf, spectra, chan_names, crit, model_order_range, p_opt
+
+
+# ----------------------------------------------------------------------------- FAD decomposition (mtmvar.py:607-845)
+_FAD_POLE_KEYS = ("poles", "C", "alpha", "freq_hz", "omega_rad_s", "beta", "bandwidth_hz", "phi", "B")
+
+
+def _fad_orders(model_order, max_model_order, crit_type, n):
+    """(order code, pmax, crit code) for hmv_fad_f64, with the reference's ValueError for an unknown criterion."""
+    if model_order is None:
+        if crit_type not in Engine.FAD_CRIT:
+            raise ValueError("Invalid criterion type. Choose from 'AIC', 'HQ', 'SC'.")
+        order, pmax, crit = 0, int(max_model_order), Engine.FAD_CRIT[crit_type]
+    else:
+        order = pmax = int(model_order)
+        crit = 0
+    if not 1 <= pmax <= 32:
+        raise ValueError(f"FAD supports model orders 1..32, got {pmax}")
+    if n <= pmax:
+        raise ValueError(f"need more samples ({n}) than the model order ({pmax})")
+    return order, pmax, crit
+
+
+def _fad_host(d: dict, model_order, pair_conjugates: bool):
+    """Device dict of Engine.fad -> the reference's dict layout with a leading series axis (NumPy, padded rows)."""
+    h = {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in d.items()}
+    S, P = h["freq_hz"].shape
+    orders = h["order"].astype(np.int64) if "order" in h else np.full(S, P, dtype=np.int64)
+    out = {
+        "model_order": orders,
+        "poles": h["poles"], "C": h["C"], "alpha": h["alpha"], "freq_hz": h["freq_hz"],
+        "omega_rad_s": h["alpha"].imag.copy(), "beta": h["beta"], "bandwidth_hz": h["bandwidth_hz"],
+        "phi": h["phi"], "B": h["B"],
+        "noise_variance": h.get("noise_variance"),
+        "osc_mask": h["osc_mask"],
+        "ar_coeffs": h.get("ar"),
+    }
+    idx = h["paired_index"].astype(np.int64)
+    have = idx >= 0
+    safe = np.where(have, idx, 0)
+    paired = {"pole_index": np.where(have, idx, -1)}
+    for k in _FAD_POLE_KEYS:
+        v = np.take_along_axis(out[k], safe, axis=1)
+        paired[k] = np.where(have, v, np.nan)
+    paired["n_components"] = h["n_paired"].astype(np.int64)
+    out["paired_components"] = paired
+    out["info"] = h["info"]
+    if h.get("crit") is not None:
+        out["crit"] = h["crit"]
+    return out
+
+
+def _fad_run(signals, fs, model_order, max_model_order, crit_type, pair_conjugates, imag_tol, eng: Engine | None):
+    x = np.ascontiguousarray(np.asarray(signals, dtype=np.float64))
+    S, n = x.shape
+    order, pmax, crit = _fad_orders(model_order, max_model_order, crit_type, n)
+    eng = eng or default_engine()
+    xd = eng.to_device(x[:, None, :])                                  # S recordings of one channel
+    rec = torch.arange(S, dtype=torch.int64, device=eng.device)
+    start = torch.zeros(S, dtype=torch.int64, device=eng.device)
+    d = eng.fad(xd, rec, start, n, pmax, order, crit, fs, imag_tol, pair_conjugates)
+    return _fad_host(d, model_order, pair_conjugates), order
+
+
+def fad_decomposition_batch(signals, fs, model_order=None, max_model_order=20, crit_type='AIC', pair_conjugates=True,
+                            imag_tol=1e-8, engine: Engine | None = None):
+    """`fad_decomposition` of every row of signals (S, N) in one pass on the GPU.
+
+    Same keys as `fad_decomposition` with a leading (S,) axis: per-pole arrays (S, pmax), NaN-padded past each
+    series' order (`osc_mask` padded with False), `model_order` (S,) int64, `noise_variance` (S,), `ar_coeffs`
+    (S, pmax); `paired_components` arrays (S, pmax) padded with NaN (`pole_index` with -1) plus `n_components` (S,);
+    `info` (S,) (bit 0: fit breakdown, bit 1: root iteration did not converge, bit 2: ambiguous pole grouping) and,
+    in automatic mode, `crit` (S, max_model_order).  pmax is max_model_order in automatic mode, else model_order.
+    Nothing is printed and nothing is raised for individual series: failed rows are NaN and flagged in `info`.
+    Row s is bit-for-bit what `fad_decomposition(signals[s], ...)` returns.
+    """
+    x = np.asarray(signals, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError("signals must have shape (n_series, n_samples)")
+    out, _ = _fad_run(x, fs, model_order, max_model_order, crit_type, pair_conjugates, imag_tol, engine)
+    return out
+
+
+def fad_decomposition(signal, fs, model_order=None, max_model_order=20, crit_type='AIC', plot=False,
+                      pair_conjugates=True, imag_tol=1e-8):
+    """FAD (frequency-amplitude-damping) decomposition of a univariate AR model (mtmvar.py:607-757).
+
+    Same signature, defaults, dict keys, shapes, dtypes, printed line and errors as the reference: the AR fit
+    (order by AIC / HQ / SC when model_order is None), the poles z_j and residues C_j of H(z) = 1 / A(z^-1) as
+    scipy.signal.residuez returns them, alpha = log(z) fs, beta = -Re alpha, omega = Im alpha, freq_hz = omega / 2 pi,
+    bandwidth_hz = beta / 2 pi, phi = arg C, B = 2 |C|, osc_mask and `paired_components`.  The fit (Levinson-Durbin)
+    and the root finding (Aberth-Ehrlich) run on the GPU; results agree with the reference to rounding.
+    Raises numpy.linalg.LinAlgError('Singular matrix') when the fit breaks down (all-zero input), RuntimeError when
+    the root iteration does not converge, and warns (RuntimeWarning) when poles form a chain within 1e-3 that is wider
+    than 1e-3 (residuez's grouping then depends on the root order; here connected components are grouped).
+    """
+    x = np.atleast_2d(np.asarray(signal, dtype=float))
+    if x.shape[0] != 1:
+        raise ValueError("fad_decomposition expects a univariate signal, shape (N,) or (1, N).")
+    b, order = _fad_run(x, fs, model_order, max_model_order, crit_type, pair_conjugates, imag_tol, None)
+    info = int(b["info"][0])
+    if info & 1:
+        raise SingularMatrixError("Singular matrix")
+    if info & 2:
+        raise RuntimeError("fad_decomposition: the root iteration did not converge")
+    if info & 4:
+        import warnings
+        warnings.warn("fad_decomposition: poles within 1e-3 of each other form a chain wider than 1e-3; grouped by "
+                      "connected components", RuntimeWarning, stacklevel=2)
+    p = int(b["model_order"][0])
+    if model_order is None:
+        if plot:
+            crit = b["crit"][0]
+            _criterion_figure(np.arange(1, len(crit) + 1), crit, int(np.argmin(crit)), crit_type)
+        print(f'FAD: optimal AR model order ({crit_type}) = {p}')
+        model_order = np.int64(p)                  # what the reference's arg-min over an int array gives
+    k = int(b["paired_components"]["n_components"][0])
+    paired = {key: b["paired_components"][key][0, :k].copy() for key in ("pole_index",) + _FAD_POLE_KEYS}
+    fad_params = {
+        'model_order': model_order,
+        **{key: b[key][0, :p].copy() for key in _FAD_POLE_KEYS},
+        'noise_variance': float(b["noise_variance"][0]),
+        'osc_mask': b["osc_mask"][0, :p].copy(),
+        'ar_coeffs': b["ar_coeffs"][0, :p].copy(),
+        'paired_components': paired,
+    }
+    if plot:
+        _fad_figure(x.ravel(), fs, fad_params)
+    return fad_params
+
+
+def fad_components_table(fad_params, output='dataframe', decimals=None):
+    """One row per entry of fad_params['paired_components'] (mtmvar.py:759-842), columns
+    component, freq_hz, omega_rad_s, beta_s_1, bandwidth_hz, B, phi_rad, pole_real, pole_imag, residue_real,
+    residue_imag; `output` 'ndarray' (float array, the columns in this order) or 'dataframe' (pandas, integer
+    `component`); `decimals` rounds every value."""
+    pc = fad_params.get('paired_components', None)
+    if pc is None:
+        raise ValueError("fad_params does not contain 'paired_components'.")
+    rows = len(pc['freq_hz'])
+    cols = [np.arange(1, rows + 1, dtype=int), pc['freq_hz'], pc['omega_rad_s'], pc['beta'], pc['bandwidth_hz'],
+            pc['B'], pc['phi'], np.real(pc['poles']), np.imag(pc['poles']), np.real(pc['C']), np.imag(pc['C'])]
+    table = np.column_stack(cols)
+    if decimals is not None:
+        table = np.round(table, decimals=decimals)
+    if output == 'ndarray':
+        return table
+    if output != 'dataframe':
+        raise ValueError("output must be 'dataframe' or 'ndarray'.")
+    try:
+        import pandas as pd
+    except ImportError as exc:
+        raise ImportError("pandas is required for output='dataframe'. Use output='ndarray' instead.") from exc
+    df = pd.DataFrame(table, columns=FAD_TABLE_COLUMNS)
+    df['component'] = df['component'].astype(int)
+    return df
+
+
+FAD_TABLE_COLUMNS = ['component', 'freq_hz', 'omega_rad_s', 'beta_s_1', 'bandwidth_hz', 'B', 'phi_rad', 'pole_real',
+                     'pole_imag', 'residue_real', 'residue_imag']
+
+
+def _fad_figure(signal, fs, fad):
+    """The figure of fad_decomposition(..., plot=True): poles against the unit circle (left), the AR spectrum
+    sigma^2 / |A(f)|^2 with every oscillator's frequency, half-power bandwidth and amplitude marked (right)."""
+    import matplotlib.pyplot as plt
+    z = fad['poles']
+    pc = fad['paired_components']
+    up = np.imag(pc['poles']) > 1e-8                 # one marker per conjugate pair, whatever pair_conjugates was
+    comp = {key: np.asarray(pc[key])[up] for key in ('pole_index', 'freq_hz', 'B', 'bandwidth_hz')}
+    colors = plt.cm.viridis(np.linspace(0.15, 0.9, max(len(comp['freq_hz']), 1)))
+    f = np.linspace(0.0, fs / 2.0, 1025)
+    a = np.asarray(fad['ar_coeffs'])
+    A = 1.0 - np.exp(-2j * np.pi * np.outer(f / fs, np.arange(1, len(a) + 1))) @ a
+    spec = fad['noise_variance'] / np.abs(A) ** 2
+    fig, (ax0, ax1) = plt.subplots(1, 2, figsize=(13, 5))
+    fig.suptitle(f"FAD decomposition  (AR order p = {fad['model_order']})", fontsize=13)
+    t = np.linspace(0.0, 2.0 * np.pi, 300)
+    ax0.plot(np.cos(t), np.sin(t), "k-", lw=0.9, alpha=0.4)
+    ax0.axhline(0, color="k", lw=0.5, alpha=0.4)
+    ax0.axvline(0, color="k", lw=0.5, alpha=0.4)
+    real = ~np.asarray(fad['osc_mask'])
+    ax0.scatter(z[real].real, z[real].imag, color="gray", s=40, marker="s", zorder=4)
+    for c, j, fj in zip(colors, comp['pole_index'], comp['freq_hz']):
+        ax0.scatter(z[j].real, z[j].imag, color=c, s=70, zorder=5, label=f"{fj:.2f} Hz")
+        ax0.scatter(z[j].real, -z[j].imag, color=c, s=70, zorder=5, marker="x")
+    ax0.set(xlim=(-1.25, 1.25), ylim=(-1.25, 1.25), xlabel="Re(z)", ylabel="Im(z)", title="Poles in the complex plane")
+    ax0.set_aspect("equal")
+    if len(comp['freq_hz']):
+        ax0.legend(fontsize=8, loc="upper left", title="freq [Hz]")
+    ax0.grid(True, alpha=0.3)
+    ax1.plot(f, spec, "k-", lw=1.5, label="AR spectrum")
+    for c, fj, bj, bw in zip(colors, comp['freq_hz'], comp['B'], comp['bandwidth_hz']):
+        peak = spec[np.argmin(np.abs(f - fj))]
+        ax1.plot([fj, fj], [0, peak], color="r", lw=1.2, alpha=0.9)
+        ax1.plot([max(0.0, fj - bw), min(fs / 2.0, fj + bw)], [peak / 2, peak / 2], color="m", lw=1.8, alpha=0.9)
+        ax1.scatter([fj], [peak], color=c, s=28, zorder=6)
+        ax1.annotate(f"{fj:.1f} Hz\nBW={bw:.2f} Hz\nB={bj:.3g}", xy=(fj, peak), xytext=(6, 8),
+                     textcoords="offset points", fontsize=7, color=c)
+    ax1.set(xlabel="Frequency [Hz]", ylabel="Power", title="AR spectrum and FAD components", xlim=(0, fs / 2.0))
+    ax1.legend(fontsize=8)
+    ax1.grid(True, alpha=0.3)
+    fig.tight_layout()
+    plt.show()
+    return fig

@@ -4,6 +4,7 @@
 (/root/reference/src/eeg_alpha_ibi_ffdtf.py:451-518) -- same start positions, same ValueErrors.
 `sliding_ffdtf` is the batched equivalent of calling `full_freq_dtf(window, freqs, fs,
 optimal_model_order=p)` (/root/reference/src/mtmvar.py:237-284) on every window of every recording.
+`sliding_fad` is `fad_decomposition` (mtmvar.py:607-757) of every channel of every window.
 """
 from __future__ import annotations
 
@@ -13,7 +14,7 @@ import torch
 from .engine import Engine, default_engine
 
 __all__ = ["window_positions", "hop_positions", "create_windows", "sliding_ffdtf", "sliding_ffdtf_device", "window_items",
-           "regular_grid"]
+           "regular_grid", "sliding_fad"]
 
 
 def window_positions(T: int, n_windows: int = 3, window_size=None):
@@ -109,3 +110,35 @@ def sliding_ffdtf(x, window_size, n_windows, p, freqs, fs, engine: Engine | None
     xd = eng.to_device(x[None] if single else x)
     ff = sliding_ffdtf_device(xd, window_size, n_windows, p, freqs, fs, eng).cpu().numpy()
     return ff[0] if single else ff
+
+
+def sliding_fad(signals, fs, window_size=None, n_windows=3, hop=None, model_order=None, max_model_order=20,
+                crit_type='AIC', pair_conjugates=True, imag_tol=1e-8, engine: Engine | None = None):
+    """FAD decomposition of every channel of every window of one recording signals (m, T): what
+    `fad_decomposition(window[ch], fs, ...)` (/root/reference/src/mtmvar.py:607-757) gives for each window of
+    `_create_windows` -- starts from `window_positions(T, n_windows, window_size)`, or every `hop` samples
+    (`hop_positions`, window_size required) when `hop` is given.  Returns `fad_decomposition_batch`'s dict with the
+    leading series axis split into (n_windows, m).  The recording is uploaded once and the windows are read in place."""
+    from .mtmvar import _fad_host, _fad_orders
+    eng = engine or default_engine()
+    x = np.asarray(signals, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError("signals must have shape (channels, samples)")
+    m, T = x.shape
+    if hop is not None:
+        if window_size is None:
+            raise ValueError("hop needs a window_size")
+        positions, w = hop_positions(T, window_size, hop), int(window_size)
+    else:
+        positions, w = window_positions(T, n_windows, window_size)
+    order, pmax, crit = _fad_orders(model_order, max_model_order, crit_type, w)
+    xd = eng.to_device(x[None])
+    item_rec, item_start = window_items(1, positions, eng.device)
+    d = eng.fad(xd, item_rec, item_start, w, pmax, order, crit, fs, imag_tol, pair_conjugates)
+    out = _fad_host(d, model_order, pair_conjugates)
+    nw = len(positions)
+
+    def split(v):
+        return v.reshape((nw, m) + v.shape[1:]) if isinstance(v, np.ndarray) else v
+    out = {k: ({kk: split(vv) for kk, vv in v.items()} if isinstance(v, dict) else split(v)) for k, v in out.items()}
+    return out

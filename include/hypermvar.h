@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define HMV_VERSION 120            /* 0.1.2 */
+#define HMV_VERSION 130            /* 0.1.3 */
 #define HMV_MAX_CHANNELS 64
 #define HMV_MAX_ORDER 32
 
@@ -272,6 +272,39 @@ int hmv_sliding_ffdtf_spectra_f64(const double* x, int64_t rec_stride, int64_t l
                                   double pivot_tau, int64_t flags,
                                   int64_t grid_hop, int64_t grid_first, int64_t grid_nwin, int64_t grid_T,
                                   void* stream, void* aux_stream);
+
+/* FAD (frequency-amplitude-damping) decomposition of univariate AR models, batched over series.  Replaces
+ * fad_decomposition (src/mtmvar.py:607-757): order selection as mvar_criterion at m = 1 (:551-601), the fit of ar_coeff
+ * (:90-123, count_corr :35-87: biased 1/n autocovariance, no demeaning) by Levinson-Durbin, and the partial-fraction
+ * expansion of scipy.signal.residuez([1], [1, -a_1, .., -a_p]) with its default grouping (poles within 1e-3 averaged
+ * and treated as one repeated pole, unique poles sorted by |z|, repeated-pole residues ascending in power).
+ * Series s = item * m + ch is channel ch of window `item`, addressed as in hmv_lagcov_f64 (x: [n_rec][m][ld]; window
+ * item covers samples item_start[item] .. + n of recording item_rec[item]).  pmax: 1..32, n > pmax.
+ * order: 0 = automatic (first arg-min of log V_p + c p / n, p = 1..pmax, c = 2 / 2 log log n / log n for
+ * crit = 0 / 1 / 2 = AIC / HQ / SC), else the fixed order 1..pmax.
+ * Outputs, one row of pmax per series (entries past the series' order: NaN, osc_mask 0, paired -1):
+ *   order_out int32 [S];  crit_out [S][pmax] (optional, automatic mode: the criterion curve);  ar [S][pmax];
+ *   noise_variance [S] = r_0 - a . r_{1..p};  poles, C, alpha complex128 [S][pmax] (alpha = log(z) fs);  freq = Im alpha
+ *   / 2 pi, beta = -Re alpha, bandwidth = beta / 2 pi, phi = arg C, B = 2 |C|  [S][pmax];  osc_mask uint8 [S][pmax]
+ *   (|Im z| > imag_tol);  paired int32 [S][pmax] + n_paired int32 [S]: the poles with Im z > imag_tol sorted by
+ *   frequency (pair_conjugates != 0), else every oscillatory pole in pole order;
+ *   info int32 [S]: bit 0 fit breakdown (r_0 = 0, V <= 0 or non-finite; outputs NaN), bit 1 root iteration did not
+ *   converge (outputs NaN), bit 2 a chain of poles within 1e-3 wider than 1e-3 (residuez's grouping would depend on
+ *   the root order; grouped here by connected components).
+ * hmv_fad_workspace_bytes: scratch of hmv_fad_f64 -- 0 for valid arguments (every intermediate lives in LDS), -1
+ * otherwise; there so that callers size buffers the same way as for the other entries. */
+int64_t hmv_fad_workspace_bytes(int64_t n_series, int pmax);
+int hmv_fad_f64(const double* x, int64_t rec_stride, int64_t ld, const int64_t* item_rec, const int64_t* item_start,
+                int64_t n_items, int m, int n, int pmax, int order, int crit, double fs, double imag_tol,
+                int pair_conjugates, int32_t* order_out, double* crit_out, double* ar, double* noise_variance,
+                double* poles, double* C, double* alpha, double* freq, double* beta, double* bandwidth, double* phi,
+                double* B, uint8_t* osc_mask, int32_t* paired, int32_t* n_paired, int32_t* info, void* stream);
+/* Stages C-D of hmv_fad_f64 on given coefficients ar [S][p] (residuez on [1, -a_1, .., -a_p], src/mtmvar.py:643-652
+ * onwards); outputs as above with pmax = p. */
+int hmv_fad_decompose_f64(const double* ar, int64_t n_series, int p, double fs, double imag_tol, int pair_conjugates,
+                          double* poles, double* C, double* alpha, double* freq, double* beta, double* bandwidth,
+                          double* phi, double* B, uint8_t* osc_mask, int32_t* paired, int32_t* n_paired, int32_t* info,
+                          void* stream);
 
 #ifdef __cplusplus
 }
