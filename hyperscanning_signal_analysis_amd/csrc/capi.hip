@@ -424,10 +424,13 @@ int hmv_tf_ffdtf_bands_f64(const double* ar, int64_t n_items, int m, int p, cons
 
 // ---- fused sliding-window path ----------------------------------------------------------------------
 namespace {
+// what the fused call computes on top of K1 / K2: ffDTF (K3), dDTF (K3 + sliding_conn.hip), GPDC (sliding_conn.hip only)
+enum Measure { MEAS_FFDTF = 0, MEAS_DDTF = 1, MEAS_GPDC = 2 };
 struct SlidingWs {
-  size_t off_R, off_Q, off_ws, off_ar, off_V, off_tf, off_den, off_tw, off_H, total;
+  size_t off_R, off_Q, off_ws, off_ar, off_V, off_tf, off_den, off_tw, off_H, off_B, off_G, off_full, total;
 };
-SlidingWs sliding_layout(int64_t chunk, int mp, int p, int F, bool bands = false, bool spectra = false) {
+// `bands` with dDTF / GPDC: the chunk's full array passes through scratch (off_full) before its band sums are taken
+SlidingWs sliding_layout(int64_t chunk, int mp, int p, int F, bool bands = false, bool spectra = false, int measure = MEAS_FFDTF) {
   SlidingWs w;
   size_t o = 0;
   const size_t t = (size_t)mp * mp;
@@ -436,11 +439,18 @@ SlidingWs sliding_layout(int64_t chunk, int mp, int p, int F, bool bands = false
   w.off_ws = o;     o += align256(sizeof(double) * chunk * hmv::yw_ws_tiles(p) * t);
   w.off_ar = o;     o += align256(sizeof(double) * chunk * t * p);
   w.off_V = o;      o += align256(sizeof(double) * chunk * t);
-  w.off_tf = o;     o += tf_ff_layout(chunk, mp, p, F, bands).total;
+  w.off_tf = o;
+  if (measure != MEAS_GPDC) o += tf_ff_layout(chunk, mp, p, F, bands && measure == MEAS_FFDTF).total;
   w.off_den = o;    o += align256(sizeof(double) * chunk * mp);
   w.off_tw = o;     o += align256(sizeof(double) * F * p * 2);
   w.off_H = o;
   if (spectra) o += align256(sizeof(double) * 2 * chunk * F * t);       // H (complex) of one chunk, between K3 and K5
+  w.off_B = o;
+  if (measure == MEAS_DDTF) o += align256(sizeof(double) * chunk * (p + 1) * t);
+  w.off_G = o;
+  if (measure == MEAS_DDTF) o += align256(sizeof(double) * chunk * (2 * p + 1) * t);
+  w.off_full = o;
+  if (measure != MEAS_FFDTF && bands) o += align256(sizeof(double) * chunk * (mp * mp) * F);
   w.total = o;
   return w;
 }
@@ -474,7 +484,7 @@ int sliding_impl(const char* who, const double* x, int64_t rec_stride, int64_t l
                  double* ffdtf, double* band_out, const int32_t* bin_lo, const int32_t* bin_hi, int n_bands, double* S_out,
                  double* ar_out, double* V_out, int32_t* info_yw, int32_t* info_tf, void* workspace, int64_t workspace_bytes, int64_t chunk,
                  double pivot_tau, int64_t flags, int64_t grid_hop, int64_t grid_first, int64_t grid_nwin, int64_t grid_T,
-                 void* ev_k3_start, void* ev_k3_stop, void* stream, void* aux_stream) {
+                 void* ev_k3_start, void* ev_k3_stop, void* stream, void* aux_stream, int measure = MEAS_FFDTF) {
   const bool bands = (band_out != nullptr);
   auto fail = [&](int code, const char* msg) {
     const char* own = strchr(msg, ':');             // messages below are written "hmv_sliding_ffdtf_f64: ..."
@@ -487,10 +497,11 @@ int sliding_impl(const char* who, const double* x, int64_t rec_stride, int64_t l
   if (p < 1 || p > HMV_MAX_ORDER) return fail(-2, "hmv_sliding_ffdtf_f64: model order must be in 1..32");
   if (n <= p) return fail(-3, "hmv_sliding_ffdtf_f64: window shorter than the model order");
   if (n_items == 0) return 0;                                    // empty batch: nothing to do, nothing to check
-  if (!x || !item_rec || !item_start || !freqs || (!ffdtf && !bands) || !info_yw || !info_tf || !workspace || F < 1 || chunk < 1)
+  if (!x || !item_rec || !item_start || !freqs || (!ffdtf && !bands) || !info_yw || (!info_tf && measure != MEAS_GPDC) ||
+      !workspace || F < 1 || chunk < 1)
     return fail(-4, "hmv_sliding_ffdtf_f64: null pointer / empty grid");
   if (bands && (!bin_lo || !bin_hi || n_bands < 1)) return fail(-4, "hmv_sliding_ffdtf_f64: band bins missing");
-  const SlidingWs w = sliding_layout(chunk, mp, p, F, bands, S_out != nullptr);
+  const SlidingWs w = sliding_layout(chunk, mp, p, F, bands, S_out != nullptr, measure);
   if ((int64_t)w.total > workspace_bytes) return fail(-7, "hmv_sliding_ffdtf_f64: workspace too small");
   // Regular grid (the caller vouches: item = rec * grid_nwin + w starts at grid_first + w * grid_hop of recording rec,
   // recordings are grid_T samples long): K1 sums every hop block once and assembles the windows from the blocks.
@@ -525,7 +536,8 @@ int sliding_impl(const char* who, const double* x, int64_t rec_stride, int64_t l
   void* tfws = base + w.off_tf;
   double* den = reinterpret_cast<double*>(base + w.off_den);
   double* tw = reinterpret_cast<double*>(base + w.off_tw);
-  const int64_t tfws_bytes = (int64_t)tf_ff_layout(chunk, mp, p, F, bands).total;
+  const bool k3_bands = bands && measure == MEAS_FFDTF;
+  const int64_t tfws_bytes = (int64_t)tf_ff_layout(chunk, mp, p, F, k3_bands).total;
   rc = hmv_twiddles_f64(freqs, F, fs, p, tw, st0);
   const size_t ws_item = (size_t)hmv_yw_workspace_doubles(m, p);
   for (int64_t ci = 0; ci < n_chunks && rc == 0; ++ci) {
@@ -574,10 +586,27 @@ int sliding_impl(const char* who, const double* x, int64_t rec_stride, int64_t l
     if (rc) break;
     const bool last = (ci == n_chunks - 1);
     double* Hc = S_out ? reinterpret_cast<double*>(base + w.off_H) : nullptr;
-    rc = tf_ffdtf_impl(who, ar_c, c, m, p, tw, F, bands ? nullptr : ffdtf + (size_t)i0 * m * m * F,
-                       bands ? band_out + (size_t)i0 * m * m * n_bands : nullptr, bin_lo, bin_hi, n_bands, den, Hc,
-                       info_tf + (size_t)i0 * F, pivot_tau, tfws, tfws_bytes, flags, last ? ev_k3_start : nullptr,
-                       last ? ev_k3_stop : nullptr, st0);
+    // dDTF / GPDC: the chunk's full array goes to the output, or (band form) to scratch ahead of its band sums
+    double* full_c = (measure == MEAS_FFDTF) ? nullptr
+                     : bands ? reinterpret_cast<double*>(base + w.off_full) : ffdtf + (size_t)i0 * m * m * F;
+    if (measure == MEAS_GPDC) {
+      rc = hmv::launch_gpdc_sliding(ar_c, V_c, tw, full_c, c, F, m, mp, p, st0);
+    } else {
+      rc = tf_ffdtf_impl(who, ar_c, c, m, p, tw, F, k3_bands ? nullptr : (full_c ? full_c : ffdtf + (size_t)i0 * m * m * F),
+                         k3_bands ? band_out + (size_t)i0 * m * m * n_bands : nullptr, bin_lo, bin_hi, n_bands, den, Hc,
+                         info_tf + (size_t)i0 * F, pivot_tau, tfws, tfws_bytes, flags, last ? ev_k3_start : nullptr,
+                         last ? ev_k3_stop : nullptr, st0);
+    }
+    if (!rc && measure == MEAS_DDTF) {     // |kappa| from W(f) = A^T V^-1 A, multiplied into K3's ffDTF in place
+      hmv::DdtfArgs da{};
+      da.ar = ar_c; da.V = V_c; da.info_yw = info_yw + i0;
+      da.B = reinterpret_cast<double*>(base + w.off_B); da.G = reinterpret_cast<double*>(base + w.off_G);
+      da.freqs = freqs; da.fs = fs; da.ff = full_c; da.out = full_c; da.n_items = c; da.F = F; da.m = m; da.p = p;
+      rc = hmv::launch_ddtf_sliding(da, mp, st0);
+    }
+    if (!rc && measure != MEAS_FFDTF && bands)
+      rc = hmv::launch_band_sums(full_c, reinterpret_cast<const int*>(bin_lo), reinterpret_cast<const int*>(bin_hi),
+                                 band_out + (size_t)i0 * m * m * n_bands, c * (long long)m * m, F, n_bands, st0);
     if (!rc && S_out) {      // K5 from the same inverses and the same fit; V is this library's own (symmetric) estimate
       hmv::SpecArgs sa;
       sa.H = Hc; sa.V = V_c; sa.S = nullptr; sa.S_mmf = S_out + (size_t)i0 * m * m * F * 2; sa.n_items = c; sa.F = F; sa.m = m;
@@ -640,6 +669,51 @@ int hmv_sliding_ffdtf_spectra_f64(const double* x, int64_t rec_stride, int64_t l
                       fs, ffdtf, nullptr, nullptr, nullptr, 0, S_out, ar_out, V_out, info_yw, info_tf, workspace,
                       workspace_bytes, chunk, pivot_tau, flags, grid_hop, grid_first, grid_nwin, grid_T, nullptr, nullptr,
                       stream, aux_stream);
+}
+
+// ---- sliding-window dDTF / GPDC (sliding_conn.hip) ------------------------------------------------------
+// direct_dtf (/root/reference/src/mtmvar.py:341-385) and gen_partial_directed_coherence (mtmvar.py:388-468) of every
+// window; n_bands = 0: the full (m, m, F) arrays, n_bands >= 1: their band sums.
+int64_t hmv_sliding_ddtf_workspace_bytes(int64_t chunk, int m, int p, int F, int n_bands) {
+  const int mp = pad_of(m);
+  if (mp < 0 || chunk < 1 || p < 1 || p > HMV_MAX_ORDER || F < 1 || n_bands < 0) return -1;
+  return (int64_t)sliding_layout(chunk, mp, p, F, n_bands > 0, false, MEAS_DDTF).total;
+}
+
+int hmv_sliding_ddtf_f64(const double* x, int64_t rec_stride, int64_t ld, const int64_t* item_rec,
+                         const int64_t* item_start, int64_t n_items, int m, int n, int p, const double* freqs, int F,
+                         double fs, double* out, const int32_t* bin_lo, const int32_t* bin_hi, int n_bands,
+                         double* ar_out, double* V_out, int32_t* info_yw, int32_t* info_tf, void* workspace,
+                         int64_t workspace_bytes, int64_t chunk, double pivot_tau, int64_t flags, int64_t grid_hop,
+                         int64_t grid_first, int64_t grid_nwin, int64_t grid_T, void* stream, void* aux_stream) {
+  if (n_bands < 0) return fail(-4, "hmv_sliding_ddtf_f64: n_bands must be >= 0");
+  if (!out && n_items != 0) return fail(-4, "hmv_sliding_ddtf_f64: null pointer / empty grid");
+  const bool bands = n_bands > 0;
+  return sliding_impl("hmv_sliding_ddtf_f64", x, rec_stride, ld, item_rec, item_start, n_items, m, n, p, freqs, F, fs,
+                      bands ? nullptr : out, bands ? out : nullptr, bin_lo, bin_hi, n_bands, nullptr, ar_out, V_out, info_yw,
+                      info_tf, workspace, workspace_bytes, chunk, pivot_tau, flags, grid_hop, grid_first, grid_nwin, grid_T,
+                      nullptr, nullptr, stream, aux_stream, MEAS_DDTF);
+}
+
+int64_t hmv_sliding_gpdc_workspace_bytes(int64_t chunk, int m, int p, int F, int n_bands) {
+  const int mp = pad_of(m);
+  if (mp < 0 || chunk < 1 || p < 1 || p > HMV_MAX_ORDER || F < 1 || n_bands < 0) return -1;
+  return (int64_t)sliding_layout(chunk, mp, p, F, n_bands > 0, false, MEAS_GPDC).total;
+}
+
+int hmv_sliding_gpdc_f64(const double* x, int64_t rec_stride, int64_t ld, const int64_t* item_rec,
+                         const int64_t* item_start, int64_t n_items, int m, int n, int p, const double* freqs, int F,
+                         double fs, double* out, const int32_t* bin_lo, const int32_t* bin_hi, int n_bands,
+                         double* ar_out, double* V_out, int32_t* info_yw, void* workspace, int64_t workspace_bytes,
+                         int64_t chunk, int64_t flags, int64_t grid_hop, int64_t grid_first, int64_t grid_nwin,
+                         int64_t grid_T, void* stream, void* aux_stream) {
+  if (n_bands < 0) return fail(-4, "hmv_sliding_gpdc_f64: n_bands must be >= 0");
+  if (!out && n_items != 0) return fail(-4, "hmv_sliding_gpdc_f64: null pointer / empty grid");
+  const bool bands = n_bands > 0;
+  return sliding_impl("hmv_sliding_gpdc_f64", x, rec_stride, ld, item_rec, item_start, n_items, m, n, p, freqs, F, fs,
+                      bands ? nullptr : out, bands ? out : nullptr, bin_lo, bin_hi, n_bands, nullptr, ar_out, V_out, info_yw,
+                      nullptr, workspace, workspace_bytes, chunk, 1.0, flags, grid_hop, grid_first, grid_nwin, grid_T,
+                      nullptr, nullptr, stream, aux_stream, MEAS_GPDC);
 }
 
 int64_t hmv_fad_workspace_bytes(int64_t n_series, int pmax) {

@@ -134,6 +134,24 @@ int launch_pack_c128(const double* in, double* out, long long n_items, int F, in
 int launch_pcoh(const double* Sinv, const double* detph, double* out, long long n_items, int F, int m, int m_pad, hipStream_t st);
 int launch_gpdc(const double* A, const double* V, double* out, long long n_items, int F, int m, int m_pad, hipStream_t st);
 
+// ---- sliding-window dDTF / GPDC (sliding_conn.hip) --------------------------------------------------------------
+struct DdtfArgs {
+  const double* ar;         // [n_items][MP][MP][p]   K2
+  const double* V;          // [n_items][MP][MP]      K2 (symmetric)
+  int* info_yw;             // [n_items]: set to -(column + 1) where V is not positive definite (and was 0)
+  double* B;                // scratch [n_items][p+1][MP][MP]: L^-1 A_k
+  double* G;                // scratch [n_items][2p+1][MP][MP]: coefficients of W(f) = A^T V^-1 A
+  const double* freqs;      // [F] device
+  double fs;
+  const double* ff;         // [n_items][m][m][F]     ffDTF of K3's fused path
+  double* out;              // [n_items][m][m][F]     dDTF (may be ff)
+  long long n_items;
+  int F, m, p;
+};
+int launch_ddtf_sliding(const DdtfArgs& a, int m_pad, hipStream_t st);
+int launch_gpdc_sliding(const double* ar, const double* V, const double* tw, double* out, long long n_items, int F, int m,
+                        int m_pad, int p, hipStream_t st);
+
 // ---- multitaper PSD (psd.hip; hipFFT for the transforms) -------------------------------------------------
 long long psd_workspace_bytes(long long ch_chunk, long long n, int K);
 int launch_psd(const double* x, long long n_ch, long long n, long long ld, const double* tapers, const double* w, int K,

@@ -465,6 +465,113 @@ class Engine:
             return out, ar, V, (info_yw, info_tf)
         return out
 
+    def sliding_ddtf(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, p: int, freqs,
+                     fs: float, out: torch.Tensor | None = None, return_ar: bool = False, check=True,
+                     chunk: int | None = None, overlap: bool = True, flags: int = 0, grid=None, validate: bool = True,
+                     bands=None):
+        """dDTF of every window (`direct_dtf`, mtmvar.py:341-385): x (n_rec, m, T) -> (items, m, m, F), or its band sums
+        (items, m, m, n_bands) with `bands=(bin_lo, bin_hi)`.  One C-ABI call (`hmv_sliding_ddtf_f64`): K1 -> K2 -> K3's
+        fused ffDTF -> |kappa| from W(f) = A^T V^-1 A (sliding_conn.hip).  The keywords mean what they mean for
+        `sliding_ffdtf`; a window also fails where its residual covariance is not positive definite (info_yw < 0).
+        Equal to the reference's minors-based dDTF to rounding, not bitwise (no minors, no second inversion)."""
+        return self._sliding_conn("ddtf", x, item_rec, item_start, n, p, freqs, fs, out, return_ar, check, chunk, overlap,
+                                  flags, grid, validate, bands)
+
+    def sliding_gpdc(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, p: int, freqs,
+                     fs: float, out: torch.Tensor | None = None, return_ar: bool = False, check=True,
+                     chunk: int | None = None, overlap: bool = True, flags: int = 0, grid=None, validate: bool = True,
+                     bands=None):
+        """GPDC of every window (`gen_partial_directed_coherence`, mtmvar.py:388-468): x (n_rec, m, T) -> (items, m, m, F),
+        or its band sums with `bands=(bin_lo, bin_hi)`.  One C-ABI call (`hmv_sliding_gpdc_f64`): K1 -> K2 -> one kernel
+        that builds A(f) on chip; no K3.  The keywords mean what they mean for `sliding_ffdtf`.  Only the Yule-Walker
+        failure is reported: A(f) is never inverted, so an exactly singular A(f), on which the reference's
+        mvar_transfer_function raises, goes through (`return_ar` gives (out, ar, V, info_yw))."""
+        return self._sliding_conn("gpdc", x, item_rec, item_start, n, p, freqs, fs, out, return_ar, check, chunk, overlap,
+                                  flags, grid, validate, bands)
+
+    def _sliding_conn(self, measure, x, item_rec, item_start, n, p, freqs, fs, out, return_ar, check, chunk, overlap, flags,
+                      grid, validate, bands):
+        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
+        x = x if x.stride(2) == 1 else x.contiguous()
+        n_rec, m, T = x.shape
+        mp = self.pad(m)
+        ddtf = measure == "ddtf"
+        if validate:
+            self.check_items(x, item_rec, item_start, n, p)
+        n_items = int(item_rec.numel())
+        f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
+        F = int(f.numel())
+        nb = 0
+        if bands is not None:
+            b_lo, b_hi = self.band_tables(bands[0], bands[1], F)
+            nb = int(b_lo.numel())
+        last = nb if bands is not None else F
+
+        def finish(res, ar, V, infos):
+            return (res, ar, V, infos) if return_ar else res
+        if n_items == 0:                      # empty batch (torch gives empty tensors a null data pointer)
+            infos = (self.empty(0, dtype=torch.int32),) * 2
+            return finish(self.empty(0, m, m, last), self.empty(0, mp, mp, p), self.empty(0, mp, mp),
+                          infos if ddtf else infos[0])
+        if bands is not None and nb == 0:     # an empty band set: the full arrays, then their (empty) band sums
+            res = self._sliding_conn(measure, x, item_rec, item_start, n, p, f, fs, None, return_ar, check, chunk, overlap,
+                                     flags, grid, validate, None)
+            full = res[0] if isinstance(res, tuple) else res
+            red = self.band_sums(full, bands[0], bands[1])
+            return (red,) + tuple(res[1:]) if isinstance(res, tuple) else red
+        if out is None:
+            out = self.empty(n_items, m, m, last)
+        assert out.is_contiguous() and tuple(out.shape) == (n_items, m, m, last)
+        wsf = self.lib.hmv_sliding_ddtf_workspace_bytes if ddtf else self.lib.hmv_sliding_gpdc_workspace_bytes
+        if chunk is None:
+            per_item = int(wsf(1, m, p, F, nb))
+            chunk = max(1, min(n_items, self.max_workspace_bytes // max(per_item, 1)))
+        chunk = int(chunk)
+        nbytes = int(wsf(chunk, m, p, F, nb))
+        if nbytes < 0:
+            raise ValueError(f"sliding_{measure}: bad sizes (m={m}, p={p}, F={F}, chunk={chunk})")
+        ws = self._workspace(nbytes)
+        aux = self.aux_stream().cuda_stream if overlap else 0
+        ar = self.empty(n_items, mp, mp, p) if return_ar else None
+        V = self.empty(n_items, mp, mp) if return_ar else None
+        info_yw = self.empty(n_items, dtype=torch.int32)
+        info_tf = self.empty(n_items * F, dtype=torch.int32) if ddtf else None
+        g_hop, g_first, g_nwin = (int(v) for v in grid) if grid is not None else (0, 0, 0)
+        if grid is not None:        # the same contract as sliding_ffdtf(grid=...)
+            if g_nwin < 1 or n_items % g_nwin or g_hop < 1 or n_items // g_nwin > n_rec:
+                raise ValueError("grid = (hop, first, n_win) does not match the number of items / recordings")
+            k = torch.arange(n_items, dtype=torch.int64, device=self.device)
+            same = (not validate) or (torch.equal(item_rec, k // g_nwin) and
+                                      torch.equal(item_start, g_first + (k % g_nwin) * g_hop))
+            if not same:
+                raise ValueError("grid = (hop, first, n_win) contradicts item_rec / item_start "
+                                 "(items must be recording-major, window-minor on the declared grid)")
+        lo_p, hi_p = (b_lo.data_ptr(), b_hi.data_ptr()) if nb else (0, 0)
+        common = (x.data_ptr(), x.stride(0), x.stride(1), item_rec.data_ptr(), item_start.data_ptr(), n_items, m, int(n),
+                  int(p), f.data_ptr(), F, float(fs), out.data_ptr(), lo_p, hi_p, nb, _ptr(ar), _ptr(V), info_yw.data_ptr())
+        grid_args = (g_hop, g_first, g_nwin, T, self.stream(), aux)
+        with torch.cuda.device(self.device):
+            if ddtf:
+                rc = self.lib.hmv_sliding_ddtf_f64(*common, info_tf.data_ptr(), ws.data_ptr(), nbytes, chunk, self.pivot_tau,
+                                                   int(flags), *grid_args)
+            else:
+                rc = self.lib.hmv_sliding_gpdc_f64(*common, ws.data_ptr(), nbytes, chunk, int(flags), *grid_args)
+        _lib.check(rc, f"hmv_sliding_{measure}_f64")
+        badw = info_yw != 0
+        if ddtf:
+            badw = badw | (info_tf.view(n_items, F) != 0).any(dim=1)
+        infos = (info_yw, info_tf) if ddtf else info_yw
+        if check == "nan":
+            if bool(badw.any()):
+                out[badw] = float("nan")
+        elif check == "mask":
+            return out, badw
+        elif check:
+            self.raise_on_info(info_yw, "ar_coeff (Yule-Walker solve; a negative info: residual covariance not "
+                                        "positive definite)")
+            if ddtf:
+                self.raise_on_info(info_tf, "mvar_transfer_function (inverse of A(f))", per_item=F)
+        return finish(out, ar, V, infos)
 
     # ------------------------------------------------------------------ recordings streamed from the host
     def stream_dyads(self, dyads, n: int, positions, p: int, freqs, fs: float, bands=None, reduce=None, depth: int = 3,

@@ -40,6 +40,7 @@ from .sliding import hop_positions, regular_grid, window_items
 __all__ = ["discover_dyads", "decode_events", "segment_block", "prepare_dyad", "run", "savez_fast", "xarray_reader"]
 
 ROLES = (("ch", "child"), ("cg", "caregiver"))
+MEASURES = ("ffdtf", "ddtf", "gpdc")          # what run(measures=...) can compute per window; ffDTF always
 _FILE_RE = re.compile(r"^(?P<dyad>.+)_EEG_(?P<role>ch|cg)_(?P<task>.+)$")
 
 
@@ -174,13 +175,15 @@ def savez_fast(path, compresslevel=0, **arrays):
 def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, freqs=None, bands=hdist.DEFAULT_BANDS,
         low_cutoff_hz=None, high_cutoff_hz=None, channel_subset=None, with_psd=False, psd_fmin=1.0, psd_fmax=30.0,
         psd_bandwidth=2.0, save_full=False, skip_existing=True, reader=None, engine=None, world=1, rank=0,
-        verbose=True, prefetch=2, timing=None, save_workers=4, compresslevel=0):
+        verbose=True, prefetch=2, timing=None, save_workers=4, compresslevel=0, measures=("ffdtf",)):
     """Process every dyad under <root>/EEG.  Per dyad one `<out_dir>/<dyad>_ffdtf.npz` with, per segment `<task>/<event>`:
         <seg>/ffdtf_bands   (windows, n, n, n_bands)   band-integrated ffDTF of every window
         <seg>/ffdtf         (windows, n, n, F)         only with save_full=True (8.4 MB per window at 64 channels)
         <seg>/starts        (windows,)                 first sample of every window inside the segment
         <seg>/psd, <seg>/psd_freqs                     multitaper PSD of the segment block (with_psd=True)
-      plus `channels`, `freqs`, `meta` (JSON).  Returns {"done": [...], "skipped": [...], "failed": [(dyad, error)],
+        <seg>/ddtf_bands, <seg>/gpdc_bands (and <seg>/ddtf, <seg>/gpdc with save_full=True)
+                                                       with measures=(..., "ddtf", "gpdc"): dDTF / GPDC of the same windows
+      plus `channels`, `freqs`, `meta` (JSON, its `measures` field lists what was computed).  Returns {"done": [...], "skipped": [...], "failed": [(dyad, error)],
       "timing": {...}}.
     A window whose fit is singular is NaN-filled, not fatal (the reference would raise and lose the dyad); a segment that
     cannot be processed is logged in the dyad's meta and does not discard the dyad's other segments.
@@ -190,6 +193,10 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
     import concurrent.futures as cf
 
     import torch
+    measures = tuple(measures)
+    unknown = [m_ for m_ in measures if m_ not in MEASURES]
+    if unknown or "ffdtf" not in measures or len(set(measures)) != len(measures):
+        raise ValueError(f"measures must list 'ffdtf' and any of {MEASURES[1:]} once each, got {measures}")
     eng = engine or default_engine()
     reader = reader or xarray_reader
     out_dir = Path(out_dir)
@@ -233,7 +240,8 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                 for line in prep["notes"]:
                     say(line)
                 result, meta = {}, {"dyad": dyad, "segments": [], "failed_segments": [], "model_order": int(model_order),
-                                    "window_s": window_s, "overlap": overlap, "created": time.strftime("%Y-%m-%dT%H:%M:%S")}
+                                    "window_s": window_s, "overlap": overlap, "measures": list(measures),
+                                    "created": time.strftime("%Y-%m-%dT%H:%M:%S")}
                 names_out, freqs_out = None, None
                 tg = time.perf_counter()
                 pending = []                                       # device results of this dyad, fetched after the last launch
@@ -269,16 +277,32 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                             bsum, bad = eng.sliding_ffdtf(xd, rec_i, st_i, W, int(model_order), f, fs, check="mask",
                                                           grid=grid_w, bands=(lo, hi))
                         bsum.masked_fill_(bad.view(-1, 1, 1, 1), float("nan"))
-                        pending.append((seg, key, pos, W, f, bsum, ff if save_full else None, bad, psd_dev, pf if with_psd else None))
+                        extra = {}                                 # dDTF / GPDC of the same windows, NaN-filled alike
+                        for meas in (m_ for m_ in measures if m_ != "ffdtf"):
+                            run_m = eng.sliding_ddtf if meas == "ddtf" else eng.sliding_gpdc
+                            if save_full:
+                                full_m, bad_m = run_m(xd, rec_i, st_i, W, int(model_order), f, fs, check="mask", grid=grid_w)
+                                red_m = eng.band_sums(full_m, lo, hi)
+                                full_m.masked_fill_(bad_m.view(-1, 1, 1, 1), float("nan"))
+                                extra[meas] = full_m
+                            else:
+                                red_m, bad_m = run_m(xd, rec_i, st_i, W, int(model_order), f, fs, check="mask", grid=grid_w,
+                                                     bands=(lo, hi))
+                            red_m.masked_fill_(bad_m.view(-1, 1, 1, 1), float("nan"))
+                            extra[f"{meas}_bands"] = red_m
+                        pending.append((seg, key, pos, W, f, bsum, ff if save_full else None, bad, psd_dev, pf if with_psd else None,
+                                        extra))
                     except Exception as e:                         # one bad segment does not discard the dyad
                         meta["failed_segments"].append({"segment": key, "error": f"{type(e).__name__}: {e}"})
                         say(f"Failed segment: {dyad} {key} -> {e}")
                 if psd_stream is not None:
                     torch.cuda.current_stream(eng.device).wait_stream(psd_stream)
-                for seg, key, pos, W, f, bsum, ff, bad, psd_dev, pf in pending:
+                for seg, key, pos, W, f, bsum, ff, bad, psd_dev, pf, extra in pending:
                     result[f"{key}/ffdtf_bands"] = bsum.cpu().numpy()
                     if ff is not None:
                         result[f"{key}/ffdtf"] = ff.cpu().numpy()
+                    for name, arr in extra.items():
+                        result[f"{key}/{name}"] = arr.cpu().numpy()
                     result[f"{key}/starts"] = np.asarray(pos)
                     if psd_dev is not None:
                         result[f"{key}/psd"], result[f"{key}/psd_freqs"] = psd_dev.cpu().numpy(), pf

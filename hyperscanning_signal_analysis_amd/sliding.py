@@ -4,6 +4,8 @@
 (/root/reference/src/eeg_alpha_ibi_ffdtf.py:451-518) -- same start positions, same ValueErrors.
 `sliding_ffdtf` is the batched equivalent of calling `full_freq_dtf(window, freqs, fs,
 optimal_model_order=p)` (/root/reference/src/mtmvar.py:237-284) on every window of every recording.
+`sliding_ddtf` / `sliding_gpdc` are `direct_dtf` (mtmvar.py:341-385) / `gen_partial_directed_coherence`
+(mtmvar.py:388-468) with `optimal_model_order=p` on every window, in the same batched form.
 `sliding_fad` is `fad_decomposition` (mtmvar.py:607-757) of every channel of every window.
 """
 from __future__ import annotations
@@ -14,7 +16,7 @@ import torch
 from .engine import Engine, default_engine
 
 __all__ = ["window_positions", "hop_positions", "create_windows", "sliding_ffdtf", "sliding_ffdtf_device", "window_items",
-           "regular_grid", "sliding_fad"]
+           "regular_grid", "sliding_ddtf", "sliding_ddtf_device", "sliding_gpdc", "sliding_gpdc_device", "sliding_fad"]
 
 
 def window_positions(T: int, n_windows: int = 3, window_size=None):
@@ -110,6 +112,64 @@ def sliding_ffdtf(x, window_size, n_windows, p, freqs, fs, engine: Engine | None
     xd = eng.to_device(x[None] if single else x)
     ff = sliding_ffdtf_device(xd, window_size, n_windows, p, freqs, fs, eng).cpu().numpy()
     return ff[0] if single else ff
+
+
+def _positions(T: int, window_size, n_windows: int, hop):
+    if hop is not None:
+        if window_size is None:
+            raise ValueError("hop needs a window_size")
+        return hop_positions(T, window_size, hop), int(window_size)
+    return window_positions(T, n_windows, window_size)
+
+
+def _sliding_conn_device(measure, x, window_size, n_windows, p, freqs, fs, engine, out, check, share_overlap, hop, bands):
+    eng = engine or default_engine()
+    n_rec, m, T = x.shape
+    positions, w = _positions(T, window_size, n_windows, hop)
+    item_rec, item_start = window_items(n_rec, positions, eng.device)
+    run = eng.sliding_ddtf if measure == "ddtf" else eng.sliding_gpdc
+    res = run(x, item_rec, item_start, w, p, freqs, fs, out=out, check=check, bands=bands,
+              grid=regular_grid(positions, w, p) if share_overlap else None)
+    return res.view(n_rec, len(positions), m, m, -1)
+
+
+def sliding_ddtf_device(x: torch.Tensor, window_size, n_windows: int, p: int, freqs, fs: float, engine: Engine | None = None,
+                        out: torch.Tensor | None = None, check=True, share_overlap: bool = True, hop=None, bands=None):
+    """dDTF of every window: x device tensor (n_rec, m, T) -> device tensor (n_rec, n_windows, m, m, F), or
+    (..., n_bands) with `bands=(bin_lo, bin_hi)`.  Windows from `window_positions`, or every `hop` samples
+    (`hop_positions`) when `hop` is given.  check: True raises LinAlgError naming the failed window, "nan" NaN-fills it
+    (`Engine.sliding_ddtf`)."""
+    return _sliding_conn_device("ddtf", x, window_size, n_windows, p, freqs, fs, engine, out, check, share_overlap, hop, bands)
+
+
+def sliding_gpdc_device(x: torch.Tensor, window_size, n_windows: int, p: int, freqs, fs: float, engine: Engine | None = None,
+                        out: torch.Tensor | None = None, check=True, share_overlap: bool = True, hop=None, bands=None):
+    """GPDC of every window, in the form of `sliding_ddtf_device` (`Engine.sliding_gpdc`)."""
+    return _sliding_conn_device("gpdc", x, window_size, n_windows, p, freqs, fs, engine, out, check, share_overlap, hop, bands)
+
+
+def _sliding_conn_host(fn, x, window_size, n_windows, p, freqs, fs, engine, hop, bands, check):
+    eng = engine or default_engine()
+    x = np.asarray(x, dtype=np.float64) if not isinstance(x, torch.Tensor) else x
+    single = x.ndim == 2
+    if isinstance(x, torch.Tensor):
+        xd = (x[None] if single else x).to(device=eng.device, dtype=torch.float64)
+    else:
+        xd = eng.to_device(x[None] if single else x)
+    res = fn(xd, window_size, n_windows, p, freqs, fs, eng, check=check, hop=hop, bands=bands).cpu().numpy()
+    return res[0] if single else res
+
+
+def sliding_ddtf(x, window_size, n_windows, p, freqs, fs, engine: Engine | None = None, hop=None, bands=None, check=True):
+    """NumPy (or tensor) in / NumPy out.  x: (m, T) or (n_rec, m, T) -> (n_windows, m, m, F) or (n_rec, n_windows, ...):
+    `direct_dtf(window, freqs, fs, optimal_model_order=p)` (mtmvar.py:341-385) of every window."""
+    return _sliding_conn_host(sliding_ddtf_device, x, window_size, n_windows, p, freqs, fs, engine, hop, bands, check)
+
+
+def sliding_gpdc(x, window_size, n_windows, p, freqs, fs, engine: Engine | None = None, hop=None, bands=None, check=True):
+    """NumPy (or tensor) in / NumPy out: `gen_partial_directed_coherence(window, freqs, fs, optimal_model_order=p)`
+    (mtmvar.py:388-468) of every window, shaped as `sliding_ddtf`."""
+    return _sliding_conn_host(sliding_gpdc_device, x, window_size, n_windows, p, freqs, fs, engine, hop, bands, check)
 
 
 def sliding_fad(signals, fs, window_size=None, n_windows=3, hop=None, model_order=None, max_model_order=20,

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define HMV_VERSION 130            /* 0.1.3 */
+#define HMV_VERSION 140            /* 0.1.4 */
 #define HMV_MAX_CHANNELS 64
 #define HMV_MAX_ORDER 32
 
@@ -272,6 +272,40 @@ int hmv_sliding_ffdtf_spectra_f64(const double* x, int64_t rec_stride, int64_t l
                                   double pivot_tau, int64_t flags,
                                   int64_t grid_hop, int64_t grid_first, int64_t grid_nwin, int64_t grid_T,
                                   void* stream, void* aux_stream);
+
+/* Sliding-window dDTF and GPDC: direct_dtf (src/mtmvar.py:341-385) and gen_partial_directed_coherence (:388-468) of
+ * every window, with the conventions of hmv_sliding_ffdtf_f64 (device pointers, `chunk` items at a time, grid_hop /
+ * grid_first / grid_nwin / grid_T for the shared-overlap K1, optional ar_out / V_out).
+ * n_bands = 0: out is [n_items][m][m][F]; n_bands >= 1: out is [n_items][m][m][n_bands], band b the sum over the bins
+ * bin_lo[b] <= f < bin_hi[b] (int32 device arrays) -- the chunk's full array passes through the workspace first.
+ * dDTF = ffDTF * |kappa| (kappa_ii = 1).  The ffDTF is the one K3's fused pass writes for the chunk (hmv_tf_ffdtf_f64);
+ * |kappa_ij| = |W_ji| / sqrt(|W_ii| |W_jj|) with W(f) = S(f)^-1 = A(f)^T V^-1 A(f), evaluated per window as a
+ * trigonometric polynomial of degree 2p with real coefficients (no minors, no determinant, no inverse of S: equal to the
+ * reference's minors-based kappa to rounding, not bitwise).  info_yw: [n_items] as K2, and -(c + 1) where V is not
+ * positive definite (Cholesky pivot c); info_tf: [n_items*F] as hmv_sliding_ffdtf_f64.
+ * GPDC_ij(f) = (|A_ij(f)| / sigma_i) / sqrt(sum_k |A_kj(f)|^2 / sigma_k^2), 0 where the denominator vanishes.  No K3 and
+ * no inversion: A(f) is built on chip and never stored, so unlike the reference (which inverts A(f) in
+ * mvar_transfer_function and raises on an exactly singular one) only the Yule-Walker failure is reported, in info_yw.
+ * workspace: hmv_sliding_{ddtf,gpdc}_workspace_bytes(chunk, m, p, F, n_bands) bytes (-1 for bad arguments). */
+int64_t hmv_sliding_ddtf_workspace_bytes(int64_t chunk, int m, int p, int F, int n_bands);
+int hmv_sliding_ddtf_f64(const double* x, int64_t rec_stride, int64_t ld,
+                         const int64_t* item_rec, const int64_t* item_start, int64_t n_items,
+                         int m, int n, int p, const double* freqs, int F, double fs,
+                         double* out, const int32_t* bin_lo, const int32_t* bin_hi, int n_bands,
+                         double* ar_out, double* V_out, int32_t* info_yw, int32_t* info_tf,
+                         void* workspace, int64_t workspace_bytes, int64_t chunk,
+                         double pivot_tau, int64_t flags,
+                         int64_t grid_hop, int64_t grid_first, int64_t grid_nwin, int64_t grid_T,
+                         void* stream, void* aux_stream);
+int64_t hmv_sliding_gpdc_workspace_bytes(int64_t chunk, int m, int p, int F, int n_bands);
+int hmv_sliding_gpdc_f64(const double* x, int64_t rec_stride, int64_t ld,
+                         const int64_t* item_rec, const int64_t* item_start, int64_t n_items,
+                         int m, int n, int p, const double* freqs, int F, double fs,
+                         double* out, const int32_t* bin_lo, const int32_t* bin_hi, int n_bands,
+                         double* ar_out, double* V_out, int32_t* info_yw,
+                         void* workspace, int64_t workspace_bytes, int64_t chunk, int64_t flags,
+                         int64_t grid_hop, int64_t grid_first, int64_t grid_nwin, int64_t grid_T,
+                         void* stream, void* aux_stream);
 
 /* FAD (frequency-amplitude-damping) decomposition of univariate AR models, batched over series.  Replaces
  * fad_decomposition (src/mtmvar.py:607-757): order selection as mvar_criterion at m = 1 (:551-601), the fit of ar_coeff
