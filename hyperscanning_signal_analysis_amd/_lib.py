@@ -85,6 +85,10 @@ SIGNATURES = {
     "hmv_fad_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int,
                             c_double, c_double, c_int] + [c_void_p] * 17),
     "hmv_fad_decompose_f64": (c_int, [c_void_p, c_int64, c_int, c_double, c_double, c_int] + [c_void_p] * 13),
+    "hmv_surrogate_shift_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                                        c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "hmv_surrogate_phase_c128": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "hmv_null_accumulate_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int] + [c_void_p] * 12),
 }
 
 # option bits of the fused entry points (include/hypermvar.h)

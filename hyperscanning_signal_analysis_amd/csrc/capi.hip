@@ -764,4 +764,52 @@ int hmv_fad_decompose_f64(const double* ar, int64_t n_series, int p, double fs, 
   return hmv::launch_fad(a, S(stream));
 }
 
+// ---- surrogate significance (surrogate.hip) --------------------------------------------------------------------
+int hmv_surrogate_shift_f64(const double* x, int64_t rec_stride, int64_t ld, int64_t T, const int64_t* item_rec,
+                            const int64_t* item_start, int64_t n_win, const int64_t* shift, int64_t n_rec, int n_surr, int m,
+                            int n, int split, double* out, void* stream) {
+  if (m < 1 || m > HMV_MAX_CHANNELS) return fail(-1, "hmv_surrogate_shift_f64: channel count must be in 1..64");
+  if (n < 2 || n > T) return fail(-3, "hmv_surrogate_shift_f64: window length must be in 2..T");
+  if (split < 1 || split >= m) return fail(-5, "hmv_surrogate_shift_f64: split must be in 1..m-1");
+  if (n_surr < 1) return fail(-6, "hmv_surrogate_shift_f64: surrogate count must be >= 1");
+  if (n_win < 0 || n_rec < 1) return fail(-4, "hmv_surrogate_shift_f64: bad window / recording count");
+  if (n_win == 0) return 0;
+  if (!x || !item_rec || !item_start || !shift || !out) return fail(-4, "hmv_surrogate_shift_f64: null pointer");
+  return hmv::launch_surrogate_shift(x, rec_stride, ld, T, reinterpret_cast<const long long*>(item_rec),
+                                     reinterpret_cast<const long long*>(item_start), n_win,
+                                     reinterpret_cast<const long long*>(shift), n_rec, n_surr, m, n, split, out, S(stream));
+}
+
+int hmv_surrogate_phase_c128(const double* spec, int64_t n_win, const double* phi, int n_surr, int m, int n, double* out,
+                             void* stream) {
+  if (m < 1 || m > HMV_MAX_CHANNELS) return fail(-1, "hmv_surrogate_phase_c128: channel count must be in 1..64");
+  if (n < 2) return fail(-3, "hmv_surrogate_phase_c128: window length must be >= 2");
+  if (n_surr < 1) return fail(-6, "hmv_surrogate_phase_c128: surrogate count must be >= 1");
+  if (n_win < 0) return fail(-4, "hmv_surrogate_phase_c128: bad window count");
+  if (n_win == 0) return 0;
+  if (!spec || !phi || !out) return fail(-4, "hmv_surrogate_phase_c128: null pointer");
+  return hmv::launch_surrogate_phase(spec, n_win, phi, n_surr, m, n, out, S(stream));
+}
+
+int hmv_null_accumulate_f64(const double* observed, const double* surr, const uint8_t* surr_bad, const uint8_t* tested,
+                            int64_t n_win, int n_surr, int m, int n_bands, double* M, int32_t* n_valid, int32_t* count,
+                            int32_t* count_fwe, int32_t* n_cell, double* mean, double* m2, double* p, double* p_fwe,
+                            double* null_mean, double* null_std, void* stream) {
+  if (m < 1 || m > HMV_MAX_CHANNELS) return fail(-1, "hmv_null_accumulate_f64: channel count must be in 1..64");
+  if (n_bands < 1) return fail(-2, "hmv_null_accumulate_f64: band count must be >= 1");
+  if (n_surr < 1) return fail(-6, "hmv_null_accumulate_f64: surrogate count must be >= 1");
+  if (n_win < 0) return fail(-4, "hmv_null_accumulate_f64: bad window count");
+  const int fin = (p != nullptr) + (p_fwe != nullptr) + (null_mean != nullptr) + (null_std != nullptr);
+  if (fin != 0 && fin != 4) return fail(-7, "hmv_null_accumulate_f64: p, p_fwe, null_mean and null_std go together");
+  if (n_win == 0) return 0;
+  if (!observed || !surr || !surr_bad || !tested || !M || !n_valid || !count || !count_fwe || !n_cell || !mean || !m2)
+    return fail(-4, "hmv_null_accumulate_f64: null pointer");
+  hmv::NullAccArgs a{};
+  a.obs = observed; a.surr = surr; a.bad = surr_bad; a.tested = tested;
+  a.n_win = n_win; a.n_surr = n_surr; a.m = m; a.nb = n_bands;
+  a.M = M; a.n_valid = n_valid; a.cnt = count; a.cnt_fwe = count_fwe; a.n_cell = n_cell; a.mean = mean; a.m2 = m2;
+  a.p = p; a.p_fwe = p_fwe; a.null_mean = null_mean; a.null_std = null_std;
+  return hmv::launch_null_accumulate(a, S(stream));
+}
+
 }  // extern "C"

@@ -191,4 +191,25 @@ struct FadArgs {
 };
 int launch_fad(const FadArgs& a, hipStream_t st);
 
+// ---- surrogate significance (surrogate.hip) ---------------------------------------------------------------------
+int launch_surrogate_shift(const double* x, long long rec_stride, long long ld, long long T, const long long* item_rec,
+                           const long long* item_start, long long n_win, const long long* shift, long long n_rec, int n_surr,
+                           int m, int n, int split, double* out, hipStream_t st);
+int launch_surrogate_phase(const double* spec, long long n_win, const double* phi, int n_surr, int m, int n, double* out,
+                           hipStream_t st);
+struct NullAccArgs {
+  const double* obs;          // [n_win][m][m][nb]
+  const double* surr;         // [n_surr][n_win][m][m][nb]
+  const unsigned char* bad;   // [n_surr][n_win]: the surrogate's fit failed
+  const unsigned char* tested;  // [m][m]
+  long long n_win;
+  int n_surr, m, nb;
+  double* M;                  // [n_surr][n_win][nb] out
+  int* n_valid;               // [n_win]            running state
+  int* cnt, *cnt_fwe, *n_cell;  // [n_win][m][m][nb]  running state
+  double* mean, *m2;          // [n_win][m][m][nb]  running state
+  double* p, *p_fwe, *null_mean, *null_std;   // [n_win][m][m][nb] out, optional (all or none)
+};
+int launch_null_accumulate(const NullAccArgs& a, hipStream_t st);
+
 }  // namespace hmv

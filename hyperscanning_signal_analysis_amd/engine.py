@@ -573,6 +573,166 @@ class Engine:
                 self.raise_on_info(info_tf, "mvar_transfer_function (inverse of A(f))", per_item=F)
         return finish(out, ar, V, infos)
 
+    # ------------------------------------------------------------------ surrogate significance (surrogate.hip)
+    def surrogate_shift(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, shift: torch.Tensor,
+                        split: int, out: torch.Tensor | None = None):
+        """Shift surrogates of a block (`hmv_surrogate_shift_f64`): x (n_rec, m, T), shift int64 (S_blk, n_rec) ->
+        (S_blk * W, m, n), item s * W + w = window w with the channels >= split circularly shifted by shift[s, rec]."""
+        n_rec, m, T = x.shape
+        x = x if x.stride(2) == 1 else x.contiguous()
+        Sb, W = int(shift.shape[0]), int(item_rec.numel())
+        out = self.empty(Sb * W, m, int(n)) if out is None else out
+        with torch.cuda.device(self.device):
+            rc = self.lib.hmv_surrogate_shift_f64(x.data_ptr(), x.stride(0), x.stride(1), T, item_rec.data_ptr(),
+                                                  item_start.data_ptr(), W, shift.data_ptr(), n_rec, Sb, m, int(n), int(split),
+                                                  out.data_ptr(), self.stream())
+        _lib.check(rc, "hmv_surrogate_shift_f64")
+        return out
+
+    def window_spectra(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int):
+        """rfft of every window, raw samples as K1 reads them: (W, m, n // 2 + 1) complex128 (one batched transform)."""
+        win = x.unfold(2, int(n), 1)[item_rec, :, item_start]            # (W, m, n): the windows only, not the recordings
+        return torch.fft.rfft(win, dim=-1)
+
+    def surrogate_phase_spectra(self, spec: torch.Tensor, phi: torch.Tensor, n: int):
+        """spec (W, m, nf) complex128, phi (S_blk, m, nf) -> (S_blk * W, m, nf) complex128 (`hmv_surrogate_phase_c128`)."""
+        W, m, nf = spec.shape
+        Sb = int(phi.shape[0])
+        sr = torch.view_as_real(spec.contiguous())
+        out = self.empty(Sb * W, m, nf, 2)
+        with torch.cuda.device(self.device):
+            rc = self.lib.hmv_surrogate_phase_c128(sr.data_ptr(), W, phi.data_ptr(), Sb, m, int(n), out.data_ptr(),
+                                                   self.stream())
+        _lib.check(rc, "hmv_surrogate_phase_c128")
+        return torch.view_as_complex(out)
+
+    def surrogate_phase(self, spec: torch.Tensor, phi: torch.Tensor, n: int):
+        """Phase surrogates of a block: irfft(rfft(window) exp(i phi[s]), n) -> (S_blk * W, m, n), item s * W + w.  The
+        inverse transform runs on the whole block at once: rocFFT's result for one transform does not depend on the
+        batch it is planned with (measured on the MI355X), so neither do the surrogates' bits."""
+        return torch.fft.irfft(self.surrogate_phase_spectra(spec, phi, n), n=int(n), dim=-1)
+
+    def null_accumulate(self, observed, surr, bad, tested, state, finalize: bool, n_surr: int):
+        """One block of surrogates (`hmv_null_accumulate_f64`): observed (W, m, m, nb), surr (n_surr * W, m, m, nb), bad
+        (n_surr * W,) bool, tested (m, m) uint8; `state` is the running dict of `null_state`, updated in place.
+        finalize: also write state["p"], ["p_fwe"], ["null_mean"], ["null_std"]."""
+        W, m, _, nb = observed.shape
+        bad8 = bad.to(torch.uint8).contiguous()
+        M = self.empty(n_surr * W, nb)
+        fin = [state[k].data_ptr() for k in ("p", "p_fwe", "null_mean", "null_std")] if finalize else [0] * 4
+        with torch.cuda.device(self.device):
+            rc = self.lib.hmv_null_accumulate_f64(
+                observed.data_ptr(), surr.data_ptr(), bad8.data_ptr(), tested.data_ptr(), W, int(n_surr), m, nb, M.data_ptr(),
+                state["n_valid"].data_ptr(), state["count"].data_ptr(), state["count_fwe"].data_ptr(),
+                state["n_cell"].data_ptr(), state["mean"].data_ptr(), state["m2"].data_ptr(), *fin, self.stream())
+        _lib.check(rc, "hmv_null_accumulate_f64")
+        return M
+
+    def null_state(self, W: int, m: int, nb: int):
+        z = dict(dtype=torch.int32, device=self.device)
+        st = {"n_valid": torch.zeros(W, **z), "count": torch.zeros(W, m, m, nb, **z), "count_fwe": torch.zeros(W, m, m, nb, **z),
+              "n_cell": torch.zeros(W, m, m, nb, **z)}
+        for k in ("mean", "m2"):
+            st[k] = torch.zeros(W, m, m, nb, dtype=torch.float64, device=self.device)
+        for k in ("p", "p_fwe", "null_mean", "null_std"):
+            st[k] = self.empty(W, m, m, nb)
+        return st
+
+    def significance_chunk(self, measure: str, null: str, W: int, m: int, n: int, p: int, F: int, nb: int) -> int:
+        """Items (surrogate x window) per block: `max_workspace_bytes` over what one item needs -- the measure's
+        workspace, the item buffer (m n doubles; the phase null also its spectrum) and the surrogate's band values."""
+        wsf = {"ffdtf": None, "ddtf": self.lib.hmv_sliding_ddtf_workspace_bytes,
+               "gpdc": self.lib.hmv_sliding_gpdc_workspace_bytes}[measure]
+        ws = int(self.lib.hmv_sliding_bands_workspace_bytes(1, m, p, F)) if wsf is None else int(wsf(1, m, p, F, nb))
+        per_item = ws + 8 * m * n + 8 * m * m * nb + 8 * nb + 1
+        if null == "phase":
+            per_item += 16 * m * (n // 2 + 1)
+        return max(1, self.max_workspace_bytes // per_item)
+
+    def sliding_significance(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, p: int, freqs,
+                             fs: float, bands, *, measure: str, null: str, n_surrogates: int, seed, split=None,
+                             min_shift=None, check=True, chunk: int | None = None, grid=None):
+        """Surrogate test of the band values of `sliding_<measure>(..., bands=bands)` for every window.
+
+        null="shift": surrogate s of window (r, w) keeps the channels < split and reads the channels >= split circularly
+        shifted by d[s, r] (the second participant against the first); tests the pairs with exactly one index < split.
+        null="phase": every channel of the window with the phases of its rfft replaced (Kaminski et al. 2001); tests i != j.
+        The draws are `surrogates.shift_offsets` / `phase_draws` from numpy.random.default_rng(seed).  Per tested cell,
+        over the n_valid surrogates whose fit succeeded: p = (1 + #{T_s >= T_obs}) / (1 + n_valid), p_fwe the same with
+        the maximum over the tested pairs, null_mean and null_std (ddof 1, Welford in surrogate order); untested cells NaN.
+        check: True raises LinAlgError for a failed observed window, "nan" gives NaN statistics for it.  chunk: items
+        (surrogate x window) per block (default: `significance_chunk`); the results are the same bits for any chunk.
+        grid: (hop, first, n_win) for the OBSERVED call only (`sliding_ffdtf(grid=...)`); the surrogates are separate
+        recordings.  Returns a dict of device tensors: observed, p, p_fwe, null_mean, null_std (W, m, m, n_bands),
+        n_valid (W,) int32, tested (m, m) bool."""
+        from . import surrogates as sg
+        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
+        x = x if x.stride(2) == 1 else x.contiguous()
+        n_rec, m, T = x.shape
+        n = int(n)
+        S, split, min_shift = sg.significance_args(measure, null, n_surrogates, m, T, n, split, min_shift)
+        if check is not True and check != "nan":
+            raise ValueError(f"check must be True or 'nan', got {check!r}")
+        self.pad(m)
+        self.check_items(x, item_rec, item_start, n, p)
+        W = int(item_rec.numel())
+        f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
+        F = int(f.numel())
+        lo, hi = (np.asarray(b, dtype=np.int32) for b in bands)
+        nb = int(lo.size)
+        if nb < 1:
+            raise ValueError("sliding_significance needs at least one band")
+        self.band_tables(lo, hi, F)
+        tested_h = sg.tested_mask(m, null, split)
+        tested = torch.as_tensor(tested_h.astype(np.uint8)).to(self.device)
+        run = {"ffdtf": self.sliding_ffdtf, "ddtf": self.sliding_ddtf, "gpdc": self.sliding_gpdc}[measure]
+        res = {"tested": torch.as_tensor(tested_h).to(self.device)}
+        if W == 0:
+            for k in ("observed", "p", "p_fwe", "null_mean", "null_std"):
+                res[k] = self.empty(0, m, m, nb)
+            res["n_valid"] = self.empty(0, dtype=torch.int32)
+            return res
+        if check is True:
+            obs = run(x, item_rec, item_start, n, p, f, fs, bands=(lo, hi), check=True, grid=grid)
+            obs_bad = None
+        else:
+            obs, obs_bad = run(x, item_rec, item_start, n, p, f, fs, bands=(lo, hi), check="mask", grid=grid)
+        rng = np.random.default_rng(seed)
+        if null == "shift":
+            d_all = torch.as_tensor(sg.shift_offsets(rng, S, n_rec, T, min_shift)).to(self.device)
+        else:
+            spec = self.window_spectra(x, item_rec, item_start, n)
+        chunk = self.significance_chunk(measure, null, W, m, n, p, F, nb) if chunk is None else max(1, int(chunk))
+        Wb = min(W, chunk)
+        Sb = min(S, max(1, chunk // W)) if Wb == W else 1
+        st = self.null_state(W, m, nb)
+        zeros = None
+        for s0 in range(0, S, Sb):
+            sb = min(Sb, S - s0)
+            if null == "phase":
+                phi = torch.as_tensor(sg.phase_draws(rng, sb, m, n)).to(self.device)
+            for w0 in range(0, W, Wb):
+                wb = min(Wb, W - w0)
+                ws = slice(w0, w0 + wb)
+                if null == "shift":
+                    xs = self.surrogate_shift(x, item_rec[ws], item_start[ws], n, d_all[s0:s0 + sb], split)
+                else:
+                    xs = self.surrogate_phase(spec[ws], phi, n)
+                items = sb * wb
+                if zeros is None or zeros.numel() < items:
+                    zeros = torch.zeros(items, dtype=torch.int64, device=self.device)
+                    ar_items = torch.arange(items, dtype=torch.int64, device=self.device)
+                vals, bad = run(xs.view(items, m, n), ar_items[:items], zeros[:items], n, p, f, fs, bands=(lo, hi),
+                                check="mask", validate=False)
+                sub = {k: v[ws] for k, v in st.items()}               # window-major: contiguous views
+                self.null_accumulate(obs[ws], vals, bad, tested, sub, s0 + sb >= S, sb)
+        res.update(observed=obs, p=st["p"], p_fwe=st["p_fwe"], null_mean=st["null_mean"], null_std=st["null_std"],
+                   n_valid=st["n_valid"])
+        if obs_bad is not None and bool(obs_bad.any()):
+            for k in ("observed", "p", "p_fwe", "null_mean", "null_std"):
+                res[k][obs_bad] = float("nan")
+        return res
+
     # ------------------------------------------------------------------ recordings streamed from the host
     def stream_dyads(self, dyads, n: int, positions, p: int, freqs, fs: float, bands=None, reduce=None, depth: int = 3,
                      check="nan", keep_full=None, timeline=None, out=None):

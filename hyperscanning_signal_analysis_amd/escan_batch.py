@@ -175,7 +175,7 @@ def savez_fast(path, compresslevel=0, **arrays):
 def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, freqs=None, bands=hdist.DEFAULT_BANDS,
         low_cutoff_hz=None, high_cutoff_hz=None, channel_subset=None, with_psd=False, psd_fmin=1.0, psd_fmax=30.0,
         psd_bandwidth=2.0, save_full=False, skip_existing=True, reader=None, engine=None, world=1, rank=0,
-        verbose=True, prefetch=2, timing=None, save_workers=4, compresslevel=0, measures=("ffdtf",)):
+        verbose=True, prefetch=2, timing=None, save_workers=4, compresslevel=0, measures=("ffdtf",), significance=None):
     """Process every dyad under <root>/EEG.  Per dyad one `<out_dir>/<dyad>_ffdtf.npz` with, per segment `<task>/<event>`:
         <seg>/ffdtf_bands   (windows, n, n, n_bands)   band-integrated ffDTF of every window
         <seg>/ffdtf         (windows, n, n, F)         only with save_full=True (8.4 MB per window at 64 channels)
@@ -183,7 +183,13 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
         <seg>/psd, <seg>/psd_freqs                     multitaper PSD of the segment block (with_psd=True)
         <seg>/ddtf_bands, <seg>/gpdc_bands (and <seg>/ddtf, <seg>/gpdc with save_full=True)
                                                        with measures=(..., "ddtf", "gpdc"): dDTF / GPDC of the same windows
-      plus `channels`, `freqs`, `meta` (JSON, its `measures` field lists what was computed).  Returns {"done": [...], "skipped": [...], "failed": [(dyad, error)],
+        <seg>/<measure>_bands_p, _p_fwe, _null_mean, _null_std   (windows, n, n, n_bands)
+        <seg>/<measure>_bands_n_valid                           (windows,)
+                                                       with significance=dict(null=..., n_surrogates=..., seed=...,
+                                                       min_shift=None): the surrogate test of every computed measure
+                                                       (`Engine.sliding_significance`; split = the child's channel count,
+                                                       the same seed for every segment)
+      plus `channels`, `freqs`, `meta` (JSON, its `measures` field lists what was computed, `significance` the test).  Returns {"done": [...], "skipped": [...], "failed": [(dyad, error)],
       "timing": {...}}.
     A window whose fit is singular is NaN-filled, not fatal (the reference would raise and lose the dyad); a segment that
     cannot be processed is logged in the dyad's meta and does not discard the dyad's other segments.
@@ -197,6 +203,9 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
     unknown = [m_ for m_ in measures if m_ not in MEASURES]
     if unknown or "ffdtf" not in measures or len(set(measures)) != len(measures):
         raise ValueError(f"measures must list 'ffdtf' and any of {MEASURES[1:]} once each, got {measures}")
+    if significance is not None:
+        from .surrogates import check_significance_dict
+        significance = check_significance_dict(significance)
     eng = engine or default_engine()
     reader = reader or xarray_reader
     out_dir = Path(out_dir)
@@ -242,6 +251,8 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                 result, meta = {}, {"dyad": dyad, "segments": [], "failed_segments": [], "model_order": int(model_order),
                                     "window_s": window_s, "overlap": overlap, "measures": list(measures),
                                     "created": time.strftime("%Y-%m-%dT%H:%M:%S")}
+                if significance is not None:
+                    meta["significance"] = dict(significance)
                 names_out, freqs_out = None, None
                 tg = time.perf_counter()
                 pending = []                                       # device results of this dyad, fetched after the last launch
@@ -290,6 +301,16 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                                                      bands=(lo, hi))
                             red_m.masked_fill_(bad_m.view(-1, 1, 1, 1), float("nan"))
                             extra[f"{meas}_bands"] = red_m
+                        if significance is not None:             # the child block comes first (segment_block)
+                            split = sum(1 for nm in seg["names"] if nm.endswith("_ch"))
+                            for meas in measures:
+                                sig = eng.sliding_significance(xd, rec_i, st_i, W, int(model_order), f, fs, (lo, hi),
+                                                               measure=meas, null=significance["null"],
+                                                               n_surrogates=significance["n_surrogates"],
+                                                               seed=significance["seed"], split=split,
+                                                               min_shift=significance["min_shift"], check="nan", grid=grid_w)
+                                for k_ in ("p", "p_fwe", "null_mean", "null_std", "n_valid"):
+                                    extra[f"{meas}_bands_{k_}"] = sig[k_]
                         pending.append((seg, key, pos, W, f, bsum, ff if save_full else None, bad, psd_dev, pf if with_psd else None,
                                         extra))
                     except Exception as e:                         # one bad segment does not discard the dyad

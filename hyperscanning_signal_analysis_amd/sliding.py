@@ -6,6 +6,7 @@
 optimal_model_order=p)` (/root/reference/src/mtmvar.py:237-284) on every window of every recording.
 `sliding_ddtf` / `sliding_gpdc` are `direct_dtf` (mtmvar.py:341-385) / `gen_partial_directed_coherence`
 (mtmvar.py:388-468) with `optimal_model_order=p` on every window, in the same batched form.
+`sliding_significance` adds a surrogate test (shift or phase null) to the band values of any of the three.
 `sliding_fad` is `fad_decomposition` (mtmvar.py:607-757) of every channel of every window.
 """
 from __future__ import annotations
@@ -16,7 +17,8 @@ import torch
 from .engine import Engine, default_engine
 
 __all__ = ["window_positions", "hop_positions", "create_windows", "sliding_ffdtf", "sliding_ffdtf_device", "window_items",
-           "regular_grid", "sliding_ddtf", "sliding_ddtf_device", "sliding_gpdc", "sliding_gpdc_device", "sliding_fad"]
+           "regular_grid", "sliding_ddtf", "sliding_ddtf_device", "sliding_gpdc", "sliding_gpdc_device", "sliding_fad",
+           "sliding_significance"]
 
 
 def window_positions(T: int, n_windows: int = 3, window_size=None):
@@ -170,6 +172,41 @@ def sliding_gpdc(x, window_size, n_windows, p, freqs, fs, engine: Engine | None 
     """NumPy (or tensor) in / NumPy out: `gen_partial_directed_coherence(window, freqs, fs, optimal_model_order=p)`
     (mtmvar.py:388-468) of every window, shaped as `sliding_ddtf`."""
     return _sliding_conn_host(sliding_gpdc_device, x, window_size, n_windows, p, freqs, fs, engine, hop, bands, check)
+
+
+def sliding_significance(x, window_size, n_windows, p, freqs, fs, bands, *, measure, null, n_surrogates, seed, split=None,
+                         min_shift=None, check=True, chunk=None, hop=None, share_overlap: bool = True,
+                         engine: Engine | None = None):
+    """NumPy (or tensor) in / NumPy out: the surrogate test of `Engine.sliding_significance` for the band values
+    `sliding_<measure>(x, window_size, n_windows, p, freqs, fs, hop=hop, bands=bands)` of every window.
+    x: (m, T) or (n_rec, m, T); bands = (bin_lo, bin_hi) from `distributed.band_bins`.  Returns a dict: observed, p,
+    p_fwe, null_mean, null_std shaped like `sliding_ddtf` with bands -- (n_windows, m, m, n_bands) or (n_rec, n_windows,
+    ...) --, n_valid (n_windows,) or (n_rec, n_windows), tested (m, m).  The arguments are checked before the GPU is
+    touched (`surrogates.significance_args`)."""
+    from . import surrogates as sg
+    single = np.ndim(x) == 2
+    shape = tuple(np.shape(x))
+    n_rec, m, T = (1,) + shape if single else shape
+    positions, w = _positions(T, window_size, n_windows, hop)
+    sg.significance_args(measure, null, n_surrogates, m, T, w, split, min_shift)
+    eng = engine or default_engine()
+    if isinstance(x, torch.Tensor):
+        xd = (x[None] if single else x).to(device=eng.device, dtype=torch.float64).contiguous()
+    else:
+        xd = eng.to_device(np.asarray(x, dtype=np.float64)[None] if single else np.asarray(x, dtype=np.float64))
+    item_rec, item_start = window_items(n_rec, positions, eng.device)
+    grid = regular_grid(positions, w, p) if share_overlap else None
+    res = eng.sliding_significance(xd, item_rec, item_start, w, p, freqs, fs, bands, measure=measure, null=null,
+                                   n_surrogates=n_surrogates, seed=seed, split=split, min_shift=min_shift, check=check,
+                                   chunk=chunk, grid=grid)
+    nw = len(positions)
+    out = {"tested": res["tested"].cpu().numpy()}
+    for k, v in res.items():
+        if k == "tested":
+            continue
+        a = v.cpu().numpy().reshape((n_rec, nw) + tuple(v.shape[1:]))
+        out[k] = a[0] if single else a
+    return out
 
 
 def sliding_fad(signals, fs, window_size=None, n_windows=3, hop=None, model_order=None, max_model_order=20,

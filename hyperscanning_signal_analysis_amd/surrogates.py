@@ -1,0 +1,98 @@
+"""Host side of the surrogate significance tests (`Engine.sliding_significance`): argument checks, the random draws and
+the tested family.  Pure NumPy, so that every surrogate can be rebuilt on the host from the seed.
+
+All randomness comes from `rng = numpy.random.default_rng(seed)`, in this order:
+    null="shift":  d = rng.integers(min_shift, T - min_shift, size=(S, n_rec), endpoint=True)        (once)
+    null="phase":  phi = 2 pi rng.random((S, m, n // 2 + 1)), phi[..., 0] = 0, phi[..., n // 2] = 0 for even n
+                   (drawn in consecutive surrogate blocks: one double per draw, so the stream is the same)
+"""
+from __future__ import annotations
+
+import numpy as np
+
+__all__ = ["NULLS", "MEASURES", "significance_args", "shift_offsets", "phase_draws", "tested_mask",
+           "check_significance_dict"]
+
+NULLS = ("shift", "phase")
+MEASURES = ("ffdtf", "ddtf", "gpdc")
+
+
+def _int(v, name):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+        raise ValueError(f"{name} must be an integer, got {v!r}")
+    return int(v)
+
+
+def significance_args(measure, null, n_surrogates, m, T, n, split=None, min_shift=None):
+    """Check the arguments of a significance run BEFORE anything is drawn or launched; returns (S, split, min_shift) with
+    the defaults filled in: split = m // 2 for even m (odd m must pass it; the phase null does not use it), min_shift = n
+    (the window length).  ValueError for an unknown measure or null, S < 1, a split outside 1..m-1 and, under the shift
+    null, T < 2 min_shift."""
+    if measure not in MEASURES:
+        raise ValueError(f"measure must be one of {MEASURES}, got {measure!r}")
+    if null not in NULLS:
+        raise ValueError(f"null must be one of {NULLS}, got {null!r}")
+    S = _int(n_surrogates, "n_surrogates")
+    if S < 1:
+        raise ValueError(f"n_surrogates must be >= 1, got {S}")
+    m, T, n = int(m), int(T), int(n)
+    if split is None:
+        if null == "shift" and m % 2:
+            raise ValueError(f"an odd channel count ({m}) needs an explicit split")
+        split = m // 2
+    else:
+        split = _int(split, "split")
+    if null == "shift" and not 1 <= split <= m - 1:
+        raise ValueError(f"split must be in 1..{m - 1}, got {split}")
+    if null == "phase" and not 0 <= split <= m:
+        raise ValueError(f"split must be in 0..{m}, got {split}")
+    min_shift = n if min_shift is None else _int(min_shift, "min_shift")
+    if min_shift < 0:
+        raise ValueError(f"min_shift must be >= 0, got {min_shift}")
+    if null == "shift" and T < 2 * min_shift:
+        raise ValueError(f"the shift null needs T >= 2 min_shift (T = {T}, min_shift = {min_shift})")
+    return S, split, min_shift
+
+
+def shift_offsets(rng, S: int, n_rec: int, T: int, min_shift: int):
+    """(S, n_rec) int64 circular shifts of the second participant, in [min_shift, T - min_shift]."""
+    return np.asarray(rng.integers(min_shift, T - min_shift, size=(S, n_rec), endpoint=True), dtype=np.int64)
+
+
+def phase_draws(rng, S: int, m: int, n: int):
+    """(S, m, n // 2 + 1) phases of the next S surrogates; 0 at bin 0 and, for even n, at bin n / 2."""
+    phi = 2.0 * np.pi * rng.random((S, m, n // 2 + 1))
+    phi[..., 0] = 0.0
+    if n % 2 == 0:
+        phi[..., n // 2] = 0.0
+    return phi
+
+
+def tested_mask(m: int, null: str, split: int):
+    """(m, m) bool: the pairs a null tests.  shift: exactly one index < split (the inter-brain pairs); phase: i != j."""
+    i, j = np.meshgrid(np.arange(m), np.arange(m), indexing="ij")
+    if null == "shift":
+        return (i < split) != (j < split)
+    return i != j
+
+
+def check_significance_dict(sig):
+    """escan_batch.run(significance=...): dict(null=..., n_surrogates=..., seed=..., min_shift=None), checked before
+    anything is read.  Returns a normalised copy."""
+    if not isinstance(sig, dict):
+        raise ValueError(f"significance must be a dict(null=..., n_surrogates=..., seed=..., min_shift=None), got {sig!r}")
+    allowed = {"null", "n_surrogates", "seed", "min_shift"}
+    extra = sorted(set(sig) - allowed)
+    missing = sorted({"null", "n_surrogates", "seed"} - set(sig))
+    if extra or missing:
+        raise ValueError(f"significance: unknown keys {extra}, missing keys {missing}")
+    if sig["null"] not in NULLS:
+        raise ValueError(f"significance: null must be one of {NULLS}, got {sig['null']!r}")
+    S = _int(sig["n_surrogates"], "significance: n_surrogates")
+    if S < 1:
+        raise ValueError(f"significance: n_surrogates must be >= 1, got {S}")
+    seed = _int(sig["seed"], "significance: seed")
+    ms = sig.get("min_shift")
+    if ms is not None and _int(ms, "significance: min_shift") < 0:
+        raise ValueError(f"significance: min_shift must be >= 0, got {ms}")
+    return {"null": sig["null"], "n_surrogates": S, "seed": seed, "min_shift": None if ms is None else int(ms)}

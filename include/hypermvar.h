@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define HMV_VERSION 140            /* 0.1.4 */
+#define HMV_VERSION 150            /* 0.1.5 */
 #define HMV_MAX_CHANNELS 64
 #define HMV_MAX_ORDER 32
 
@@ -339,6 +339,35 @@ int hmv_fad_decompose_f64(const double* ar, int64_t n_series, int p, double fs, 
                           double* poles, double* C, double* alpha, double* freq, double* beta, double* bandwidth,
                           double* phi, double* B, uint8_t* osc_mask, int32_t* paired, int32_t* n_paired, int32_t* info,
                           void* stream);
+
+/* Surrogate significance of the sliding-window measures (hmv_sliding_ffdtf_bands_f64, hmv_sliding_ddtf_f64,
+ * hmv_sliding_gpdc_f64 with bands).  A block of surrogates x windows is laid out surrogate-major: item
+ * k = s * n_win + w is surrogate s of window w.  The surrogate windows go through the sliding entries as n_items
+ * recordings of n samples (start 0, no grid); their band values come back as surr [n_surr][n_win][m][m][n_bands].
+ * hmv_surrogate_shift_f64: out[k][c][t] = x[rec][c][start + t] for c < split and x[rec][c][(start + t + shift[s][rec])
+ *   mod T] for c >= split (t = 0..n-1; rec = item_rec[w], start = item_start[w]; shift: int64 [n_surr][n_rec]) -- the
+ *   second participant circularly shifted against the first.  out: [n_surr][n_win][m][n].  The windows must lie inside
+ *   their recordings (the caller checks item_rec / item_start as for hmv_lagcov_f64).
+ * hmv_surrogate_phase_c128: out[k][c][f] = spec[w][c][f] exp(i phi[s][c][f]), except bins f = 0 and (even n) f = n/2,
+ *   which are copied.  spec: complex128 [n_win][m][n/2+1], the rfft of every window; phi: [n_surr][m][n/2+1]; out:
+ *   complex128 [n_surr][n_win][m][n/2+1] (the inverse rfft gives the phase-randomised windows).
+ * hmv_null_accumulate_f64: per cell (w, i, j, b) of the tested pairs (tested: uint8 [m][m]), walks the block's
+ *   surrogates in order, skips those whose fit failed (surr_bad: uint8 [n_surr][n_win]) and NaN values, and updates
+ *   the running state: n_valid int32 [n_win], count / count_fwe / n_cell int32 and mean / m2 [n_win][m][m][n_bands]
+ *   (zero before the first block).  count: surrogate values >= observed; count_fwe: surrogates whose maximum over the
+ *   tested pairs (M [n_surr][n_win][n_bands], written) is >= observed; mean / m2: Welford in surrogate order.  No
+ *   atomics: the result does not depend on how the surrogates are split into blocks.  p, p_fwe, null_mean, null_std
+ *   (optional, all or none, [n_win][m][m][n_bands]): (1 + count) / (1 + n_valid), (1 + count_fwe) / (1 + n_valid), mean
+ *   and sqrt(m2 / (n_cell - 1)) after this block; NaN on untested cells. */
+int hmv_surrogate_shift_f64(const double* x, int64_t rec_stride, int64_t ld, int64_t T, const int64_t* item_rec,
+                            const int64_t* item_start, int64_t n_win, const int64_t* shift, int64_t n_rec, int n_surr, int m,
+                            int n, int split, double* out, void* stream);
+int hmv_surrogate_phase_c128(const double* spec, int64_t n_win, const double* phi, int n_surr, int m, int n, double* out,
+                             void* stream);
+int hmv_null_accumulate_f64(const double* observed, const double* surr, const uint8_t* surr_bad, const uint8_t* tested,
+                            int64_t n_win, int n_surr, int m, int n_bands, double* M, int32_t* n_valid, int32_t* count,
+                            int32_t* count_fwe, int32_t* n_cell, double* mean, double* m2, double* p, double* p_fwe,
+                            double* null_mean, double* null_std, void* stream);
 
 #ifdef __cplusplus
 }
