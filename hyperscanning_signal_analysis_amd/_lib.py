@@ -81,6 +81,12 @@ SIGNATURES = {
                                      c_int, c_double, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p,
                                      c_void_p]),
+    "hmv_yw_solve_auto_f64": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int] + [c_void_p] * 7 + [c_int64, c_void_p]),
+    "hmv_sliding_auto_workspace_bytes": (c_int64, [c_int, c_int64, c_int, c_int, c_int, c_int]),
+    "hmv_sliding_auto_f64": (c_int, [c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
+                                     c_int, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int] +
+                             [c_void_p] * 8 + [c_int64, c_int64, c_double, c_int64, c_int64, c_int64, c_int64, c_int64,
+                                               c_void_p, c_void_p]),
     "hmv_fad_workspace_bytes": (c_int64, [c_int64, c_int]),
     "hmv_fad_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int,
                             c_double, c_double, c_int] + [c_void_p] * 17),
@@ -96,6 +102,11 @@ FLAG_UNFUSED_NORM = 1
 FLAG_YW_TILED = 2
 FLAG_YW_ONE_LAUNCH = 4
 FLAG_DIRECT_LAGCOV = 8
+# measures of hmv_sliding_auto_f64 and the criterion numbering it shares with hmv_fad_f64
+MEASURE_FFDTF = 0
+MEASURE_DDTF = 1
+MEASURE_GPDC = 2
+CRITERIA = {"AIC": 0, "HQ": 1, "SC": 2}
 # hmv_set_tuning keys
 TUNE_NORM_LAG = 1
 TUNE_LAG_GROUP = 2

@@ -3,6 +3,7 @@
 #include "hmv_kernels.h"
 
 #include <atomic>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -121,10 +122,36 @@ int hmv_yw_solve_f64(const double* R, int64_t n_items, int m, int p, double* ws,
   if (mp < 0) return fail(-1, "hmv_yw_solve_f64: channel count must be in 1..64");
   if (p < 1 || p > HMV_MAX_ORDER) return fail(-2, "hmv_yw_solve_f64: model order must be in 1..32");
   if (!R || !ws || !ar || !V || !info || n_items < 0) return fail(-4, "hmv_yw_solve_f64: null pointer");
-  hmv::YwArgs a;
+  hmv::YwArgs a{};
   a.R = R; a.n_items = n_items; a.m = m; a.p = p; a.ws = ws; a.ar = ar; a.V = V;
   a.Vq_logdet = vq_logdet; a.info = info; a.tiled = (flags & HMV_FLAG_YW_TILED) ? 1 : ((flags & HMV_FLAG_YW_ONE_LAUNCH) ? 0 : -1);
   return hmv::launch_yw(a, mp, S(stream));
+}
+
+namespace {
+// c of the criterion's penalty c q m^2 / n (mtmvar.py:580-587); crit as in hmv_fad_f64: 0 AIC, 1 HQ, 2 SC
+double crit_factor(int crit, int n) {
+  return crit == 0 ? 2.0 : (crit == 1 ? 2.0 * log(log((double)n)) : log((double)n));
+}
+}  // namespace
+
+int hmv_yw_solve_auto_f64(const double* R, int64_t n_items, int m, int pmax, int n, int crit, double* ws, double* ar,
+                          double* V, int32_t* order_out, double* crit_out, double* vq_logdet, int32_t* info, int64_t flags,
+                          void* stream) {
+  const int mp = pad_of(m);
+  if (mp < 0) return fail(-1, "hmv_yw_solve_auto_f64: channel count must be in 1..64");
+  if (pmax < 1 || pmax > HMV_MAX_ORDER) return fail(-2, "hmv_yw_solve_auto_f64: largest model order must be in 1..32");
+  if (n <= pmax) return fail(-3, "hmv_yw_solve_auto_f64: window shorter than the largest model order");
+  if (crit < 0 || crit > 2) return fail(-5, "hmv_yw_solve_auto_f64: criterion must be 0 (AIC), 1 (HQ) or 2 (SC)");
+  if (flags & (HMV_FLAG_YW_TILED | HMV_FLAG_YW_ONE_LAUNCH))
+    return fail(-6, "hmv_yw_solve_auto_f64: the LDL^T forms of K2 have no automatic order");
+  if (!R || !ws || !ar || !V || !order_out || !info || n_items < 0) return fail(-4, "hmv_yw_solve_auto_f64: null pointer");
+  hmv::YwArgs a{};
+  a.R = R; a.n_items = n_items; a.m = m; a.p = pmax; a.ws = ws; a.ar = ar; a.V = V; a.Vq_logdet = vq_logdet; a.info = info;
+  a.tiled = -1;
+  hmv::YwAutoArgs sel{};
+  sel.n = n; sel.crit_c = crit_factor(crit, n); sel.order_out = order_out; sel.crit_out = crit_out;
+  return hmv::launch_yw_auto(a, sel, mp, S(stream));
 }
 
 int hmv_twiddles_f64(const double* freqs, int F, double fs, int p, double* tw, void* stream) {
@@ -484,7 +511,12 @@ int sliding_impl(const char* who, const double* x, int64_t rec_stride, int64_t l
                  double* ffdtf, double* band_out, const int32_t* bin_lo, const int32_t* bin_hi, int n_bands, double* S_out,
                  double* ar_out, double* V_out, int32_t* info_yw, int32_t* info_tf, void* workspace, int64_t workspace_bytes, int64_t chunk,
                  double pivot_tau, int64_t flags, int64_t grid_hop, int64_t grid_first, int64_t grid_nwin, int64_t grid_T,
-                 void* ev_k3_start, void* ev_k3_stop, void* stream, void* aux_stream, int measure = MEAS_FFDTF) {
+                 void* ev_k3_start, void* ev_k3_stop, void* stream, void* aux_stream, int measure = MEAS_FFDTF,
+                 int crit = -1, int32_t* order_out = nullptr, double* crit_out = nullptr) {
+  // crit >= 0: automatic order (hmv_sliding_auto_f64) -- p is the largest order tried, K1 sums p + 1 lags, K2 selects every
+  // window's order and leaves its coefficients zero-padded to p lags, and every later stage runs at p on those (the
+  // added terms of A(f) = I - sum_k ar_k tw_k are exact zeros)
+  const bool automatic = crit >= 0;
   const bool bands = (band_out != nullptr);
   auto fail = [&](int code, const char* msg) {
     const char* own = strchr(msg, ':');             // messages below are written "hmv_sliding_ffdtf_f64: ..."
@@ -496,7 +528,11 @@ int sliding_impl(const char* who, const double* x, int64_t rec_stride, int64_t l
   if (mp < 0) return fail(-1, "hmv_sliding_ffdtf_f64: channel count must be in 1..64");
   if (p < 1 || p > HMV_MAX_ORDER) return fail(-2, "hmv_sliding_ffdtf_f64: model order must be in 1..32");
   if (n <= p) return fail(-3, "hmv_sliding_ffdtf_f64: window shorter than the model order");
+  if (automatic && crit > 2) return fail(-5, "hmv_sliding_ffdtf_f64: criterion must be 0 (AIC), 1 (HQ) or 2 (SC)");
+  if (automatic && (flags & (HMV_FLAG_YW_TILED | HMV_FLAG_YW_ONE_LAUNCH)))
+    return fail(-6, "hmv_sliding_ffdtf_f64: the LDL^T forms of K2 have no automatic order");
   if (n_items == 0) return 0;                                    // empty batch: nothing to do, nothing to check
+  if (automatic && !order_out) return fail(-4, "hmv_sliding_ffdtf_f64: null pointer / empty grid");
   if (!x || !item_rec || !item_start || !freqs || (!ffdtf && !bands) || !info_yw || (!info_tf && measure != MEAS_GPDC) ||
       !workspace || F < 1 || chunk < 1)
     return fail(-4, "hmv_sliding_ffdtf_f64: null pointer / empty grid");
@@ -558,6 +594,16 @@ int sliding_impl(const char* who, const double* x, int64_t rec_stride, int64_t l
       rc = hmv_lagcov_f64(x, rec_stride, ld, item_rec + i0, item_start + i0, c, m, n, p, R, st0);
     }
     if (rc) break;
+    if (automatic) {
+      hmv::YwArgs ya{};
+      ya.R = R; ya.n_items = c; ya.m = m; ya.p = p; ya.ws = ws; ya.ar = ar_c; ya.V = V_c; ya.info = info_yw + i0;
+      ya.tiled = -1;
+      hmv::YwAutoArgs sel{};
+      sel.n = n; sel.crit_c = crit_factor(crit, n); sel.order_out = order_out + i0;
+      sel.crit_out = crit_out ? crit_out + (size_t)i0 * p : nullptr;
+      rc = hmv::launch_yw_auto(ya, sel, mp, st0);
+      if (rc) break;
+    }
     // the tiled form of K2 (asked for, or chosen for a large 64-channel chunk) as two half-batches
     // K2: the Levinson-Whittle recursion unless an LDL^T form is asked for (or HMV_TUNE_YW_FORM = 1, which picks the
     // LDL^T form by batch shape as before: the launch chain for large 64-channel chunks)
@@ -566,7 +612,7 @@ int sliding_impl(const char* who, const double* x, int64_t rec_stride, int64_t l
     const int64_t yw_flags = (flags & ~(int64_t)(HMV_FLAG_YW_TILED | HMV_FLAG_YW_ONE_LAUNCH)) |
                              (ldl ? (tiled ? HMV_FLAG_YW_TILED : HMV_FLAG_YW_ONE_LAUNCH) : 0);
     const int64_t c0 = (split && tiled && c >= 16) ? (c + 1) / 2 : c, c1 = c - c0;
-    if (c1 > 0) {
+    if (c1 > 0 && !automatic) {
       // fork: st1 may start once K1 is done.  Whatever happens on st1 afterwards, st0 joins it again before this call
       // returns, so that the caller's stream never runs ahead of work this call put on the second stream.
       int hrc = (int)hipEventRecord(fj->fork, st0);
@@ -582,7 +628,7 @@ int sliding_impl(const char* who, const double* x, int64_t rec_stride, int64_t l
       }
       if (rc) break;
     }
-    rc = hmv_yw_solve_f64(R, c0, m, p, ws, ar_c, V_c, nullptr, info_yw + i0, yw_flags, st0);
+    if (!automatic) rc = hmv_yw_solve_f64(R, c0, m, p, ws, ar_c, V_c, nullptr, info_yw + i0, yw_flags, st0);
     if (rc) break;
     const bool last = (ci == n_chunks - 1);
     double* Hc = S_out ? reinterpret_cast<double*>(base + w.off_H) : nullptr;
@@ -714,6 +760,39 @@ int hmv_sliding_gpdc_f64(const double* x, int64_t rec_stride, int64_t ld, const 
                       bands ? nullptr : out, bands ? out : nullptr, bin_lo, bin_hi, n_bands, nullptr, ar_out, V_out, info_yw,
                       nullptr, workspace, workspace_bytes, chunk, 1.0, flags, grid_hop, grid_first, grid_nwin, grid_T,
                       nullptr, nullptr, stream, aux_stream, MEAS_GPDC);
+}
+
+// ---- automatic model order (yw_auto.hip): mvar_criterion (mtmvar.py:551-601) per window inside the fused call -------
+int64_t hmv_sliding_auto_workspace_bytes(int measure, int64_t chunk, int m, int pmax, int F, int n_bands) {
+  const int mp = pad_of(m);
+  // n_bands = -1: the full ffDTF together with S_out (one chunk of H passes through the workspace between K3 and K5)
+  const bool spectra = (n_bands == -1 && measure == HMV_MEASURE_FFDTF);
+  if (mp < 0 || chunk < 1 || pmax < 1 || pmax > HMV_MAX_ORDER || F < 1 || (n_bands < 0 && !spectra) ||
+      measure < HMV_MEASURE_FFDTF || measure > HMV_MEASURE_GPDC)
+    return -1;
+  return (int64_t)sliding_layout(chunk, mp, pmax, F, n_bands > 0, spectra, measure).total;
+}
+
+int hmv_sliding_auto_f64(int measure, const double* x, int64_t rec_stride, int64_t ld, const int64_t* item_rec,
+                         const int64_t* item_start, int64_t n_items, int m, int n, int pmax, int crit, const double* freqs,
+                         int F, double fs, double* out, const int32_t* bin_lo, const int32_t* bin_hi, int n_bands,
+                         double* S_out, double* ar_out, double* V_out, int32_t* order_out, double* crit_out,
+                         int32_t* info_yw, int32_t* info_tf, void* workspace, int64_t workspace_bytes, int64_t chunk,
+                         double pivot_tau, int64_t flags, int64_t grid_hop, int64_t grid_first, int64_t grid_nwin,
+                         int64_t grid_T, void* stream, void* aux_stream) {
+  if (measure < HMV_MEASURE_FFDTF || measure > HMV_MEASURE_GPDC)
+    return fail(-4, "hmv_sliding_auto_f64: measure must be HMV_MEASURE_FFDTF, _DDTF or _GPDC");
+  if (crit < 0 || crit > 2) return fail(-5, "hmv_sliding_auto_f64: criterion must be 0 (AIC), 1 (HQ) or 2 (SC)");
+  if (n_bands < 0) return fail(-4, "hmv_sliding_auto_f64: n_bands must be >= 0");
+  if (S_out && (measure != HMV_MEASURE_FFDTF || n_bands != 0))
+    return fail(-4, "hmv_sliding_auto_f64: spectra come with the full ffDTF only");
+  if (!out && n_items != 0) return fail(-4, "hmv_sliding_auto_f64: null pointer / empty grid");
+  const bool bands = n_bands > 0;
+  return sliding_impl("hmv_sliding_auto_f64", x, rec_stride, ld, item_rec, item_start, n_items, m, n, pmax, freqs, F, fs,
+                      bands ? nullptr : out, bands ? out : nullptr, bin_lo, bin_hi, n_bands, S_out, ar_out, V_out, info_yw,
+                      measure == HMV_MEASURE_GPDC ? nullptr : info_tf, workspace, workspace_bytes, chunk,
+                      measure == HMV_MEASURE_GPDC ? 1.0 : pivot_tau, flags, grid_hop, grid_first, grid_nwin, grid_T, nullptr,
+                      nullptr, stream, aux_stream, measure, crit, order_out, crit_out);
 }
 
 int64_t hmv_fad_workspace_bytes(int64_t n_series, int pmax) {

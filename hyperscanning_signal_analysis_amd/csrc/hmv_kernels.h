@@ -50,11 +50,29 @@ struct YwArgs {
                             // per tile, p + 2 launches;  -1: no form asked for -- the block Levinson-Whittle recursion
                             // (yw_lwr.hip) unless HMV_TUNE_YW_FORM says otherwise
   int only_guarded;         // internal: the one-launch LDL^T kernel re-solves only the windows the recursion flagged
+  // per-window order (one-launch LDL^T kernel only; nullptr: the uniform order p).  Window `item` is solved at order[item]
+  // <= p from the first order[item] + 1 lag blocks of its [p+1]-strided R, in its ws_tiles(p)-strided scratch, and its
+  // [MP][MP][p] coefficients are written with the lags >= order[item] as +0.0.
+  const int* order;
+};
+// automatic model order (yw_auto.hip only; a struct of its own so that the fixed-order kernels' arguments stay as they
+// were): YwArgs::p is the largest order tried, criterion of order q = log det Vf_q + crit_c * q * m^2 / n
+// (crit_c = 2: AIC, 2 log log n: HQ, log n: SC)
+struct YwAutoArgs {
+  int n;                    // window length
+  double crit_c;
+  int* order_out;           // [n_items] selected order, 0 for a failed window
+  double* crit_out;         // optional [n_items][p]
 };
 long long yw_ws_tiles(int p);
 int launch_yw(const YwArgs& a, int m_pad, hipStream_t st);
 int launch_yw_lwr(const YwArgs& a, int m_pad, hipStream_t st);
 int launch_yw_lwr2(const YwArgs& a, int m_pad, hipStream_t st);
+// K2 with on-device order selection: the recursion to order p with criterion, first arg-min and snapshot, then the LDL^T
+// re-solve of the guarded windows at their own orders
+int launch_yw_auto(const YwArgs& a, const YwAutoArgs& s, int m_pad, hipStream_t st);
+// internal: the one-launch LDL^T kernel over the windows flagged in the scratch, at order[item] (yw_solve.hip)
+int launch_yw_guarded(const YwArgs& a, int m_pad, hipStream_t st);
 
 // ---- K3 transfer matrix inverse ---------------------------------------------------------------
 struct TfArgs {

@@ -41,14 +41,14 @@ struct YwPtrs {
   const double* R;
   double *Yt, *Lt, *Dinv, *Zt;
 };
+// p: the order this window is solved at (a.p, or a.order[item] <= a.p); the strides between windows are always a.p's
 template <int MP>
-__device__ __forceinline__ YwPtrs yw_ptrs(const YwArgs& a, long long item) {
+__device__ __forceinline__ YwPtrs yw_ptrs(const YwArgs& a, long long item, int p) {
   constexpr int TILE = MP * MP;
-  const int p = a.p;
-  double* ws = a.ws + (size_t)item * yw_ws_tiles_d(p) * TILE;
+  double* ws = a.ws + (size_t)item * yw_ws_tiles_d(a.p) * TILE;
   const long long ntri = yw_tri(p + 1, 0);
   YwPtrs q;
-  q.R = a.R + (size_t)item * (p + 1) * TILE;
+  q.R = a.R + (size_t)item * (a.p + 1) * TILE;
   q.Yt = ws;
   q.Lt = ws + ntri * TILE;
   q.Dinv = ws + 2 * ntri * TILE;
@@ -100,7 +100,7 @@ __global__ void __launch_bounds__(256, VQ ? 2 : (MODE == 2 ? 4 : 3)) yw_window_k
   double* Xh = buf;                 // [MP][SH]  k-half of the A-operand tile
   double* Yh = buf + MP * SH;       // [MP][SH]  k-half of the B-operand tile (rows = output columns)
   const int wv = uni(threadIdx.x >> 6);
-  const int p = a.p;
+  int p = a.p;
   long long item = blockIdx.x;
   int ta_col = 0;
   if (MODE == 2) {
@@ -115,7 +115,8 @@ __global__ void __launch_bounds__(256, VQ ? 2 : (MODE == 2 ? 4 : 3)) yw_window_k
   if (MODE == 0 && a.only_guarded) {          // re-solve pass behind the Levinson-Whittle recursion: flagged windows only
     if (*yw_guard_ptr(a.ws, item, p, TILE) == 0) return;
   }
-  const YwPtrs q = yw_ptrs<MP>(a, item);
+  if (MODE == 0 && a.order) p = uni(a.order[item]);     // this window's own order (<= a.p); nullptr: the uniform one
+  const YwPtrs q = yw_ptrs<MP>(a, item, p);
   if (threadIdx.x == 0) s_info = 0;
 
   // Lane and thread indices are re-derived from an opaque lane id inside every helper: otherwise the compiler
@@ -370,11 +371,13 @@ __global__ void __launch_bounds__(256, VQ ? 2 : (MODE == 2 ? 4 : 3)) yw_window_k
     __syncthreads();                   // Z[b] is in global memory before row b - 1 reads it
   }
   // ---- ar[item][row][col][k] = Z[k][row][col]  (lag fastest: the reference's (m, m, p) layout)
-  double* ar = a.ar + (size_t)item * TILE * p;
-  const int total = TILE * p;
+  // (rows of a.p lags; with a per-window order the lags >= p are +0.0)
+  const int pa = a.p;
+  double* ar = a.ar + (size_t)item * TILE * pa;
+  const int total = TILE * pa;
   for (int idx = threadIdx.x; idx < total; idx += 256) {
-    const int e = idx / p, k = idx - e * p;
-    ar[idx] = q.Zt[(size_t)k * TILE + e];
+    const int e = idx / pa, k = idx - e * pa;
+    ar[idx] = (k < p) ? q.Zt[(size_t)k * TILE + e] : 0.0;
   }
 }
 
@@ -394,9 +397,27 @@ static int launch_yw_nt(const YwArgs& a, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
+int launch_yw_guarded(const YwArgs& a_in, int m_pad, hipStream_t st) {
+  YwArgs a = a_in;
+  a.only_guarded = 1;
+  a.tiled = 0;
+  a.Vq_logdet = nullptr;
+  if (a.n_items == 0) return 0;
+  const dim3 grid((unsigned)a.n_items), block(256);
+  switch (m_pad) {
+    case 16: hipLaunchKernelGGL((yw_window_kernel<1, false>), grid, block, 0, st, a, 0); break;
+    case 32: hipLaunchKernelGGL((yw_window_kernel<2, false>), grid, block, 0, st, a, 0); break;
+    case 48: hipLaunchKernelGGL((yw_window_kernel<3, false>), grid, block, 0, st, a, 0); break;
+    case 64: hipLaunchKernelGGL((yw_window_kernel<4, false>), grid, block, 0, st, a, 0); break;
+    default: return -1;
+  }
+  return (int)hipGetLastError();
+}
+
 int launch_yw(const YwArgs& a_in, int m_pad, hipStream_t st) {
   YwArgs a = a_in;
   a.only_guarded = 0;
+  a.order = nullptr;                          // (fixed-order entry: one order for the batch)
   if (a.n_items == 0) return 0;
   // No LDL^T form asked for: the block Levinson-Whittle recursion (half the tile products, a quarter of the state), then
   // the one-launch LDL^T over the windows whose tile inverses tripped the conditioning guard (normally none: every other
@@ -431,6 +452,7 @@ int launch_yw(const YwArgs& a_in, int m_pad, hipStream_t st) {
     }
     return (int)hipGetLastError();
   }
+  if (a.order) return -1;                     // a per-window order exists in the one-launch form only
   switch (m_pad) {
     case 16: return launch_yw_nt<1>(a, st);
     case 32: return launch_yw_nt<2>(a, st);

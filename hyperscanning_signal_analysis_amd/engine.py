@@ -63,6 +63,32 @@ def validate_items(x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Te
         raise ValueError(f"windows [start, start + {n}) must lie in [0, {T}), got starts in [{lim[2]}, {lim[3]}]")
 
 
+MAX_ORDER = 32          # HMV_MAX_ORDER of include/hypermvar.h
+
+
+def auto_order_args(max_model_order, crit_type, n):
+    """Arguments of the automatic model order (`p=None`), checked before the GPU is touched: the reference's ValueError
+    for an unknown criterion (mtmvar.py:588-589), the largest order within 1..32, a window longer than it.  Returns
+    (pmax, criterion number of the C ABI)."""
+    if crit_type not in _lib.CRITERIA:
+        raise ValueError("Invalid criterion type. Choose from 'AIC', 'HQ', 'SC'.")
+    if isinstance(max_model_order, bool) or int(max_model_order) != max_model_order:
+        raise ValueError(f"max_model_order must be an integer in 1..{MAX_ORDER}, got {max_model_order!r}")
+    pmax = int(max_model_order)
+    if not 1 <= pmax <= MAX_ORDER:
+        raise ValueError(f"max_model_order must be an integer in 1..{MAX_ORDER}, got {max_model_order!r}")
+    if int(n) <= pmax:
+        raise ValueError(f"window length ({n}) must exceed max_model_order ({pmax})")
+    return pmax, _lib.CRITERIA[crit_type]
+
+
+def no_auto_order(p, where: str):
+    """`p=None` where the automatic order is not offered yet."""
+    if p is None:
+        raise ValueError(f"{where}: the automatic model order (p=None) is not offered here yet; pass an integer p "
+                         "(sliding_ffdtf / sliding_ddtf / sliding_gpdc / sliding_ffdtf_spectra select it per window)")
+
+
 class Engine:
     def __init__(self, device=None, pivot_tau: float | None = None, max_workspace_bytes: int = 24 << 30):
         import os
@@ -184,6 +210,25 @@ class Engine:
                                            _ptr(logdet), info.data_ptr(), int(flags), self.stream())
         _lib.check(rc, "hmv_yw_solve_f64")
         return ar, V, logdet, info
+
+    def yw_solve_auto(self, R: torch.Tensor, m: int, n: int, crit_type: str = "AIC"):
+        """K2 with the order chosen per item (`hmv_yw_solve_auto_f64`): R (items, pmax+1, MP, MP) from K1 at p = pmax, n the
+        window length -> (ar (items, MP, MP, pmax) of the selected order, zero beyond it; V; orders int32, 0 for a failed
+        item; crit (items, pmax), the criterion curve of `mvar_criterion` (mtmvar.py:551-601); info)."""
+        n_items, p1, mp, _ = R.shape
+        pmax, crit = auto_order_args(p1 - 1, crit_type, n)
+        ws = self.empty(max(1, n_items * int(self.lib.hmv_yw_workspace_doubles(m, pmax))))
+        ar = self.empty(n_items, mp, mp, pmax)
+        V = self.empty(n_items, mp, mp)
+        orders = self.empty(n_items, dtype=torch.int32)
+        curve = self.empty(n_items, pmax)
+        info = self.empty(n_items, dtype=torch.int32)
+        with torch.cuda.device(self.device):
+            rc = self.lib.hmv_yw_solve_auto_f64(_ptr(R), n_items, m, pmax, int(n), crit, ws.data_ptr(), _ptr(ar), _ptr(V),
+                                                _ptr(orders), _ptr(curve), 0, _ptr(info), 0, self.stream())
+        if n_items:
+            _lib.check(rc, "hmv_yw_solve_auto_f64")
+        return ar, V, orders, curve, info
 
     # ------------------------------------------------------------------ K3 (+K4/K5 layout kernels)
     def twiddles(self, freqs, fs: float, p: int):
@@ -357,8 +402,15 @@ class Engine:
     def sliding_ffdtf(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, p: int,
                       freqs, fs: float, out: torch.Tensor | None = None, return_ar: bool = False,
                       check: bool = True, chunk: int | None = None, k3_events=None, overlap: bool = True,
-                      flags: int = 0, grid=None, validate: bool = True, bands=None):
+                      flags: int = 0, grid=None, validate: bool = True, bands=None, max_model_order: int = 20,
+                      crit_type: str = "AIC", return_orders: bool = False):
         """ffDTF of every window: x (n_rec, m, T) -> (items, m, m, F).  One C-ABI call (K1->K2->K3->K4).
+
+        p=None: the reference's default, `optimal_model_order=None` -- every window gets the order that
+        `mvar_criterion(window, max_model_order, crit_type)` (mtmvar.py:551-601) picks for it, selected on the device in
+        the same single call (`hmv_sliding_auto_f64`).  `return_orders=True` then appends `orders` (items,) int32, 0 for
+        a failed window, and `crit` (items, max_model_order) to whatever the call returns; `return_ar` gives the
+        coefficients zero-padded to max_model_order lags.  With an integer p these three keywords are not looked at.
 
         check: True raises numpy.linalg.LinAlgError("Singular matrix") if ANY window failed, like the reference's
         np.linalg.solve / inv (the exception names the windows); "nan" returns every window and NaN-fills the
@@ -381,6 +433,9 @@ class Engine:
         same bits as `band_sums(sliding_ffdtf(...))`, which is also what runs when the grid does not suit the kernel
         (`bands_in_kernel`).  `out`, if given, is the band array.
         """
+        if p is None:
+            return self._sliding_auto("ffdtf", x, item_rec, item_start, n, freqs, fs, max_model_order, crit_type, out,
+                                      return_ar, return_orders, check, chunk, overlap, flags, grid, validate, bands)
         assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
         x = x if x.stride(2) == 1 else x.contiguous()
         n_rec, m, T = x.shape
@@ -468,24 +523,32 @@ class Engine:
     def sliding_ddtf(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, p: int, freqs,
                      fs: float, out: torch.Tensor | None = None, return_ar: bool = False, check=True,
                      chunk: int | None = None, overlap: bool = True, flags: int = 0, grid=None, validate: bool = True,
-                     bands=None):
+                     bands=None, max_model_order: int = 20, crit_type: str = "AIC", return_orders: bool = False):
         """dDTF of every window (`direct_dtf`, mtmvar.py:341-385): x (n_rec, m, T) -> (items, m, m, F), or its band sums
         (items, m, m, n_bands) with `bands=(bin_lo, bin_hi)`.  One C-ABI call (`hmv_sliding_ddtf_f64`): K1 -> K2 -> K3's
         fused ffDTF -> |kappa| from W(f) = A^T V^-1 A (sliding_conn.hip).  The keywords mean what they mean for
         `sliding_ffdtf`; a window also fails where its residual covariance is not positive definite (info_yw < 0).
-        Equal to the reference's minors-based dDTF to rounding, not bitwise (no minors, no second inversion)."""
+        Equal to the reference's minors-based dDTF to rounding, not bitwise (no minors, no second inversion).
+        p=None / max_model_order / crit_type / return_orders: the automatic order, as in `sliding_ffdtf`."""
+        if p is None:
+            return self._sliding_auto("ddtf", x, item_rec, item_start, n, freqs, fs, max_model_order, crit_type, out,
+                                      return_ar, return_orders, check, chunk, overlap, flags, grid, validate, bands)
         return self._sliding_conn("ddtf", x, item_rec, item_start, n, p, freqs, fs, out, return_ar, check, chunk, overlap,
                                   flags, grid, validate, bands)
 
     def sliding_gpdc(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, p: int, freqs,
                      fs: float, out: torch.Tensor | None = None, return_ar: bool = False, check=True,
                      chunk: int | None = None, overlap: bool = True, flags: int = 0, grid=None, validate: bool = True,
-                     bands=None):
+                     bands=None, max_model_order: int = 20, crit_type: str = "AIC", return_orders: bool = False):
         """GPDC of every window (`gen_partial_directed_coherence`, mtmvar.py:388-468): x (n_rec, m, T) -> (items, m, m, F),
         or its band sums with `bands=(bin_lo, bin_hi)`.  One C-ABI call (`hmv_sliding_gpdc_f64`): K1 -> K2 -> one kernel
         that builds A(f) on chip; no K3.  The keywords mean what they mean for `sliding_ffdtf`.  Only the Yule-Walker
         failure is reported: A(f) is never inverted, so an exactly singular A(f), on which the reference's
-        mvar_transfer_function raises, goes through (`return_ar` gives (out, ar, V, info_yw))."""
+        mvar_transfer_function raises, goes through (`return_ar` gives (out, ar, V, info_yw)).
+        p=None / max_model_order / crit_type / return_orders: the automatic order, as in `sliding_ffdtf`."""
+        if p is None:
+            return self._sliding_auto("gpdc", x, item_rec, item_start, n, freqs, fs, max_model_order, crit_type, out,
+                                      return_ar, return_orders, check, chunk, overlap, flags, grid, validate, bands)
         return self._sliding_conn("gpdc", x, item_rec, item_start, n, p, freqs, fs, out, return_ar, check, chunk, overlap,
                                   flags, grid, validate, bands)
 
@@ -572,6 +635,115 @@ class Engine:
             if ddtf:
                 self.raise_on_info(info_tf, "mvar_transfer_function (inverse of A(f))", per_item=F)
         return finish(out, ar, V, infos)
+
+    # ------------------------------------------------------------------ automatic model order (yw_auto.hip)
+    def _sliding_auto(self, measure, x, item_rec, item_start, n, freqs, fs, max_model_order, crit_type, out, return_ar,
+                      return_orders, check, chunk, overlap, flags, grid, validate, bands, out_S=None, spectra=False):
+        """`p=None` of sliding_ffdtf / _ddtf / _gpdc / _ffdtf_spectra: one call of `hmv_sliding_auto_f64`.  K1 sums
+        max_model_order + 1 lags, K2 walks every order, keeps the criterion's first arg-min per window and leaves that
+        order's coefficients zero-padded to max_model_order lags; the later stages run at max_model_order on them."""
+        pmax, crit = auto_order_args(max_model_order, crit_type, n)
+        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
+        x = x if x.stride(2) == 1 else x.contiguous()
+        n_rec, m, T = x.shape
+        mp = self.pad(m)
+        code = {"ffdtf": _lib.MEASURE_FFDTF, "ddtf": _lib.MEASURE_DDTF, "gpdc": _lib.MEASURE_GPDC}[measure]
+        gpdc = measure == "gpdc"
+        if validate:
+            self.check_items(x, item_rec, item_start, n, pmax)
+        n_items = int(item_rec.numel())
+        f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
+        F = int(f.numel())
+        nb = 0
+        if bands is not None:
+            b_lo, b_hi = self.band_tables(bands[0], bands[1], F)
+            nb = int(b_lo.numel())
+        last = nb if bands is not None else F
+
+        def finish(res, bad, ar, V, infos, orders, curve, S=None):
+            r = (res,) if S is None else (res, torch.view_as_complex(S))
+            if check == "mask":
+                r += (bad,)
+            if return_ar:
+                r += (ar, V, infos)
+            if return_orders:
+                r += (orders, curve)
+            return r if len(r) > 1 else r[0]
+        if n_items == 0:                      # empty batch (torch gives empty tensors a null data pointer)
+            i32 = self.empty(0, dtype=torch.int32)
+            return finish(self.empty(0, m, m, last), torch.zeros(0, dtype=torch.bool, device=self.device),
+                          self.empty(0, mp, mp, pmax), self.empty(0, mp, mp), i32 if gpdc else (i32, i32), i32,
+                          self.empty(0, pmax), self.empty(0, m, m, F, 2) if spectra else None)
+        full_then_sum = bands is not None and (nb == 0 or (measure == "ffdtf" and (
+            not self.bands_in_kernel(m, F) or (flags & _lib.FLAG_UNFUSED_NORM))))
+        if full_then_sum:                     # the full arrays, then their band sums (as the fixed-order calls do)
+            r = self._sliding_auto(measure, x, item_rec, item_start, n, f, fs, pmax, crit_type, None, True, True, "mask",
+                                   chunk, overlap, flags, grid, validate, None)
+            full, bad, ar, V, infos, orders, curve = r
+            red = self.band_sums(full, bands[0], bands[1])
+            if out is not None:
+                out.copy_(red)
+                red = out
+            self._auto_check(check, red, bad, infos, F, gpdc)
+            return finish(red, bad, ar, V, infos, orders, curve)
+        if out is None:
+            out = self.empty(n_items, m, m, last)
+        assert out.is_contiguous() and tuple(out.shape) == (n_items, m, m, last)
+        S = None
+        if spectra:
+            S = self.empty(n_items, m, m, F, 2) if out_S is None else out_S
+        ws_bands = -1 if spectra else nb
+        if chunk is None:
+            per_item = int(self.lib.hmv_sliding_auto_workspace_bytes(code, 1, m, pmax, F, ws_bands))
+            chunk = max(1, min(n_items, self.max_workspace_bytes // max(per_item, 1)))
+        chunk = int(chunk)
+        nbytes = int(self.lib.hmv_sliding_auto_workspace_bytes(code, chunk, m, pmax, F, ws_bands))
+        if nbytes < 0:
+            raise ValueError(f"sliding_{measure}: bad sizes (m={m}, max_model_order={pmax}, F={F}, chunk={chunk})")
+        ws = self._workspace(nbytes)
+        aux = self.aux_stream().cuda_stream if overlap else 0
+        ar = self.empty(n_items, mp, mp, pmax) if return_ar else None
+        V = self.empty(n_items, mp, mp) if return_ar else None
+        orders = self.empty(n_items, dtype=torch.int32)
+        curve = self.empty(n_items, pmax) if return_orders else None
+        info_yw = self.empty(n_items, dtype=torch.int32)
+        info_tf = None if gpdc else self.empty(n_items * F, dtype=torch.int32)
+        g_hop, g_first, g_nwin = (int(v) for v in grid) if grid is not None else (0, 0, 0)
+        if grid is not None:        # the same contract as sliding_ffdtf(grid=...)
+            if g_nwin < 1 or n_items % g_nwin or g_hop < 1 or n_items // g_nwin > n_rec:
+                raise ValueError("grid = (hop, first, n_win) does not match the number of items / recordings")
+            k = torch.arange(n_items, dtype=torch.int64, device=self.device)
+            same = (not validate) or (torch.equal(item_rec, k // g_nwin) and
+                                      torch.equal(item_start, g_first + (k % g_nwin) * g_hop))
+            if not same:
+                raise ValueError("grid = (hop, first, n_win) contradicts item_rec / item_start "
+                                 "(items must be recording-major, window-minor on the declared grid)")
+        lo_p, hi_p = (b_lo.data_ptr(), b_hi.data_ptr()) if nb else (0, 0)
+        with torch.cuda.device(self.device):
+            rc = self.lib.hmv_sliding_auto_f64(
+                code, x.data_ptr(), x.stride(0), x.stride(1), item_rec.data_ptr(), item_start.data_ptr(), n_items, m, int(n),
+                pmax, crit, f.data_ptr(), F, float(fs), out.data_ptr(), lo_p, hi_p, nb, _ptr(S), _ptr(ar), _ptr(V),
+                orders.data_ptr(), _ptr(curve), info_yw.data_ptr(), _ptr(info_tf), ws.data_ptr(), nbytes, chunk,
+                self.pivot_tau, int(flags), g_hop, g_first, g_nwin, T, self.stream(), aux)
+        _lib.check(rc, "hmv_sliding_auto_f64")
+        bad = info_yw != 0
+        if not gpdc:
+            bad = bad | (info_tf.view(n_items, F) != 0).any(dim=1)
+        infos = info_yw if gpdc else (info_yw, info_tf)
+        self._auto_check(check, out, bad, infos, F, gpdc, S)
+        return finish(out, bad, ar, V, infos, orders, curve, S)
+
+    def _auto_check(self, check, out, bad, infos, F, gpdc, S=None):
+        if check == "nan":
+            if bool(bad.any()):
+                out[bad] = float("nan")
+                if S is not None:
+                    S[bad] = float("nan")
+        elif check and check != "mask":
+            self.raise_on_info(infos if gpdc else infos[0], "ar_coeff (Yule-Walker solve at the automatic order; a negative "
+                                                            "info: residual covariance not positive definite)")
+            if not gpdc:
+                self.raise_on_info(infos[1], "mvar_transfer_function (inverse of A(f))", per_item=F)
 
     # ------------------------------------------------------------------ surrogate significance (surrogate.hip)
     def surrogate_shift(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, shift: torch.Tensor,
@@ -666,6 +838,7 @@ class Engine:
         recordings.  Returns a dict of device tensors: observed, p, p_fwe, null_mean, null_std (W, m, m, n_bands),
         n_valid (W,) int32, tested (m, m) bool."""
         from . import surrogates as sg
+        no_auto_order(p, "sliding_significance")
         assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
         x = x if x.stride(2) == 1 else x.contiguous()
         n_rec, m, T = x.shape
@@ -753,6 +926,7 @@ class Engine:
         bits as the resident path: the arithmetic does not know where its input came from (tests/test_gpu_pipeline.py)."""
         from . import distributed as hdist
         from .sliding import regular_grid, window_items
+        no_auto_order(p, "stream_dyads")
         dev = self.device
         f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
         fhost = f.cpu().numpy()
@@ -895,13 +1069,20 @@ class Engine:
     # ------------------------------------------------------------------ ffDTF + spectra from ONE fit
     def sliding_ffdtf_spectra(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, p: int,
                               freqs, fs: float, chunk: int | None = None, check: bool = True, out_ff=None, out_S=None,
-                              grid=None, flags: int = 0):
+                              grid=None, flags: int = 0, max_model_order: int = 20, crit_type: str = "AIC",
+                              return_orders: bool = False):
         """Both products the reference's orchestrators always compute together (full_freq_dtf + multivariate_spectra,
         /root/reference/src/eeg_alpha_ibi_ffdtf.py:592-604, src/mtmvar.py:1100-1113) from ONE fit and ONE set of
         inverses per window, in ONE C-ABI call (`hmv_sliding_ffdtf_spectra_f64`): K1 -> K2 -> K3 (ffDTF normalised
         in-kernel, H left in the workspace) -> K5 (S written in the reference's (m, m, F) layout), `chunk` windows at a
         time (H is 16.8 MB per window; default: as many as `max_workspace_bytes` allows).  grid / flags as in
-        `sliding_ffdtf`.  Returns (ffdtf (items, m, m, F) real, S (items, m, m, F) complex)."""
+        `sliding_ffdtf`.  Returns (ffdtf (items, m, m, F) real, S (items, m, m, F) complex).
+        p=None / max_model_order / crit_type: the automatic order, as in `sliding_ffdtf`; `return_orders=True` appends
+        `orders` and `crit`."""
+        if p is None:
+            return self._sliding_auto("ffdtf", x, item_rec, item_start, n, freqs, fs, max_model_order, crit_type, out_ff,
+                                      False, return_orders, check, chunk, True, flags, grid, True, None, out_S=out_S,
+                                      spectra=True)
         assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
         x = x if x.stride(2) == 1 else x.contiguous()
         n_rec, m, T = x.shape

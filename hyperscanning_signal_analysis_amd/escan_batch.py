@@ -175,7 +175,8 @@ def savez_fast(path, compresslevel=0, **arrays):
 def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, freqs=None, bands=hdist.DEFAULT_BANDS,
         low_cutoff_hz=None, high_cutoff_hz=None, channel_subset=None, with_psd=False, psd_fmin=1.0, psd_fmax=30.0,
         psd_bandwidth=2.0, save_full=False, skip_existing=True, reader=None, engine=None, world=1, rank=0,
-        verbose=True, prefetch=2, timing=None, save_workers=4, compresslevel=0, measures=("ffdtf",), significance=None):
+        verbose=True, prefetch=2, timing=None, save_workers=4, compresslevel=0, measures=("ffdtf",), significance=None,
+        max_model_order=20, crit_type="AIC"):
     """Process every dyad under <root>/EEG.  Per dyad one `<out_dir>/<dyad>_ffdtf.npz` with, per segment `<task>/<event>`:
         <seg>/ffdtf_bands   (windows, n, n, n_bands)   band-integrated ffDTF of every window
         <seg>/ffdtf         (windows, n, n, F)         only with save_full=True (8.4 MB per window at 64 channels)
@@ -189,6 +190,12 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                                                        min_shift=None): the surrogate test of every computed measure
                                                        (`Engine.sliding_significance`; split = the child's channel count,
                                                        the same seed for every segment)
+        <seg>/orders        (windows,) int32           only with model_order=None: the order `mvar_criterion(window,
+                                                       max_model_order, crit_type)` (mtmvar.py:551-601) picks for every
+                                                       window, selected on the device inside the same call (0: failed
+                                                       window); meta then says "model_order": "auto" and carries
+                                                       `max_model_order` and `crit_type`.  Every measure of a window uses
+                                                       that window's order.  Not offered together with `significance`.
       plus `channels`, `freqs`, `meta` (JSON, its `measures` field lists what was computed, `significance` the test).  Returns {"done": [...], "skipped": [...], "failed": [(dyad, error)],
       "timing": {...}}.
     A window whose fit is singular is NaN-filled, not fatal (the reference would raise and lose the dyad); a segment that
@@ -206,6 +213,14 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
     if significance is not None:
         from .surrogates import check_significance_dict
         significance = check_significance_dict(significance)
+    auto = model_order is None
+    if auto:
+        from .engine import auto_order_args, no_auto_order
+        pmax, _ = auto_order_args(max_model_order, crit_type, 1 << 62)     # (the window length is checked per segment)
+        if significance is not None:
+            no_auto_order(None, "escan_batch.run(significance=...)")
+    order = None if auto else int(model_order)
+    order_kw = dict(max_model_order=pmax, crit_type=crit_type) if auto else {}
     eng = engine or default_engine()
     reader = reader or xarray_reader
     out_dir = Path(out_dir)
@@ -248,9 +263,12 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                 submit(k + max(1, int(prefetch)))
                 for line in prep["notes"]:
                     say(line)
-                result, meta = {}, {"dyad": dyad, "segments": [], "failed_segments": [], "model_order": int(model_order),
+                result, meta = {}, {"dyad": dyad, "segments": [], "failed_segments": [],
+                                    "model_order": "auto" if auto else order,
                                     "window_s": window_s, "overlap": overlap, "measures": list(measures),
                                     "created": time.strftime("%Y-%m-%dT%H:%M:%S")}
+                if auto:
+                    meta["max_model_order"], meta["crit_type"] = pmax, crit_type
                 if significance is not None:
                     meta["significance"] = dict(significance)
                 names_out, freqs_out = None, None
@@ -278,33 +296,38 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                                 pf, psd_dev = compute_psd_multitaper_device(xd[0], fs, psd_fmin, psd_fmax, psd_bandwidth, engine=eng)
                             xd.record_stream(psd_stream)
                         lo, hi = hdist.band_bins(f, bands)
-                        grid_w = regular_grid(pos, W, int(model_order))
+                        grid_w = regular_grid(pos, W, pmax if auto else order)
+                        extra = {}                                 # dDTF / GPDC of the same windows, NaN-filled alike
                         if save_full:
-                            ff, bad = eng.sliding_ffdtf(xd, rec_i, st_i, W, int(model_order), f, fs, check="mask", grid=grid_w)
+                            r = eng.sliding_ffdtf(xd, rec_i, st_i, W, order, f, fs, check="mask", grid=grid_w,
+                                                  return_orders=auto, **order_kw)
+                            ff, bad = r[0], r[1]
                             bsum = eng.band_sums(ff, lo, hi)
                             ff.masked_fill_(bad.view(-1, 1, 1, 1), float("nan"))
                         else:          # the reduced product straight from K3's row workers: the full array is never written
                             ff = None
-                            bsum, bad = eng.sliding_ffdtf(xd, rec_i, st_i, W, int(model_order), f, fs, check="mask",
-                                                          grid=grid_w, bands=(lo, hi))
+                            r = eng.sliding_ffdtf(xd, rec_i, st_i, W, order, f, fs, check="mask", grid=grid_w, bands=(lo, hi),
+                                                  return_orders=auto, **order_kw)
+                            bsum, bad = r[0], r[1]
+                        if auto:
+                            extra["orders"] = r[2]
                         bsum.masked_fill_(bad.view(-1, 1, 1, 1), float("nan"))
-                        extra = {}                                 # dDTF / GPDC of the same windows, NaN-filled alike
                         for meas in (m_ for m_ in measures if m_ != "ffdtf"):
                             run_m = eng.sliding_ddtf if meas == "ddtf" else eng.sliding_gpdc
                             if save_full:
-                                full_m, bad_m = run_m(xd, rec_i, st_i, W, int(model_order), f, fs, check="mask", grid=grid_w)
+                                full_m, bad_m = run_m(xd, rec_i, st_i, W, order, f, fs, check="mask", grid=grid_w, **order_kw)
                                 red_m = eng.band_sums(full_m, lo, hi)
                                 full_m.masked_fill_(bad_m.view(-1, 1, 1, 1), float("nan"))
                                 extra[meas] = full_m
                             else:
-                                red_m, bad_m = run_m(xd, rec_i, st_i, W, int(model_order), f, fs, check="mask", grid=grid_w,
-                                                     bands=(lo, hi))
+                                red_m, bad_m = run_m(xd, rec_i, st_i, W, order, f, fs, check="mask", grid=grid_w,
+                                                     bands=(lo, hi), **order_kw)
                             red_m.masked_fill_(bad_m.view(-1, 1, 1, 1), float("nan"))
                             extra[f"{meas}_bands"] = red_m
                         if significance is not None:             # the child block comes first (segment_block)
                             split = sum(1 for nm in seg["names"] if nm.endswith("_ch"))
                             for meas in measures:
-                                sig = eng.sliding_significance(xd, rec_i, st_i, W, int(model_order), f, fs, (lo, hi),
+                                sig = eng.sliding_significance(xd, rec_i, st_i, W, order, f, fs, (lo, hi),
                                                                measure=meas, null=significance["null"],
                                                                n_surrogates=significance["n_surrogates"],
                                                                seed=significance["seed"], split=split,

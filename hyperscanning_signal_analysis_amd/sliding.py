@@ -6,6 +6,8 @@
 optimal_model_order=p)` (/root/reference/src/mtmvar.py:237-284) on every window of every recording.
 `sliding_ddtf` / `sliding_gpdc` are `direct_dtf` (mtmvar.py:341-385) / `gen_partial_directed_coherence`
 (mtmvar.py:388-468) with `optimal_model_order=p` on every window, in the same batched form.
+With `p=None` every window gets the order `mvar_criterion(window, max_model_order, crit_type)` (mtmvar.py:551-601)
+picks for it -- the reference's own default, `optimal_model_order=None` -- selected on the device in the same call.
 `sliding_significance` adds a surrogate test (shift or phase null) to the band values of any of the three.
 `sliding_fad` is `fad_decomposition` (mtmvar.py:607-757) of every channel of every window.
 """
@@ -95,25 +97,63 @@ def regular_grid(positions, window_size: int, p: int):
 
 def sliding_ffdtf_device(x: torch.Tensor, window_size: int, n_windows: int, p: int, freqs, fs: float,
                          engine: Engine | None = None, out: torch.Tensor | None = None, check: bool = True,
-                         share_overlap: bool = True):
-    """x: device tensor (n_rec, m, T) -> device tensor (n_rec, n_windows, m, m, F).  No host copies."""
+                         share_overlap: bool = True, max_model_order: int = 20, crit_type: str = "AIC",
+                         return_orders: bool = False):
+    """x: device tensor (n_rec, m, T) -> device tensor (n_rec, n_windows, m, m, F).  No host copies.
+    p=None: the automatic order per window (`Engine.sliding_ffdtf`); `return_orders=True` then returns
+    (ffdtf, orders (n_rec, n_windows) int32, crit (n_rec, n_windows, max_model_order))."""
     eng = engine or default_engine()
     n_rec, m, T = x.shape
     positions, w = window_positions(T, n_windows, window_size)
+    if p is None:
+        from .engine import auto_order_args
+        auto_order_args(max_model_order, crit_type, w)
     item_rec, item_start = window_items(n_rec, positions, eng.device)
-    ff = eng.sliding_ffdtf(x, item_rec, item_start, w, p, freqs, fs, out=out, check=check,
-                           grid=regular_grid(positions, w, p) if share_overlap else None)
-    return ff.view(n_rec, len(positions), m, m, -1)
+    res = eng.sliding_ffdtf(x, item_rec, item_start, w, p, freqs, fs, out=out, check=check,
+                            grid=regular_grid(positions, w, _grid_order(p, max_model_order)) if share_overlap else None,
+                            **_auto_kw(p, max_model_order, crit_type, return_orders))
+    return _shape_windows(res, n_rec, len(positions), m)
 
 
-def sliding_ffdtf(x, window_size, n_windows, p, freqs, fs, engine: Engine | None = None):
-    """NumPy in / NumPy out.  x: (m, T) or (n_rec, m, T) -> (n_windows, m, m, F) or (n_rec, n_windows, ...)."""
+def _grid_order(p, max_model_order):
+    return int(max_model_order) if p is None else p
+
+
+def _auto_kw(p, max_model_order, crit_type, return_orders):
+    """The automatic-order keywords, passed on only with p=None (an integer p takes the fixed-order call as it is)."""
+    return dict(max_model_order=max_model_order, crit_type=crit_type, return_orders=return_orders) if p is None else {}
+
+
+def _shape_windows(res, n_rec, n_win, m):
+    """(items, m, m, last) -> (n_rec, n_windows, m, m, last); with return_orders the orders and criterion curves alike."""
+    if isinstance(res, tuple):
+        out, orders, crit = res
+        return out.view(n_rec, n_win, m, m, -1), orders.view(n_rec, n_win), crit.view(n_rec, n_win, -1)
+    return res.view(n_rec, n_win, m, m, -1)
+
+
+def _to_host(res, single):
+    if isinstance(res, tuple):
+        return tuple((a.cpu().numpy()[0] if single else a.cpu().numpy()) for a in res)
+    a = res.cpu().numpy()
+    return a[0] if single else a
+
+
+def sliding_ffdtf(x, window_size, n_windows, p, freqs, fs, engine: Engine | None = None, max_model_order: int = 20,
+                  crit_type: str = "AIC", return_orders: bool = False):
+    """NumPy in / NumPy out.  x: (m, T) or (n_rec, m, T) -> (n_windows, m, m, F) or (n_rec, n_windows, ...).
+    p=None: `full_freq_dtf(window, freqs, fs, max_model_order, None, crit_type)` of every window, i.e. the automatic order;
+    `return_orders=True` then returns (ffdtf, orders, crit)."""
+    if p is None:
+        from .engine import auto_order_args
+        auto_order_args(max_model_order, crit_type, 1 << 62)         # (the window length: in sliding_ffdtf_device)
     eng = engine or default_engine()
     x = np.asarray(x, dtype=np.float64)
     single = x.ndim == 2
     xd = eng.to_device(x[None] if single else x)
-    ff = sliding_ffdtf_device(xd, window_size, n_windows, p, freqs, fs, eng).cpu().numpy()
-    return ff[0] if single else ff
+    res = sliding_ffdtf_device(xd, window_size, n_windows, p, freqs, fs, eng,
+                               **_auto_kw(p, max_model_order, crit_type, return_orders))
+    return _to_host(res, single)
 
 
 def _positions(T: int, window_size, n_windows: int, hop):
@@ -124,33 +164,47 @@ def _positions(T: int, window_size, n_windows: int, hop):
     return window_positions(T, n_windows, window_size)
 
 
-def _sliding_conn_device(measure, x, window_size, n_windows, p, freqs, fs, engine, out, check, share_overlap, hop, bands):
+def _sliding_conn_device(measure, x, window_size, n_windows, p, freqs, fs, engine, out, check, share_overlap, hop, bands,
+                         max_model_order=20, crit_type="AIC", return_orders=False):
     eng = engine or default_engine()
     n_rec, m, T = x.shape
     positions, w = _positions(T, window_size, n_windows, hop)
+    if p is None:
+        from .engine import auto_order_args
+        auto_order_args(max_model_order, crit_type, w)
     item_rec, item_start = window_items(n_rec, positions, eng.device)
     run = eng.sliding_ddtf if measure == "ddtf" else eng.sliding_gpdc
     res = run(x, item_rec, item_start, w, p, freqs, fs, out=out, check=check, bands=bands,
-              grid=regular_grid(positions, w, p) if share_overlap else None)
-    return res.view(n_rec, len(positions), m, m, -1)
+              grid=regular_grid(positions, w, _grid_order(p, max_model_order)) if share_overlap else None,
+              **_auto_kw(p, max_model_order, crit_type, return_orders))
+    return _shape_windows(res, n_rec, len(positions), m)
 
 
 def sliding_ddtf_device(x: torch.Tensor, window_size, n_windows: int, p: int, freqs, fs: float, engine: Engine | None = None,
-                        out: torch.Tensor | None = None, check=True, share_overlap: bool = True, hop=None, bands=None):
+                        out: torch.Tensor | None = None, check=True, share_overlap: bool = True, hop=None, bands=None,
+                        max_model_order: int = 20, crit_type: str = "AIC", return_orders: bool = False):
     """dDTF of every window: x device tensor (n_rec, m, T) -> device tensor (n_rec, n_windows, m, m, F), or
     (..., n_bands) with `bands=(bin_lo, bin_hi)`.  Windows from `window_positions`, or every `hop` samples
     (`hop_positions`) when `hop` is given.  check: True raises LinAlgError naming the failed window, "nan" NaN-fills it
-    (`Engine.sliding_ddtf`)."""
-    return _sliding_conn_device("ddtf", x, window_size, n_windows, p, freqs, fs, engine, out, check, share_overlap, hop, bands)
+    (`Engine.sliding_ddtf`).  p=None: the automatic order per window; `return_orders=True` then returns (out, orders
+    (n_rec, n_windows), crit (n_rec, n_windows, max_model_order))."""
+    return _sliding_conn_device("ddtf", x, window_size, n_windows, p, freqs, fs, engine, out, check, share_overlap, hop, bands,
+                                max_model_order, crit_type, return_orders)
 
 
 def sliding_gpdc_device(x: torch.Tensor, window_size, n_windows: int, p: int, freqs, fs: float, engine: Engine | None = None,
-                        out: torch.Tensor | None = None, check=True, share_overlap: bool = True, hop=None, bands=None):
+                        out: torch.Tensor | None = None, check=True, share_overlap: bool = True, hop=None, bands=None,
+                        max_model_order: int = 20, crit_type: str = "AIC", return_orders: bool = False):
     """GPDC of every window, in the form of `sliding_ddtf_device` (`Engine.sliding_gpdc`)."""
-    return _sliding_conn_device("gpdc", x, window_size, n_windows, p, freqs, fs, engine, out, check, share_overlap, hop, bands)
+    return _sliding_conn_device("gpdc", x, window_size, n_windows, p, freqs, fs, engine, out, check, share_overlap, hop, bands,
+                                max_model_order, crit_type, return_orders)
 
 
-def _sliding_conn_host(fn, x, window_size, n_windows, p, freqs, fs, engine, hop, bands, check):
+def _sliding_conn_host(fn, x, window_size, n_windows, p, freqs, fs, engine, hop, bands, check, max_model_order=20,
+                       crit_type="AIC", return_orders=False):
+    if p is None:
+        from .engine import auto_order_args
+        auto_order_args(max_model_order, crit_type, 1 << 62)         # (the window length: in _sliding_conn_device)
     eng = engine or default_engine()
     x = np.asarray(x, dtype=np.float64) if not isinstance(x, torch.Tensor) else x
     single = x.ndim == 2
@@ -158,20 +212,25 @@ def _sliding_conn_host(fn, x, window_size, n_windows, p, freqs, fs, engine, hop,
         xd = (x[None] if single else x).to(device=eng.device, dtype=torch.float64)
     else:
         xd = eng.to_device(x[None] if single else x)
-    res = fn(xd, window_size, n_windows, p, freqs, fs, eng, check=check, hop=hop, bands=bands).cpu().numpy()
-    return res[0] if single else res
+    res = fn(xd, window_size, n_windows, p, freqs, fs, eng, check=check, hop=hop, bands=bands,
+             **_auto_kw(p, max_model_order, crit_type, return_orders))
+    return _to_host(res, single)
 
 
-def sliding_ddtf(x, window_size, n_windows, p, freqs, fs, engine: Engine | None = None, hop=None, bands=None, check=True):
+def sliding_ddtf(x, window_size, n_windows, p, freqs, fs, engine: Engine | None = None, hop=None, bands=None, check=True,
+                 max_model_order: int = 20, crit_type: str = "AIC", return_orders: bool = False):
     """NumPy (or tensor) in / NumPy out.  x: (m, T) or (n_rec, m, T) -> (n_windows, m, m, F) or (n_rec, n_windows, ...):
     `direct_dtf(window, freqs, fs, optimal_model_order=p)` (mtmvar.py:341-385) of every window."""
-    return _sliding_conn_host(sliding_ddtf_device, x, window_size, n_windows, p, freqs, fs, engine, hop, bands, check)
+    return _sliding_conn_host(sliding_ddtf_device, x, window_size, n_windows, p, freqs, fs, engine, hop, bands, check,
+                              max_model_order, crit_type, return_orders)
 
 
-def sliding_gpdc(x, window_size, n_windows, p, freqs, fs, engine: Engine | None = None, hop=None, bands=None, check=True):
+def sliding_gpdc(x, window_size, n_windows, p, freqs, fs, engine: Engine | None = None, hop=None, bands=None, check=True,
+                 max_model_order: int = 20, crit_type: str = "AIC", return_orders: bool = False):
     """NumPy (or tensor) in / NumPy out: `gen_partial_directed_coherence(window, freqs, fs, optimal_model_order=p)`
     (mtmvar.py:388-468) of every window, shaped as `sliding_ddtf`."""
-    return _sliding_conn_host(sliding_gpdc_device, x, window_size, n_windows, p, freqs, fs, engine, hop, bands, check)
+    return _sliding_conn_host(sliding_gpdc_device, x, window_size, n_windows, p, freqs, fs, engine, hop, bands, check,
+                              max_model_order, crit_type, return_orders)
 
 
 def sliding_significance(x, window_size, n_windows, p, freqs, fs, bands, *, measure, null, n_surrogates, seed, split=None,
@@ -184,6 +243,8 @@ def sliding_significance(x, window_size, n_windows, p, freqs, fs, bands, *, meas
     ...) --, n_valid (n_windows,) or (n_rec, n_windows), tested (m, m).  The arguments are checked before the GPU is
     touched (`surrogates.significance_args`)."""
     from . import surrogates as sg
+    from .engine import no_auto_order
+    no_auto_order(p, "sliding_significance")
     single = np.ndim(x) == 2
     shape = tuple(np.shape(x))
     n_rec, m, T = (1,) + shape if single else shape

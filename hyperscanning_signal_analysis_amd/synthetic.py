@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["synthetic_var_dyad", "northstar_freqs", "NORTHSTAR"]
+__all__ = ["synthetic_var_dyad", "mixed_order_recording", "northstar_freqs", "NORTHSTAR"]
 
 NORTHSTAR = dict(m=64, fs=500.0, window=1000, hop=500, p=8, F=256, T=300_000)
 
@@ -51,5 +51,33 @@ def synthetic_var_dyad(dyad: int, m: int = 64, p: int = 8, T: int = 300_000, fs:
     for t in range(p, n_tot):
         x[t] = e[t] + x[t - p:t][::-1].reshape(-1) @ W
     x = x[burn:].T
+    x = (x - x.mean(axis=1, keepdims=True)) / x.std(axis=1, keepdims=True)
+    return np.ascontiguousarray(x)
+
+
+def mixed_order_recording(seed: int, m: int, orders, seg: int, burn: int = 500):
+    """Recording (m, len(orders) * seg) whose windows need DIFFERENT model orders: one stable VAR(q) stretch of `seg`
+    samples per entry q of `orders`, concatenated.  `synthetic_var_dyad` is AR(2)-dominated -- the model-order criterion
+    picks order 2 for every window of it -- and cannot test a selection.  Stretch i, seeded default_rng(seed + i): lag-1
+    diagonal U(0.1, 0.3); -0.5 * U(0.7, 1.0) added to the lag-q diagonal; lag-q coupling i <- i + 1 (mod m) of +0.15; unit
+    innovations; `burn` samples dropped.  The whole recording is z-scored per channel."""
+    idx = np.arange(m)
+    parts = []
+    for i, q in enumerate(orders):
+        q = int(q)
+        rng = np.random.default_rng(seed + i)
+        A = np.zeros((q, m, m))
+        A[0, idx, idx] = rng.uniform(0.1, 0.3, m)
+        A[q - 1, idx, idx] += -0.5 * rng.uniform(0.7, 1.0, m)
+        A[q - 1, idx, (idx + 1) % m] = 0.15
+        n_tot = seg + burn
+        e = rng.standard_normal((n_tot, m))
+        x = np.zeros((n_tot, m))
+        W = np.ascontiguousarray(np.concatenate([A[k].T for k in range(q)], axis=0))
+        x[:q] = e[:q]
+        for t in range(q, n_tot):
+            x[t] = e[t] + x[t - q:t][::-1].reshape(-1) @ W
+        parts.append(x[burn:].T)
+    x = np.concatenate(parts, axis=1)
     x = (x - x.mean(axis=1, keepdims=True)) / x.std(axis=1, keepdims=True)
     return np.ascontiguousarray(x)

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define HMV_VERSION 150            /* 0.1.5 */
+#define HMV_VERSION 160            /* 0.1.6 */
 #define HMV_MAX_CHANNELS 64
 #define HMV_MAX_ORDER 32
 
@@ -304,6 +304,55 @@ int hmv_sliding_gpdc_f64(const double* x, int64_t rec_stride, int64_t ld,
                          double* out, const int32_t* bin_lo, const int32_t* bin_hi, int n_bands,
                          double* ar_out, double* V_out, int32_t* info_yw,
                          void* workspace, int64_t workspace_bytes, int64_t chunk, int64_t flags,
+                         int64_t grid_hop, int64_t grid_first, int64_t grid_nwin, int64_t grid_T,
+                         void* stream, void* aux_stream);
+
+/* Automatic model order, window by window (csrc/yw_auto.hip).  Every connectivity function of the reference takes
+ * `max_model_order=20, optimal_model_order=None, crit_type='AIC'`: with no order given it calls mvar_criterion
+ * (src/mtmvar.py:551-601), which fits EVERY order 1..pmax with ar_coeff (:90-123) and returns the first arg-min of
+ *   crit_q = log det V_q + c q m^2 / n,    c = 2 (AIC), 2 log log n (HQ), log n (SC),
+ * and then fits that order once more.  The two entries below do this in one pass of K2's block Levinson-Whittle
+ * recursion, which holds the complete order-q model (coefficients, V_q, log det V_q) on its way to order pmax.
+ * crit: 0 AIC, 1 HQ, 2 SC (the numbering of hmv_fad_f64).
+ *
+ * hmv_yw_solve_auto_f64: K2 alone.  R [item][pmax+1][MP][MP] (K1 at p = pmax), n the window length, ws
+ *   hmv_yw_workspace_doubles(m, pmax) doubles per item.  Outputs: order_out int32 [n_items], the selected order q*;
+ *   ar [item][MP][MP][pmax], the order-q* coefficients with the lags >= q* written as +0.0;  V [item][MP][MP] = V_q*;
+ *   crit_out [item][pmax] (optional) the criterion curve;  vq_logdet [item][pmax] (optional) log det V_q.
+ *   info [item]: a non-positive pivot at ANY order <= pmax fails the window (info != 0, order_out = 0, ar = 0, V = R_0).
+ *   The reference would take the log of a non-positive determinant there, get NaN, and let argmin return that index; that
+ *   is not reproduced.  A window whose tile inverses were badly conditioned at an order <= q* is re-solved by the block
+ *   LDL^T at its own order on the device (no host round trip); its selected order stays the recursion's.
+ *   flags: 0 (the LDL^T forms HMV_FLAG_YW_TILED / _ONE_LAUNCH have no automatic order: refused).
+ *
+ * hmv_sliding_auto_f64: ONE entry for all fused sliding-window routes -- hmv_sliding_ffdtf_f64 / _bands / _spectra
+ *   (full_freq_dtf, src/mtmvar.py:236-284; multivariate_spectra, :165-201), hmv_sliding_ddtf_f64 (direct_dtf, :341-385)
+ *   and hmv_sliding_gpdc_f64 (gen_partial_directed_coherence, :388-468) -- with `optimal_model_order=None`:
+ *   K1 sums pmax + 1 lags, K2 selects, and every later stage runs at p = pmax on the zero-padded coefficients (the added
+ *   terms of A(f) = I - sum_k ar_k e^{-2 pi i f k / fs} are exact zeros).
+ *   measure: HMV_MEASURE_FFDTF, _DDTF or _GPDC.  n_bands = 0: out is [n_items][m][m][F]; n_bands >= 1: out is
+ *   [n_items][m][m][n_bands] (bin_lo / bin_hi as in the fixed-order entries).  S_out (optional; measure = FFDTF and
+ *   n_bands = 0 only): complex128 [n_items][m][m][F] as hmv_sliding_ffdtf_spectra_f64.  order_out int32 [n_items]
+ *   (required), crit_out [n_items][pmax] (optional), ar_out [n_items][MP][MP][pmax] zero-padded (optional), V_out
+ *   (optional).  info_tf is unused for GPDC (may be NULL).  Grid arguments, chunk, flags, info_yw and info_tf as in the
+ *   fixed-order entries.  Refused: pmax outside 1..HMV_MAX_ORDER, n <= pmax, crit outside 0..2, and what the fixed-order
+ *   entries refuse.
+ *   workspace: hmv_sliding_auto_workspace_bytes(measure, chunk, m, pmax, F, n_bands) bytes, with n_bands = -1 for the
+ *   full ffDTF together with S_out (-1 for bad arguments). */
+#define HMV_MEASURE_FFDTF 0
+#define HMV_MEASURE_DDTF 1
+#define HMV_MEASURE_GPDC 2
+int hmv_yw_solve_auto_f64(const double* R, int64_t n_items, int m, int pmax, int n, int crit, double* ws, double* ar,
+                          double* V, int32_t* order_out, double* crit_out, double* vq_logdet, int32_t* info,
+                          int64_t flags, void* stream);
+int64_t hmv_sliding_auto_workspace_bytes(int measure, int64_t chunk, int m, int pmax, int F, int n_bands);
+int hmv_sliding_auto_f64(int measure, const double* x, int64_t rec_stride, int64_t ld,
+                         const int64_t* item_rec, const int64_t* item_start, int64_t n_items,
+                         int m, int n, int pmax, int crit, const double* freqs, int F, double fs,
+                         double* out, const int32_t* bin_lo, const int32_t* bin_hi, int n_bands, double* S_out,
+                         double* ar_out, double* V_out, int32_t* order_out, double* crit_out,
+                         int32_t* info_yw, int32_t* info_tf, void* workspace, int64_t workspace_bytes, int64_t chunk,
+                         double pivot_tau, int64_t flags,
                          int64_t grid_hop, int64_t grid_first, int64_t grid_nwin, int64_t grid_T,
                          void* stream, void* aux_stream);
 
