@@ -87,6 +87,15 @@ SIGNATURES = {
                                      c_int, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int] +
                              [c_void_p] * 8 + [c_int64, c_int64, c_double, c_int64, c_int64, c_int64, c_int64, c_int64,
                                                c_void_p, c_void_p]),
+    "hmv_lagcov_ensemble_workspace_doubles": (c_int64, [c_int64, c_int, c_int, c_int, c_int64, c_int64]),
+    "hmv_lagcov_ensemble_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                        c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int64,
+                                        c_int64, c_int64, c_int64, c_void_p]),
+    "hmv_sliding_ensemble_workspace_bytes": (c_int64, [c_int, c_int64, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64]),
+    "hmv_sliding_ensemble_f64": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                         c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_double,
+                                         c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 6 +
+                                 [c_int64, c_int64, c_double, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
     "hmv_fad_workspace_bytes": (c_int64, [c_int64, c_int]),
     "hmv_fad_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int,
                             c_double, c_double, c_int] + [c_void_p] * 17),

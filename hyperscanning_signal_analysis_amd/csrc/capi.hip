@@ -116,6 +116,60 @@ int hmv_lagcov_regular_f64(const double* x, int64_t ld, int64_t T, int64_t first
   return hmv::launch_lagcomb(c, mp, S(stream));
 }
 
+// ---- K1 of an event-locked ensemble (lagcov_ensemble.hip) -------------------------------------------------------
+namespace {
+// Which form of the ensemble K1 runs: the shared-overlap form where the declared grid allows it (whole hops, 2..32 hops
+// per window, a hop longer than the order, a hop block and its lags within one LDS fill), else the direct form.
+bool ens_shared_form(int n, int p, int64_t grid_hop, int64_t flags) {
+  return grid_hop > 0 && !(flags & HMV_FLAG_DIRECT_LAGCOV) &&
+         hmv::lagcov_ensemble_shared_ok(n, grid_hop, p, HMV_MAX_HOPS_ENSEMBLE);
+}
+bool ens_grid_ok(int64_t n_items, int64_t n_groups, int n, int64_t ld, int64_t T, int64_t grid_hop, int64_t grid_nwin) {
+  return grid_hop > 0 && grid_nwin >= 1 && n_items == n_groups * grid_nwin && (grid_nwin - 1) * grid_hop + n <= T && ld >= T;
+}
+int64_t ens_q_tiles(int64_t n_items, int n, int p, int64_t grid_hop, int64_t grid_nwin) {
+  if (grid_hop <= 0 || grid_nwin < 1 || !ens_shared_form(n, p, grid_hop, 0)) return 0;
+  return hmv::lagcov_ensemble_q_tiles(n_items, grid_nwin, (int)(n / grid_hop));
+}
+}  // namespace
+
+int64_t hmv_lagcov_ensemble_workspace_doubles(int64_t n_items, int m, int n, int p, int64_t grid_hop, int64_t grid_nwin) {
+  const int mp = pad_of(m);
+  if (mp < 0 || n_items < 0 || p < 1 || p > HMV_MAX_ORDER || n <= p || grid_hop < 0 || grid_nwin < 0) return -1;
+  return ens_q_tiles(n_items, n, p, grid_hop, grid_nwin) * (int64_t)(p + 1) * mp * mp;
+}
+
+int hmv_lagcov_ensemble_f64(const double* x, int64_t rec_stride, int64_t ld, int64_t T, const int64_t* trial_rec,
+                            const int64_t* trial_start, const int64_t* group_ptr, int64_t n_groups,
+                            const int64_t* item_group, const int64_t* item_offset, int64_t n_items, int m, int n, int p,
+                            double* R, double* workspace, int64_t workspace_doubles, int64_t grid_hop, int64_t grid_nwin,
+                            int64_t flags, void* stream) {
+  const int mp = pad_of(m);
+  if (mp < 0) return fail(-1, "hmv_lagcov_ensemble_f64: channel count must be in 1..64");
+  if (p < 1 || p > HMV_MAX_ORDER) return fail(-2, "hmv_lagcov_ensemble_f64: model order must be in 1..32");
+  if (n <= p) return fail(-3, "hmv_lagcov_ensemble_f64: window shorter than the model order");
+  if (!x || !trial_rec || !trial_start || !group_ptr || !item_group || !item_offset || !R || n_items < 0)
+    return fail(-4, "hmv_lagcov_ensemble_f64: null pointer");
+  if (n_groups < 1) return fail(-10, "hmv_lagcov_ensemble_f64: n_groups must be >= 1");
+  if (grid_hop != 0 && !ens_grid_ok(n_items, n_groups, n, ld, T, grid_hop, grid_nwin))
+    return fail(-9, "hmv_lagcov_ensemble_f64: inconsistent regular window grid");
+  const bool shared = ens_shared_form(n, p, grid_hop, flags);
+  if (shared) {
+    const int64_t need = ens_q_tiles(n_items, n, p, grid_hop, grid_nwin) * (int64_t)(p + 1) * mp * mp;
+    if (!workspace || workspace_doubles < need) return fail(-7, "hmv_lagcov_ensemble_f64: workspace too small");
+  }
+  hmv::LagcovEnsArgs a{};
+  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.T = T;
+  a.trial_rec = reinterpret_cast<const long long*>(trial_rec);
+  a.trial_start = reinterpret_cast<const long long*>(trial_start);
+  a.group_ptr = reinterpret_cast<const long long*>(group_ptr);
+  a.item_group = reinterpret_cast<const long long*>(item_group);
+  a.item_offset = reinterpret_cast<const long long*>(item_offset);
+  a.n_items = n_items; a.m = m; a.n = n; a.p = p; a.R = R;
+  if (shared) { a.it0 = 0; a.nwin = grid_nwin; a.hop = grid_hop; a.k = (int)(n / grid_hop); a.Q = workspace; }
+  return hmv::launch_lagcov_ensemble(a, mp, shared, S(stream));
+}
+
 int hmv_yw_solve_f64(const double* R, int64_t n_items, int m, int p, double* ws, double* ar, double* V,
                      double* vq_logdet, int32_t* info, int64_t flags, void* stream) {
   const int mp = pad_of(m);
@@ -457,12 +511,14 @@ struct SlidingWs {
   size_t off_R, off_Q, off_ws, off_ar, off_V, off_tf, off_den, off_tw, off_H, off_B, off_G, off_full, total;
 };
 // `bands` with dDTF / GPDC: the chunk's full array passes through scratch (off_full) before its band sums are taken
-SlidingWs sliding_layout(int64_t chunk, int mp, int p, int F, bool bands = false, bool spectra = false, int measure = MEAS_FFDTF) {
+// q_tiles >= 0: the hop-block scratch of the ensemble K1 (in stacks of p + 1 tiles) instead of the single-trial one
+SlidingWs sliding_layout(int64_t chunk, int mp, int p, int F, bool bands = false, bool spectra = false, int measure = MEAS_FFDTF,
+                         int64_t q_tiles = -1) {
   SlidingWs w;
   size_t o = 0;
   const size_t t = (size_t)mp * mp;
   w.off_R = o;      o += align256(sizeof(double) * chunk * (p + 1) * t);
-  w.off_Q = o;      o += align256(sizeof(double) * (chunk + HMV_MAX_HOPS_PER_WINDOW - 1) * (p + 1) * t);   // hop-block sums
+  w.off_Q = o;      o += align256(sizeof(double) * (q_tiles >= 0 ? q_tiles : chunk + HMV_MAX_HOPS_PER_WINDOW - 1) * (p + 1) * t);   // hop-block sums
   w.off_ws = o;     o += align256(sizeof(double) * chunk * hmv::yw_ws_tiles(p) * t);
   w.off_ar = o;     o += align256(sizeof(double) * chunk * t * p);
   w.off_V = o;      o += align256(sizeof(double) * chunk * t);
@@ -506,13 +562,21 @@ int64_t hmv_sliding_workspace_bytes(int64_t chunk, int m, int p, int F) {
 }
 
 namespace {
+// An event-locked ensemble in place of single windows (hmv_sliding_ensemble_f64): item_rec / item_start of sliding_impl
+// then carry item_group / item_offset, grid_hop / grid_nwin describe the offsets, and only K1 differs.
+struct EnsDesc {
+  const int64_t* trial_rec;
+  const int64_t* trial_start;
+  const int64_t* group_ptr;
+  int64_t n_groups, T;
+};
 int sliding_impl(const char* who, const double* x, int64_t rec_stride, int64_t ld, const int64_t* item_rec,
                  const int64_t* item_start, int64_t n_items, int m, int n, int p, const double* freqs, int F, double fs,
                  double* ffdtf, double* band_out, const int32_t* bin_lo, const int32_t* bin_hi, int n_bands, double* S_out,
                  double* ar_out, double* V_out, int32_t* info_yw, int32_t* info_tf, void* workspace, int64_t workspace_bytes, int64_t chunk,
                  double pivot_tau, int64_t flags, int64_t grid_hop, int64_t grid_first, int64_t grid_nwin, int64_t grid_T,
                  void* ev_k3_start, void* ev_k3_stop, void* stream, void* aux_stream, int measure = MEAS_FFDTF,
-                 int crit = -1, int32_t* order_out = nullptr, double* crit_out = nullptr) {
+                 int crit = -1, int32_t* order_out = nullptr, double* crit_out = nullptr, const EnsDesc* ens = nullptr) {
   // crit >= 0: automatic order (hmv_sliding_auto_f64) -- p is the largest order tried, K1 sums p + 1 lags, K2 selects every
   // window's order and leaves its coefficients zero-padded to p lags, and every later stage runs at p on those (the
   // added terms of A(f) = I - sum_k ar_k tw_k are exact zeros)
@@ -537,11 +601,20 @@ int sliding_impl(const char* who, const double* x, int64_t rec_stride, int64_t l
       !workspace || F < 1 || chunk < 1)
     return fail(-4, "hmv_sliding_ffdtf_f64: null pointer / empty grid");
   if (bands && (!bin_lo || !bin_hi || n_bands < 1)) return fail(-4, "hmv_sliding_ffdtf_f64: band bins missing");
-  const SlidingWs w = sliding_layout(chunk, mp, p, F, bands, S_out != nullptr, measure);
+  bool ens_shared = false;
+  if (ens) {
+    if (!ens->trial_rec || !ens->trial_start || !ens->group_ptr) return fail(-4, "hmv_sliding_ffdtf_f64: null pointer / empty grid");
+    if (ens->n_groups < 1) return fail(-10, "hmv_sliding_ffdtf_f64: n_groups must be >= 1");
+    if (grid_hop != 0 && !ens_grid_ok(n_items, ens->n_groups, n, ld, ens->T, grid_hop, grid_nwin))
+      return fail(-9, "hmv_sliding_ffdtf_f64: inconsistent regular window grid");
+    ens_shared = ens_shared_form(n, p, grid_hop, flags);
+  }
+  const SlidingWs w = sliding_layout(chunk, mp, p, F, bands, S_out != nullptr, measure,
+                                     ens ? (ens_shared ? ens_q_tiles(chunk, n, p, grid_hop, grid_nwin) : 0) : -1);
   if ((int64_t)w.total > workspace_bytes) return fail(-7, "hmv_sliding_ffdtf_f64: workspace too small");
   // Regular grid (the caller vouches: item = rec * grid_nwin + w starts at grid_first + w * grid_hop of recording rec,
   // recordings are grid_T samples long): K1 sums every hop block once and assembles the windows from the blocks.
-  bool regular = grid_hop > 0 && !(flags & HMV_FLAG_DIRECT_LAGCOV);
+  bool regular = !ens && grid_hop > 0 && !(flags & HMV_FLAG_DIRECT_LAGCOV);
   if (regular) {
     if (grid_nwin < 1 || grid_first < 0 || n_items % grid_nwin != 0 || grid_first + (grid_nwin - 1) * grid_hop + n > grid_T ||
         ld < grid_T)
@@ -581,7 +654,18 @@ int sliding_impl(const char* who, const double* x, int64_t rec_stride, int64_t l
     const int64_t c = (n_items - i0 < chunk) ? (n_items - i0) : chunk;
     double* ar_c = ar_out ? ar_out + (size_t)i0 * t * p : ar;
     double* V_c = V_out ? V_out + (size_t)i0 * t : V;
-    if (regular) {
+    if (ens) {
+      hmv::LagcovEnsArgs ea{};
+      ea.x = x; ea.rec_stride = rec_stride; ea.ld = ld; ea.T = ens->T;
+      ea.trial_rec = reinterpret_cast<const long long*>(ens->trial_rec);
+      ea.trial_start = reinterpret_cast<const long long*>(ens->trial_start);
+      ea.group_ptr = reinterpret_cast<const long long*>(ens->group_ptr);
+      ea.item_group = reinterpret_cast<const long long*>(item_rec + i0);
+      ea.item_offset = reinterpret_cast<const long long*>(item_start + i0);
+      ea.n_items = c; ea.m = m; ea.n = n; ea.p = p; ea.R = R;
+      if (ens_shared) { ea.it0 = i0; ea.nwin = grid_nwin; ea.hop = grid_hop; ea.k = (int)(n / grid_hop); ea.Q = Qb; }
+      rc = hmv::launch_lagcov_ensemble(ea, mp, ens_shared, st0);
+    } else if (regular) {
       // items i0 .. i0+c-1 as runs of consecutive windows of one recording each (item = rec * grid_nwin + w)
       for (int64_t it = i0; it < i0 + c && rc == 0;) {
         const int64_t rec = it / grid_nwin, w0 = it - rec * grid_nwin;
@@ -793,6 +877,44 @@ int hmv_sliding_auto_f64(int measure, const double* x, int64_t rec_stride, int64
                       measure == HMV_MEASURE_GPDC ? nullptr : info_tf, workspace, workspace_bytes, chunk,
                       measure == HMV_MEASURE_GPDC ? 1.0 : pivot_tau, flags, grid_hop, grid_first, grid_nwin, grid_T, nullptr,
                       nullptr, stream, aux_stream, measure, crit, order_out, crit_out);
+}
+
+// ---- event-locked ensembles: the fused path with the trial-averaged K1 (lagcov_ensemble.hip) ----------------------------
+int64_t hmv_sliding_ensemble_workspace_bytes(int measure, int64_t chunk, int m, int n, int p, int F, int n_bands,
+                                             int64_t grid_hop, int64_t grid_nwin) {
+  const int mp = pad_of(m);
+  // n_bands = -1: the full ffDTF together with S_out, as hmv_sliding_auto_workspace_bytes
+  const bool spectra = (n_bands == -1 && measure == HMV_MEASURE_FFDTF);
+  if (mp < 0 || chunk < 1 || p < 1 || p > HMV_MAX_ORDER || n <= p || F < 1 || (n_bands < 0 && !spectra) ||
+      measure < HMV_MEASURE_FFDTF || measure > HMV_MEASURE_GPDC || grid_hop < 0 || grid_nwin < 0)
+    return -1;
+  return (int64_t)sliding_layout(chunk, mp, p, F, n_bands > 0, spectra, measure,
+                                 ens_q_tiles(chunk, n, p, grid_hop, grid_nwin)).total;
+}
+
+int hmv_sliding_ensemble_f64(int measure, const double* x, int64_t rec_stride, int64_t ld, int64_t T,
+                             const int64_t* trial_rec, const int64_t* trial_start, const int64_t* group_ptr,
+                             int64_t n_groups, const int64_t* item_group, const int64_t* item_offset, int64_t n_items,
+                             int m, int n, int p, const double* freqs, int F, double fs, double* out,
+                             const int32_t* bin_lo, const int32_t* bin_hi, int n_bands, double* S_out, double* ar_out,
+                             double* V_out, int32_t* info_yw, int32_t* info_tf, void* workspace, int64_t workspace_bytes,
+                             int64_t chunk, double pivot_tau, int64_t flags, int64_t grid_hop, int64_t grid_nwin,
+                             void* stream, void* aux_stream) {
+  if (measure < HMV_MEASURE_FFDTF || measure > HMV_MEASURE_GPDC)
+    return fail(-4, "hmv_sliding_ensemble_f64: measure must be HMV_MEASURE_FFDTF, _DDTF or _GPDC");
+  if (n_bands < 0) return fail(-4, "hmv_sliding_ensemble_f64: n_bands must be >= 0");
+  if (S_out && (measure != HMV_MEASURE_FFDTF || n_bands != 0))
+    return fail(-4, "hmv_sliding_ensemble_f64: spectra come with the full ffDTF only");
+  const int mp = pad_of(m);                              // ahead of the pointer checks, in the order of the other entries
+  if (mp >= 0 && p >= 1 && p <= HMV_MAX_ORDER && n > p && !out && n_items != 0)
+    return fail(-4, "hmv_sliding_ensemble_f64: null pointer / empty grid");
+  const bool bands = n_bands > 0;
+  const EnsDesc ens{trial_rec, trial_start, group_ptr, n_groups, T};
+  return sliding_impl("hmv_sliding_ensemble_f64", x, rec_stride, ld, item_group, item_offset, n_items, m, n, p, freqs, F, fs,
+                      bands ? nullptr : out, bands ? out : nullptr, bin_lo, bin_hi, n_bands, S_out, ar_out, V_out, info_yw,
+                      measure == HMV_MEASURE_GPDC ? nullptr : info_tf, workspace, workspace_bytes, chunk,
+                      measure == HMV_MEASURE_GPDC ? 1.0 : pivot_tau, flags, grid_hop, 0, grid_nwin, T, nullptr, nullptr,
+                      stream, aux_stream, measure, -1, nullptr, nullptr, &ens);
 }
 
 int64_t hmv_fad_workspace_bytes(int64_t n_series, int pmax) {

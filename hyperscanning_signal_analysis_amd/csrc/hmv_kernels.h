@@ -35,6 +35,30 @@ struct LagcombArgs {
   double* R;                // [n_win][p+1][MP][MP]
 };
 int launch_lagcomb(const LagcombArgs& a, int m_pad, hipStream_t st);
+// K1 of an event-locked ensemble (lagcov_ensemble.hip): trials (trial_rec, trial_start) in groups (CSR group_ptr), item =
+// (group, offset from every trial start of the group); R = the mean over the group's trials of the window's lag
+// covariances.  Every index array lives on the device.
+struct LagcovEnsArgs {
+  const double* x;          // [n_rec][m][ld]
+  long long rec_stride, ld;
+  long long T;              // samples per recording (shared form: lagged partners past it count as zero)
+  const long long* trial_rec;     // [n_trials]
+  const long long* trial_start;   // [n_trials]
+  const long long* group_ptr;     // [n_groups + 1]
+  const long long* item_group;    // [n_items]  } direct form only, of the items of THIS launch
+  const long long* item_offset;   // [n_items]  }
+  long long n_items;        // items of this launch
+  int m, n, p;
+  double* R;                // [n_items][p+1][MP][MP]
+  // shared-overlap form: the items of this launch are it0 .. it0 + n_items - 1 of the grid item = g * nwin + w, window w
+  // at offset w * hop, n = k * hop
+  long long it0, nwin, hop;
+  int k;
+  double* Q;                // scratch, lagcov_ensemble_q_tiles() * (p+1) * MP * MP doubles
+};
+bool lagcov_ensemble_shared_ok(int n, long long hop, int p, int max_k);      // does the shared form take this grid?
+long long lagcov_ensemble_q_tiles(long long n_items, long long nwin, int k);  // in stacks of (p+1) tiles
+int launch_lagcov_ensemble(const LagcovEnsArgs& a, int m_pad, bool shared, hipStream_t st);
 
 // ---- K2 Yule-Walker solve (block LDL^T of the block-Toeplitz normal equations) ------------------
 struct YwArgs {

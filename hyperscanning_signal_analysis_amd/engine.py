@@ -18,7 +18,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["Engine", "default_engine", "SingularMatrixError", "validate_items"]
+__all__ = ["Engine", "default_engine", "SingularMatrixError", "validate_items", "validate_trials"]
 
 
 # Pivot threshold of the per-frequency inverses of A(f) (K3): a row interchange happens only when some row's |re| + |im|
@@ -61,6 +61,69 @@ def validate_items(x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Te
         raise ValueError(f"item_rec must lie in [0, {n_rec}), got [{lim[0]}, {lim[1]}]")
     if lim[2] < 0 or lim[3] + int(n) > T:
         raise ValueError(f"windows [start, start + {n}) must lie in [0, {T}), got starts in [{lim[2]}, {lim[3]}]")
+
+
+def validate_trials(x: torch.Tensor, trial_rec: torch.Tensor, trial_start: torch.Tensor, group_ptr: torch.Tensor,
+                    item_group: torch.Tensor, item_offset: torch.Tensor, n: int, p: int):
+    """Refuse an event-locked ensemble the kernels would read out of bounds with, BEFORE anything is launched (the
+    counterpart of `validate_items` for `Engine.lagcov_ensemble` / `sliding_ensemble`).  x: (n_rec, m, T); trial e is the
+    epoch starting at trial_start[e] of recording trial_rec[e]; group g owns the trials group_ptr[g] .. group_ptr[g+1]-1;
+    item `it` is the window of n samples item_offset[it] samples after every trial start of group item_group[it].
+    Checked: int64 1-D tensors on x's device, group_ptr non-decreasing from 0 to the number of trials with no empty group,
+    trial_rec and item_group in range, every window of every trial inside its recording, n > p.  The ValueError names the
+    first offender.  Pure tensor logic: also runs on CPU tensors."""
+    n_rec, m, T = x.shape
+    n, p = int(n), int(p)
+    named = (("trial_rec", trial_rec), ("trial_start", trial_start), ("group_ptr", group_ptr), ("item_group", item_group),
+             ("item_offset", item_offset))
+    for name, t in named:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.device != x.device or t.dim() != 1:
+            raise ValueError(f"{name} must be a 1-D int64 tensor on {x.device}")
+    if trial_rec.numel() != trial_start.numel():
+        raise ValueError("trial_rec and trial_start must have the same length")
+    if item_group.numel() != item_offset.numel():
+        raise ValueError("item_group and item_offset must have the same length")
+    if n <= p:
+        raise ValueError(f"window length ({n}) must exceed the model order ({p})")
+    if n > T:
+        raise ValueError(f"window length ({n}) exceeds the recording length ({T})")
+    n_trials, n_groups = int(trial_rec.numel()), int(group_ptr.numel()) - 1
+    if n_groups < 1:
+        raise ValueError("group_ptr must have at least two entries (one group)")
+    gp = group_ptr.cpu()
+    if int(gp[0]) != 0 or int(gp[-1]) != n_trials:
+        raise ValueError(f"group_ptr must run from 0 to the number of trials ({n_trials}), got {int(gp[0])} .. {int(gp[-1])}")
+    counts = gp[1:] - gp[:-1]
+    if bool((counts < 0).any()):
+        g = int(torch.nonzero(counts < 0)[0])
+        raise ValueError(f"group_ptr must be non-decreasing (group {g}: {int(gp[g])} > {int(gp[g + 1])})")
+    if bool((counts == 0).any()):
+        raise ValueError(f"group {int(torch.nonzero(counts == 0)[0])} is empty: every group needs at least one trial")
+    bad = torch.nonzero((trial_rec < 0) | (trial_rec >= n_rec)).flatten()
+    if bad.numel():
+        e = int(bad[0])
+        raise ValueError(f"trial_rec must lie in [0, {n_rec}), got {int(trial_rec[e])} for trial {e}")
+    if item_group.numel() == 0:
+        return
+    bad = torch.nonzero((item_group < 0) | (item_group >= n_groups)).flatten()
+    if bad.numel():
+        it = int(bad[0])
+        raise ValueError(f"item_group must lie in [0, {n_groups}), got {int(item_group[it])} for item {it}")
+    # earliest and latest trial start of every group: a window lies inside for all trials iff it does for these two
+    gid = torch.repeat_interleave(torch.arange(n_groups, dtype=torch.int64), counts).to(x.device)
+    lo = torch.full((n_groups,), torch.iinfo(torch.int64).max, dtype=torch.int64, device=x.device)
+    hi = torch.full((n_groups,), torch.iinfo(torch.int64).min, dtype=torch.int64, device=x.device)
+    lo = lo.scatter_reduce(0, gid, trial_start, "amin")
+    hi = hi.scatter_reduce(0, gid, trial_start, "amax")
+    bad = torch.nonzero((lo[item_group] + item_offset < 0) | (hi[item_group] + item_offset + n > T)).flatten()
+    if bad.numel():
+        it = int(bad[0])
+        g, off = int(item_group[it]), int(item_offset[it])
+        st = trial_start[int(gp[g]):int(gp[g + 1])] + off
+        e = int(gp[g]) + int(torch.nonzero((st < 0) | (st + n > T))[0])
+        s0 = int(trial_start[e]) + off
+        raise ValueError(f"windows [start, start + {n}) must lie in [0, {T}): item {it} (group {g}, offset {off}) of "
+                         f"trial {e} covers [{s0}, {s0 + n})")
 
 
 MAX_ORDER = 32          # HMV_MAX_ORDER of include/hypermvar.h
@@ -744,6 +807,167 @@ class Engine:
                                                             "info: residual covariance not positive definite)")
             if not gpdc:
                 self.raise_on_info(infos[1], "mvar_transfer_function (inverse of A(f))", per_item=F)
+
+    # ------------------------------------------------------------------ event-locked ensembles (lagcov_ensemble.hip)
+    def _ensemble_args(self, x, trial_rec, trial_start, group_ptr, item_group, item_offset, n, p, grid, validate):
+        """Common front of `lagcov_ensemble` / `sliding_ensemble`: every index array checked (`validate_trials`), a declared
+        grid compared with item_group / item_offset.  Returns (x, n_groups, n_items, grid_hop, grid_nwin)."""
+        if p is None:
+            raise ValueError("ensemble fits need an integer model order p: the reference's mvar_criterion does not take "
+                             "(channels, samples, trials) input, so there is no automatic order to reproduce")
+        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
+        x = x if x.stride(2) == 1 else x.contiguous()
+        if validate:
+            validate_trials(x, trial_rec, trial_start, group_ptr, item_group, item_offset, n, p)
+        n_groups, n_items = int(group_ptr.numel()) - 1, int(item_group.numel())
+        g_hop, g_nwin = (int(v) for v in grid) if grid is not None else (0, 0)
+        if grid is not None and n_items:
+            # with a declared grid the shared form addresses by (item // n_win, (item % n_win) * hop) and never reads
+            # item_group / item_offset: they must say the same thing
+            if g_hop < 1 or g_nwin < 1 or n_items != n_groups * g_nwin:
+                raise ValueError("grid = (hop, n_win) does not match the number of items / groups")
+            k = torch.arange(n_items, dtype=torch.int64, device=self.device)
+            if validate and not (torch.equal(item_group, k // g_nwin) and torch.equal(item_offset, (k % g_nwin) * g_hop)):
+                raise ValueError("grid = (hop, n_win) contradicts item_group / item_offset "
+                                 "(items must be group-major, window-minor on the declared grid)")
+        return x, n_groups, n_items, g_hop, g_nwin
+
+    def lagcov_ensemble(self, x: torch.Tensor, trial_rec: torch.Tensor, trial_start: torch.Tensor, group_ptr: torch.Tensor,
+                        item_group: torch.Tensor, item_offset: torch.Tensor, n: int, p: int, grid=None, flags: int = 0,
+                        validate: bool = True):
+        """K1 of an event-locked ensemble: x (n_rec, m, T) -> R (items, p+1, MP, MP), the lag covariances of the window
+        item_offset[it] samples after every trial start of group item_group[it], averaged over the group's trials
+        (`count_corr` on 3-D input, mtmvar.py:54-85).  Index tensors as in `validate_trials`.  grid = (hop, n_win) declares
+        item = g * n_win + w at offset w * hop and lets the library share the overlap between windows
+        (`hmv_lagcov_ensemble_f64`; `_lib.FLAG_DIRECT_LAGCOV` keeps the direct form)."""
+        x, n_groups, n_items, g_hop, g_nwin = self._ensemble_args(x, trial_rec, trial_start, group_ptr, item_group,
+                                                                  item_offset, n, p, grid, validate)
+        n_rec, m, T = x.shape
+        mp = self.pad(m)
+        R = self.empty(n_items, p + 1, mp, mp)
+        if n_items == 0:
+            return R
+        nws = int(self.lib.hmv_lagcov_ensemble_workspace_doubles(n_items, m, int(n), int(p), g_hop, g_nwin))
+        if nws < 0:
+            raise ValueError(f"lagcov_ensemble: bad sizes (m={m}, n={n}, p={p})")
+        ws = self.empty(max(nws, 1))
+        with torch.cuda.device(self.device):
+            rc = self.lib.hmv_lagcov_ensemble_f64(
+                x.data_ptr(), x.stride(0), x.stride(1), T, trial_rec.data_ptr(), trial_start.data_ptr(), group_ptr.data_ptr(),
+                n_groups, item_group.data_ptr(), item_offset.data_ptr(), n_items, m, int(n), int(p), R.data_ptr(),
+                ws.data_ptr(), nws, g_hop, g_nwin, int(flags), self.stream())
+        _lib.check(rc, "hmv_lagcov_ensemble_f64")
+        return R
+
+    def sliding_ensemble(self, x: torch.Tensor, trial_rec: torch.Tensor, trial_start: torch.Tensor, group_ptr: torch.Tensor,
+                         item_group: torch.Tensor, item_offset: torch.Tensor, n: int, p: int, freqs, fs: float,
+                         measure: str = "ffdtf", bands=None, spectra: bool = False, out: torch.Tensor | None = None,
+                         return_ar: bool = False, check=True, chunk: int | None = None, grid=None, flags: int = 0,
+                         validate: bool = True):
+        """Connectivity of event-locked ensembles: for every item (group, offset) ONE model of order p is fitted to the lag
+        covariances averaged over the group's trials and `measure` ("ffdtf", "ddtf", "gpdc") is computed from it -- what the
+        reference's full_freq_dtf / direct_dtf / gen_partial_directed_coherence give for
+        `np.stack([trial windows], axis=2)` with `optimal_model_order=p`.  x (n_rec, m, T) -> (items, m, m, F), or the band
+        sums (items, m, m, n_bands) with `bands=(bin_lo, bin_hi)`.  One C-ABI call (`hmv_sliding_ensemble_f64`); only K1
+        differs from the single-trial calls.  Index tensors as in `validate_trials`, grid as in `lagcov_ensemble`.
+        spectra=True (ffdtf, no bands): returns (out, S) with S (items, m, m, F) complex, `multivariate_spectra` of the
+        same fit.  check: True raises SingularMatrixError naming item, group and offset of the failed fits; "nan"
+        NaN-fills them; "mask" appends the boolean mask of the failed items without synchronising; False skips the check.
+        return_ar appends (ar, V, infos).  p=None raises ValueError (no automatic order for ensembles)."""
+        if measure not in ("ffdtf", "ddtf", "gpdc"):
+            raise ValueError(f"measure must be 'ffdtf', 'ddtf' or 'gpdc', got {measure!r}")
+        if spectra and (measure != "ffdtf" or bands is not None):
+            raise ValueError("spectra come with the full ffDTF only")
+        x, n_groups, n_items, g_hop, g_nwin = self._ensemble_args(x, trial_rec, trial_start, group_ptr, item_group,
+                                                                  item_offset, n, p, grid, validate)
+        n_rec, m, T = x.shape
+        mp = self.pad(m)
+        n, p = int(n), int(p)
+        code = {"ffdtf": _lib.MEASURE_FFDTF, "ddtf": _lib.MEASURE_DDTF, "gpdc": _lib.MEASURE_GPDC}[measure]
+        gpdc = measure == "gpdc"
+        f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
+        F = int(f.numel())
+        nb = 0
+        if bands is not None:
+            b_lo, b_hi = self.band_tables(bands[0], bands[1], F)
+            nb = int(b_lo.numel())
+        last = nb if bands is not None else F
+
+        def finish(res, bad, ar, V, infos, S=None):
+            r = (res,) if S is None else (res, torch.view_as_complex(S))
+            if check == "mask":
+                r += (bad,)
+            if return_ar:
+                r += (ar, V, infos)
+            return r if len(r) > 1 else r[0]
+        if n_items == 0:                      # empty batch (torch gives empty tensors a null data pointer)
+            i32 = self.empty(0, dtype=torch.int32)
+            return finish(self.empty(0, m, m, last), torch.zeros(0, dtype=torch.bool, device=self.device),
+                          self.empty(0, mp, mp, p), self.empty(0, mp, mp), i32 if gpdc else (i32, i32),
+                          self.empty(0, m, m, F, 2) if spectra else None)
+        full_then_sum = bands is not None and (nb == 0 or (measure == "ffdtf" and (
+            not self.bands_in_kernel(m, F) or (flags & _lib.FLAG_UNFUSED_NORM))))
+        if full_then_sum:                     # the full arrays, then their band sums (as the single-trial calls do)
+            full, bad, ar, V, infos = self.sliding_ensemble(x, trial_rec, trial_start, group_ptr, item_group, item_offset, n,
+                                                            p, f, fs, measure, None, False, None, True, "mask", chunk, grid,
+                                                            flags, False)
+            red = self.band_sums(full, bands[0], bands[1])
+            if out is not None:
+                out.copy_(red)
+                red = out
+            self._ensemble_check(check, red, bad, infos, F, gpdc, item_group, item_offset)
+            return finish(red, bad, ar, V, infos)
+        if out is None:
+            out = self.empty(n_items, m, m, last)
+        assert out.is_contiguous() and tuple(out.shape) == (n_items, m, m, last)
+        S = self.empty(n_items, m, m, F, 2) if spectra else None
+        ws_bands = -1 if spectra else nb
+        wsf = self.lib.hmv_sliding_ensemble_workspace_bytes
+        if chunk is None:
+            per_item = int(wsf(code, 1, m, n, p, F, ws_bands, 0, 0))
+            chunk = max(1, min(n_items, self.max_workspace_bytes // max(per_item, 1)))
+        chunk = int(chunk)
+        nbytes = int(wsf(code, chunk, m, n, p, F, ws_bands, g_hop, g_nwin))
+        if nbytes < 0:
+            raise ValueError(f"sliding_ensemble: bad sizes (m={m}, n={n}, p={p}, F={F}, chunk={chunk})")
+        ws = self._workspace(nbytes)
+        ar = self.empty(n_items, mp, mp, p) if return_ar else None
+        V = self.empty(n_items, mp, mp) if return_ar else None
+        info_yw = self.empty(n_items, dtype=torch.int32)
+        info_tf = None if gpdc else self.empty(n_items * F, dtype=torch.int32)
+        lo_p, hi_p = (b_lo.data_ptr(), b_hi.data_ptr()) if nb else (0, 0)
+        with torch.cuda.device(self.device):
+            rc = self.lib.hmv_sliding_ensemble_f64(
+                code, x.data_ptr(), x.stride(0), x.stride(1), T, trial_rec.data_ptr(), trial_start.data_ptr(),
+                group_ptr.data_ptr(), n_groups, item_group.data_ptr(), item_offset.data_ptr(), n_items, m, n, p, f.data_ptr(),
+                F, float(fs), out.data_ptr(), lo_p, hi_p, nb, _ptr(S), _ptr(ar), _ptr(V), info_yw.data_ptr(), _ptr(info_tf),
+                ws.data_ptr(), nbytes, chunk, self.pivot_tau, int(flags), g_hop, g_nwin, self.stream(), 0)
+        _lib.check(rc, "hmv_sliding_ensemble_f64")
+        bad = info_yw != 0
+        if not gpdc:
+            bad = bad | (info_tf.view(n_items, F) != 0).any(dim=1)
+        infos = info_yw if gpdc else (info_yw, info_tf)
+        self._ensemble_check(check, out, bad, infos, F, gpdc, item_group, item_offset, S)
+        return finish(out, bad, ar, V, infos, S)
+
+    def _ensemble_check(self, check, out, bad, infos, F, gpdc, item_group, item_offset, S=None):
+        if check == "nan":
+            if bool(bad.any()):
+                out[bad] = float("nan")
+                if S is not None:
+                    S[bad] = float("nan")
+        elif check and check != "mask":
+            try:
+                self.raise_on_info(infos if gpdc else infos[0], "ar_coeff (Yule-Walker solve of the trial-averaged "
+                                   "covariances; a negative info: residual covariance not positive definite)")
+                if not gpdc:
+                    self.raise_on_info(infos[1], "mvar_transfer_function (inverse of A(f))", per_item=F)
+            except SingularMatrixError as err:       # say which group and which window of the epoch
+                items = torch.as_tensor(err.items, dtype=torch.int64, device=item_group.device)
+                err.groups = item_group[items].cpu().numpy()
+                err.offsets = item_offset[items].cpu().numpy()
+                err.args = (err.args[0], err.args[1] + f" (group {int(err.groups[0])}, window at offset {int(err.offsets[0])})")
+                raise
 
     # ------------------------------------------------------------------ surrogate significance (surrogate.hip)
     def surrogate_shift(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, shift: torch.Tensor,

@@ -10,6 +10,9 @@ With `p=None` every window gets the order `mvar_criterion(window, max_model_orde
 picks for it -- the reference's own default, `optimal_model_order=None` -- selected on the device in the same call.
 `sliding_significance` adds a surrogate test (shift or phase null) to the band values of any of the three.
 `sliding_fad` is `fad_decomposition` (mtmvar.py:607-757) of every channel of every window.
+`sliding_ensemble` / `sliding_ensemble_epochs` are the event-locked form: the reference's functions take `signals` of shape
+(channels, samples, trials) and fit ONE model to the trial-averaged covariances (`count_corr`, mtmvar.py:54-85); here a
+window slides through the epoch and every position is fitted from all repetitions of the event.
 """
 from __future__ import annotations
 
@@ -20,7 +23,7 @@ from .engine import Engine, default_engine
 
 __all__ = ["window_positions", "hop_positions", "create_windows", "sliding_ffdtf", "sliding_ffdtf_device", "window_items",
            "regular_grid", "sliding_ddtf", "sliding_ddtf_device", "sliding_gpdc", "sliding_gpdc_device", "sliding_fad",
-           "sliding_significance"]
+           "sliding_significance", "ensemble_items", "sliding_ensemble", "sliding_ensemble_epochs"]
 
 
 def window_positions(T: int, n_windows: int = 3, window_size=None):
@@ -300,3 +303,98 @@ def sliding_fad(signals, fs, window_size=None, n_windows=3, hop=None, model_orde
         return v.reshape((nw, m) + v.shape[1:]) if isinstance(v, np.ndarray) else v
     out = {k: ({kk: split(vv) for kk, vv in v.items()} if isinstance(v, dict) else split(v)) for k, v in out.items()}
     return out
+
+
+# ---- event-locked ensembles ---------------------------------------------------------------------------------------------
+def ensemble_items(onsets, pre: int, post: int, window_size: int, hop: int):
+    """Trial starts and window offsets of an event-locked analysis: every epoch runs from `pre` samples before its onset to
+    `post` samples after it, and windows of `window_size` samples start every `hop` samples inside it
+    (`hop_positions(pre + post, window_size, hop)`).  Returns (trial_start = onsets - pre, offsets), both int64."""
+    pre, post = int(pre), int(post)
+    if pre < 0 or post < 0:
+        raise ValueError("pre and post must be non-negative")
+    on = np.asarray(onsets, dtype=np.int64)
+    if on.ndim != 1:
+        raise ValueError("onsets must be one-dimensional")
+    return on - pre, hop_positions(pre + post, window_size, hop).astype(np.int64)
+
+
+def _ensemble_run(eng, xd, trial_rec, trial_start, counts, offsets, window_size, p, freqs, fs, measure, bands, spectra, check,
+                  share_overlap):
+    """Groups of counts[g] consecutive trials, every group with the same window offsets -> arrays (n_groups, n_windows, ...)."""
+    n_groups, n_win = len(counts), len(offsets)
+    dev = eng.device
+    group_ptr = torch.as_tensor(np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)).to(dev)
+    item_group = torch.arange(n_groups, dtype=torch.int64).repeat_interleave(n_win).to(dev)
+    item_offset = torch.as_tensor(np.asarray(offsets, dtype=np.int64)).repeat(n_groups).to(dev)
+    hop = int(offsets[1] - offsets[0]) if n_win > 1 else int(window_size)
+    regular = n_win >= 1 and np.array_equal(np.asarray(offsets), np.arange(n_win) * hop)
+    res = eng.sliding_ensemble(xd, torch.as_tensor(trial_rec).to(dev), torch.as_tensor(trial_start).to(dev), group_ptr,
+                               item_group, item_offset, int(window_size), p, freqs, fs, measure=measure, bands=bands,
+                               spectra=spectra, check=check, grid=(hop, n_win) if share_overlap and regular else None)
+    m = xd.shape[1]
+    shape = lambda a: a.view(n_groups, n_win, m, m, a.shape[-1]) if a.dim() == 4 else a.view(n_groups, n_win)  # noqa: E731
+    return tuple(shape(a) for a in res) if isinstance(res, tuple) else shape(res)
+
+
+def sliding_ensemble(x, onsets, window_size, p, freqs, fs, *, pre, post, hop, measure="ffdtf", bands=None, spectra=False,
+                     check=True, share_overlap=True, engine: Engine | None = None):
+    """Short-time connectivity of event-locked data.  x (m, T) with 1-D `onsets` -> (n_windows, m, m, F | n_bands); or
+    x (n_rec, m, T) with a list of onset arrays, one per recording (they may differ in length) -> (n_rec, n_windows, ...).
+    Window w covers the samples onset - pre + w * hop .. + window_size of every epoch; the result for it is the reference's
+    `full_freq_dtf` / `direct_dtf` / `gen_partial_directed_coherence` (measure "ffdtf" / "ddtf" / "gpdc") called with
+    `np.stack([x[:, s:s + window_size] for s in onsets - pre + w * hop], axis=2)` and `optimal_model_order=p`.
+    bands = (bin_lo, bin_hi): band sums instead of the full arrays.  spectra=True (ffdtf): (out, S) with
+    `multivariate_spectra` of the same fit.  check: True raises LinAlgError naming the failed window, "nan" NaN-fills it,
+    "mask" appends the boolean mask.  share_overlap=False keeps the direct form of K1.  p=None raises ValueError: the
+    reference's `mvar_criterion` does not take 3-D input, so there is no automatic order to reproduce."""
+    if p is None:
+        raise ValueError("sliding_ensemble needs an integer model order p (no automatic order for ensembles)")
+    single = np.ndim(x) == 2
+    on_list = [onsets] if single else list(onsets)
+    n_rec = 1 if single else int(np.shape(x)[0])
+    if len(on_list) != n_rec:
+        raise ValueError(f"{n_rec} recording(s) need {n_rec} onset array(s), got {len(on_list)}")
+    starts, offsets, counts = [], None, []
+    for on in on_list:
+        st, offsets = ensemble_items(on, pre, post, window_size, hop)
+        starts.append(st)
+        counts.append(len(st))
+    if min(counts) < 1:
+        raise ValueError(f"recording {int(np.argmin(counts))} has no onsets: every group needs at least one trial")
+    eng = engine or default_engine()
+    if isinstance(x, torch.Tensor):
+        xd = (x[None] if single else x).to(device=eng.device, dtype=torch.float64).contiguous()
+    else:
+        xd = eng.to_device(np.asarray(x, dtype=np.float64)[None] if single else np.asarray(x, dtype=np.float64))
+    trial_rec = np.repeat(np.arange(n_rec, dtype=np.int64), counts)
+    res = _ensemble_run(eng, xd, trial_rec, np.concatenate(starts), counts, offsets, window_size, p, freqs, fs, measure, bands,
+                        spectra, check, share_overlap)
+    return _to_host(res, single)
+
+
+def sliding_ensemble_epochs(epochs, window_size, hop, p, freqs, fs, *, measure="ffdtf", bands=None, spectra=False,
+                            check=True, share_overlap=True, engine: Engine | None = None):
+    """`sliding_ensemble` for epochs that are already cut, in the reference's own layout (m, L, trials): windows of
+    `window_size` samples every `hop` samples of the L-sample epoch, each fitted from all trials -> (n_windows, m, m, F |
+    n_bands).  A list of such arrays (same m and L, any numbers of trials) -> (n_groups, n_windows, ...)."""
+    if p is None:
+        raise ValueError("sliding_ensemble_epochs needs an integer model order p (no automatic order for ensembles)")
+    single = not isinstance(epochs, (list, tuple))
+    groups = [np.asarray(e, dtype=np.float64) for e in ([epochs] if single else epochs)]
+    if any(e.ndim != 3 for e in groups):
+        raise ValueError("epochs must have shape (channels, samples, trials)")
+    m, L = groups[0].shape[:2]
+    if any(e.shape[:2] != (m, L) for e in groups):
+        raise ValueError("all groups of epochs must share channels and samples")
+    counts = [e.shape[2] for e in groups]
+    if min(counts) < 1:
+        raise ValueError(f"group {int(np.argmin(counts))} has no trials: every group needs at least one trial")
+    eng = engine or default_engine()
+    # every trial becomes one recording of L samples that starts at its own sample 0
+    xd = eng.to_device(np.concatenate([np.moveaxis(e, 2, 0) for e in groups], axis=0))
+    n_tr = int(sum(counts))
+    res = _ensemble_run(eng, xd, np.arange(n_tr, dtype=np.int64), np.zeros(n_tr, dtype=np.int64), counts,
+                        hop_positions(L, window_size, hop).astype(np.int64), window_size, p, freqs, fs, measure, bands, spectra,
+                        check, share_overlap)
+    return _to_host(res, single)

@@ -356,6 +356,53 @@ int hmv_sliding_auto_f64(int measure, const double* x, int64_t rec_stride, int64
                          int64_t grid_hop, int64_t grid_first, int64_t grid_nwin, int64_t grid_T,
                          void* stream, void* aux_stream);
 
+/* Event-locked ensembles (csrc/lagcov_ensemble.hip).  Every estimator of the reference takes `signals` of shape
+ * (channels, samples, trials): count_corr (src/mtmvar.py:54-85) averages the lag covariances over the trials, ar_coeff
+ * (:96, :106-108) fits ONE model to the average, and full_freq_dtf (:236-284), multivariate_spectra (:165-201), direct_dtf
+ * (:341-385) and gen_partial_directed_coherence (:388-468) reach it through ar_coeff when a model order is given.  The
+ * two entries below do that for every window of an epoch in one call.
+ *   Trials: trial e is the epoch starting at sample trial_start[e] of recording trial_rec[e] (x: [n_rec][m][ld], T
+ *   samples per recording).  Groups (one dyad x condition each), CSR: group g owns the trials group_ptr[g] ..
+ *   group_ptr[g+1]-1 (group_ptr: n_groups + 1 entries; groups may differ in size, none may be empty).  Item `it` is the
+ *   window of n samples that starts item_offset[it] samples after every trial start of group item_group[it]:
+ *       R_l(it) = (1/E_g) sum_{e in g} (1/n) X_e[:, :n-l] X_e[:, l:]^T,  X_e = x[trial_rec[e]][:, trial_start[e] + item_offset[it] : + n]
+ *   (biased, not demeaned).  All five index arrays are int64 DEVICE arrays whose contents the caller has checked
+ *   (hyperscanning_signal_analysis_amd.engine.validate_trials): the kernels address with them.
+ *   grid_hop = 0: arbitrary offsets.  grid_hop > 0 declares a regular grid: the caller vouches that n_items = n_groups *
+ *   grid_nwin and that item g * grid_nwin + w belongs to group g and has offset w * grid_hop.  K1 then takes the
+ *   shared-overlap form -- hop-block sums over all trials once, windows assembled from k = n / grid_hop blocks -- when
+ *   n is a whole number of hops, 2 <= k <= HMV_MAX_HOPS_ENSEMBLE, grid_hop > p, the hop rounded up to 4 samples plus p is
+ *   at most 96 and HMV_FLAG_DIRECT_LAGCOV is not set; otherwise the direct form (the trial loop inside lagcov_kernel's
+ *   mapping), whose result for groups of ONE trial has the bits of hmv_lagcov_f64.  The two forms agree to rounding.
+ *
+ * hmv_lagcov_ensemble_f64: K1 alone.  R [n_items][p+1][MP][MP]; workspace: hmv_lagcov_ensemble_workspace_doubles(n_items,
+ *   m, n, p, grid_hop, grid_nwin) doubles (0 without a grid; -1 for bad arguments), workspace_doubles its size.
+ * hmv_sliding_ensemble_f64: the fused path K1 -> K2 -> K3 (-> K5) / dDTF / GPDC on the trial-averaged covariances; every
+ *   stage after K1 is that of the single-trial entries.  measure, out, bin_lo / bin_hi / n_bands, S_out, ar_out, V_out,
+ *   info_yw, info_tf, chunk, pivot_tau, flags as in hmv_sliding_auto_f64 (fixed order p).  workspace:
+ *   hmv_sliding_ensemble_workspace_bytes(measure, chunk, m, n, p, F, n_bands, grid_hop, grid_nwin), n_bands = -1 for the
+ *   full ffDTF together with S_out.
+ * Refused before any launch: channel count (-1), order (-2), n <= p (-3), null pointers (-4), workspace too small (-7),
+ *   an inconsistent grid (-9: grid_hop < 0, grid_nwin < 1, n_items != n_groups * grid_nwin, (grid_nwin - 1) * grid_hop + n >
+ *   T, ld < T), n_groups < 1 (-10). */
+#define HMV_MAX_HOPS_ENSEMBLE 32
+int64_t hmv_lagcov_ensemble_workspace_doubles(int64_t n_items, int m, int n, int p, int64_t grid_hop, int64_t grid_nwin);
+int hmv_lagcov_ensemble_f64(const double* x, int64_t rec_stride, int64_t ld, int64_t T,
+                            const int64_t* trial_rec, const int64_t* trial_start, const int64_t* group_ptr,
+                            int64_t n_groups, const int64_t* item_group, const int64_t* item_offset, int64_t n_items,
+                            int m, int n, int p, double* R, double* workspace, int64_t workspace_doubles,
+                            int64_t grid_hop, int64_t grid_nwin, int64_t flags, void* stream);
+int64_t hmv_sliding_ensemble_workspace_bytes(int measure, int64_t chunk, int m, int n, int p, int F, int n_bands,
+                                             int64_t grid_hop, int64_t grid_nwin);
+int hmv_sliding_ensemble_f64(int measure, const double* x, int64_t rec_stride, int64_t ld, int64_t T,
+                             const int64_t* trial_rec, const int64_t* trial_start, const int64_t* group_ptr,
+                             int64_t n_groups, const int64_t* item_group, const int64_t* item_offset, int64_t n_items,
+                             int m, int n, int p, const double* freqs, int F, double fs,
+                             double* out, const int32_t* bin_lo, const int32_t* bin_hi, int n_bands, double* S_out,
+                             double* ar_out, double* V_out, int32_t* info_yw, int32_t* info_tf,
+                             void* workspace, int64_t workspace_bytes, int64_t chunk, double pivot_tau, int64_t flags,
+                             int64_t grid_hop, int64_t grid_nwin, void* stream, void* aux_stream);
+
 /* FAD (frequency-amplitude-damping) decomposition of univariate AR models, batched over series.  Replaces
  * fad_decomposition (src/mtmvar.py:607-757): order selection as mvar_criterion at m = 1 (:551-601), the fit of ar_coeff
  * (:90-123, count_corr :35-87: biased 1/n autocovariance, no demeaning) by Levinson-Durbin, and the partial-fraction
