@@ -537,6 +537,15 @@ SlidingWs sliding_layout(int64_t chunk, int mp, int p, int F, bool bands = false
   w.total = o;
   return w;
 }
+// The range checks every hmv_sliding_*_workspace_bytes shares, then the layout's size; -1 for sizes no entry accepts.
+int64_t sliding_bytes(int64_t chunk, int m, int p, int F, int n_bands = 0, bool spectra = false, int measure = MEAS_FFDTF,
+                      int64_t q_tiles = -1) {
+  const int mp = pad_of(m);
+  if (mp < 0 || chunk < 1 || p < 1 || p > HMV_MAX_ORDER || F < 1 || n_bands < 0 || measure < MEAS_FFDTF ||
+      measure > MEAS_GPDC)
+    return -1;
+  return (int64_t)sliding_layout(chunk, mp, p, F, n_bands > 0, spectra, measure, q_tiles).total;
+}
 // Fork / join events of the two-stream K2 split: created once per (host thread, device), not per call.
 struct ForkJoin {
   hipEvent_t fork = nullptr, join = nullptr;
@@ -555,11 +564,7 @@ ForkJoin* fork_join_events() {
 }
 }  // namespace
 
-int64_t hmv_sliding_workspace_bytes(int64_t chunk, int m, int p, int F) {
-  const int mp = pad_of(m);
-  if (mp < 0 || chunk < 1 || p < 1 || p > HMV_MAX_ORDER || F < 1) return -1;
-  return (int64_t)sliding_layout(chunk, mp, p, F).total;
-}
+int64_t hmv_sliding_workspace_bytes(int64_t chunk, int m, int p, int F) { return sliding_bytes(chunk, m, p, F); }
 
 namespace {
 // An event-locked ensemble in place of single windows (hmv_sliding_ensemble_f64): item_rec / item_start of sliding_impl
@@ -570,64 +575,97 @@ struct EnsDesc {
   const int64_t* group_ptr;
   int64_t n_groups, T;
 };
-int sliding_impl(const char* who, const double* x, int64_t rec_stride, int64_t ld, const int64_t* item_rec,
-                 const int64_t* item_start, int64_t n_items, int m, int n, int p, const double* freqs, int F, double fs,
-                 double* ffdtf, double* band_out, const int32_t* bin_lo, const int32_t* bin_hi, int n_bands, double* S_out,
-                 double* ar_out, double* V_out, int32_t* info_yw, int32_t* info_tf, void* workspace, int64_t workspace_bytes, int64_t chunk,
-                 double pivot_tau, int64_t flags, int64_t grid_hop, int64_t grid_first, int64_t grid_nwin, int64_t grid_T,
-                 void* ev_k3_start, void* ev_k3_stop, void* stream, void* aux_stream, int measure = MEAS_FFDTF,
-                 int crit = -1, int32_t* order_out = nullptr, double* crit_out = nullptr, const EnsDesc* ens = nullptr) {
+// Everything sliding_impl is told, by name; a field left alone means "not asked for".  The exported entries below fill in
+// what they have.  `ffdtf` receives the full (m, m, F) arrays, `band_out` (with bin_lo / bin_hi / n_bands) the band sums.
+struct SlidingArgs {
+  const char* who;                                  // the entry's own name, for hmv_last_error()
+  const double* x = nullptr;
+  int64_t rec_stride = 0, ld = 0;
+  const int64_t* item_rec = nullptr;                // (ensemble: item_group)
+  const int64_t* item_start = nullptr;              // (ensemble: item_offset)
+  int64_t n_items = 0;
+  int m = 0, n = 0, p = 0;
+  const double* freqs = nullptr;
+  int F = 0;
+  double fs = 0.0;
+  double* ffdtf = nullptr;
+  double* band_out = nullptr;
+  const int32_t* bin_lo = nullptr;
+  const int32_t* bin_hi = nullptr;
+  int n_bands = 0;
+  double* S_out = nullptr;
+  double* ar_out = nullptr;
+  double* V_out = nullptr;
+  int32_t* info_yw = nullptr;
+  int32_t* info_tf = nullptr;
+  void* workspace = nullptr;
+  int64_t workspace_bytes = 0, chunk = 0;
+  double pivot_tau = 1.0;
+  int64_t flags = 0, grid_hop = 0, grid_first = 0, grid_nwin = 0, grid_T = 0;
+  void* ev_k3_start = nullptr;
+  void* ev_k3_stop = nullptr;
+  void* stream = nullptr;
+  void* aux_stream = nullptr;
+  int measure = MEAS_FFDTF;
+  int crit = -1;                                    // >= 0: automatic order, with order_out (and crit_out)
+  int32_t* order_out = nullptr;
+  double* crit_out = nullptr;
+  const EnsDesc* ens = nullptr;
+};
+int sliding_impl(const SlidingArgs& a) {
   // crit >= 0: automatic order (hmv_sliding_auto_f64) -- p is the largest order tried, K1 sums p + 1 lags, K2 selects every
   // window's order and leaves its coefficients zero-padded to p lags, and every later stage runs at p on those (the
   // added terms of A(f) = I - sum_k ar_k tw_k are exact zeros)
-  const bool automatic = crit >= 0;
-  const bool bands = (band_out != nullptr);
+  const bool automatic = a.crit >= 0;
+  const bool bands = (a.band_out != nullptr);
   auto fail = [&](int code, const char* msg) {
     const char* own = strchr(msg, ':');             // messages below are written "hmv_sliding_ffdtf_f64: ..."
     char buf[220];
-    snprintf(buf, sizeof(buf), "%s%s", who, own ? own : msg);
+    snprintf(buf, sizeof(buf), "%s%s", a.who, own ? own : msg);
     return ::fail(code, buf);
   };
-  const int mp = pad_of(m);
+  const int mp = pad_of(a.m);
   if (mp < 0) return fail(-1, "hmv_sliding_ffdtf_f64: channel count must be in 1..64");
-  if (p < 1 || p > HMV_MAX_ORDER) return fail(-2, "hmv_sliding_ffdtf_f64: model order must be in 1..32");
-  if (n <= p) return fail(-3, "hmv_sliding_ffdtf_f64: window shorter than the model order");
-  if (automatic && crit > 2) return fail(-5, "hmv_sliding_ffdtf_f64: criterion must be 0 (AIC), 1 (HQ) or 2 (SC)");
-  if (automatic && (flags & (HMV_FLAG_YW_TILED | HMV_FLAG_YW_ONE_LAUNCH)))
+  if (a.p < 1 || a.p > HMV_MAX_ORDER) return fail(-2, "hmv_sliding_ffdtf_f64: model order must be in 1..32");
+  if (a.n <= a.p) return fail(-3, "hmv_sliding_ffdtf_f64: window shorter than the model order");
+  if (automatic && a.crit > 2) return fail(-5, "hmv_sliding_ffdtf_f64: criterion must be 0 (AIC), 1 (HQ) or 2 (SC)");
+  if (automatic && (a.flags & (HMV_FLAG_YW_TILED | HMV_FLAG_YW_ONE_LAUNCH)))
     return fail(-6, "hmv_sliding_ffdtf_f64: the LDL^T forms of K2 have no automatic order");
-  if (n_items == 0) return 0;                                    // empty batch: nothing to do, nothing to check
-  if (automatic && !order_out) return fail(-4, "hmv_sliding_ffdtf_f64: null pointer / empty grid");
-  if (!x || !item_rec || !item_start || !freqs || (!ffdtf && !bands) || !info_yw || (!info_tf && measure != MEAS_GPDC) ||
-      !workspace || F < 1 || chunk < 1)
+  if (a.n_items == 0) return 0;                                    // empty batch: nothing to do, nothing to check
+  if (automatic && !a.order_out) return fail(-4, "hmv_sliding_ffdtf_f64: null pointer / empty grid");
+  if (!a.x || !a.item_rec || !a.item_start || !a.freqs || (!a.ffdtf && !bands) || !a.info_yw ||
+      (!a.info_tf && a.measure != MEAS_GPDC) || !a.workspace || a.F < 1 || a.chunk < 1)
     return fail(-4, "hmv_sliding_ffdtf_f64: null pointer / empty grid");
-  if (bands && (!bin_lo || !bin_hi || n_bands < 1)) return fail(-4, "hmv_sliding_ffdtf_f64: band bins missing");
+  if (bands && (!a.bin_lo || !a.bin_hi || a.n_bands < 1)) return fail(-4, "hmv_sliding_ffdtf_f64: band bins missing");
   bool ens_shared = false;
-  if (ens) {
-    if (!ens->trial_rec || !ens->trial_start || !ens->group_ptr) return fail(-4, "hmv_sliding_ffdtf_f64: null pointer / empty grid");
-    if (ens->n_groups < 1) return fail(-10, "hmv_sliding_ffdtf_f64: n_groups must be >= 1");
-    if (grid_hop != 0 && !ens_grid_ok(n_items, ens->n_groups, n, ld, ens->T, grid_hop, grid_nwin))
+  if (a.ens) {
+    if (!a.ens->trial_rec || !a.ens->trial_start || !a.ens->group_ptr)
+      return fail(-4, "hmv_sliding_ffdtf_f64: null pointer / empty grid");
+    if (a.ens->n_groups < 1) return fail(-10, "hmv_sliding_ffdtf_f64: n_groups must be >= 1");
+    if (a.grid_hop != 0 && !ens_grid_ok(a.n_items, a.ens->n_groups, a.n, a.ld, a.ens->T, a.grid_hop, a.grid_nwin))
       return fail(-9, "hmv_sliding_ffdtf_f64: inconsistent regular window grid");
-    ens_shared = ens_shared_form(n, p, grid_hop, flags);
+    ens_shared = ens_shared_form(a.n, a.p, a.grid_hop, a.flags);
   }
-  const SlidingWs w = sliding_layout(chunk, mp, p, F, bands, S_out != nullptr, measure,
-                                     ens ? (ens_shared ? ens_q_tiles(chunk, n, p, grid_hop, grid_nwin) : 0) : -1);
-  if ((int64_t)w.total > workspace_bytes) return fail(-7, "hmv_sliding_ffdtf_f64: workspace too small");
+  const SlidingWs w = sliding_layout(a.chunk, mp, a.p, a.F, bands, a.S_out != nullptr, a.measure,
+                                     a.ens ? (ens_shared ? ens_q_tiles(a.chunk, a.n, a.p, a.grid_hop, a.grid_nwin) : 0) : -1);
+  if ((int64_t)w.total > a.workspace_bytes) return fail(-7, "hmv_sliding_ffdtf_f64: workspace too small");
   // Regular grid (the caller vouches: item = rec * grid_nwin + w starts at grid_first + w * grid_hop of recording rec,
   // recordings are grid_T samples long): K1 sums every hop block once and assembles the windows from the blocks.
-  bool regular = !ens && grid_hop > 0 && !(flags & HMV_FLAG_DIRECT_LAGCOV);
+  bool regular = !a.ens && a.grid_hop > 0 && !(a.flags & HMV_FLAG_DIRECT_LAGCOV);
   if (regular) {
-    if (grid_nwin < 1 || grid_first < 0 || n_items % grid_nwin != 0 || grid_first + (grid_nwin - 1) * grid_hop + n > grid_T ||
-        ld < grid_T)
+    if (a.grid_nwin < 1 || a.grid_first < 0 || a.n_items % a.grid_nwin != 0 ||
+        a.grid_first + (a.grid_nwin - 1) * a.grid_hop + a.n > a.grid_T || a.ld < a.grid_T)
       return fail(-9, "hmv_sliding_ffdtf_f64: inconsistent regular window grid");
-    regular = (n % grid_hop == 0) && (n / grid_hop >= 2) && (n / grid_hop <= HMV_MAX_HOPS_PER_WINDOW) && grid_hop > p;
+    regular = (a.n % a.grid_hop == 0) && (a.n / a.grid_hop >= 2) && (a.n / a.grid_hop <= HMV_MAX_HOPS_PER_WINDOW) &&
+              a.grid_hop > a.p;
   }
   // Second stream (HMV_FLAG_YW_TILED only): the tile-per-workgroup form of K2 is a chain of ~25 launches of at
   // most a few workgroups per window that cannot fill the chip; it runs as two half-batches, one per stream,
   // whose launches interleave on the device (fork after K1, join before K3).  The default one-launch form of K2
   // needs none of this.  Chunk pipelining (K1/K2 of chunk c+1 under K3 of chunk c) was measured and does NOT
   // work: K3 holds every wave slot and starves the other stream.
-  hipStream_t st0 = S(stream), st1 = S(aux_stream);
-  const bool split = (aux_stream && aux_stream != stream) && !(flags & HMV_FLAG_YW_ONE_LAUNCH);
+  hipStream_t st0 = S(a.stream), st1 = S(a.aux_stream);
+  const bool split = (a.aux_stream && a.aux_stream != a.stream) && !(a.flags & HMV_FLAG_YW_ONE_LAUNCH);
   ForkJoin* fj = nullptr;
   if (split) {
     fj = fork_join_events();
@@ -635,8 +673,8 @@ int sliding_impl(const char* who, const double* x, int64_t rec_stride, int64_t l
   }
   int rc = 0;
   const size_t t = (size_t)mp * mp;
-  const int64_t n_chunks = (n_items + chunk - 1) / chunk;
-  char* base = static_cast<char*>(workspace);
+  const int64_t n_chunks = (a.n_items + a.chunk - 1) / a.chunk;
+  char* base = static_cast<char*>(a.workspace);
   double* R = reinterpret_cast<double*>(base + w.off_R);
   double* Qb = reinterpret_cast<double*>(base + w.off_Q);
   double* ws = reinterpret_cast<double*>(base + w.off_ws);
@@ -645,55 +683,57 @@ int sliding_impl(const char* who, const double* x, int64_t rec_stride, int64_t l
   void* tfws = base + w.off_tf;
   double* den = reinterpret_cast<double*>(base + w.off_den);
   double* tw = reinterpret_cast<double*>(base + w.off_tw);
-  const bool k3_bands = bands && measure == MEAS_FFDTF;
-  const int64_t tfws_bytes = (int64_t)tf_ff_layout(chunk, mp, p, F, k3_bands).total;
-  rc = hmv_twiddles_f64(freqs, F, fs, p, tw, st0);
-  const size_t ws_item = (size_t)hmv_yw_workspace_doubles(m, p);
+  const bool k3_bands = bands && a.measure == MEAS_FFDTF;
+  const int64_t tfws_bytes = (int64_t)tf_ff_layout(a.chunk, mp, a.p, a.F, k3_bands).total;
+  rc = hmv_twiddles_f64(a.freqs, a.F, a.fs, a.p, tw, st0);
+  const size_t ws_item = (size_t)hmv_yw_workspace_doubles(a.m, a.p);
   for (int64_t ci = 0; ci < n_chunks && rc == 0; ++ci) {
-    const int64_t i0 = ci * chunk;
-    const int64_t c = (n_items - i0 < chunk) ? (n_items - i0) : chunk;
-    double* ar_c = ar_out ? ar_out + (size_t)i0 * t * p : ar;
-    double* V_c = V_out ? V_out + (size_t)i0 * t : V;
-    if (ens) {
+    const int64_t i0 = ci * a.chunk;
+    const int64_t c = (a.n_items - i0 < a.chunk) ? (a.n_items - i0) : a.chunk;
+    double* ar_c = a.ar_out ? a.ar_out + (size_t)i0 * t * a.p : ar;
+    double* V_c = a.V_out ? a.V_out + (size_t)i0 * t : V;
+    if (a.ens) {
       hmv::LagcovEnsArgs ea{};
-      ea.x = x; ea.rec_stride = rec_stride; ea.ld = ld; ea.T = ens->T;
-      ea.trial_rec = reinterpret_cast<const long long*>(ens->trial_rec);
-      ea.trial_start = reinterpret_cast<const long long*>(ens->trial_start);
-      ea.group_ptr = reinterpret_cast<const long long*>(ens->group_ptr);
-      ea.item_group = reinterpret_cast<const long long*>(item_rec + i0);
-      ea.item_offset = reinterpret_cast<const long long*>(item_start + i0);
-      ea.n_items = c; ea.m = m; ea.n = n; ea.p = p; ea.R = R;
-      if (ens_shared) { ea.it0 = i0; ea.nwin = grid_nwin; ea.hop = grid_hop; ea.k = (int)(n / grid_hop); ea.Q = Qb; }
+      ea.x = a.x; ea.rec_stride = a.rec_stride; ea.ld = a.ld; ea.T = a.ens->T;
+      ea.trial_rec = reinterpret_cast<const long long*>(a.ens->trial_rec);
+      ea.trial_start = reinterpret_cast<const long long*>(a.ens->trial_start);
+      ea.group_ptr = reinterpret_cast<const long long*>(a.ens->group_ptr);
+      ea.item_group = reinterpret_cast<const long long*>(a.item_rec + i0);
+      ea.item_offset = reinterpret_cast<const long long*>(a.item_start + i0);
+      ea.n_items = c; ea.m = a.m; ea.n = a.n; ea.p = a.p; ea.R = R;
+      if (ens_shared) {
+        ea.it0 = i0; ea.nwin = a.grid_nwin; ea.hop = a.grid_hop; ea.k = (int)(a.n / a.grid_hop); ea.Q = Qb;
+      }
       rc = hmv::launch_lagcov_ensemble(ea, mp, ens_shared, st0);
     } else if (regular) {
       // items i0 .. i0+c-1 as runs of consecutive windows of one recording each (item = rec * grid_nwin + w)
       for (int64_t it = i0; it < i0 + c && rc == 0;) {
-        const int64_t rec = it / grid_nwin, w0 = it - rec * grid_nwin;
-        const int64_t run = ((grid_nwin - w0) < (i0 + c - it)) ? (grid_nwin - w0) : (i0 + c - it);
-        rc = hmv_lagcov_regular_f64(x + rec * rec_stride, ld, grid_T, grid_first + w0 * grid_hop, grid_hop, run, m, n, p,
-                                    R + (size_t)(it - i0) * (p + 1) * t, Qb, st0);
+        const int64_t rec = it / a.grid_nwin, w0 = it - rec * a.grid_nwin;
+        const int64_t run = ((a.grid_nwin - w0) < (i0 + c - it)) ? (a.grid_nwin - w0) : (i0 + c - it);
+        rc = hmv_lagcov_regular_f64(a.x + rec * a.rec_stride, a.ld, a.grid_T, a.grid_first + w0 * a.grid_hop, a.grid_hop,
+                                    run, a.m, a.n, a.p, R + (size_t)(it - i0) * (a.p + 1) * t, Qb, st0);
         it += run;
       }
     } else {
-      rc = hmv_lagcov_f64(x, rec_stride, ld, item_rec + i0, item_start + i0, c, m, n, p, R, st0);
+      rc = hmv_lagcov_f64(a.x, a.rec_stride, a.ld, a.item_rec + i0, a.item_start + i0, c, a.m, a.n, a.p, R, st0);
     }
     if (rc) break;
     if (automatic) {
       hmv::YwArgs ya{};
-      ya.R = R; ya.n_items = c; ya.m = m; ya.p = p; ya.ws = ws; ya.ar = ar_c; ya.V = V_c; ya.info = info_yw + i0;
+      ya.R = R; ya.n_items = c; ya.m = a.m; ya.p = a.p; ya.ws = ws; ya.ar = ar_c; ya.V = V_c; ya.info = a.info_yw + i0;
       ya.tiled = -1;
       hmv::YwAutoArgs sel{};
-      sel.n = n; sel.crit_c = crit_factor(crit, n); sel.order_out = order_out + i0;
-      sel.crit_out = crit_out ? crit_out + (size_t)i0 * p : nullptr;
+      sel.n = a.n; sel.crit_c = crit_factor(a.crit, a.n); sel.order_out = a.order_out + i0;
+      sel.crit_out = a.crit_out ? a.crit_out + (size_t)i0 * a.p : nullptr;
       rc = hmv::launch_yw_auto(ya, sel, mp, st0);
       if (rc) break;
     }
     // the tiled form of K2 (asked for, or chosen for a large 64-channel chunk) as two half-batches
     // K2: the Levinson-Whittle recursion unless an LDL^T form is asked for (or HMV_TUNE_YW_FORM = 1, which picks the
     // LDL^T form by batch shape as before: the launch chain for large 64-channel chunks)
-    const bool ldl = (flags & (HMV_FLAG_YW_TILED | HMV_FLAG_YW_ONE_LAUNCH)) || hmv::tuning(HMV_TUNE_YW_FORM) == 1;
-    const bool tiled = (flags & HMV_FLAG_YW_TILED) || (ldl && !(flags & HMV_FLAG_YW_ONE_LAUNCH) && mp == 64 && c >= 128);
-    const int64_t yw_flags = (flags & ~(int64_t)(HMV_FLAG_YW_TILED | HMV_FLAG_YW_ONE_LAUNCH)) |
+    const bool ldl = (a.flags & (HMV_FLAG_YW_TILED | HMV_FLAG_YW_ONE_LAUNCH)) || hmv::tuning(HMV_TUNE_YW_FORM) == 1;
+    const bool tiled = (a.flags & HMV_FLAG_YW_TILED) || (ldl && !(a.flags & HMV_FLAG_YW_ONE_LAUNCH) && mp == 64 && c >= 128);
+    const int64_t yw_flags = (a.flags & ~(int64_t)(HMV_FLAG_YW_TILED | HMV_FLAG_YW_ONE_LAUNCH)) |
                              (ldl ? (tiled ? HMV_FLAG_YW_TILED : HMV_FLAG_YW_ONE_LAUNCH) : 0);
     const int64_t c0 = (split && tiled && c >= 16) ? (c + 1) / 2 : c, c1 = c - c0;
     if (c1 > 0 && !automatic) {
@@ -702,8 +742,8 @@ int sliding_impl(const char* who, const double* x, int64_t rec_stride, int64_t l
       int hrc = (int)hipEventRecord(fj->fork, st0);
       if (!hrc) hrc = (int)hipStreamWaitEvent(st1, fj->fork, 0);
       if (hrc) { rc = hrc; break; }                      // nothing was put on st1
-      rc = hmv_yw_solve_f64(R + (size_t)c0 * (p + 1) * t, c1, m, p, ws + (size_t)c0 * ws_item,
-                            ar_c + (size_t)c0 * t * p, V_c + (size_t)c0 * t, nullptr, info_yw + i0 + c0, yw_flags, st1);
+      rc = hmv_yw_solve_f64(R + (size_t)c0 * (a.p + 1) * t, c1, a.m, a.p, ws + (size_t)c0 * ws_item,
+                            ar_c + (size_t)c0 * t * a.p, V_c + (size_t)c0 * t, nullptr, a.info_yw + i0 + c0, yw_flags, st1);
       hrc = (int)hipEventRecord(fj->join, st1);
       if (!hrc) hrc = (int)hipStreamWaitEvent(st0, fj->join, 0);
       if (hrc) {                                         // cannot express the join as an event: join on the host
@@ -712,35 +752,38 @@ int sliding_impl(const char* who, const double* x, int64_t rec_stride, int64_t l
       }
       if (rc) break;
     }
-    if (!automatic) rc = hmv_yw_solve_f64(R, c0, m, p, ws, ar_c, V_c, nullptr, info_yw + i0, yw_flags, st0);
+    if (!automatic) rc = hmv_yw_solve_f64(R, c0, a.m, a.p, ws, ar_c, V_c, nullptr, a.info_yw + i0, yw_flags, st0);
     if (rc) break;
     const bool last = (ci == n_chunks - 1);
-    double* Hc = S_out ? reinterpret_cast<double*>(base + w.off_H) : nullptr;
+    double* Hc = a.S_out ? reinterpret_cast<double*>(base + w.off_H) : nullptr;
     // dDTF / GPDC: the chunk's full array goes to the output, or (band form) to scratch ahead of its band sums
-    double* full_c = (measure == MEAS_FFDTF) ? nullptr
-                     : bands ? reinterpret_cast<double*>(base + w.off_full) : ffdtf + (size_t)i0 * m * m * F;
-    if (measure == MEAS_GPDC) {
-      rc = hmv::launch_gpdc_sliding(ar_c, V_c, tw, full_c, c, F, m, mp, p, st0);
+    double* full_c = (a.measure == MEAS_FFDTF) ? nullptr
+                     : bands ? reinterpret_cast<double*>(base + w.off_full) : a.ffdtf + (size_t)i0 * a.m * a.m * a.F;
+    if (a.measure == MEAS_GPDC) {
+      rc = hmv::launch_gpdc_sliding(ar_c, V_c, tw, full_c, c, a.F, a.m, mp, a.p, st0);
     } else {
-      rc = tf_ffdtf_impl(who, ar_c, c, m, p, tw, F, k3_bands ? nullptr : (full_c ? full_c : ffdtf + (size_t)i0 * m * m * F),
-                         k3_bands ? band_out + (size_t)i0 * m * m * n_bands : nullptr, bin_lo, bin_hi, n_bands, den, Hc,
-                         info_tf + (size_t)i0 * F, pivot_tau, tfws, tfws_bytes, flags, last ? ev_k3_start : nullptr,
-                         last ? ev_k3_stop : nullptr, st0);
+      rc = tf_ffdtf_impl(a.who, ar_c, c, a.m, a.p, tw, a.F,
+                         k3_bands ? nullptr : (full_c ? full_c : a.ffdtf + (size_t)i0 * a.m * a.m * a.F),
+                         k3_bands ? a.band_out + (size_t)i0 * a.m * a.m * a.n_bands : nullptr, a.bin_lo, a.bin_hi,
+                         a.n_bands, den, Hc, a.info_tf + (size_t)i0 * a.F, a.pivot_tau, tfws, tfws_bytes, a.flags,
+                         last ? a.ev_k3_start : nullptr, last ? a.ev_k3_stop : nullptr, st0);
     }
-    if (!rc && measure == MEAS_DDTF) {     // |kappa| from W(f) = A^T V^-1 A, multiplied into K3's ffDTF in place
+    if (!rc && a.measure == MEAS_DDTF) {     // |kappa| from W(f) = A^T V^-1 A, multiplied into K3's ffDTF in place
       hmv::DdtfArgs da{};
-      da.ar = ar_c; da.V = V_c; da.info_yw = info_yw + i0;
+      da.ar = ar_c; da.V = V_c; da.info_yw = a.info_yw + i0;
       da.B = reinterpret_cast<double*>(base + w.off_B); da.G = reinterpret_cast<double*>(base + w.off_G);
-      da.freqs = freqs; da.fs = fs; da.ff = full_c; da.out = full_c; da.n_items = c; da.F = F; da.m = m; da.p = p;
+      da.freqs = a.freqs; da.fs = a.fs; da.ff = full_c; da.out = full_c;
+      da.n_items = c; da.F = a.F; da.m = a.m; da.p = a.p;
       rc = hmv::launch_ddtf_sliding(da, mp, st0);
     }
-    if (!rc && measure != MEAS_FFDTF && bands)
-      rc = hmv::launch_band_sums(full_c, reinterpret_cast<const int*>(bin_lo), reinterpret_cast<const int*>(bin_hi),
-                                 band_out + (size_t)i0 * m * m * n_bands, c * (long long)m * m, F, n_bands, st0);
-    if (!rc && S_out) {      // K5 from the same inverses and the same fit; V is this library's own (symmetric) estimate
+    if (!rc && a.measure != MEAS_FFDTF && bands)
+      rc = hmv::launch_band_sums(full_c, reinterpret_cast<const int*>(a.bin_lo), reinterpret_cast<const int*>(a.bin_hi),
+                                 a.band_out + (size_t)i0 * a.m * a.m * a.n_bands, c * (long long)a.m * a.m, a.F,
+                                 a.n_bands, st0);
+    if (!rc && a.S_out) {      // K5 from the same inverses and the same fit; V is this library's own (symmetric) estimate
       hmv::SpecArgs sa;
-      sa.H = Hc; sa.V = V_c; sa.S = nullptr; sa.S_mmf = S_out + (size_t)i0 * m * m * F * 2; sa.n_items = c; sa.F = F; sa.m = m;
-      sa.sym = 1;
+      sa.H = Hc; sa.V = V_c; sa.S = nullptr; sa.S_mmf = a.S_out + (size_t)i0 * a.m * a.m * a.F * 2;
+      sa.n_items = c; sa.F = a.F; sa.m = a.m; sa.sym = 1;
       rc = hmv::launch_spectra(sa, mp, st0);
     }
   }
@@ -748,11 +791,7 @@ int sliding_impl(const char* who, const double* x, int64_t rec_stride, int64_t l
 }
 }  // namespace
 
-int64_t hmv_sliding_bands_workspace_bytes(int64_t chunk, int m, int p, int F) {
-  const int mp = pad_of(m);
-  if (mp < 0 || chunk < 1 || p < 1 || p > HMV_MAX_ORDER || F < 1) return -1;
-  return (int64_t)sliding_layout(chunk, mp, p, F, true).total;
-}
+int64_t hmv_sliding_bands_workspace_bytes(int64_t chunk, int m, int p, int F) { return sliding_bytes(chunk, m, p, F, 1); }
 
 int hmv_sliding_ffdtf_f64(const double* x, int64_t rec_stride, int64_t ld, const int64_t* item_rec,
                           const int64_t* item_start, int64_t n_items, int m, int n, int p,
@@ -761,9 +800,16 @@ int hmv_sliding_ffdtf_f64(const double* x, int64_t rec_stride, int64_t ld, const
                           int64_t chunk, double pivot_tau, int64_t flags, int64_t grid_hop, int64_t grid_first,
                           int64_t grid_nwin, int64_t grid_T, void* ev_k3_start, void* ev_k3_stop, void* stream,
                           void* aux_stream) {
-  return sliding_impl("hmv_sliding_ffdtf_f64", x, rec_stride, ld, item_rec, item_start, n_items, m, n, p, freqs, F, fs, ffdtf,
-                      nullptr, nullptr, nullptr, 0, nullptr, ar_out, V_out, info_yw, info_tf, workspace, workspace_bytes, chunk,
-                      pivot_tau, flags, grid_hop, grid_first, grid_nwin, grid_T, ev_k3_start, ev_k3_stop, stream, aux_stream);
+  SlidingArgs a{"hmv_sliding_ffdtf_f64"};
+  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.item_rec = item_rec; a.item_start = item_start; a.n_items = n_items;
+  a.m = m; a.n = n; a.p = p; a.freqs = freqs; a.F = F; a.fs = fs;
+  a.ffdtf = ffdtf;
+  a.ar_out = ar_out; a.V_out = V_out; a.info_yw = info_yw; a.info_tf = info_tf;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.pivot_tau = pivot_tau; a.flags = flags;
+  a.grid_hop = grid_hop; a.grid_first = grid_first; a.grid_nwin = grid_nwin; a.grid_T = grid_T;
+  a.ev_k3_start = ev_k3_start; a.ev_k3_stop = ev_k3_stop;
+  a.stream = stream; a.aux_stream = aux_stream;
+  return sliding_impl(a);
 }
 
 int hmv_sliding_ffdtf_bands_f64(const double* x, int64_t rec_stride, int64_t ld, const int64_t* item_rec,
@@ -775,16 +821,20 @@ int hmv_sliding_ffdtf_bands_f64(const double* x, int64_t rec_stride, int64_t ld,
                                 int64_t grid_nwin, int64_t grid_T, void* ev_k3_start, void* ev_k3_stop, void* stream,
                                 void* aux_stream) {
   if (!band_out && n_items != 0) return fail(-4, "hmv_sliding_ffdtf_bands_f64: null pointer / empty grid");
-  return sliding_impl("hmv_sliding_ffdtf_bands_f64", x, rec_stride, ld, item_rec, item_start, n_items, m, n, p, freqs, F, fs,
-                      nullptr, band_out, bin_lo, bin_hi, n_bands, nullptr, ar_out, V_out, info_yw, info_tf, workspace,
-                      workspace_bytes, chunk, pivot_tau, flags, grid_hop, grid_first, grid_nwin, grid_T, ev_k3_start, ev_k3_stop,
-                      stream, aux_stream);
+  SlidingArgs a{"hmv_sliding_ffdtf_bands_f64"};
+  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.item_rec = item_rec; a.item_start = item_start; a.n_items = n_items;
+  a.m = m; a.n = n; a.p = p; a.freqs = freqs; a.F = F; a.fs = fs;
+  a.band_out = band_out; a.bin_lo = bin_lo; a.bin_hi = bin_hi; a.n_bands = n_bands;
+  a.ar_out = ar_out; a.V_out = V_out; a.info_yw = info_yw; a.info_tf = info_tf;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.pivot_tau = pivot_tau; a.flags = flags;
+  a.grid_hop = grid_hop; a.grid_first = grid_first; a.grid_nwin = grid_nwin; a.grid_T = grid_T;
+  a.ev_k3_start = ev_k3_start; a.ev_k3_stop = ev_k3_stop;
+  a.stream = stream; a.aux_stream = aux_stream;
+  return sliding_impl(a);
 }
 
 int64_t hmv_sliding_spectra_workspace_bytes(int64_t chunk, int m, int p, int F) {
-  const int mp = pad_of(m);
-  if (mp < 0 || chunk < 1 || p < 1 || p > HMV_MAX_ORDER || F < 1) return -1;
-  return (int64_t)sliding_layout(chunk, mp, p, F, false, true).total;
+  return sliding_bytes(chunk, m, p, F, 0, true);
 }
 
 int hmv_sliding_ffdtf_spectra_f64(const double* x, int64_t rec_stride, int64_t ld, const int64_t* item_rec,
@@ -795,19 +845,22 @@ int hmv_sliding_ffdtf_spectra_f64(const double* x, int64_t rec_stride, int64_t l
                                   int64_t grid_hop, int64_t grid_first, int64_t grid_nwin, int64_t grid_T, void* stream,
                                   void* aux_stream) {
   if (!S_out && n_items != 0) return fail(-4, "hmv_sliding_ffdtf_spectra_f64: null pointer / empty grid");
-  return sliding_impl("hmv_sliding_ffdtf_spectra_f64", x, rec_stride, ld, item_rec, item_start, n_items, m, n, p, freqs, F,
-                      fs, ffdtf, nullptr, nullptr, nullptr, 0, S_out, ar_out, V_out, info_yw, info_tf, workspace,
-                      workspace_bytes, chunk, pivot_tau, flags, grid_hop, grid_first, grid_nwin, grid_T, nullptr, nullptr,
-                      stream, aux_stream);
+  SlidingArgs a{"hmv_sliding_ffdtf_spectra_f64"};
+  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.item_rec = item_rec; a.item_start = item_start; a.n_items = n_items;
+  a.m = m; a.n = n; a.p = p; a.freqs = freqs; a.F = F; a.fs = fs;
+  a.ffdtf = ffdtf; a.S_out = S_out;
+  a.ar_out = ar_out; a.V_out = V_out; a.info_yw = info_yw; a.info_tf = info_tf;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.pivot_tau = pivot_tau; a.flags = flags;
+  a.grid_hop = grid_hop; a.grid_first = grid_first; a.grid_nwin = grid_nwin; a.grid_T = grid_T;
+  a.stream = stream; a.aux_stream = aux_stream;
+  return sliding_impl(a);
 }
 
 // ---- sliding-window dDTF / GPDC (sliding_conn.hip) ------------------------------------------------------
 // direct_dtf (/root/reference/src/mtmvar.py:341-385) and gen_partial_directed_coherence (mtmvar.py:388-468) of every
 // window; n_bands = 0: the full (m, m, F) arrays, n_bands >= 1: their band sums.
 int64_t hmv_sliding_ddtf_workspace_bytes(int64_t chunk, int m, int p, int F, int n_bands) {
-  const int mp = pad_of(m);
-  if (mp < 0 || chunk < 1 || p < 1 || p > HMV_MAX_ORDER || F < 1 || n_bands < 0) return -1;
-  return (int64_t)sliding_layout(chunk, mp, p, F, n_bands > 0, false, MEAS_DDTF).total;
+  return sliding_bytes(chunk, m, p, F, n_bands, false, MEAS_DDTF);
 }
 
 int hmv_sliding_ddtf_f64(const double* x, int64_t rec_stride, int64_t ld, const int64_t* item_rec,
@@ -818,17 +871,21 @@ int hmv_sliding_ddtf_f64(const double* x, int64_t rec_stride, int64_t ld, const 
                          int64_t grid_first, int64_t grid_nwin, int64_t grid_T, void* stream, void* aux_stream) {
   if (n_bands < 0) return fail(-4, "hmv_sliding_ddtf_f64: n_bands must be >= 0");
   if (!out && n_items != 0) return fail(-4, "hmv_sliding_ddtf_f64: null pointer / empty grid");
-  const bool bands = n_bands > 0;
-  return sliding_impl("hmv_sliding_ddtf_f64", x, rec_stride, ld, item_rec, item_start, n_items, m, n, p, freqs, F, fs,
-                      bands ? nullptr : out, bands ? out : nullptr, bin_lo, bin_hi, n_bands, nullptr, ar_out, V_out, info_yw,
-                      info_tf, workspace, workspace_bytes, chunk, pivot_tau, flags, grid_hop, grid_first, grid_nwin, grid_T,
-                      nullptr, nullptr, stream, aux_stream, MEAS_DDTF);
+  SlidingArgs a{"hmv_sliding_ddtf_f64"};
+  a.measure = MEAS_DDTF;
+  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.item_rec = item_rec; a.item_start = item_start; a.n_items = n_items;
+  a.m = m; a.n = n; a.p = p; a.freqs = freqs; a.F = F; a.fs = fs;
+  if (n_bands > 0) a.band_out = out; else a.ffdtf = out;
+  a.bin_lo = bin_lo; a.bin_hi = bin_hi; a.n_bands = n_bands;
+  a.ar_out = ar_out; a.V_out = V_out; a.info_yw = info_yw; a.info_tf = info_tf;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.pivot_tau = pivot_tau; a.flags = flags;
+  a.grid_hop = grid_hop; a.grid_first = grid_first; a.grid_nwin = grid_nwin; a.grid_T = grid_T;
+  a.stream = stream; a.aux_stream = aux_stream;
+  return sliding_impl(a);
 }
 
 int64_t hmv_sliding_gpdc_workspace_bytes(int64_t chunk, int m, int p, int F, int n_bands) {
-  const int mp = pad_of(m);
-  if (mp < 0 || chunk < 1 || p < 1 || p > HMV_MAX_ORDER || F < 1 || n_bands < 0) return -1;
-  return (int64_t)sliding_layout(chunk, mp, p, F, n_bands > 0, false, MEAS_GPDC).total;
+  return sliding_bytes(chunk, m, p, F, n_bands, false, MEAS_GPDC);
 }
 
 int hmv_sliding_gpdc_f64(const double* x, int64_t rec_stride, int64_t ld, const int64_t* item_rec,
@@ -839,22 +896,24 @@ int hmv_sliding_gpdc_f64(const double* x, int64_t rec_stride, int64_t ld, const 
                          int64_t grid_T, void* stream, void* aux_stream) {
   if (n_bands < 0) return fail(-4, "hmv_sliding_gpdc_f64: n_bands must be >= 0");
   if (!out && n_items != 0) return fail(-4, "hmv_sliding_gpdc_f64: null pointer / empty grid");
-  const bool bands = n_bands > 0;
-  return sliding_impl("hmv_sliding_gpdc_f64", x, rec_stride, ld, item_rec, item_start, n_items, m, n, p, freqs, F, fs,
-                      bands ? nullptr : out, bands ? out : nullptr, bin_lo, bin_hi, n_bands, nullptr, ar_out, V_out, info_yw,
-                      nullptr, workspace, workspace_bytes, chunk, 1.0, flags, grid_hop, grid_first, grid_nwin, grid_T,
-                      nullptr, nullptr, stream, aux_stream, MEAS_GPDC);
+  SlidingArgs a{"hmv_sliding_gpdc_f64"};
+  a.measure = MEAS_GPDC;
+  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.item_rec = item_rec; a.item_start = item_start; a.n_items = n_items;
+  a.m = m; a.n = n; a.p = p; a.freqs = freqs; a.F = F; a.fs = fs;
+  if (n_bands > 0) a.band_out = out; else a.ffdtf = out;
+  a.bin_lo = bin_lo; a.bin_hi = bin_hi; a.n_bands = n_bands;
+  a.ar_out = ar_out; a.V_out = V_out; a.info_yw = info_yw;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.flags = flags;
+  a.grid_hop = grid_hop; a.grid_first = grid_first; a.grid_nwin = grid_nwin; a.grid_T = grid_T;
+  a.stream = stream; a.aux_stream = aux_stream;
+  return sliding_impl(a);
 }
 
 // ---- automatic model order (yw_auto.hip): mvar_criterion (mtmvar.py:551-601) per window inside the fused call -------
 int64_t hmv_sliding_auto_workspace_bytes(int measure, int64_t chunk, int m, int pmax, int F, int n_bands) {
-  const int mp = pad_of(m);
   // n_bands = -1: the full ffDTF together with S_out (one chunk of H passes through the workspace between K3 and K5)
   const bool spectra = (n_bands == -1 && measure == HMV_MEASURE_FFDTF);
-  if (mp < 0 || chunk < 1 || pmax < 1 || pmax > HMV_MAX_ORDER || F < 1 || (n_bands < 0 && !spectra) ||
-      measure < HMV_MEASURE_FFDTF || measure > HMV_MEASURE_GPDC)
-    return -1;
-  return (int64_t)sliding_layout(chunk, mp, pmax, F, n_bands > 0, spectra, measure).total;
+  return sliding_bytes(chunk, m, pmax, F, spectra ? 0 : n_bands, spectra, measure);
 }
 
 int hmv_sliding_auto_f64(int measure, const double* x, int64_t rec_stride, int64_t ld, const int64_t* item_rec,
@@ -871,25 +930,29 @@ int hmv_sliding_auto_f64(int measure, const double* x, int64_t rec_stride, int64
   if (S_out && (measure != HMV_MEASURE_FFDTF || n_bands != 0))
     return fail(-4, "hmv_sliding_auto_f64: spectra come with the full ffDTF only");
   if (!out && n_items != 0) return fail(-4, "hmv_sliding_auto_f64: null pointer / empty grid");
-  const bool bands = n_bands > 0;
-  return sliding_impl("hmv_sliding_auto_f64", x, rec_stride, ld, item_rec, item_start, n_items, m, n, pmax, freqs, F, fs,
-                      bands ? nullptr : out, bands ? out : nullptr, bin_lo, bin_hi, n_bands, S_out, ar_out, V_out, info_yw,
-                      measure == HMV_MEASURE_GPDC ? nullptr : info_tf, workspace, workspace_bytes, chunk,
-                      measure == HMV_MEASURE_GPDC ? 1.0 : pivot_tau, flags, grid_hop, grid_first, grid_nwin, grid_T, nullptr,
-                      nullptr, stream, aux_stream, measure, crit, order_out, crit_out);
+  SlidingArgs a{"hmv_sliding_auto_f64"};
+  a.measure = measure; a.crit = crit; a.order_out = order_out; a.crit_out = crit_out;
+  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.item_rec = item_rec; a.item_start = item_start; a.n_items = n_items;
+  a.m = m; a.n = n; a.p = pmax; a.freqs = freqs; a.F = F; a.fs = fs;
+  if (n_bands > 0) a.band_out = out; else a.ffdtf = out;
+  a.bin_lo = bin_lo; a.bin_hi = bin_hi; a.n_bands = n_bands; a.S_out = S_out;
+  a.ar_out = ar_out; a.V_out = V_out; a.info_yw = info_yw; a.info_tf = info_tf;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.pivot_tau = pivot_tau; a.flags = flags;
+  if (measure == HMV_MEASURE_GPDC) { a.info_tf = nullptr; a.pivot_tau = 1.0; }
+  a.grid_hop = grid_hop; a.grid_first = grid_first; a.grid_nwin = grid_nwin; a.grid_T = grid_T;
+  a.stream = stream; a.aux_stream = aux_stream;
+  return sliding_impl(a);
 }
 
 // ---- event-locked ensembles: the fused path with the trial-averaged K1 (lagcov_ensemble.hip) ----------------------------
 int64_t hmv_sliding_ensemble_workspace_bytes(int measure, int64_t chunk, int m, int n, int p, int F, int n_bands,
                                              int64_t grid_hop, int64_t grid_nwin) {
-  const int mp = pad_of(m);
   // n_bands = -1: the full ffDTF together with S_out, as hmv_sliding_auto_workspace_bytes
   const bool spectra = (n_bands == -1 && measure == HMV_MEASURE_FFDTF);
-  if (mp < 0 || chunk < 1 || p < 1 || p > HMV_MAX_ORDER || n <= p || F < 1 || (n_bands < 0 && !spectra) ||
-      measure < HMV_MEASURE_FFDTF || measure > HMV_MEASURE_GPDC || grid_hop < 0 || grid_nwin < 0)
-    return -1;
-  return (int64_t)sliding_layout(chunk, mp, p, F, n_bands > 0, spectra, measure,
-                                 ens_q_tiles(chunk, n, p, grid_hop, grid_nwin)).total;
+  if (n <= p || grid_hop < 0 || grid_nwin < 0) return -1;
+  // (ens_q_tiles sees chunk, m and p before sliding_bytes range-checks them: it guards every division itself)
+  const int64_t q_tiles = ens_q_tiles(chunk, n, p, grid_hop, grid_nwin);
+  return sliding_bytes(chunk, m, p, F, spectra ? 0 : n_bands, spectra, measure, q_tiles);
 }
 
 int hmv_sliding_ensemble_f64(int measure, const double* x, int64_t rec_stride, int64_t ld, int64_t T,
@@ -908,13 +971,19 @@ int hmv_sliding_ensemble_f64(int measure, const double* x, int64_t rec_stride, i
   const int mp = pad_of(m);                              // ahead of the pointer checks, in the order of the other entries
   if (mp >= 0 && p >= 1 && p <= HMV_MAX_ORDER && n > p && !out && n_items != 0)
     return fail(-4, "hmv_sliding_ensemble_f64: null pointer / empty grid");
-  const bool bands = n_bands > 0;
   const EnsDesc ens{trial_rec, trial_start, group_ptr, n_groups, T};
-  return sliding_impl("hmv_sliding_ensemble_f64", x, rec_stride, ld, item_group, item_offset, n_items, m, n, p, freqs, F, fs,
-                      bands ? nullptr : out, bands ? out : nullptr, bin_lo, bin_hi, n_bands, S_out, ar_out, V_out, info_yw,
-                      measure == HMV_MEASURE_GPDC ? nullptr : info_tf, workspace, workspace_bytes, chunk,
-                      measure == HMV_MEASURE_GPDC ? 1.0 : pivot_tau, flags, grid_hop, 0, grid_nwin, T, nullptr, nullptr,
-                      stream, aux_stream, measure, -1, nullptr, nullptr, &ens);
+  SlidingArgs a{"hmv_sliding_ensemble_f64"};
+  a.measure = measure; a.ens = &ens;
+  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.item_rec = item_group; a.item_start = item_offset; a.n_items = n_items;
+  a.m = m; a.n = n; a.p = p; a.freqs = freqs; a.F = F; a.fs = fs;
+  if (n_bands > 0) a.band_out = out; else a.ffdtf = out;
+  a.bin_lo = bin_lo; a.bin_hi = bin_hi; a.n_bands = n_bands; a.S_out = S_out;
+  a.ar_out = ar_out; a.V_out = V_out; a.info_yw = info_yw; a.info_tf = info_tf;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.pivot_tau = pivot_tau; a.flags = flags;
+  if (measure == HMV_MEASURE_GPDC) { a.info_tf = nullptr; a.pivot_tau = 1.0; }
+  a.grid_hop = grid_hop; a.grid_nwin = grid_nwin; a.grid_T = T;
+  a.stream = stream; a.aux_stream = aux_stream;
+  return sliding_impl(a);
 }
 
 int64_t hmv_fad_workspace_bytes(int64_t n_series, int pmax) {

@@ -13,6 +13,10 @@ Layouts ("MP layout": channels padded to MP = 16*ceil(m/16)):
 """
 from __future__ import annotations
 
+import dataclasses
+import types
+from typing import Callable
+
 import numpy as np
 import torch
 
@@ -150,6 +154,38 @@ def no_auto_order(p, where: str):
     if p is None:
         raise ValueError(f"{where}: the automatic model order (p=None) is not offered here yet; pass an integer p "
                          "(sliding_ffdtf / sliding_ddtf / sliding_gpdc / sliding_ffdtf_spectra select it per window)")
+
+
+_MEASURES = {"ffdtf": _lib.MEASURE_FFDTF, "ddtf": _lib.MEASURE_DDTF, "gpdc": _lib.MEASURE_GPDC}
+_NO_ENSEMBLE_ORDER = ("ensemble fits need an integer model order p: the reference's mvar_criterion does not take "
+                      "(channels, samples, trials) input, so there is no automatic order to reproduce")
+
+
+@dataclasses.dataclass(frozen=True)
+class _Route:
+    """What is particular to one fused C entry (`Engine._route`, `Engine._ensemble_route`); `Engine._sliding_call` is
+    everything the entries share.  A new entry is a new route, not a new driver."""
+    name: str                   # who the "bad sizes" refusal says it is (sliding_<measure>, with or without spectra)
+    measure: str                # "ffdtf", "ddtf" or "gpdc"
+    p: int                      # lags of the coefficient arrays: the order, or max_model_order of the automatic order
+    order_text: str             # the order as the "bad sizes" refusal words it
+    yw_text: str                # the Yule-Walker stage as `raise_on_info` words it
+    validate: Callable          # (x, items): the descriptors against x, ValueError before anything is launched
+    grid: Callable              # (x, items, n_items, grid, compare) -> the grid arguments of the C entry
+    ws_bytes: Callable          # (chunk, m, F, n_bands, grid arguments) -> hmv_sliding_*_workspace_bytes
+    call: Callable              # (the driver's pointers and sizes) -> (name of the C entry, its argument tuple)
+    spectra: bool = False       # S comes out as well (full ffDTF only)
+    automatic: bool = False     # the order is selected per window: `orders` and `crit` exist
+    per_item: Callable | None = None    # (m, F, n_bands) -> bytes that size the chunk, where not ws_bytes(1, ...)
+    blame: Callable | None = None       # (SingularMatrixError, items): what the route adds to the error
+
+    @property
+    def has_tf(self) -> bool:           # GPDC never inverts A(f): the Yule-Walker info is all it reports
+        return self.measure != "gpdc"
+
+    @property
+    def bands_in_k3(self) -> bool:      # ffDTF: K3's row workers add the bands up (where `bands_in_kernel` allows)
+        return self.measure == "ffdtf"
 
 
 class Engine:
@@ -439,11 +475,14 @@ class Engine:
         return out
 
     # ------------------------------------------------------------------ fused sliding-window path
+    @staticmethod
+    def _chunk(n_items: int, per_item: int, cap_bytes: int) -> int:
+        """Items per chunk of a fused call: all of them, unless their workspace would exceed cap_bytes."""
+        return max(1, min(n_items, max(1, cap_bytes // max(per_item, 1))))
+
     def sliding_chunk(self, n_items: int, m: int, p: int, F: int, lanes: int = 1) -> int:
         per_item = int(self.lib.hmv_sliding_workspace_bytes(1, m, p, F))
-        cap = max(1, self.max_workspace_bytes // max(per_item * lanes, 1))
-        want = n_items
-        return max(1, min(want, cap))
+        return self._chunk(n_items, per_item * lanes, self.max_workspace_bytes)
 
     def copy_streams(self):
         """The upload and the download stream of `stream_dyads`, created ONCE per engine.  HIP streams share a handful of
@@ -461,6 +500,218 @@ class Engine:
         if key not in self._aux:
             self._aux[key] = torch.cuda.Stream(device=self.device)
         return self._aux[key]
+
+    # The routes: what is particular to one fused C entry, written down once each.  `_sliding_call` is all they share.
+    def _window_grid(self, x, items, n_items, grid, compare):
+        """grid = (hop, first, n_win) of the single-trial routes -> the three grid arguments of the C call."""
+        if grid is None:
+            return 0, 0, 0
+        g_hop, g_first, g_nwin = (int(v) for v in grid)
+        # With a declared grid K1 addresses the windows by (item // n_win, first + (item % n_win) * hop) and never
+        # reads item_rec / item_start: they must say the same thing, or the results belong to other windows (and a
+        # recording index past n_rec would be read out of bounds).  One device comparison per call.
+        if g_nwin < 1 or n_items % g_nwin or g_hop < 1 or n_items // g_nwin > x.shape[0]:
+            raise ValueError("grid = (hop, first, n_win) does not match the number of items / recordings")
+        if compare:
+            k = torch.arange(n_items, dtype=torch.int64, device=self.device)
+            if not (torch.equal(items[0], k // g_nwin) and torch.equal(items[1], g_first + (k % g_nwin) * g_hop)):
+                raise ValueError("grid = (hop, first, n_win) contradicts item_rec / item_start "
+                                 "(items must be recording-major, window-minor on the declared grid)")
+        return g_hop, g_first, g_nwin
+
+    def _ensemble_grid(self, n_groups, items, n_items, grid, compare):
+        """grid = (hop, n_win) of the ensemble routes -> the two grid arguments of the C call."""
+        g_hop, g_nwin = (int(v) for v in grid) if grid is not None else (0, 0)
+        if grid is not None and n_items:
+            # with a declared grid the shared form addresses by (item // n_win, (item % n_win) * hop) and never reads
+            # item_group / item_offset: they must say the same thing
+            if g_hop < 1 or g_nwin < 1 or n_items != n_groups * g_nwin:
+                raise ValueError("grid = (hop, n_win) does not match the number of items / groups")
+            k = torch.arange(n_items, dtype=torch.int64, device=self.device)
+            if compare and not (torch.equal(items[0], k // g_nwin) and torch.equal(items[1], (k % g_nwin) * g_hop)):
+                raise ValueError("grid = (hop, n_win) contradicts item_group / item_offset "
+                                 "(items must be group-major, window-minor on the declared grid)")
+        return g_hop, g_nwin
+
+    def _route(self, measure, n, p, max_model_order=20, crit_type="AIC", spectra=False):
+        """Route of a single-trial call: `hmv_sliding_<measure>_f64` at the fixed order p, or with p=None
+        `hmv_sliding_auto_f64` -- K1 sums max_model_order + 1 lags, K2 walks every order, keeps the criterion's first
+        arg-min per window and leaves that order's coefficients zero-padded to max_model_order lags; the later stages run
+        at max_model_order on them."""
+        lib, n, code = self.lib, int(n), _MEASURES[measure]
+        common = dict(measure=measure, spectra=spectra, grid=self._window_grid)
+
+        def windows(a, order):
+            return (*a.x, *a.items, a.n_items, a.m, n, *order, a.f, a.F, a.fs)
+
+        def tail(a):
+            return (*a.grid, a.T, a.stream, a.aux)
+        if p is None:
+            pmax, crit = auto_order_args(max_model_order, crit_type, n)
+            return _Route(
+                name=f"sliding_{measure}", p=pmax, order_text=f"max_model_order={pmax}", automatic=True,
+                yw_text="ar_coeff (Yule-Walker solve at the automatic order; a negative info: residual covariance not "
+                        "positive definite)",
+                validate=lambda x, items: self.check_items(x, items[0], items[1], n, pmax),
+                ws_bytes=lambda chunk, m, F, nb, g: lib.hmv_sliding_auto_workspace_bytes(code, chunk, m, pmax, F,
+                                                                                           -1 if spectra else nb),
+                call=lambda a: ("hmv_sliding_auto_f64", (
+                    code, *windows(a, (pmax, crit)), a.out, a.lo, a.hi, a.nb, a.S, a.ar, a.V, a.orders, a.curve, a.info_yw,
+                    a.info_tf, a.ws, a.nbytes, a.chunk, a.tau, a.flags, *tail(a))),
+                **common)
+        p = int(p)
+        fixed = dict(name=f"sliding_{measure}", p=p, order_text=f"p={p}",
+                     validate=lambda x, items: self.check_items(x, items[0], items[1], n, p), **common)
+        if measure != "ffdtf":
+            wsf = lib.hmv_sliding_ddtf_workspace_bytes if measure == "ddtf" else lib.hmv_sliding_gpdc_workspace_bytes
+
+            def call(a):
+                front = (*windows(a, (p,)), a.out, a.lo, a.hi, a.nb, a.ar, a.V, a.info_yw)
+                if measure == "gpdc":           # no inverse of A(f): neither info_tf nor the pivot threshold
+                    return "hmv_sliding_gpdc_f64", (*front, a.ws, a.nbytes, a.chunk, a.flags, *tail(a))
+                return "hmv_sliding_ddtf_f64", (*front, a.info_tf, a.ws, a.nbytes, a.chunk, a.tau, a.flags, *tail(a))
+            return _Route(yw_text="ar_coeff (Yule-Walker solve; a negative info: residual covariance not positive definite)",
+                          ws_bytes=lambda chunk, m, F, nb, g: wsf(chunk, m, p, F, nb), call=call, **fixed)
+
+        def ws_bytes(chunk, m, F, nb, g):
+            if spectra:
+                return lib.hmv_sliding_spectra_workspace_bytes(chunk, m, p, F)
+            return (lib.hmv_sliding_bands_workspace_bytes if nb else lib.hmv_sliding_workspace_bytes)(chunk, m, p, F)
+
+        def call(a):
+            work = (a.info_yw, a.info_tf, a.ws, a.nbytes, a.chunk, a.tau, a.flags, *a.grid, a.T)
+            if spectra:
+                return "hmv_sliding_ffdtf_spectra_f64", (*windows(a, (p,)), a.out, a.S, a.ar, a.V, *work, a.stream, a.aux)
+            if a.nb:
+                return "hmv_sliding_ffdtf_bands_f64", (*windows(a, (p,)), a.out, a.lo, a.hi, a.nb, a.ar, a.V, *work, *a.k3,
+                                                       a.stream, a.aux)
+            return "hmv_sliding_ffdtf_f64", (*windows(a, (p,)), a.out, a.ar, a.V, *work, *a.k3, a.stream, a.aux)
+        # (the chunk of the full and the band form is sized by the full form's workspace: `sliding_chunk`'s rule)
+        return _Route(yw_text="ar_coeff (Yule-Walker solve)", ws_bytes=ws_bytes, call=call,
+                      per_item=None if spectra else lambda m, F, nb: lib.hmv_sliding_workspace_bytes(1, m, p, F), **fixed)
+
+    def _ensemble_route(self, measure, n, p, trial_rec, trial_start, group_ptr, spectra=False):
+        """Route of `sliding_ensemble` (`hmv_sliding_ensemble_f64`): the items are (group, offset) pairs, the validation
+        is `validate_trials`, the grid has two parts, and a failed fit is reported with its group and offset."""
+        if p is None:
+            raise ValueError(_NO_ENSEMBLE_ORDER)
+        lib, n, p, code = self.lib, int(n), int(p), _MEASURES[measure]
+        n_groups = int(group_ptr.numel()) - 1
+
+        def blame(err, items):       # say which group and which window of the epoch
+            idx = torch.as_tensor(err.items, dtype=torch.int64, device=items[0].device)
+            err.groups = items[0][idx].cpu().numpy()
+            err.offsets = items[1][idx].cpu().numpy()
+            err.args = (err.args[0], err.args[1] + f" (group {int(err.groups[0])}, window at offset {int(err.offsets[0])})")
+        return _Route(
+            name="sliding_ensemble", measure=measure, p=p, order_text=f"n={n}, p={p}", spectra=spectra, blame=blame,
+            yw_text="ar_coeff (Yule-Walker solve of the trial-averaged covariances; a negative info: residual covariance "
+                    "not positive definite)",
+            validate=lambda x, items: validate_trials(x, trial_rec, trial_start, group_ptr, items[0], items[1], n, p),
+            grid=lambda x, items, n_items, grid, compare: self._ensemble_grid(n_groups, items, n_items, grid, compare),
+            ws_bytes=lambda chunk, m, F, nb, g: lib.hmv_sliding_ensemble_workspace_bytes(
+                code, chunk, m, n, p, F, -1 if spectra else nb, *g),
+            call=lambda a: ("hmv_sliding_ensemble_f64", (
+                code, *a.x, a.T, trial_rec.data_ptr(), trial_start.data_ptr(), group_ptr.data_ptr(), n_groups, *a.items,
+                a.n_items, a.m, n, p, a.f, a.F, a.fs, a.out, a.lo, a.hi, a.nb, a.S, a.ar, a.V, a.info_yw, a.info_tf, a.ws,
+                a.nbytes, a.chunk, a.tau, a.flags, *a.grid, a.stream, a.aux)))
+
+    def _sliding_call(self, rt, x, items, freqs, fs, *, bands=None, out=None, out_S=None, return_ar=False,
+                      return_orders=False, check=True, chunk=None, overlap=False, flags=0, grid=None, validate=True,
+                      k3_events=None):
+        """The one driver of the fused entries; `rt` (a `_Route`) carries what differs between them.  Top to bottom: the
+        inputs, the empty batch, the grid, where the C call writes, chunk and workspace, the outputs, the call, the band
+        sums of the two-step form, `check`, the result `(out[, S][, bad][, ar, V, infos][, orders, crit])`."""
+        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
+        x = x if x.stride(2) == 1 else x.contiguous()
+        n_rec, m, T = x.shape
+        mp = self.pad(m)
+        if validate:
+            rt.validate(x, items)
+        n_items = int(items[0].numel())
+        f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
+        F = int(f.numel())
+        nb = 0
+        if bands is not None:
+            b_lo, b_hi = self.band_tables(bands[0], bands[1], F)
+            nb = int(b_lo.numel())
+        has_tf = rt.has_tf
+        return_orders = return_orders and rt.automatic
+
+        def result(out, S, bad, ar, V, info_yw, info_tf, orders, curve):
+            r = (out,) if S is None else (out, torch.view_as_complex(S))
+            if check == "mask":
+                r += (bad,)
+            if return_ar:
+                r += (ar, V, (info_yw, info_tf) if has_tf else info_yw)
+            if return_orders:
+                r += (orders, curve)
+            return r if len(r) > 1 else r[0]
+        if n_items == 0:                      # empty batch (torch gives empty tensors a null data pointer)
+            i32 = self.empty(0, dtype=torch.int32)
+            return result(self.empty(0, m, m, nb if bands is not None else F), self.empty(0, m, m, F, 2) if rt.spectra else None,
+                          torch.zeros(0, dtype=torch.bool, device=self.device), self.empty(0, mp, mp, rt.p),
+                          self.empty(0, mp, mp), i32, i32, i32, self.empty(0, rt.p))
+        g = rt.grid(x, items, n_items, grid, validate)
+        # Two steps -- the full array (scratch), then its band sums -- where the kernels cannot add the bands up themselves:
+        # an empty band set, and for the ffDTF a frequency grid that does not suit K3's row workers or the unfused norm
+        two_step = bands is not None and (nb == 0 or (rt.bands_in_k3 and (
+            not self.bands_in_kernel(m, F) or (flags & _lib.FLAG_UNFUSED_NORM))))
+        knb = 0 if two_step else nb           # the bands the C call sums itself
+        res = self.empty(n_items, m, m, knb or F) if out is None or two_step else out
+        assert res.is_contiguous() and tuple(res.shape) == (n_items, m, m, knb or F)
+        S = None
+        if rt.spectra:
+            S = self.empty(n_items, m, m, F, 2) if out_S is None else out_S
+        if chunk is None:
+            per_item = rt.ws_bytes(1, m, F, knb, (0,) * len(g)) if rt.per_item is None else rt.per_item(m, F, knb)
+            chunk = self._chunk(n_items, int(per_item), self.max_workspace_bytes)
+        chunk = int(chunk)
+        nbytes = int(rt.ws_bytes(chunk, m, F, knb, g))
+        if nbytes < 0:
+            raise ValueError(f"{rt.name}: bad sizes (m={m}, {rt.order_text}, F={F}, chunk={chunk})")
+        ws = self._workspace(nbytes)
+        ar = self.empty(n_items, mp, mp, rt.p) if return_ar else None
+        V = self.empty(n_items, mp, mp) if return_ar else None
+        orders = self.empty(n_items, dtype=torch.int32) if rt.automatic else None
+        curve = self.empty(n_items, rt.p) if return_orders else None
+        info_yw = self.empty(n_items, dtype=torch.int32)
+        info_tf = self.empty(n_items * F, dtype=torch.int32) if has_tf else None
+        entry, args = rt.call(types.SimpleNamespace(
+            x=(x.data_ptr(), x.stride(0), x.stride(1)), T=T, items=(items[0].data_ptr(), items[1].data_ptr()),
+            n_items=n_items, m=m, f=f.data_ptr(), F=F, fs=float(fs), out=res.data_ptr(), nb=knb,
+            lo=b_lo.data_ptr() if knb else 0, hi=b_hi.data_ptr() if knb else 0, S=_ptr(S), ar=_ptr(ar), V=_ptr(V),
+            orders=_ptr(orders), curve=_ptr(curve), info_yw=info_yw.data_ptr(), info_tf=_ptr(info_tf), ws=ws.data_ptr(),
+            nbytes=nbytes, chunk=chunk, tau=self.pivot_tau, flags=int(flags), grid=g, k3=tuple(k3_events) if k3_events else (0, 0),
+            stream=self.stream(), aux=self.aux_stream().cuda_stream if overlap else 0))
+        with torch.cuda.device(self.device):
+            rc = getattr(self.lib, entry)(*args)
+        _lib.check(rc, entry)
+        if two_step:
+            res = self.band_sums(res, bands[0], bands[1])
+            if out is not None:
+                out.copy_(res)
+                res = out
+        bad = None
+        if check == "nan" or check == "mask":   # "mask": no host synchronisation, the caller decides what to NaN-fill
+            bad = info_yw != 0
+            if has_tf:
+                bad = bad | (info_tf.view(n_items, F) != 0).any(dim=1)
+        if check == "nan":          # keep the good windows, NaN-fill the ones whose fit or inverse was singular
+            if bool(bad.any()):
+                res[bad] = float("nan")
+                if S is not None:
+                    S[bad] = float("nan")
+        elif check and check != "mask":
+            try:
+                self.raise_on_info(info_yw, rt.yw_text)
+                if has_tf:
+                    self.raise_on_info(info_tf, "mvar_transfer_function (inverse of A(f))", per_item=F)
+            except SingularMatrixError as err:
+                if rt.blame is not None:
+                    rt.blame(err, items)
+                raise
+        return result(res, S, bad, ar, V, info_yw, info_tf, orders, curve)
 
     def sliding_ffdtf(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, p: int,
                       freqs, fs: float, out: torch.Tensor | None = None, return_ar: bool = False,
@@ -496,92 +747,10 @@ class Engine:
         same bits as `band_sums(sliding_ffdtf(...))`, which is also what runs when the grid does not suit the kernel
         (`bands_in_kernel`).  `out`, if given, is the band array.
         """
-        if p is None:
-            return self._sliding_auto("ffdtf", x, item_rec, item_start, n, freqs, fs, max_model_order, crit_type, out,
-                                      return_ar, return_orders, check, chunk, overlap, flags, grid, validate, bands)
-        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
-        x = x if x.stride(2) == 1 else x.contiguous()
-        n_rec, m, T = x.shape
-        mp = self.pad(m)
-        if validate:
-            self.check_items(x, item_rec, item_start, n, p)
-        n_items = int(item_rec.numel())
-        f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
-        F = int(f.numel())
-        if n_items == 0:                      # empty batch (torch gives empty tensors a null data pointer)
-            empty = self.empty(0, m, m, F)
-            if return_ar:
-                return empty, self.empty(0, mp, mp, p), self.empty(0, mp, mp), (self.empty(0, dtype=torch.int32),) * 2
-            return empty
-        band_out = None
-        if bands is not None:
-            b_lo, b_hi = self.band_tables(bands[0], bands[1], F)
-            nb = int(b_lo.numel())
-            if nb == 0 or not self.bands_in_kernel(m, F) or (flags & _lib.FLAG_UNFUSED_NORM):
-                # two calls: the full array (scratch), then its band sums
-                res = self.sliding_ffdtf(x, item_rec, item_start, n, p, f, fs, return_ar=return_ar, check=check, chunk=chunk,
-                                         k3_events=k3_events, overlap=overlap, flags=flags, grid=grid, validate=validate)
-                full = res[0] if isinstance(res, tuple) else res
-                red = self.band_sums(full, bands[0], bands[1])
-                if out is not None:
-                    out.copy_(red)
-                    red = out
-                return (red,) + tuple(res[1:]) if isinstance(res, tuple) else red
-            band_out = self.empty(n_items, m, m, nb) if out is None else out
-            assert band_out.is_contiguous() and tuple(band_out.shape) == (n_items, m, m, nb)
-        chunk = self.sliding_chunk(n_items, m, p, F) if chunk is None else int(chunk)
-        wsf = self.lib.hmv_sliding_workspace_bytes if band_out is None else self.lib.hmv_sliding_bands_workspace_bytes
-        nbytes = int(wsf(chunk, m, p, F))
-        ws = self._workspace(nbytes)
-        aux = self.aux_stream().cuda_stream if overlap else 0
-        if out is None and band_out is None:
-            out = self.empty(n_items, m, m, F)
-        ar = self.empty(n_items, mp, mp, p) if return_ar else None
-        V = self.empty(n_items, mp, mp) if return_ar else None
-        info_yw = self.empty(n_items, dtype=torch.int32)
-        info_tf = self.empty(n_items * F, dtype=torch.int32)
-        g_hop, g_first, g_nwin = (int(v) for v in grid) if grid is not None else (0, 0, 0)
-        if grid is not None:
-            # With a declared grid K1 addresses the windows by (item // n_win, first + (item % n_win) * hop) and never
-            # reads item_rec / item_start: they must say the same thing, or the results belong to other windows (and a
-            # recording index past n_rec would be read out of bounds).  One device comparison per call.
-            if g_nwin < 1 or n_items % g_nwin or g_hop < 1 or n_items // g_nwin > n_rec:
-                raise ValueError("grid = (hop, first, n_win) does not match the number of items / recordings")
-            k = torch.arange(n_items, dtype=torch.int64, device=self.device)
-            same = (not validate) or (torch.equal(item_rec, k // g_nwin) and
-                                      torch.equal(item_start, g_first + (k % g_nwin) * g_hop))
-            if not same:
-                raise ValueError("grid = (hop, first, n_win) contradicts item_rec / item_start "
-                                 "(items must be recording-major, window-minor on the declared grid)")
-        with torch.cuda.device(self.device):
-            if band_out is None:
-                rc = self.lib.hmv_sliding_ffdtf_f64(
-                    x.data_ptr(), x.stride(0), x.stride(1), item_rec.data_ptr(), item_start.data_ptr(), n_items,
-                    m, int(n), int(p), f.data_ptr(), F, float(fs), out.data_ptr(), _ptr(ar), _ptr(V),
-                    info_yw.data_ptr(), info_tf.data_ptr(), ws.data_ptr(), nbytes, chunk, self.pivot_tau, int(flags),
-                    g_hop, g_first, g_nwin, T, k3_events[0] if k3_events else 0, k3_events[1] if k3_events else 0,
-                    self.stream(), aux)
-            else:
-                rc = self.lib.hmv_sliding_ffdtf_bands_f64(
-                    x.data_ptr(), x.stride(0), x.stride(1), item_rec.data_ptr(), item_start.data_ptr(), n_items,
-                    m, int(n), int(p), f.data_ptr(), F, float(fs), band_out.data_ptr(), b_lo.data_ptr(), b_hi.data_ptr(), nb,
-                    _ptr(ar), _ptr(V), info_yw.data_ptr(), info_tf.data_ptr(), ws.data_ptr(), nbytes, chunk, self.pivot_tau,
-                    int(flags), g_hop, g_first, g_nwin, T, k3_events[0] if k3_events else 0,
-                    k3_events[1] if k3_events else 0, self.stream(), aux)
-                out = band_out
-        _lib.check(rc, "hmv_sliding_ffdtf_f64" if band_out is None else "hmv_sliding_ffdtf_bands_f64")
-        if check == "nan":          # keep the good windows, NaN-fill the ones whose fit or inverse was singular
-            badw = (info_yw != 0) | (info_tf.view(n_items, F) != 0).any(dim=1)
-            if bool(badw.any()):
-                out[badw] = float("nan")
-        elif check == "mask":       # no host synchronisation: the caller decides what to NaN-fill (streamed recordings)
-            return out, (info_yw != 0) | (info_tf.view(n_items, F) != 0).any(dim=1)
-        elif check:
-            self.raise_on_info(info_yw, "ar_coeff (Yule-Walker solve)")
-            self.raise_on_info(info_tf, "mvar_transfer_function (inverse of A(f))", per_item=F)
-        if return_ar:
-            return out, ar, V, (info_yw, info_tf)
-        return out
+        rt = self._route("ffdtf", n, p, max_model_order, crit_type)
+        return self._sliding_call(rt, x, (item_rec, item_start), freqs, fs, bands=bands, out=out, return_ar=return_ar,
+                                  return_orders=return_orders, check=check, chunk=chunk, overlap=overlap, flags=flags,
+                                  grid=grid, validate=validate, k3_events=k3_events)
 
     def sliding_ddtf(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, p: int, freqs,
                      fs: float, out: torch.Tensor | None = None, return_ar: bool = False, check=True,
@@ -593,11 +762,10 @@ class Engine:
         `sliding_ffdtf`; a window also fails where its residual covariance is not positive definite (info_yw < 0).
         Equal to the reference's minors-based dDTF to rounding, not bitwise (no minors, no second inversion).
         p=None / max_model_order / crit_type / return_orders: the automatic order, as in `sliding_ffdtf`."""
-        if p is None:
-            return self._sliding_auto("ddtf", x, item_rec, item_start, n, freqs, fs, max_model_order, crit_type, out,
-                                      return_ar, return_orders, check, chunk, overlap, flags, grid, validate, bands)
-        return self._sliding_conn("ddtf", x, item_rec, item_start, n, p, freqs, fs, out, return_ar, check, chunk, overlap,
-                                  flags, grid, validate, bands)
+        rt = self._route("ddtf", n, p, max_model_order, crit_type)
+        return self._sliding_call(rt, x, (item_rec, item_start), freqs, fs, bands=bands, out=out, return_ar=return_ar,
+                                  return_orders=return_orders, check=check, chunk=chunk, overlap=overlap, flags=flags,
+                                  grid=grid, validate=validate)
 
     def sliding_gpdc(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, p: int, freqs,
                      fs: float, out: torch.Tensor | None = None, return_ar: bool = False, check=True,
@@ -609,229 +777,12 @@ class Engine:
         failure is reported: A(f) is never inverted, so an exactly singular A(f), on which the reference's
         mvar_transfer_function raises, goes through (`return_ar` gives (out, ar, V, info_yw)).
         p=None / max_model_order / crit_type / return_orders: the automatic order, as in `sliding_ffdtf`."""
-        if p is None:
-            return self._sliding_auto("gpdc", x, item_rec, item_start, n, freqs, fs, max_model_order, crit_type, out,
-                                      return_ar, return_orders, check, chunk, overlap, flags, grid, validate, bands)
-        return self._sliding_conn("gpdc", x, item_rec, item_start, n, p, freqs, fs, out, return_ar, check, chunk, overlap,
-                                  flags, grid, validate, bands)
-
-    def _sliding_conn(self, measure, x, item_rec, item_start, n, p, freqs, fs, out, return_ar, check, chunk, overlap, flags,
-                      grid, validate, bands):
-        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
-        x = x if x.stride(2) == 1 else x.contiguous()
-        n_rec, m, T = x.shape
-        mp = self.pad(m)
-        ddtf = measure == "ddtf"
-        if validate:
-            self.check_items(x, item_rec, item_start, n, p)
-        n_items = int(item_rec.numel())
-        f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
-        F = int(f.numel())
-        nb = 0
-        if bands is not None:
-            b_lo, b_hi = self.band_tables(bands[0], bands[1], F)
-            nb = int(b_lo.numel())
-        last = nb if bands is not None else F
-
-        def finish(res, ar, V, infos):
-            return (res, ar, V, infos) if return_ar else res
-        if n_items == 0:                      # empty batch (torch gives empty tensors a null data pointer)
-            infos = (self.empty(0, dtype=torch.int32),) * 2
-            return finish(self.empty(0, m, m, last), self.empty(0, mp, mp, p), self.empty(0, mp, mp),
-                          infos if ddtf else infos[0])
-        if bands is not None and nb == 0:     # an empty band set: the full arrays, then their (empty) band sums
-            res = self._sliding_conn(measure, x, item_rec, item_start, n, p, f, fs, None, return_ar, check, chunk, overlap,
-                                     flags, grid, validate, None)
-            full = res[0] if isinstance(res, tuple) else res
-            red = self.band_sums(full, bands[0], bands[1])
-            return (red,) + tuple(res[1:]) if isinstance(res, tuple) else red
-        if out is None:
-            out = self.empty(n_items, m, m, last)
-        assert out.is_contiguous() and tuple(out.shape) == (n_items, m, m, last)
-        wsf = self.lib.hmv_sliding_ddtf_workspace_bytes if ddtf else self.lib.hmv_sliding_gpdc_workspace_bytes
-        if chunk is None:
-            per_item = int(wsf(1, m, p, F, nb))
-            chunk = max(1, min(n_items, self.max_workspace_bytes // max(per_item, 1)))
-        chunk = int(chunk)
-        nbytes = int(wsf(chunk, m, p, F, nb))
-        if nbytes < 0:
-            raise ValueError(f"sliding_{measure}: bad sizes (m={m}, p={p}, F={F}, chunk={chunk})")
-        ws = self._workspace(nbytes)
-        aux = self.aux_stream().cuda_stream if overlap else 0
-        ar = self.empty(n_items, mp, mp, p) if return_ar else None
-        V = self.empty(n_items, mp, mp) if return_ar else None
-        info_yw = self.empty(n_items, dtype=torch.int32)
-        info_tf = self.empty(n_items * F, dtype=torch.int32) if ddtf else None
-        g_hop, g_first, g_nwin = (int(v) for v in grid) if grid is not None else (0, 0, 0)
-        if grid is not None:        # the same contract as sliding_ffdtf(grid=...)
-            if g_nwin < 1 or n_items % g_nwin or g_hop < 1 or n_items // g_nwin > n_rec:
-                raise ValueError("grid = (hop, first, n_win) does not match the number of items / recordings")
-            k = torch.arange(n_items, dtype=torch.int64, device=self.device)
-            same = (not validate) or (torch.equal(item_rec, k // g_nwin) and
-                                      torch.equal(item_start, g_first + (k % g_nwin) * g_hop))
-            if not same:
-                raise ValueError("grid = (hop, first, n_win) contradicts item_rec / item_start "
-                                 "(items must be recording-major, window-minor on the declared grid)")
-        lo_p, hi_p = (b_lo.data_ptr(), b_hi.data_ptr()) if nb else (0, 0)
-        common = (x.data_ptr(), x.stride(0), x.stride(1), item_rec.data_ptr(), item_start.data_ptr(), n_items, m, int(n),
-                  int(p), f.data_ptr(), F, float(fs), out.data_ptr(), lo_p, hi_p, nb, _ptr(ar), _ptr(V), info_yw.data_ptr())
-        grid_args = (g_hop, g_first, g_nwin, T, self.stream(), aux)
-        with torch.cuda.device(self.device):
-            if ddtf:
-                rc = self.lib.hmv_sliding_ddtf_f64(*common, info_tf.data_ptr(), ws.data_ptr(), nbytes, chunk, self.pivot_tau,
-                                                   int(flags), *grid_args)
-            else:
-                rc = self.lib.hmv_sliding_gpdc_f64(*common, ws.data_ptr(), nbytes, chunk, int(flags), *grid_args)
-        _lib.check(rc, f"hmv_sliding_{measure}_f64")
-        badw = info_yw != 0
-        if ddtf:
-            badw = badw | (info_tf.view(n_items, F) != 0).any(dim=1)
-        infos = (info_yw, info_tf) if ddtf else info_yw
-        if check == "nan":
-            if bool(badw.any()):
-                out[badw] = float("nan")
-        elif check == "mask":
-            return out, badw
-        elif check:
-            self.raise_on_info(info_yw, "ar_coeff (Yule-Walker solve; a negative info: residual covariance not "
-                                        "positive definite)")
-            if ddtf:
-                self.raise_on_info(info_tf, "mvar_transfer_function (inverse of A(f))", per_item=F)
-        return finish(out, ar, V, infos)
-
-    # ------------------------------------------------------------------ automatic model order (yw_auto.hip)
-    def _sliding_auto(self, measure, x, item_rec, item_start, n, freqs, fs, max_model_order, crit_type, out, return_ar,
-                      return_orders, check, chunk, overlap, flags, grid, validate, bands, out_S=None, spectra=False):
-        """`p=None` of sliding_ffdtf / _ddtf / _gpdc / _ffdtf_spectra: one call of `hmv_sliding_auto_f64`.  K1 sums
-        max_model_order + 1 lags, K2 walks every order, keeps the criterion's first arg-min per window and leaves that
-        order's coefficients zero-padded to max_model_order lags; the later stages run at max_model_order on them."""
-        pmax, crit = auto_order_args(max_model_order, crit_type, n)
-        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
-        x = x if x.stride(2) == 1 else x.contiguous()
-        n_rec, m, T = x.shape
-        mp = self.pad(m)
-        code = {"ffdtf": _lib.MEASURE_FFDTF, "ddtf": _lib.MEASURE_DDTF, "gpdc": _lib.MEASURE_GPDC}[measure]
-        gpdc = measure == "gpdc"
-        if validate:
-            self.check_items(x, item_rec, item_start, n, pmax)
-        n_items = int(item_rec.numel())
-        f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
-        F = int(f.numel())
-        nb = 0
-        if bands is not None:
-            b_lo, b_hi = self.band_tables(bands[0], bands[1], F)
-            nb = int(b_lo.numel())
-        last = nb if bands is not None else F
-
-        def finish(res, bad, ar, V, infos, orders, curve, S=None):
-            r = (res,) if S is None else (res, torch.view_as_complex(S))
-            if check == "mask":
-                r += (bad,)
-            if return_ar:
-                r += (ar, V, infos)
-            if return_orders:
-                r += (orders, curve)
-            return r if len(r) > 1 else r[0]
-        if n_items == 0:                      # empty batch (torch gives empty tensors a null data pointer)
-            i32 = self.empty(0, dtype=torch.int32)
-            return finish(self.empty(0, m, m, last), torch.zeros(0, dtype=torch.bool, device=self.device),
-                          self.empty(0, mp, mp, pmax), self.empty(0, mp, mp), i32 if gpdc else (i32, i32), i32,
-                          self.empty(0, pmax), self.empty(0, m, m, F, 2) if spectra else None)
-        full_then_sum = bands is not None and (nb == 0 or (measure == "ffdtf" and (
-            not self.bands_in_kernel(m, F) or (flags & _lib.FLAG_UNFUSED_NORM))))
-        if full_then_sum:                     # the full arrays, then their band sums (as the fixed-order calls do)
-            r = self._sliding_auto(measure, x, item_rec, item_start, n, f, fs, pmax, crit_type, None, True, True, "mask",
-                                   chunk, overlap, flags, grid, validate, None)
-            full, bad, ar, V, infos, orders, curve = r
-            red = self.band_sums(full, bands[0], bands[1])
-            if out is not None:
-                out.copy_(red)
-                red = out
-            self._auto_check(check, red, bad, infos, F, gpdc)
-            return finish(red, bad, ar, V, infos, orders, curve)
-        if out is None:
-            out = self.empty(n_items, m, m, last)
-        assert out.is_contiguous() and tuple(out.shape) == (n_items, m, m, last)
-        S = None
-        if spectra:
-            S = self.empty(n_items, m, m, F, 2) if out_S is None else out_S
-        ws_bands = -1 if spectra else nb
-        if chunk is None:
-            per_item = int(self.lib.hmv_sliding_auto_workspace_bytes(code, 1, m, pmax, F, ws_bands))
-            chunk = max(1, min(n_items, self.max_workspace_bytes // max(per_item, 1)))
-        chunk = int(chunk)
-        nbytes = int(self.lib.hmv_sliding_auto_workspace_bytes(code, chunk, m, pmax, F, ws_bands))
-        if nbytes < 0:
-            raise ValueError(f"sliding_{measure}: bad sizes (m={m}, max_model_order={pmax}, F={F}, chunk={chunk})")
-        ws = self._workspace(nbytes)
-        aux = self.aux_stream().cuda_stream if overlap else 0
-        ar = self.empty(n_items, mp, mp, pmax) if return_ar else None
-        V = self.empty(n_items, mp, mp) if return_ar else None
-        orders = self.empty(n_items, dtype=torch.int32)
-        curve = self.empty(n_items, pmax) if return_orders else None
-        info_yw = self.empty(n_items, dtype=torch.int32)
-        info_tf = None if gpdc else self.empty(n_items * F, dtype=torch.int32)
-        g_hop, g_first, g_nwin = (int(v) for v in grid) if grid is not None else (0, 0, 0)
-        if grid is not None:        # the same contract as sliding_ffdtf(grid=...)
-            if g_nwin < 1 or n_items % g_nwin or g_hop < 1 or n_items // g_nwin > n_rec:
-                raise ValueError("grid = (hop, first, n_win) does not match the number of items / recordings")
-            k = torch.arange(n_items, dtype=torch.int64, device=self.device)
-            same = (not validate) or (torch.equal(item_rec, k // g_nwin) and
-                                      torch.equal(item_start, g_first + (k % g_nwin) * g_hop))
-            if not same:
-                raise ValueError("grid = (hop, first, n_win) contradicts item_rec / item_start "
-                                 "(items must be recording-major, window-minor on the declared grid)")
-        lo_p, hi_p = (b_lo.data_ptr(), b_hi.data_ptr()) if nb else (0, 0)
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_sliding_auto_f64(
-                code, x.data_ptr(), x.stride(0), x.stride(1), item_rec.data_ptr(), item_start.data_ptr(), n_items, m, int(n),
-                pmax, crit, f.data_ptr(), F, float(fs), out.data_ptr(), lo_p, hi_p, nb, _ptr(S), _ptr(ar), _ptr(V),
-                orders.data_ptr(), _ptr(curve), info_yw.data_ptr(), _ptr(info_tf), ws.data_ptr(), nbytes, chunk,
-                self.pivot_tau, int(flags), g_hop, g_first, g_nwin, T, self.stream(), aux)
-        _lib.check(rc, "hmv_sliding_auto_f64")
-        bad = info_yw != 0
-        if not gpdc:
-            bad = bad | (info_tf.view(n_items, F) != 0).any(dim=1)
-        infos = info_yw if gpdc else (info_yw, info_tf)
-        self._auto_check(check, out, bad, infos, F, gpdc, S)
-        return finish(out, bad, ar, V, infos, orders, curve, S)
-
-    def _auto_check(self, check, out, bad, infos, F, gpdc, S=None):
-        if check == "nan":
-            if bool(bad.any()):
-                out[bad] = float("nan")
-                if S is not None:
-                    S[bad] = float("nan")
-        elif check and check != "mask":
-            self.raise_on_info(infos if gpdc else infos[0], "ar_coeff (Yule-Walker solve at the automatic order; a negative "
-                                                            "info: residual covariance not positive definite)")
-            if not gpdc:
-                self.raise_on_info(infos[1], "mvar_transfer_function (inverse of A(f))", per_item=F)
+        rt = self._route("gpdc", n, p, max_model_order, crit_type)
+        return self._sliding_call(rt, x, (item_rec, item_start), freqs, fs, bands=bands, out=out, return_ar=return_ar,
+                                  return_orders=return_orders, check=check, chunk=chunk, overlap=overlap, flags=flags,
+                                  grid=grid, validate=validate)
 
     # ------------------------------------------------------------------ event-locked ensembles (lagcov_ensemble.hip)
-    def _ensemble_args(self, x, trial_rec, trial_start, group_ptr, item_group, item_offset, n, p, grid, validate):
-        """Common front of `lagcov_ensemble` / `sliding_ensemble`: every index array checked (`validate_trials`), a declared
-        grid compared with item_group / item_offset.  Returns (x, n_groups, n_items, grid_hop, grid_nwin)."""
-        if p is None:
-            raise ValueError("ensemble fits need an integer model order p: the reference's mvar_criterion does not take "
-                             "(channels, samples, trials) input, so there is no automatic order to reproduce")
-        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
-        x = x if x.stride(2) == 1 else x.contiguous()
-        if validate:
-            validate_trials(x, trial_rec, trial_start, group_ptr, item_group, item_offset, n, p)
-        n_groups, n_items = int(group_ptr.numel()) - 1, int(item_group.numel())
-        g_hop, g_nwin = (int(v) for v in grid) if grid is not None else (0, 0)
-        if grid is not None and n_items:
-            # with a declared grid the shared form addresses by (item // n_win, (item % n_win) * hop) and never reads
-            # item_group / item_offset: they must say the same thing
-            if g_hop < 1 or g_nwin < 1 or n_items != n_groups * g_nwin:
-                raise ValueError("grid = (hop, n_win) does not match the number of items / groups")
-            k = torch.arange(n_items, dtype=torch.int64, device=self.device)
-            if validate and not (torch.equal(item_group, k // g_nwin) and torch.equal(item_offset, (k % g_nwin) * g_hop)):
-                raise ValueError("grid = (hop, n_win) contradicts item_group / item_offset "
-                                 "(items must be group-major, window-minor on the declared grid)")
-        return x, n_groups, n_items, g_hop, g_nwin
-
     def lagcov_ensemble(self, x: torch.Tensor, trial_rec: torch.Tensor, trial_start: torch.Tensor, group_ptr: torch.Tensor,
                         item_group: torch.Tensor, item_offset: torch.Tensor, n: int, p: int, grid=None, flags: int = 0,
                         validate: bool = True):
@@ -840,8 +791,14 @@ class Engine:
         (`count_corr` on 3-D input, mtmvar.py:54-85).  Index tensors as in `validate_trials`.  grid = (hop, n_win) declares
         item = g * n_win + w at offset w * hop and lets the library share the overlap between windows
         (`hmv_lagcov_ensemble_f64`; `_lib.FLAG_DIRECT_LAGCOV` keeps the direct form)."""
-        x, n_groups, n_items, g_hop, g_nwin = self._ensemble_args(x, trial_rec, trial_start, group_ptr, item_group,
-                                                                  item_offset, n, p, grid, validate)
+        if p is None:
+            raise ValueError(_NO_ENSEMBLE_ORDER)
+        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
+        x = x if x.stride(2) == 1 else x.contiguous()
+        if validate:
+            validate_trials(x, trial_rec, trial_start, group_ptr, item_group, item_offset, n, p)
+        n_groups, n_items = int(group_ptr.numel()) - 1, int(item_group.numel())
+        g_hop, g_nwin = self._ensemble_grid(n_groups, (item_group, item_offset), n_items, grid, validate)
         n_rec, m, T = x.shape
         mp = self.pad(m)
         R = self.empty(n_items, p + 1, mp, mp)
@@ -878,96 +835,9 @@ class Engine:
             raise ValueError(f"measure must be 'ffdtf', 'ddtf' or 'gpdc', got {measure!r}")
         if spectra and (measure != "ffdtf" or bands is not None):
             raise ValueError("spectra come with the full ffDTF only")
-        x, n_groups, n_items, g_hop, g_nwin = self._ensemble_args(x, trial_rec, trial_start, group_ptr, item_group,
-                                                                  item_offset, n, p, grid, validate)
-        n_rec, m, T = x.shape
-        mp = self.pad(m)
-        n, p = int(n), int(p)
-        code = {"ffdtf": _lib.MEASURE_FFDTF, "ddtf": _lib.MEASURE_DDTF, "gpdc": _lib.MEASURE_GPDC}[measure]
-        gpdc = measure == "gpdc"
-        f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
-        F = int(f.numel())
-        nb = 0
-        if bands is not None:
-            b_lo, b_hi = self.band_tables(bands[0], bands[1], F)
-            nb = int(b_lo.numel())
-        last = nb if bands is not None else F
-
-        def finish(res, bad, ar, V, infos, S=None):
-            r = (res,) if S is None else (res, torch.view_as_complex(S))
-            if check == "mask":
-                r += (bad,)
-            if return_ar:
-                r += (ar, V, infos)
-            return r if len(r) > 1 else r[0]
-        if n_items == 0:                      # empty batch (torch gives empty tensors a null data pointer)
-            i32 = self.empty(0, dtype=torch.int32)
-            return finish(self.empty(0, m, m, last), torch.zeros(0, dtype=torch.bool, device=self.device),
-                          self.empty(0, mp, mp, p), self.empty(0, mp, mp), i32 if gpdc else (i32, i32),
-                          self.empty(0, m, m, F, 2) if spectra else None)
-        full_then_sum = bands is not None and (nb == 0 or (measure == "ffdtf" and (
-            not self.bands_in_kernel(m, F) or (flags & _lib.FLAG_UNFUSED_NORM))))
-        if full_then_sum:                     # the full arrays, then their band sums (as the single-trial calls do)
-            full, bad, ar, V, infos = self.sliding_ensemble(x, trial_rec, trial_start, group_ptr, item_group, item_offset, n,
-                                                            p, f, fs, measure, None, False, None, True, "mask", chunk, grid,
-                                                            flags, False)
-            red = self.band_sums(full, bands[0], bands[1])
-            if out is not None:
-                out.copy_(red)
-                red = out
-            self._ensemble_check(check, red, bad, infos, F, gpdc, item_group, item_offset)
-            return finish(red, bad, ar, V, infos)
-        if out is None:
-            out = self.empty(n_items, m, m, last)
-        assert out.is_contiguous() and tuple(out.shape) == (n_items, m, m, last)
-        S = self.empty(n_items, m, m, F, 2) if spectra else None
-        ws_bands = -1 if spectra else nb
-        wsf = self.lib.hmv_sliding_ensemble_workspace_bytes
-        if chunk is None:
-            per_item = int(wsf(code, 1, m, n, p, F, ws_bands, 0, 0))
-            chunk = max(1, min(n_items, self.max_workspace_bytes // max(per_item, 1)))
-        chunk = int(chunk)
-        nbytes = int(wsf(code, chunk, m, n, p, F, ws_bands, g_hop, g_nwin))
-        if nbytes < 0:
-            raise ValueError(f"sliding_ensemble: bad sizes (m={m}, n={n}, p={p}, F={F}, chunk={chunk})")
-        ws = self._workspace(nbytes)
-        ar = self.empty(n_items, mp, mp, p) if return_ar else None
-        V = self.empty(n_items, mp, mp) if return_ar else None
-        info_yw = self.empty(n_items, dtype=torch.int32)
-        info_tf = None if gpdc else self.empty(n_items * F, dtype=torch.int32)
-        lo_p, hi_p = (b_lo.data_ptr(), b_hi.data_ptr()) if nb else (0, 0)
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_sliding_ensemble_f64(
-                code, x.data_ptr(), x.stride(0), x.stride(1), T, trial_rec.data_ptr(), trial_start.data_ptr(),
-                group_ptr.data_ptr(), n_groups, item_group.data_ptr(), item_offset.data_ptr(), n_items, m, n, p, f.data_ptr(),
-                F, float(fs), out.data_ptr(), lo_p, hi_p, nb, _ptr(S), _ptr(ar), _ptr(V), info_yw.data_ptr(), _ptr(info_tf),
-                ws.data_ptr(), nbytes, chunk, self.pivot_tau, int(flags), g_hop, g_nwin, self.stream(), 0)
-        _lib.check(rc, "hmv_sliding_ensemble_f64")
-        bad = info_yw != 0
-        if not gpdc:
-            bad = bad | (info_tf.view(n_items, F) != 0).any(dim=1)
-        infos = info_yw if gpdc else (info_yw, info_tf)
-        self._ensemble_check(check, out, bad, infos, F, gpdc, item_group, item_offset, S)
-        return finish(out, bad, ar, V, infos, S)
-
-    def _ensemble_check(self, check, out, bad, infos, F, gpdc, item_group, item_offset, S=None):
-        if check == "nan":
-            if bool(bad.any()):
-                out[bad] = float("nan")
-                if S is not None:
-                    S[bad] = float("nan")
-        elif check and check != "mask":
-            try:
-                self.raise_on_info(infos if gpdc else infos[0], "ar_coeff (Yule-Walker solve of the trial-averaged "
-                                   "covariances; a negative info: residual covariance not positive definite)")
-                if not gpdc:
-                    self.raise_on_info(infos[1], "mvar_transfer_function (inverse of A(f))", per_item=F)
-            except SingularMatrixError as err:       # say which group and which window of the epoch
-                items = torch.as_tensor(err.items, dtype=torch.int64, device=item_group.device)
-                err.groups = item_group[items].cpu().numpy()
-                err.offsets = item_offset[items].cpu().numpy()
-                err.args = (err.args[0], err.args[1] + f" (group {int(err.groups[0])}, window at offset {int(err.offsets[0])})")
-                raise
+        rt = self._ensemble_route(measure, n, p, trial_rec, trial_start, group_ptr, spectra)
+        return self._sliding_call(rt, x, (item_group, item_offset), freqs, fs, bands=bands, out=out, return_ar=return_ar,
+                                  check=check, chunk=chunk, flags=flags, grid=grid, validate=validate)
 
     # ------------------------------------------------------------------ surrogate significance (surrogate.hip)
     def surrogate_shift(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, shift: torch.Tensor,
@@ -1303,48 +1173,9 @@ class Engine:
         `sliding_ffdtf`.  Returns (ffdtf (items, m, m, F) real, S (items, m, m, F) complex).
         p=None / max_model_order / crit_type: the automatic order, as in `sliding_ffdtf`; `return_orders=True` appends
         `orders` and `crit`."""
-        if p is None:
-            return self._sliding_auto("ffdtf", x, item_rec, item_start, n, freqs, fs, max_model_order, crit_type, out_ff,
-                                      False, return_orders, check, chunk, True, flags, grid, True, None, out_S=out_S,
-                                      spectra=True)
-        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
-        x = x if x.stride(2) == 1 else x.contiguous()
-        n_rec, m, T = x.shape
-        self.check_items(x, item_rec, item_start, n, p)
-        n_items = int(item_rec.numel())
-        f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
-        F = int(f.numel())
-        ff = self.empty(n_items, m, m, F) if out_ff is None else out_ff
-        S = self.empty(n_items, m, m, F, 2) if out_S is None else out_S
-        if n_items == 0:
-            return ff, torch.view_as_complex(S)
-        if chunk is None:
-            per_item = int(self.lib.hmv_sliding_spectra_workspace_bytes(1, m, p, F))
-            chunk = max(1, min(n_items, self.max_workspace_bytes // max(per_item, 1)))
-        chunk = int(chunk)
-        nbytes = int(self.lib.hmv_sliding_spectra_workspace_bytes(chunk, m, p, F))
-        ws = self._workspace(nbytes)
-        info_yw = self.empty(n_items, dtype=torch.int32)
-        info_tf = self.empty(n_items * F, dtype=torch.int32)
-        g_hop, g_first, g_nwin = (int(v) for v in grid) if grid is not None else (0, 0, 0)
-        if grid is not None:
-            if g_nwin < 1 or n_items % g_nwin or g_hop < 1 or n_items // g_nwin > n_rec:
-                raise ValueError("grid = (hop, first, n_win) does not match the number of items / recordings")
-            k = torch.arange(n_items, dtype=torch.int64, device=self.device)
-            if not (torch.equal(item_rec, k // g_nwin) and torch.equal(item_start, g_first + (k % g_nwin) * g_hop)):
-                raise ValueError("grid = (hop, first, n_win) contradicts item_rec / item_start "
-                                 "(items must be recording-major, window-minor on the declared grid)")
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_sliding_ffdtf_spectra_f64(
-                x.data_ptr(), x.stride(0), x.stride(1), item_rec.data_ptr(), item_start.data_ptr(), n_items,
-                m, int(n), int(p), f.data_ptr(), F, float(fs), ff.data_ptr(), S.data_ptr(), 0, 0,
-                info_yw.data_ptr(), info_tf.data_ptr(), ws.data_ptr(), nbytes, chunk, self.pivot_tau, int(flags),
-                g_hop, g_first, g_nwin, T, self.stream(), self.aux_stream().cuda_stream)
-        _lib.check(rc, "hmv_sliding_ffdtf_spectra_f64")
-        if check:
-            self.raise_on_info(info_yw, "ar_coeff (Yule-Walker solve)")
-            self.raise_on_info(info_tf, "mvar_transfer_function (inverse of A(f))", per_item=F)
-        return ff, torch.view_as_complex(S)
+        rt = self._route("ffdtf", n, p, max_model_order, crit_type, spectra=True)
+        return self._sliding_call(rt, x, (item_rec, item_start), freqs, fs, out=out_ff, out_S=out_S,
+                                  return_orders=return_orders, check=check, chunk=chunk, overlap=True, flags=flags, grid=grid)
 
     # ------------------------------------------------------------------ FAD (fad.hip)
     FAD_CRIT = {"AIC": 0, "HQ": 1, "SC": 2}

@@ -119,3 +119,19 @@ def test_host_sanitizer_build_of_the_c_abi():
     assert r.returncode == 0, r.stdout + r.stderr
     assert "asan driver ok" in r.stdout
     assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr
+
+
+def test_sliding_workspace_sizes_are_the_recorded_ones(lib):
+    """The seven hmv_sliding_*_workspace_bytes functions go through one helper: for a grid of small argument tuples (three
+    m, three p, two F, chunk 1 and 7, n_bands -1 / 0 / 5, the three measures, with and without an ensemble grid) and the
+    out-of-range tuples that must give -1, they return what the library returned before they were folded together
+    (tests/golden/sliding_workspace_bytes.json: argument tuples in the order of include/hypermvar.h, and the values)."""
+    import json
+    rec = json.load(open(os.path.join(ROOT, "tests", "golden", "sliding_workspace_bytes.json")))
+    assert sorted(rec) == sorted(s for s in header_symbols() if s.startswith("hmv_sliding_") and s.endswith("workspace_bytes"))
+    assert len(rec) == 7
+    for fn, table in rec.items():
+        assert len(table["args"]) == len(table["bytes"]) >= 40
+        assert any(b == -1 for b in table["bytes"]) and any(b > 0 for b in table["bytes"])
+        for args, want in zip(table["args"], table["bytes"]):
+            assert getattr(lib, fn)(*args) == want, (fn, args, want)
