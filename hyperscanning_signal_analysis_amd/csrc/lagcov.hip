@@ -123,34 +123,69 @@ __global__ void __launch_bounds__(256, 2) lagcov_kernel(LagcovArgs a) {
 //     C_l(w) = sum_{t = n - l}^{n - 1} x[s_w + t] x[s_w + t + l]^T     (the l products that reach past the window end)
 // -- half the flops of the direct form at 50 % overlap.  Same biased 1/n estimator, no demeaning (mtmvar.py:57-59,
 // 72-73); the sums are merely associated differently, so results agree with the direct form to rounding (not bitwise).
-// grid (n_win, p + 1), block 256: 16 * NT * NT / 16 elements per thread.
+// grid (n_win, p + 1), block 256: NT * NT elements per thread.
+//
+// The 2 l samples x[:, s+n-l .. s+n+l-1] that C_l needs are contiguous in time, so they are staged as ONE image
+// xs[ch][v]: lane v of wave w fetches sample v of the channels w, w + 4, ... (no division, the bounds tests hoisted out
+// of the channel loop).  The row stride LC_CS is odd: the element loop reads xs[row][u] (one address per wave at MP = 64:
+// a broadcast) and xs[col][l + u] with col running over the lanes, which at the former stride of 32 doubles put every
+// lane of a wave on the same bank.  The elements are taken LC_E at a time so that their block-sum loads are in flight
+// together; each element's sums keep their order (Q blocks ascending, then the ascending FMA chain over u).
+constexpr int LC_CS = 2 * LC_HALO + 1;     // 65
 template <int NT>
 __global__ void __launch_bounds__(256) lagcomb_kernel(LagcombArgs a) {
-  constexpr int MP = 16 * NT, TILE = MP * MP;
-  __shared__ double xa[MP * 32], xb[MP * 32];        // x[:, s+n-l .. s+n-1] and x[:, s+n .. s+n+l-1]
+  constexpr int MP = 16 * NT, TILE = MP * MP, NE = TILE / 256;
+  constexpr int LC_E = (NE % 4 == 0) ? 4 : (NE % 3 == 0) ? 3 : 1;
+  __shared__ double xs[MP * LC_CS];
   const long long w = blockIdx.x;
   const int lag = blockIdx.y;
   const int n = (int)(a.hop * a.k), m = a.m;
   const long long s = a.first + w * a.hop;
-  for (int idx = threadIdx.x; idx < MP * lag; idx += 256) {
-    const int ch = idx / lag, u = idx - ch * lag;
-    const long long ta = s + n - lag + u, tb = s + n + u;
-    xa[ch * 32 + u] = (ch < m && ta < a.T) ? a.x[(size_t)ch * a.ld + ta] : 0.0;
-    xb[ch * 32 + u] = (ch < m && tb < a.T) ? a.x[(size_t)ch * a.ld + tb] : 0.0;
+  {
+    const int v = threadIdx.x & 63, wv = uni(threadIdx.x >> 6);
+    const long long t = s + n - lag + v;
+    const bool staged = v < 2 * lag, in = staged && t < a.T;       // samples past the end of the recording are zeros
+    const double* xt = a.x + t;
+#pragma unroll
+    for (int j = 0; j < MP / 4; ++j) {
+      const int ch = 4 * j + wv;                                   // wave-uniform
+      double val = 0.0;
+      if (in && ch < m) val = xt[(size_t)ch * a.ld];
+      if (staged) xs[ch * LC_CS + v] = val;
+    }
   }
   __syncthreads();
   const double inv_n = 1.0 / (double)n;
+  const size_t qstep = (size_t)(a.p + 1) * TILE;
   const double* Q = a.Q + ((size_t)w * (a.p + 1) + lag) * TILE;
   double* R = a.R + ((size_t)w * (a.p + 1) + lag) * TILE;
-  for (int e = threadIdx.x; e < TILE; e += 256) {
-    const int row = e / MP, col = e - row * MP;
-    double acc = 0.0;
-    for (int j = 0; j < a.k; ++j) acc += Q[(size_t)j * (a.p + 1) * TILE + e];
-    double c = 0.0;
-    for (int u = 0; u < lag; ++u) c = __builtin_fma(xa[row * 32 + u], xb[col * 32 + u], c);
-    double v = (acc - c) * inv_n;
-    if (lag == 0 && row == col && row >= m) v = 1.0;    // padded channels: identity block keeps G SPD
-    R[e] = v;
+  const int k = a.k;
+  for (int eb = 0; eb < NE; eb += LC_E) {
+    double acc[LC_E], c[LC_E];
+    const double *xa[LC_E], *xb[LC_E];
+#pragma unroll
+    for (int r = 0; r < LC_E; ++r) {
+      const unsigned e = threadIdx.x + 256u * (eb + r), row = e / MP, col = e % MP;
+      xa[r] = xs + row * LC_CS;
+      xb[r] = xs + col * LC_CS + lag;
+      acc[r] = 0.0;
+      c[r] = 0.0;
+    }
+    for (int j = 0; j < k; ++j) {
+#pragma unroll
+      for (int r = 0; r < LC_E; ++r) acc[r] += Q[(size_t)j * qstep + threadIdx.x + 256u * (eb + r)];
+    }
+    for (int u = 0; u < lag; ++u) {
+#pragma unroll
+      for (int r = 0; r < LC_E; ++r) c[r] = __builtin_fma(xa[r][u], xb[r][u], c[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < LC_E; ++r) {
+      const unsigned e = threadIdx.x + 256u * (eb + r), row = e / MP, col = e % MP;
+      double v = (acc[r] - c[r]) * inv_n;
+      if (lag == 0 && row == col && (int)row >= m) v = 1.0;    // padded channels: identity block keeps G SPD
+      R[e] = v;
+    }
   }
 }
 

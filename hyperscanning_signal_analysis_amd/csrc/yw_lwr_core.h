@@ -64,51 +64,85 @@ __device__ __forceinline__ void yw_lwr_body(const YwArgs& a, const YwAutoArgs& s
 #pragma unroll
       for (int J = 0; J < NJ; ++J) v[ii][J] = 0.0;
   };
+  // ---- addressing.  Every tile base is wave-uniform (it depends on blockIdx.x, q, k and p only), so a tile element is
+  // addressed as that base, advanced by scalar adds for the steps that are compile-time or wave-uniform (wave strip, r,
+  // ii, k-half), plus an UNSIGNED 32-bit byte offset per lane: the scalar-base form of the global instructions, with the
+  // small steps (J) in their immediate field.  The per-lane offsets are shifts and masks of the thread index, recomputed
+  // where they are used (tid() is opaque to the optimiser on purpose: offsets kept live across the recursion would be
+  // spilled -- the kernel sits at its register ceiling).
+  auto tid = [&]() __attribute__((always_inline)) {
+    unsigned t;
+    asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(threadIdx.x));
+    return t;
+  };
+  // (a constant step beyond the instruction's 12-bit immediate is added to the base in scalar registers, where it is
+  // used: the empty asm keeps the optimiser from moving it behind the per-lane offset, where it would need a 64-bit
+  // vector add, and from keeping every stepped base live in scalar registers the kernel does not have)
+  typedef const char __attribute__((address_space(1))) * gcptr;
+  auto gptr = [&](const double* base, unsigned cbytes, unsigned off) __attribute__((always_inline)) {
+    unsigned long long sb = reinterpret_cast<unsigned long long>(base) + (cbytes & ~0xfffu);
+    if (cbytes & ~0xfffu) asm volatile("" : "+s"(sb));
+    return reinterpret_cast<gcptr>(sb) + (cbytes & 0xfffu) + (size_t)off;
+  };
   // ---- operand staging, one k-half at a time (as in yw_solve.hip).  Plain image: dst[row][k] = src[row][kh*KH + k];
-  // transposed image: dst[col][k] = src[kh*KH + k][col].
+  // transposed image: dst[col][k] = src[kh*KH + k][col].  Thread idx = t + 256 r moves the pair (row, 2 c2) resp.
+  // (k, 2 c2); where 256 is a multiple of the pairs per row (NT = 1, 2, 4) the r step is a whole number of rows and goes
+  // into the scalar base / the LDS immediate.
+  constexpr unsigned PR = KH / 2, PT = MP / 2;          // pairs per row of the plain / the transposed image
+  constexpr bool RSTEP = (256 % PR == 0) && (256 % PT == 0);
   auto fetch = [&](f64x2 (&v)[NV], const double* src, int kh, bool tr) __attribute__((always_inline)) {
-    const int t0 = lane() + 64 * wv;
+    const unsigned t = tid();
+    if (RSTEP) {
+      const unsigned off = !tr ? ((t / PR) * MP + 2 * (t % PR)) * 8u : ((t / PT) * MP + 2 * (t % PT)) * 8u;
 #pragma unroll
-    for (int r = 0; r < NV; ++r) {
-      const int idx = t0 + 256 * r;
-      if (NV * 256 == MP * KH / 2 || idx < MP * KH / 2) {
-        if (!tr) {
-          const int row = idx / (KH / 2), c2 = idx - row * (KH / 2);
-          v[r] = *reinterpret_cast<const f64x2*>(src + (size_t)row * MP + kh * KH + 2 * c2);
-        } else {
-          const int k = idx / (MP / 2), c2 = idx - k * (MP / 2);
-          v[r] = *reinterpret_cast<const f64x2*>(src + (size_t)(kh * KH + k) * MP + 2 * c2);
+      for (int r = 0; r < NV; ++r) {
+        const unsigned cb = !tr ? (r * (256 / PR) * MP + kh * KH) * 8u : (kh * KH + r * (256 / PT)) * MP * 8u;
+        if (NV * 256 == MP * KH / 2 || t + 256 * r < MP * KH / 2) v[r] = *reinterpret_cast<const f64x2 __attribute__((address_space(1)))*>(gptr(src, cb, off));
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < NV; ++r) {
+        const unsigned idx = t + 256 * r;
+        if (NV * 256 == MP * KH / 2 || idx < MP * KH / 2) {
+          const unsigned off = !tr ? ((idx / PR) * MP + 2 * (idx % PR)) * 8u : ((idx / PT) * MP + 2 * (idx % PT)) * 8u;
+          const unsigned cb = !tr ? kh * KH * 8u : kh * KH * MP * 8u;
+          v[r] = *reinterpret_cast<const f64x2 __attribute__((address_space(1)))*>(gptr(src, cb, off));
         }
       }
     }
   };
   auto park = [&](double* dst, const f64x2 (&v)[NV], bool tr) __attribute__((always_inline)) {
-    const int t0 = lane() + 64 * wv;
+    const unsigned t = tid();
 #pragma unroll
     for (int r = 0; r < NV; ++r) {
-      const int idx = t0 + 256 * r;
-      if (NV * 256 == MP * KH / 2 || idx < MP * KH / 2) {
+      const unsigned idx = RSTEP ? t : t + 256 * r;       // (RSTEP: the r step is the constant added below)
+      if (NV * 256 == MP * KH / 2 || t + 256 * r < MP * KH / 2) {
         if (!tr) {
-          const int row = idx / (KH / 2), c2 = idx - row * (KH / 2);
-          double* d = dst + row * SH + 2 * c2;
+          double* d = dst + (RSTEP ? r * (256 / PR) * SH : 0) + ((idx / PR) * SH + 2 * (idx % PR));
           d[0] = v[r].x;
           d[1] = v[r].y;
         } else {
-          const int k = idx / (MP / 2), c2 = idx - k * (MP / 2);
-          dst[(2 * c2) * SH + k] = v[r].x;
-          dst[(2 * c2 + 1) * SH + k] = v[r].y;
+          double* d = dst + (RSTEP ? r * (256 / PT) : 0) + ((2 * (idx % PT)) * SH + idx / PT);
+          d[0] = v[r].x;
+          d[SH] = v[r].y;
         }
       }
     }
   };
+  // (whether column block J of the strip lies in k-half kh is known at compile time unless the half's edge cuts it)
   auto park_strip = [&](const double (&v)[NIW][NJ], int kh) __attribute__((always_inline)) {
-    const int l = lane(), i = l >> 4, cc = l & 15;
+    const unsigned l = lane(), i = l >> 4, cc = l & 15;
+    double* d = Xh + (unsigned)(4 * wv * NT) * SH + (i * SH + cc);
 #pragma unroll
     for (int ii = 0; ii < NIW; ++ii)
 #pragma unroll
       for (int J = 0; J < NJ; ++J) {
-        const int col = 16 * J + cc - kh * KH;
-        if (col >= 0 && col < KH) Xh[(4 * (wv * NT + ii) + i) * SH + col] = v[ii][J];
+        const int c0 = 16 * J - kh * KH;                  // column of lane cc = 0
+        if (c0 >= 0 && c0 + 15 < KH) d[4 * ii * SH + c0] = v[ii][J];
+        else if (c0 + 15 >= 0 && c0 < KH) {
+          const int col = c0 + (int)cc;
+          if (col >= 0 && col < KH) d[4 * ii * SH + c0] = v[ii][J];
+        }
       }
   };
   // One k-half of a product: KH / 4 k-steps of NIW + NJ operand reads and NIW * NJ MFMAs.  The operands of step s + 1 are
@@ -119,9 +153,9 @@ __device__ __forceinline__ void yw_lwr_body(const YwArgs& a, const YwAutoArgs& s
 #define HMV_LWR_GEMM_PIPE 1
 #endif
   auto gemm_half = [&](double (&acc)[NIW][NJ]) __attribute__((always_inline)) {
-    const int l = lane();
-    const double* xa = Xh + (4 * wv * NT + (l & 3)) * SH + (l >> 4);
-    const double* yb = Yh + (l & 15) * SH + (l >> 4);
+    const unsigned l = lane();
+    const double* xa = Xh + (unsigned)(4 * wv * NT) * SH + ((l & 3) * SH + (l >> 4));
+    const double* yb = Yh + ((l & 15) * SH + (l >> 4));
 #if HMV_LWR_GEMM_PIPE
     constexpr int NS = KH / 4;
     double av[2][NIW], bv[2][NJ];
@@ -177,22 +211,27 @@ __device__ __forceinline__ void yw_lwr_body(const YwArgs& a, const YwAutoArgs& s
     __syncthreads();
     gemm_half(acc);
   };
+  // register tile <-> global tile: the wave's strip and the ii step (4 rows) advance the scalar base, the J step (16
+  // columns) is an immediate; the lane adds (i, cc)
   auto store_tile = [&](double* dst, const double (&v)[NIW][NJ]) __attribute__((always_inline)) {
-    const int l = lane(), i = l >> 4, cc = l & 15;
+    const unsigned l = lane(), off = ((l >> 4) * MP + (l & 15)) * 8u;
+    const double* strip = dst + (unsigned)(4 * wv * NT) * MP;
 #pragma unroll
     for (int ii = 0; ii < NIW; ++ii)
 #pragma unroll
-      for (int J = 0; J < NJ; ++J) dst[(size_t)(4 * (wv * NT + ii) + i) * MP + 16 * J + cc] = v[ii][J];
+      for (int J = 0; J < NJ; ++J)
+        *(double __attribute__((address_space(1)))*)(gptr(strip, (4 * ii * MP + 16 * J) * 8u, off)) = v[ii][J];
   };
   // tile (or its transpose) -> this workgroup's register tile
   auto load_tile = [&](double (&v)[NIW][NJ], const double* src, bool tr) __attribute__((always_inline)) {
-    const int l = lane(), i = l >> 4, cc = l & 15;
+    const unsigned l = lane(), off = !tr ? ((l >> 4) * MP + (l & 15)) * 8u : ((l & 15) * MP + (l >> 4)) * 8u;
+    const double* strip = src + (unsigned)(4 * wv * NT) * (!tr ? MP : 1);
 #pragma unroll
     for (int ii = 0; ii < NIW; ++ii)
 #pragma unroll
       for (int J = 0; J < NJ; ++J) {
-        const int row = 4 * (wv * NT + ii) + i, col = 16 * J + cc;
-        v[ii][J] = tr ? src[(size_t)col * MP + row] : src[(size_t)row * MP + col];
+        const unsigned cb = !tr ? (4 * ii * MP + 16 * J) * 8u : (16 * J * MP + 4 * ii) * 8u;
+        v[ii][J] = *reinterpret_cast<const double __attribute__((address_space(1)))*>(gptr(strip, cb, off));
       }
   };
   auto sub = [&](double (&g)[NIW][NJ], const double (&acc)[NIW][NJ]) __attribute__((always_inline)) {
@@ -239,6 +278,23 @@ __device__ __forceinline__ void yw_lwr_body(const YwArgs& a, const YwAutoArgs& s
     if (AUTO) return &s_logdet;
     return a.Vq_logdet + (size_t)item * p + (q - 1);
   };
+  // the order-q model to the output: ar[item][e][k] = A_{k+1}[e], e = row * MP + col, k < q (lag fastest: the reference's
+  // (m, m, p) layout).  Thread t takes idx = t, t + 256, ... with (e, k) = (idx / q, idx % q) carried along by the step
+  // (256 / q, 256 % q): one division per thread instead of one per element.
+  auto emit = [&](const double* Aq, int q) __attribute__((always_inline)) {
+    double* ar = a.ar + (size_t)item * TILE * p;
+    const int total = TILE * q, de = 256 / q, dk = 256 - de * q;
+    int e = (int)threadIdx.x / q, k = (int)threadIdx.x - e * q;
+    for (int idx = threadIdx.x; idx < total; idx += 256) {
+      ar[(size_t)e * p + k] = Aq[(size_t)k * TILE + e];
+      e += de;
+      k += dk;
+      if (k >= q) {
+        k -= q;
+        ++e;
+      }
+    }
+  };
   // AUTO: criterion of order q (mtmvar.py:551-601: log det V_q + c q m^2 / n, summed in the reference's order), first
   // arg-min by a strict <, and on every improvement the order-q model -- A^(q) in Agen[q & 1], Vf_q -- goes to the
   // outputs.  Orders are visited ascending, so a later snapshot only ever adds lags; lags >= q* are zeroed at the end.
@@ -257,13 +313,7 @@ __device__ __forceinline__ void yw_lwr_body(const YwArgs& a, const YwAutoArgs& s
     }
     __syncthreads();
     if (s_take) {
-      const double* Aq = Agen[q & 1];
-      double* ar = a.ar + (size_t)item * TILE * p;
-      const int total = TILE * q;
-      for (int idx = threadIdx.x; idx < total; idx += 256) {
-        const int e = idx / q, k = idx - e * q;
-        ar[(size_t)e * p + k] = Aq[(size_t)k * TILE + e];
-      }
+      emit(Agen[q & 1], q);
       double* Vo = a.V + (size_t)item * TILE;
       for (int idx = threadIdx.x; idx < TILE; idx += 256) Vo[idx] = Vf[idx];
     }
@@ -364,10 +414,12 @@ __device__ __forceinline__ void yw_lwr_body(const YwArgs& a, const YwAutoArgs& s
       *yw_guard_ptr(a.ws, item, p, TILE) = (bad == 0 && qs > 0 && s_guard != 0 && s_guard - 1 <= qs) ? 1 : 0;
     }
     double* ar = a.ar + (size_t)item * TILE * p;
-    const int total = TILE * p;
+    const int total = TILE * p, dk = 256 % p;
+    int k = (int)threadIdx.x % p;
     for (int idx = threadIdx.x; idx < total; idx += 256) {
-      const int e = idx / p, k = idx - e * p;
       if (k >= qs) ar[idx] = 0.0;
+      k += dk;
+      k = (k >= p) ? k - p : k;
     }
     if (qs == 0) {
       double* Vo = a.V + (size_t)item * TILE;
@@ -375,7 +427,7 @@ __device__ __forceinline__ void yw_lwr_body(const YwArgs& a, const YwAutoArgs& s
     }
     return;
   }
-  // ---- outputs: V = Vf_p, ar[item][row][col][k] = A_{k+1}[row][col] (lag fastest: the reference's (m, m, p) layout)
+  // ---- outputs: V = Vf_p and the order-p model
   load_tile(g, Vf, false);
   store_tile(a.V + (size_t)item * TILE, g);
   if (threadIdx.x == 0) {
@@ -383,13 +435,7 @@ __device__ __forceinline__ void yw_lwr_body(const YwArgs& a, const YwAutoArgs& s
     // (a singular window stays singular: nothing to re-solve)
     *yw_guard_ptr(a.ws, item, p, TILE) = (s_info == 0) ? s_guard : 0;
   }
-  const double* Af = Agen[p & 1];
-  double* ar = a.ar + (size_t)item * TILE * p;
-  const int total = TILE * p;
-  for (int idx = threadIdx.x; idx < total; idx += 256) {
-    const int e = idx / p, k = idx - e * p;
-    ar[idx] = Af[(size_t)k * TILE + e];
-  }
+  emit(Agen[p & 1], p);
 }
 
 }  // namespace hmv
