@@ -96,6 +96,14 @@ SIGNATURES = {
                                          c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_double,
                                          c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 6 +
                                  [c_int64, c_int64, c_double, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    "hmv_lagcov_ensemble_split_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                              c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                              c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "hmv_sliding_ensemble_split_f64": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                               c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int,
+                                               c_double, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 6 +
+                                       [c_int64, c_int64, c_double, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                        c_void_p, c_void_p]),
     "hmv_fad_workspace_bytes": (c_int64, [c_int64, c_int]),
     "hmv_fad_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int,
                             c_double, c_double, c_int] + [c_void_p] * 17),

@@ -170,6 +170,51 @@ int hmv_lagcov_ensemble_f64(const double* x, int64_t rec_stride, int64_t ld, int
   return hmv::launch_lagcov_ensemble(a, mp, shared, S(stream));
 }
 
+namespace {
+// what the two split entries refuse about their five extra arguments; 0 when they are fine
+int ens_split_check(const char* who, int m, const int64_t* trial_rec_b, const int64_t* trial_start_b, int split,
+                    const double* R_base, const int64_t* item_base) {
+  char buf[160];
+  const char* msg = nullptr;
+  int code = -4;
+  if (split < 1 || split >= m) { code = -5; msg = "split must be in 1..m-1"; }
+  else if (!trial_rec_b || !trial_start_b) msg = "null pointer (second trial table)";
+  else if ((R_base != nullptr) != (item_base != nullptr)) msg = "R_base and item_base go together";
+  if (!msg) return 0;
+  snprintf(buf, sizeof(buf), "%s: %s", who, msg);
+  return fail(code, buf);
+}
+}  // namespace
+
+int hmv_lagcov_ensemble_split_f64(const double* x, int64_t rec_stride, int64_t ld, int64_t T, const int64_t* trial_rec,
+                                  const int64_t* trial_start, const int64_t* group_ptr, int64_t n_groups,
+                                  const int64_t* item_group, const int64_t* item_offset, int64_t n_items, int m, int n, int p,
+                                  double* R, const int64_t* trial_rec_b, const int64_t* trial_start_b, int split,
+                                  const double* R_base, const int64_t* item_base, int64_t flags, void* stream) {
+  (void)flags;                                           // the direct form is the only one: nothing to choose
+  const int mp = pad_of(m);
+  if (mp < 0) return fail(-1, "hmv_lagcov_ensemble_split_f64: channel count must be in 1..64");
+  if (p < 1 || p > HMV_MAX_ORDER) return fail(-2, "hmv_lagcov_ensemble_split_f64: model order must be in 1..32");
+  if (n <= p) return fail(-3, "hmv_lagcov_ensemble_split_f64: window shorter than the model order");
+  if (!x || !trial_rec || !trial_start || !group_ptr || !item_group || !item_offset || !R || n_items < 0)
+    return fail(-4, "hmv_lagcov_ensemble_split_f64: null pointer");
+  if (n_groups < 1) return fail(-10, "hmv_lagcov_ensemble_split_f64: n_groups must be >= 1");
+  if (int rc = ens_split_check("hmv_lagcov_ensemble_split_f64", m, trial_rec_b, trial_start_b, split, R_base, item_base))
+    return rc;
+  hmv::LagcovEnsArgs a{};
+  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.T = T;
+  a.trial_rec = reinterpret_cast<const long long*>(trial_rec);
+  a.trial_start = reinterpret_cast<const long long*>(trial_start);
+  a.group_ptr = reinterpret_cast<const long long*>(group_ptr);
+  a.item_group = reinterpret_cast<const long long*>(item_group);
+  a.item_offset = reinterpret_cast<const long long*>(item_offset);
+  a.n_items = n_items; a.m = m; a.n = n; a.p = p; a.R = R;
+  a.trial_rec_b = reinterpret_cast<const long long*>(trial_rec_b);
+  a.trial_start_b = reinterpret_cast<const long long*>(trial_start_b);
+  a.split = split; a.R_base = R_base; a.item_base = reinterpret_cast<const long long*>(item_base);
+  return hmv::launch_lagcov_ensemble_split(a, mp, S(stream));
+}
+
 int hmv_yw_solve_f64(const double* R, int64_t n_items, int m, int p, double* ws, double* ar, double* V,
                      double* vq_logdet, int32_t* info, int64_t flags, void* stream) {
   const int mp = pad_of(m);
@@ -574,6 +619,13 @@ struct EnsDesc {
   const int64_t* trial_start;
   const int64_t* group_ptr;
   int64_t n_groups, T;
+  // hmv_sliding_ensemble_split_f64 only: the second trial table, the first channel read through it, and the stacks the
+  // within-participant elements are copied from (lagcov_ens_split_kernel; always the direct form)
+  const int64_t* trial_rec_b = nullptr;
+  const int64_t* trial_start_b = nullptr;
+  int split = 0;
+  const double* R_base = nullptr;
+  const int64_t* item_base = nullptr;
 };
 // Everything sliding_impl is told, by name; a field left alone means "not asked for".  The exported entries below fill in
 // what they have.  `ffdtf` receives the full (m, m, F) arrays, `band_out` (with bin_lo / bin_hi / n_bands) the band sums.
@@ -644,7 +696,7 @@ int sliding_impl(const SlidingArgs& a) {
     if (a.ens->n_groups < 1) return fail(-10, "hmv_sliding_ffdtf_f64: n_groups must be >= 1");
     if (a.grid_hop != 0 && !ens_grid_ok(a.n_items, a.ens->n_groups, a.n, a.ld, a.ens->T, a.grid_hop, a.grid_nwin))
       return fail(-9, "hmv_sliding_ffdtf_f64: inconsistent regular window grid");
-    ens_shared = ens_shared_form(a.n, a.p, a.grid_hop, a.flags);
+    ens_shared = !a.ens->split && ens_shared_form(a.n, a.p, a.grid_hop, a.flags);
   }
   const SlidingWs w = sliding_layout(a.chunk, mp, a.p, a.F, bands, a.S_out != nullptr, a.measure,
                                      a.ens ? (ens_shared ? ens_q_tiles(a.chunk, a.n, a.p, a.grid_hop, a.grid_nwin) : 0) : -1);
@@ -704,7 +756,15 @@ int sliding_impl(const SlidingArgs& a) {
       if (ens_shared) {
         ea.it0 = i0; ea.nwin = a.grid_nwin; ea.hop = a.grid_hop; ea.k = (int)(a.n / a.grid_hop); ea.Q = Qb;
       }
-      rc = hmv::launch_lagcov_ensemble(ea, mp, ens_shared, st0);
+      if (a.ens->split) {
+        ea.trial_rec_b = reinterpret_cast<const long long*>(a.ens->trial_rec_b);
+        ea.trial_start_b = reinterpret_cast<const long long*>(a.ens->trial_start_b);
+        ea.split = a.ens->split; ea.R_base = a.ens->R_base;
+        ea.item_base = a.ens->item_base ? reinterpret_cast<const long long*>(a.ens->item_base + i0) : nullptr;
+        rc = hmv::launch_lagcov_ensemble_split(ea, mp, st0);
+      } else {
+        rc = hmv::launch_lagcov_ensemble(ea, mp, ens_shared, st0);
+      }
     } else if (regular) {
       // items i0 .. i0+c-1 as runs of consecutive windows of one recording each (item = rec * grid_nwin + w)
       for (int64_t it = i0; it < i0 + c && rc == 0;) {
@@ -955,24 +1015,25 @@ int64_t hmv_sliding_ensemble_workspace_bytes(int measure, int64_t chunk, int m, 
   return sliding_bytes(chunk, m, p, F, spectra ? 0 : n_bands, spectra, measure, q_tiles);
 }
 
-int hmv_sliding_ensemble_f64(int measure, const double* x, int64_t rec_stride, int64_t ld, int64_t T,
-                             const int64_t* trial_rec, const int64_t* trial_start, const int64_t* group_ptr,
-                             int64_t n_groups, const int64_t* item_group, const int64_t* item_offset, int64_t n_items,
-                             int m, int n, int p, const double* freqs, int F, double fs, double* out,
-                             const int32_t* bin_lo, const int32_t* bin_hi, int n_bands, double* S_out, double* ar_out,
-                             double* V_out, int32_t* info_yw, int32_t* info_tf, void* workspace, int64_t workspace_bytes,
-                             int64_t chunk, double pivot_tau, int64_t flags, int64_t grid_hop, int64_t grid_nwin,
-                             void* stream, void* aux_stream) {
+namespace {
+int sliding_ensemble_entry(const char* who, int measure, const double* x, int64_t rec_stride, int64_t ld, const EnsDesc& ens,
+                           const int64_t* item_group, const int64_t* item_offset, int64_t n_items, int m, int n, int p,
+                           const double* freqs, int F, double fs, double* out, const int32_t* bin_lo, const int32_t* bin_hi,
+                           int n_bands, double* S_out, double* ar_out, double* V_out, int32_t* info_yw, int32_t* info_tf,
+                           void* workspace, int64_t workspace_bytes, int64_t chunk, double pivot_tau, int64_t flags,
+                           int64_t grid_hop, int64_t grid_nwin, void* stream, void* aux_stream) {
+  auto refuse = [&](const char* msg) {
+    char buf[200];
+    snprintf(buf, sizeof(buf), "%s: %s", who, msg);
+    return fail(-4, buf);
+  };
   if (measure < HMV_MEASURE_FFDTF || measure > HMV_MEASURE_GPDC)
-    return fail(-4, "hmv_sliding_ensemble_f64: measure must be HMV_MEASURE_FFDTF, _DDTF or _GPDC");
-  if (n_bands < 0) return fail(-4, "hmv_sliding_ensemble_f64: n_bands must be >= 0");
-  if (S_out && (measure != HMV_MEASURE_FFDTF || n_bands != 0))
-    return fail(-4, "hmv_sliding_ensemble_f64: spectra come with the full ffDTF only");
+    return refuse("measure must be HMV_MEASURE_FFDTF, _DDTF or _GPDC");
+  if (n_bands < 0) return refuse("n_bands must be >= 0");
+  if (S_out && (measure != HMV_MEASURE_FFDTF || n_bands != 0)) return refuse("spectra come with the full ffDTF only");
   const int mp = pad_of(m);                              // ahead of the pointer checks, in the order of the other entries
-  if (mp >= 0 && p >= 1 && p <= HMV_MAX_ORDER && n > p && !out && n_items != 0)
-    return fail(-4, "hmv_sliding_ensemble_f64: null pointer / empty grid");
-  const EnsDesc ens{trial_rec, trial_start, group_ptr, n_groups, T};
-  SlidingArgs a{"hmv_sliding_ensemble_f64"};
+  if (mp >= 0 && p >= 1 && p <= HMV_MAX_ORDER && n > p && !out && n_items != 0) return refuse("null pointer / empty grid");
+  SlidingArgs a{who};
   a.measure = measure; a.ens = &ens;
   a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.item_rec = item_group; a.item_start = item_offset; a.n_items = n_items;
   a.m = m; a.n = n; a.p = p; a.freqs = freqs; a.F = F; a.fs = fs;
@@ -981,9 +1042,44 @@ int hmv_sliding_ensemble_f64(int measure, const double* x, int64_t rec_stride, i
   a.ar_out = ar_out; a.V_out = V_out; a.info_yw = info_yw; a.info_tf = info_tf;
   a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.pivot_tau = pivot_tau; a.flags = flags;
   if (measure == HMV_MEASURE_GPDC) { a.info_tf = nullptr; a.pivot_tau = 1.0; }
-  a.grid_hop = grid_hop; a.grid_nwin = grid_nwin; a.grid_T = T;
+  a.grid_hop = grid_hop; a.grid_nwin = grid_nwin; a.grid_T = ens.T;
   a.stream = stream; a.aux_stream = aux_stream;
   return sliding_impl(a);
+}
+}  // namespace
+
+int hmv_sliding_ensemble_f64(int measure, const double* x, int64_t rec_stride, int64_t ld, int64_t T,
+                             const int64_t* trial_rec, const int64_t* trial_start, const int64_t* group_ptr,
+                             int64_t n_groups, const int64_t* item_group, const int64_t* item_offset, int64_t n_items,
+                             int m, int n, int p, const double* freqs, int F, double fs, double* out,
+                             const int32_t* bin_lo, const int32_t* bin_hi, int n_bands, double* S_out, double* ar_out,
+                             double* V_out, int32_t* info_yw, int32_t* info_tf, void* workspace, int64_t workspace_bytes,
+                             int64_t chunk, double pivot_tau, int64_t flags, int64_t grid_hop, int64_t grid_nwin,
+                             void* stream, void* aux_stream) {
+  const EnsDesc ens{trial_rec, trial_start, group_ptr, n_groups, T};
+  return sliding_ensemble_entry("hmv_sliding_ensemble_f64", measure, x, rec_stride, ld, ens, item_group, item_offset, n_items, m,
+                                n, p, freqs, F, fs, out, bin_lo, bin_hi, n_bands, S_out, ar_out, V_out, info_yw, info_tf,
+                                workspace, workspace_bytes, chunk, pivot_tau, flags, grid_hop, grid_nwin, stream, aux_stream);
+}
+
+int hmv_sliding_ensemble_split_f64(int measure, const double* x, int64_t rec_stride, int64_t ld, int64_t T,
+                                   const int64_t* trial_rec, const int64_t* trial_start, const int64_t* group_ptr,
+                                   int64_t n_groups, const int64_t* item_group, const int64_t* item_offset, int64_t n_items,
+                                   int m, int n, int p, const double* freqs, int F, double fs, double* out,
+                                   const int32_t* bin_lo, const int32_t* bin_hi, int n_bands, double* S_out, double* ar_out,
+                                   double* V_out, int32_t* info_yw, int32_t* info_tf, void* workspace,
+                                   int64_t workspace_bytes, int64_t chunk, double pivot_tau, int64_t flags,
+                                   const int64_t* trial_rec_b, const int64_t* trial_start_b, int split, const double* R_base,
+                                   const int64_t* item_base, void* stream, void* aux_stream) {
+  if (pad_of(m) >= 0)                                    // (a bad channel count is sliding_impl's -1)
+    if (int rc = ens_split_check("hmv_sliding_ensemble_split_f64", m, trial_rec_b, trial_start_b, split, R_base, item_base))
+      return rc;
+  EnsDesc ens{trial_rec, trial_start, group_ptr, n_groups, T};
+  ens.trial_rec_b = trial_rec_b; ens.trial_start_b = trial_start_b; ens.split = split; ens.R_base = R_base;
+  ens.item_base = item_base;
+  return sliding_ensemble_entry("hmv_sliding_ensemble_split_f64", measure, x, rec_stride, ld, ens, item_group, item_offset,
+                                n_items, m, n, p, freqs, F, fs, out, bin_lo, bin_hi, n_bands, S_out, ar_out, V_out, info_yw,
+                                info_tf, workspace, workspace_bytes, chunk, pivot_tau, flags, 0, 0, stream, aux_stream);
 }
 
 int64_t hmv_fad_workspace_bytes(int64_t n_series, int pmax) {

@@ -55,10 +55,19 @@ struct LagcovEnsArgs {
   long long it0, nwin, hop;
   int k;
   double* Q;                // scratch, lagcov_ensemble_q_tiles() * (p+1) * MP * MP doubles
+  // second trial table (launch_lagcov_ensemble_split only; direct form): trial step e reads the channels >= split from
+  // trial (trial_rec_b[e], trial_start_b[e]), indexed through the same group_ptr
+  const long long* trial_rec_b;   // [n_trials]
+  const long long* trial_start_b; // [n_trials]
+  int split;                // 1 .. m - 1
+  // optional, both or neither: the within-participant elements are copied from R_base[item_base[item]], not computed
+  const double* R_base;     // [n_base][p+1][MP][MP]
+  const long long* item_base;     // [n_items], of the items of THIS launch
 };
 bool lagcov_ensemble_shared_ok(int n, long long hop, int p, int max_k);      // does the shared form take this grid?
 long long lagcov_ensemble_q_tiles(long long n_items, long long nwin, int k);  // in stacks of (p+1) tiles
 int launch_lagcov_ensemble(const LagcovEnsArgs& a, int m_pad, bool shared, hipStream_t st);
+int launch_lagcov_ensemble_split(const LagcovEnsArgs& a, int m_pad, hipStream_t st);   // direct form, two trial tables
 
 // ---- K2 Yule-Walker solve (block LDL^T of the block-Toeplitz normal equations) ------------------
 struct YwArgs {

@@ -136,6 +136,136 @@ __global__ void __launch_bounds__(256, 2) lagcov_ens_kernel(LagcovEnsArgs a) {
   });
 }
 
+// ---- direct form with a second trial table (trial-shuffle surrogates) ----------------------------------------------------
+// Trial step e stages the channels < split from trial (trial_rec[e], trial_start[e]) and the channels >= split from trial
+// (trial_rec_b[e], trial_start_b[e]): x~_e = [a_e ; b_pi(e)], the permutation being nothing but the order of table B.  The
+// mapping, the chunks, the k-steps and the order of products per accumulator are lagcov_ens_kernel's, so table B = table A
+// gives its bits.
+// With R_base the within-participant elements -- both indices < split or both >= split, padding counting as >= split --
+// are sums over ALL trials that no permutation changes: they are copied from R_base[item_base[item]] and an accumulator
+// whose real elements (row, col < m) are all of that kind never sees an MFMA.  `need` holds one bit per accumulator
+// [I][J] of this wave; it depends on the wave, split and m only, lives in an SGPR and is formed before the trial loop.
+// An accumulator that straddles split is computed whole and its within-participant elements are then overwritten, so
+// the result does not depend on the tiling.
+template <int NT, int LG>
+__device__ __forceinline__ void le_ksteps_masked(const double* xa, const double* xb, int steps, int nl, unsigned need,
+                                                 double (&acc)[LG][NT][NT]) {
+  for (int ts = 0; ts < steps; ++ts) {
+    double av[NT];
+#pragma unroll
+    for (int I = 0; I < NT; ++I) av[I] = xa[4 * I * LE_S + 4 * ts];
+    static_for<LG>([&](auto gc) __attribute__((always_inline)) {
+      constexpr int g = decltype(gc)::value;
+      if (g < nl) {                                     // workgroup-uniform
+        static_for<NT>([&](auto jc) __attribute__((always_inline)) {
+          constexpr int J = decltype(jc)::value;
+          constexpr unsigned COL = ((1u << (NT * NT)) - 1) / ((1u << NT) - 1) << J;   // bits I * NT + J, all I
+          if (need & COL) {                             // wave-uniform
+            const double bv = xb[16 * J * LE_S + 4 * ts + g];
+#pragma unroll
+            for (int I = 0; I < NT; ++I)
+              if (need & (1u << (I * NT + J))) acc[g][I][J] = mfma4(av[I], bv, acc[g][I][J]);
+          }
+        });
+      }
+    });
+  }
+}
+
+template <int NT, int LG>
+__global__ void __launch_bounds__(256, 2) lagcov_ens_split_kernel(LagcovEnsArgs a) {
+  constexpr int MP = 16 * NT;
+  __shared__ double xs[MP * LE_S];
+  const int l = lane_id();
+  const int wv = uni(threadIdx.x >> 6);
+  const long long item = blockIdx.x;
+  const int lag0 = blockIdx.y * LG;
+  const int nl = min(LG, a.p + 1 - lag0);
+  const int i = l >> 4, cc = l & 15;
+  const int n = a.n, m = a.m, split = a.split;
+  const long long g = a.item_group[item], off = a.item_offset[item];
+  const long long e0 = a.group_ptr[g], e1 = a.group_ptr[g + 1];
+  const long long E = e1 - e0;
+  const bool based = a.R_base != nullptr;
+
+  unsigned need = 0;
+#pragma unroll
+  for (int I = 0; I < NT; ++I)
+#pragma unroll
+    for (int J = 0; J < NT; ++J) {
+      const int r0 = 4 * (NT * wv + I), c0 = 16 * J;     // rows r0 .. r0 + 3, columns c0 .. c0 + 15
+      const bool rows_a = r0 < split, rows_b = max(r0, split) <= min(r0 + 3, m - 1);
+      const bool cols_a = c0 < split, cols_b = max(c0, split) <= min(c0 + 15, m - 1);
+      if (!based || (rows_a && cols_b) || (rows_b && cols_a)) need |= 1u << (I * NT + J);
+    }
+  need = (unsigned)uni((int)need);
+
+  double acc[LG][NT][NT];
+#pragma unroll
+  for (int q = 0; q < LG; ++q)
+#pragma unroll
+    for (int I = 0; I < NT; ++I)
+#pragma unroll
+      for (int J = 0; J < NT; ++J) acc[q][I][J] = 0.0;
+
+  constexpr int NLD = (MP * LE_W + 255) / 256;
+  double stg[NLD];
+  auto load = [&](long long e, int t0) __attribute__((always_inline)) {
+    const double* xA = a.x + a.trial_rec[e] * a.rec_stride + a.trial_start[e] + off;
+    const double* xB = a.x + a.trial_rec_b[e] * a.rec_stride + a.trial_start_b[e] + off;
+#pragma unroll
+    for (int r = 0; r < NLD; ++r) {
+      const int idx = threadIdx.x + 256 * r;
+      const int ch = idx / LE_W, tt = idx - ch * LE_W;
+      const int t = t0 + tt;
+      const double* x = ch < split ? xA : xB;
+      stg[r] = (idx < MP * LE_W && ch < m && t < n) ? x[(size_t)ch * a.ld + t] : 0.0;
+    }
+  };
+  const int nch = (n + LE_TC - 1) / LE_TC;
+  const long long S = E * nch;                          // (trial, chunk) steps, trial-major
+  long long e = e0;
+  int t0 = 0;
+  const double* xa = xs + (4 * NT * wv + (l & 3)) * LE_S + (l >> 4);
+  const double* xb = xs + cc * LE_S + lag0 + (l >> 4);
+  for (long long s = 0; s < S; ++s) {
+    load(e, t0);
+    __syncthreads();                                    // the k-steps of the previous chunk have read xs
+#pragma unroll
+    for (int r = 0; r < NLD; ++r) {
+      const int idx = threadIdx.x + 256 * r;
+      const int ch = idx / LE_W, tt = idx - ch * LE_W;
+      if (idx < MP * LE_W) xs[ch * LE_S + tt] = stg[r];
+    }
+    __syncthreads();
+    const int tc = t0;
+    t0 += LE_TC;
+    if (t0 >= n) { t0 = 0; ++e; }
+    le_ksteps_masked<NT, LG>(xa, xb, min(LE_TC, n - tc + 3) >> 2, nl, need, acc);
+  }
+  const double scale = 1.0 / (double)n;
+  const double Ed = (double)E;
+  static_for<LG>([&](auto gc) __attribute__((always_inline)) {
+    constexpr int q = decltype(gc)::value;
+    if (q < nl) {
+      const int lag = lag0 + q;
+      double* R = a.R + ((size_t)item * (a.p + 1) + lag) * MP * MP;
+      const double* Rb = based ? a.R_base + ((size_t)a.item_base[item] * (a.p + 1) + lag) * MP * MP : nullptr;
+#pragma unroll
+      for (int I = 0; I < NT; ++I)
+#pragma unroll
+        for (int J = 0; J < NT; ++J) {
+          const int row = 4 * (NT * wv + I) + i, col = 16 * J + cc;
+          double v = acc[q][I][J] * scale;
+          if (E > 1) v = v / Ed;
+          if (lag == 0 && row == col && row >= m) v = 1.0;
+          if (based && (row < split) == (col < split)) v = Rb[(size_t)row * MP + col];   // (split < m: padding is >= split)
+          R[(size_t)row * MP + col] = v;
+        }
+    }
+  });
+}
+
 // ---- shared-overlap form --------------------------------------------------------------------------------------------
 // Items it0 .. it0 + n_items - 1 of the grid (item = g * nwin + w) touch the groups g0 .. g0 + ngc - 1; group g0 + gi owns
 // the Q slots gi * nblk .. + nblk - 1 (nblk = nwin + k - 1 hop blocks), of which only those under a window of the chunk
@@ -364,6 +494,23 @@ int launch_lagcov_ensemble(const LagcovEnsArgs& a, int m_pad, bool shared, hipSt
       hipLaunchKernelGGL((lagens_block_kernel<4, LG>), gq, block, 0, st, a);
       hipLaunchKernelGGL(lagens_comb_kernel<4>, gc, block, 0, st, a);
       break;
+    default: return -1;
+  }
+  return (int)hipGetLastError();
+}
+
+int launch_lagcov_ensemble_split(const LagcovEnsArgs& a, int m_pad, hipStream_t st) {
+  if (a.n_items == 0) return 0;
+  if (a.p > LE_HALO) return -2;
+  if (!a.trial_rec_b || !a.trial_start_b || a.split < 1 || a.split >= a.m || (a.R_base != nullptr) != (a.item_base != nullptr))
+    return -4;
+  constexpr int LG = 3;
+  const dim3 block(256), grid((unsigned)a.n_items, (a.p + LG) / LG);
+  switch (m_pad) {
+    case 16: hipLaunchKernelGGL((lagcov_ens_split_kernel<1, LG>), grid, block, 0, st, a); break;
+    case 32: hipLaunchKernelGGL((lagcov_ens_split_kernel<2, LG>), grid, block, 0, st, a); break;
+    case 48: hipLaunchKernelGGL((lagcov_ens_split_kernel<3, LG>), grid, block, 0, st, a); break;
+    case 64: hipLaunchKernelGGL((lagcov_ens_split_kernel<4, LG>), grid, block, 0, st, a); break;
     default: return -1;
   }
   return (int)hipGetLastError();

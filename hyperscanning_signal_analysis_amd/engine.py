@@ -590,9 +590,11 @@ class Engine:
         return _Route(yw_text="ar_coeff (Yule-Walker solve)", ws_bytes=ws_bytes, call=call,
                       per_item=None if spectra else lambda m, F, nb: lib.hmv_sliding_workspace_bytes(1, m, p, F), **fixed)
 
-    def _ensemble_route(self, measure, n, p, trial_rec, trial_start, group_ptr, spectra=False):
+    def _ensemble_route(self, measure, n, p, trial_rec, trial_start, group_ptr, spectra=False, shuffle=None):
         """Route of `sliding_ensemble` (`hmv_sliding_ensemble_f64`): the items are (group, offset) pairs, the validation
-        is `validate_trials`, the grid has two parts, and a failed fit is reported with its group and offset."""
+        is `validate_trials`, the grid has two parts, and a failed fit is reported with its group and offset.
+        shuffle = (trial_rec_b, trial_start_b, split, R_base, item_base): `hmv_sliding_ensemble_split_f64` instead -- K1
+        reads the channels >= split through the second trial table (no grid: the direct form only)."""
         if p is None:
             raise ValueError(_NO_ENSEMBLE_ORDER)
         lib, n, p, code = self.lib, int(n), int(p), _MEASURES[measure]
@@ -603,6 +605,16 @@ class Engine:
             err.groups = items[0][idx].cpu().numpy()
             err.offsets = items[1][idx].cpu().numpy()
             err.args = (err.args[0], err.args[1] + f" (group {int(err.groups[0])}, window at offset {int(err.offsets[0])})")
+
+        def call(a):
+            front = (code, *a.x, a.T, trial_rec.data_ptr(), trial_start.data_ptr(), group_ptr.data_ptr(), n_groups, *a.items,
+                     a.n_items, a.m, n, p, a.f, a.F, a.fs, a.out, a.lo, a.hi, a.nb, a.S, a.ar, a.V, a.info_yw, a.info_tf, a.ws,
+                     a.nbytes, a.chunk, a.tau, a.flags)
+            if shuffle is None:
+                return "hmv_sliding_ensemble_f64", (*front, *a.grid, a.stream, a.aux)
+            rec_b, start_b, split, R_base, item_base = shuffle
+            return "hmv_sliding_ensemble_split_f64", (*front, rec_b.data_ptr(), start_b.data_ptr(), int(split), _ptr(R_base),
+                                                      _ptr(item_base), a.stream, a.aux)
         return _Route(
             name="sliding_ensemble", measure=measure, p=p, order_text=f"n={n}, p={p}", spectra=spectra, blame=blame,
             yw_text="ar_coeff (Yule-Walker solve of the trial-averaged covariances; a negative info: residual covariance "
@@ -611,10 +623,7 @@ class Engine:
             grid=lambda x, items, n_items, grid, compare: self._ensemble_grid(n_groups, items, n_items, grid, compare),
             ws_bytes=lambda chunk, m, F, nb, g: lib.hmv_sliding_ensemble_workspace_bytes(
                 code, chunk, m, n, p, F, -1 if spectra else nb, *g),
-            call=lambda a: ("hmv_sliding_ensemble_f64", (
-                code, *a.x, a.T, trial_rec.data_ptr(), trial_start.data_ptr(), group_ptr.data_ptr(), n_groups, *a.items,
-                a.n_items, a.m, n, p, a.f, a.F, a.fs, a.out, a.lo, a.hi, a.nb, a.S, a.ar, a.V, a.info_yw, a.info_tf, a.ws,
-                a.nbytes, a.chunk, a.tau, a.flags, *a.grid, a.stream, a.aux)))
+            call=call)
 
     def _sliding_call(self, rt, x, items, freqs, fs, *, bands=None, out=None, out_S=None, return_ar=False,
                       return_orders=False, check=True, chunk=None, overlap=False, flags=0, grid=None, validate=True,
@@ -839,6 +848,171 @@ class Engine:
         return self._sliding_call(rt, x, (item_group, item_offset), freqs, fs, bands=bands, out=out, return_ar=return_ar,
                                   check=check, chunk=chunk, flags=flags, grid=grid, validate=validate)
 
+    # ------------------------------------------------------------------ trial-shuffle significance of ensembles
+    def _check_shuffle(self, x, n_items, p, split, R_base, item_base):
+        """The arguments of the split K1 that `validate_trials` does not see, before anything is launched."""
+        m, mp = x.shape[1], self.pad(x.shape[1])
+        if isinstance(split, bool) or int(split) != split or not 1 <= int(split) <= m - 1:
+            raise ValueError(f"split must be an integer in 1..{m - 1}, got {split!r}")
+        if (R_base is None) != (item_base is None):
+            raise ValueError("R_base and item_base go together")
+        if R_base is None:
+            return
+        if not (isinstance(R_base, torch.Tensor) and R_base.dtype == torch.float64 and R_base.device == x.device
+                and R_base.dim() == 4 and tuple(R_base.shape[1:]) == (int(p) + 1, mp, mp) and R_base.is_contiguous()):
+            raise ValueError(f"R_base must be a contiguous float64 tensor (n_base, {int(p) + 1}, {mp}, {mp}) on {x.device}")
+        if not (isinstance(item_base, torch.Tensor) and item_base.dtype == torch.int64 and item_base.device == x.device
+                and item_base.dim() == 1 and item_base.numel() == n_items and item_base.is_contiguous()):
+            raise ValueError(f"item_base must be a contiguous 1-D int64 tensor of {n_items} entries on {x.device}")
+        if n_items:
+            lo, hi = int(item_base.min()), int(item_base.max())
+            if lo < 0 or hi >= R_base.shape[0]:
+                raise ValueError(f"item_base must lie in [0, {R_base.shape[0]}), got [{lo}, {hi}]")
+
+    def lagcov_ensemble_split(self, x: torch.Tensor, trial_rec: torch.Tensor, trial_start: torch.Tensor,
+                              trial_rec_b: torch.Tensor, trial_start_b: torch.Tensor, group_ptr: torch.Tensor,
+                              item_group: torch.Tensor, item_offset: torch.Tensor, n: int, p: int, split: int,
+                              R_base: torch.Tensor | None = None, item_base: torch.Tensor | None = None,
+                              validate: bool = True):
+        """K1 of a trial-shuffled ensemble (`hmv_lagcov_ensemble_split_f64`): as `lagcov_ensemble` in the direct form, but
+        trial step e of a group reads the channels >= split from trial (trial_rec_b[e], trial_start_b[e]) -- table B,
+        indexed through the same group_ptr, is table A with the second participant's trials reordered.  With R_base
+        (n_base, p+1, MP, MP) and item_base (items,) the within-participant elements (both indices < split, or both
+        >= split, padding included) are copied from R_base[item_base[it]] and only the cross blocks are computed.
+        Both tables are checked with `validate_trials`."""
+        if p is None:
+            raise ValueError(_NO_ENSEMBLE_ORDER)
+        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
+        x = x if x.stride(2) == 1 else x.contiguous()
+        n_groups, n_items = int(group_ptr.numel()) - 1, int(item_group.numel())
+        if validate:
+            validate_trials(x, trial_rec, trial_start, group_ptr, item_group, item_offset, n, p)
+            validate_trials(x, trial_rec_b, trial_start_b, group_ptr, item_group, item_offset, n, p)
+            self._check_shuffle(x, n_items, p, split, R_base, item_base)
+        n_rec, m, T = x.shape
+        mp = self.pad(m)
+        R = self.empty(n_items, int(p) + 1, mp, mp)
+        if n_items == 0:
+            return R
+        with torch.cuda.device(self.device):
+            rc = self.lib.hmv_lagcov_ensemble_split_f64(
+                x.data_ptr(), x.stride(0), x.stride(1), T, trial_rec.data_ptr(), trial_start.data_ptr(), group_ptr.data_ptr(),
+                n_groups, item_group.data_ptr(), item_offset.data_ptr(), n_items, m, int(n), int(p), R.data_ptr(),
+                trial_rec_b.data_ptr(), trial_start_b.data_ptr(), int(split), _ptr(R_base), _ptr(item_base), 0, self.stream())
+        _lib.check(rc, "hmv_lagcov_ensemble_split_f64")
+        return R
+
+    def ensemble_significance_chunk(self, measure: str, m: int, n: int, p: int, F: int, nb: int) -> int:
+        """Items (surrogate x item) per block of `ensemble_significance`: `max_workspace_bytes` over what one item needs --
+        the fused call's workspace, the surrogate's band values and its index entries.  No window is ever written."""
+        ws = int(self.lib.hmv_sliding_ensemble_workspace_bytes(_MEASURES[measure], 1, m, n, p, F, nb, 0, 0))
+        return max(1, self.max_workspace_bytes // (ws + 8 * m * m * nb + 8 * nb + 1 + 3 * 8))
+
+    def ensemble_significance(self, x: torch.Tensor, trial_rec: torch.Tensor, trial_start: torch.Tensor,
+                              group_ptr: torch.Tensor, item_group: torch.Tensor, item_offset: torch.Tensor, n: int, p: int,
+                              freqs, fs: float, bands, *, measure: str, n_surrogates: int, seed, split=None, check=True,
+                              chunk: int | None = None, grid=None):
+        """Trial-shuffle test of the band values of `sliding_ensemble(..., measure=measure, bands=bands, grid=grid)`.
+
+        Surrogate s pairs trial e of group g (channels < split, participant A) with trial pi[s][g][e] of the same group
+        (channels >= split, participant B); one permutation per (s, g) serves every window of the group
+        (`surrogates.trial_permutations` from numpy.random.default_rng(seed)).  Every participant's evoked response and
+        within-brain dynamics are those of the observed fit -- the within-participant blocks of the trial-averaged lag
+        covariances are copied from it --; the trial-by-trial pairing of the two is not.  No surrogate window is
+        written: K1 reads the permuted trials in place (`hmv_sliding_ensemble_split_f64`).  Tests the pairs with exactly
+        one index < split.  Statistics, `check` (True or "nan") and the returned dict as `sliding_significance`, with
+        one entry per item.  chunk: items (surrogate x item) per block (default `ensemble_significance_chunk`); where
+        the items of one surrogate exceed it, a block holds whole groups of one surrogate.  The results are the same
+        bits for any chunk.  p=None raises ValueError (no automatic order for ensembles)."""
+        from . import surrogates as sg
+        if p is None:
+            raise ValueError(_NO_ENSEMBLE_ORDER)
+        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
+        x = x if x.stride(2) == 1 else x.contiguous()
+        n_rec, m, T = x.shape
+        n, p = int(n), int(p)
+        S, split, _ = sg.significance_args(measure, "trial", n_surrogates, m, T, n, split)
+        if check is not True and check != "nan":
+            raise ValueError(f"check must be True or 'nan', got {check!r}")
+        self.pad(m)
+        validate_trials(x, trial_rec, trial_start, group_ptr, item_group, item_offset, n, p)
+        gp = group_ptr.cpu().numpy()
+        counts = np.diff(gp)
+        G, N = len(counts), int(item_group.numel())
+        self._ensemble_grid(G, (item_group, item_offset), N, grid, True)       # checked once, for both observed calls
+        f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
+        F = int(f.numel())
+        lo, hi = (np.asarray(b, dtype=np.int32) for b in bands)
+        nb = int(lo.size)
+        if nb < 1:
+            raise ValueError("ensemble_significance needs at least one band")
+        self.band_tables(lo, hi, F)
+        perms = sg.trial_permutations(np.random.default_rng(seed), S, counts)     # (also: every group has >= 2 trials)
+        tested_h = sg.tested_mask(m, "trial", split)
+        tested = torch.as_tensor(tested_h.astype(np.uint8)).to(self.device)
+        res = {"tested": torch.as_tensor(tested_h).to(self.device)}
+        if N == 0:
+            for k in ("observed", "p", "p_fwe", "null_mean", "null_std"):
+                res[k] = self.empty(0, m, m, nb)
+            res["n_valid"] = self.empty(0, dtype=torch.int32)
+            return res
+        ens = (x, trial_rec, trial_start, group_ptr, item_group, item_offset, n, p)
+        obs = self.sliding_ensemble(*ens, f, fs, measure=measure, bands=(lo, hi), grid=grid, validate=False,
+                                    check=True if check is True else "mask")
+        obs, obs_bad = (obs, None) if check is True else obs
+        R_base = self.lagcov_ensemble(*ens, grid=grid, validate=False)
+        # table B of every surrogate: the trials of each group in the order of its permutation
+        rec_h, start_h = trial_rec.cpu().numpy(), trial_start.cpu().numpy()
+        src = np.stack([np.concatenate([gp[g] + perms[s][g] for g in range(G)]) for s in range(S)])       # (S, trials)
+        rec_b = torch.as_tensor(rec_h[src]).to(self.device)
+        start_b = torch.as_tensor(start_h[src]).to(self.device)
+        # the items group-major (a stable sort: nothing moves where they already are), so that a block of whole groups is
+        # a contiguous run of items and of the running state
+        order = torch.argsort(item_group, stable=True)
+        grp, offs = item_group[order].contiguous(), item_offset[order].contiguous()
+        first = np.searchsorted(grp.cpu().numpy(), np.arange(G + 1))           # items of group g: first[g] .. first[g+1]
+        obs_s = obs[order].contiguous()
+        chunk = self.ensemble_significance_chunk(measure, m, n, p, F, nb) if chunk is None else max(1, int(chunk))
+        if N <= chunk:
+            Sb, blocks = min(S, chunk // N), [(0, G)]
+        else:                                   # whole groups of one surrogate, as many as fit (at least one)
+            Sb, blocks, g0 = 1, [], 0
+            while g0 < G:
+                g1 = g0 + 1
+                while g1 < G and first[g1 + 1] - first[g0] <= chunk:
+                    g1 += 1
+                blocks.append((g0, g1))
+                g0 = g1
+        st = self.null_state(N, m, nb)
+        i64 = dict(dtype=torch.int64, device=self.device)
+        for s0 in range(0, S, Sb):
+            sb = min(Sb, S - s0)
+            for g0, g1 in blocks:
+                i0, i1, e0, e1 = int(first[g0]), int(first[g1]), int(gp[g0]), int(gp[g1])
+                wb, gb = i1 - i0, g1 - g0
+                if wb == 0:
+                    continue
+                srep = torch.arange(sb, **i64).repeat_interleave(wb)
+                d = dict(trial_rec=trial_rec[e0:e1].repeat(sb), trial_start=trial_start[e0:e1].repeat(sb),
+                         group_ptr=torch.as_tensor(np.concatenate([[0], np.cumsum(np.tile(counts[g0:g1], sb))]), **i64),
+                         item_group=(grp[i0:i1] - g0).repeat(sb) + srep * gb, item_offset=offs[i0:i1].repeat(sb))
+                shuffle = (rec_b[s0:s0 + sb, e0:e1].reshape(-1).contiguous(), start_b[s0:s0 + sb, e0:e1].reshape(-1).contiguous(),
+                           split, R_base, order[i0:i1].repeat(sb))
+                rt = self._ensemble_route(measure, n, p, d["trial_rec"], d["trial_start"], d["group_ptr"], shuffle=shuffle)
+                vals, bad = self._sliding_call(rt, x, (d["item_group"], d["item_offset"]), f, fs, bands=(lo, hi), check="mask",
+                                               chunk=min(sb * wb, chunk), validate=False)
+                sub = {k: v[i0:i1] for k, v in st.items()}                 # item-major: contiguous views
+                self.null_accumulate(obs_s[i0:i1], vals, bad, tested, sub, s0 + sb >= S, sb)
+        inv = torch.empty_like(order)
+        inv[order] = torch.arange(N, **i64)
+        res.update(observed=obs, n_valid=st["n_valid"][inv])
+        for k in ("p", "p_fwe", "null_mean", "null_std"):
+            res[k] = st[k][inv]
+        if obs_bad is not None and bool(obs_bad.any()):
+            for k in ("observed", "p", "p_fwe", "null_mean", "null_std"):
+                res[k][obs_bad] = float("nan")
+        return res
+
     # ------------------------------------------------------------------ surrogate significance (surrogate.hip)
     def surrogate_shift(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, shift: torch.Tensor,
                         split: int, out: torch.Tensor | None = None):
@@ -933,6 +1107,9 @@ class Engine:
         n_valid (W,) int32, tested (m, m) bool."""
         from . import surrogates as sg
         no_auto_order(p, "sliding_significance")
+        if null in sg.ENSEMBLE_NULLS:
+            raise ValueError(f"null={null!r} is the test of event-locked ensembles (ensemble_significance); "
+                             f"sliding_significance takes one of {sg.NULLS}")
         assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
         x = x if x.stride(2) == 1 else x.contiguous()
         n_rec, m, T = x.shape

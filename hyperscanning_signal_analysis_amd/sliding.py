@@ -23,7 +23,8 @@ from .engine import Engine, default_engine
 
 __all__ = ["window_positions", "hop_positions", "create_windows", "sliding_ffdtf", "sliding_ffdtf_device", "window_items",
            "regular_grid", "sliding_ddtf", "sliding_ddtf_device", "sliding_gpdc", "sliding_gpdc_device", "sliding_fad",
-           "sliding_significance", "ensemble_items", "sliding_ensemble", "sliding_ensemble_epochs"]
+           "sliding_significance", "ensemble_items", "sliding_ensemble", "sliding_ensemble_epochs",
+           "sliding_ensemble_significance", "sliding_ensemble_epochs_significance"]
 
 
 def window_positions(T: int, n_windows: int = 3, window_size=None):
@@ -248,6 +249,9 @@ def sliding_significance(x, window_size, n_windows, p, freqs, fs, bands, *, meas
     from . import surrogates as sg
     from .engine import no_auto_order
     no_auto_order(p, "sliding_significance")
+    if null in sg.ENSEMBLE_NULLS:
+        raise ValueError(f"null={null!r} is the test of event-locked ensembles (sliding_ensemble_significance); "
+                         f"sliding_significance takes one of {sg.NULLS}")
     single = np.ndim(x) == 2
     shape = tuple(np.shape(x))
     n_rec, m, T = (1,) + shape if single else shape
@@ -319,9 +323,10 @@ def ensemble_items(onsets, pre: int, post: int, window_size: int, hop: int):
     return on - pre, hop_positions(pre + post, window_size, hop).astype(np.int64)
 
 
-def _ensemble_run(eng, xd, trial_rec, trial_start, counts, offsets, window_size, p, freqs, fs, measure, bands, spectra, check,
-                  share_overlap):
-    """Groups of counts[g] consecutive trials, every group with the same window offsets -> arrays (n_groups, n_windows, ...)."""
+def _ensemble_index(eng, counts, offsets, window_size, share_overlap):
+    """Groups of counts[g] consecutive trials, every group with the same window offsets: (group_ptr, item_group, item_offset)
+    on the engine's device, items group-major, and the grid (hop, n_windows) where the offsets are regular and the overlap
+    is to be shared (else None)."""
     n_groups, n_win = len(counts), len(offsets)
     dev = eng.device
     group_ptr = torch.as_tensor(np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)).to(dev)
@@ -329,12 +334,44 @@ def _ensemble_run(eng, xd, trial_rec, trial_start, counts, offsets, window_size,
     item_offset = torch.as_tensor(np.asarray(offsets, dtype=np.int64)).repeat(n_groups).to(dev)
     hop = int(offsets[1] - offsets[0]) if n_win > 1 else int(window_size)
     regular = n_win >= 1 and np.array_equal(np.asarray(offsets), np.arange(n_win) * hop)
+    return group_ptr, item_group, item_offset, (hop, n_win) if share_overlap and regular else None
+
+
+def _ensemble_run(eng, xd, trial_rec, trial_start, counts, offsets, window_size, p, freqs, fs, measure, bands, spectra, check,
+                  share_overlap):
+    """Groups of counts[g] consecutive trials, every group with the same window offsets -> arrays (n_groups, n_windows, ...)."""
+    n_groups, n_win = len(counts), len(offsets)
+    dev = eng.device
+    group_ptr, item_group, item_offset, grid = _ensemble_index(eng, counts, offsets, window_size, share_overlap)
     res = eng.sliding_ensemble(xd, torch.as_tensor(trial_rec).to(dev), torch.as_tensor(trial_start).to(dev), group_ptr,
                                item_group, item_offset, int(window_size), p, freqs, fs, measure=measure, bands=bands,
-                               spectra=spectra, check=check, grid=(hop, n_win) if share_overlap and regular else None)
+                               spectra=spectra, check=check, grid=grid)
     m = xd.shape[1]
     shape = lambda a: a.view(n_groups, n_win, m, m, a.shape[-1]) if a.dim() == 4 else a.view(n_groups, n_win)  # noqa: E731
     return tuple(shape(a) for a in res) if isinstance(res, tuple) else shape(res)
+
+
+def _onset_trials(x, onsets, pre, post, window_size, hop):
+    """The trials of `sliding_ensemble`'s input, on the host: (single, n_rec, trial_rec, trial_start, counts, offsets)."""
+    single = np.ndim(x) == 2
+    on_list = [onsets] if single else list(onsets)
+    n_rec = 1 if single else int(np.shape(x)[0])
+    if len(on_list) != n_rec:
+        raise ValueError(f"{n_rec} recording(s) need {n_rec} onset array(s), got {len(on_list)}")
+    starts, offsets, counts = [], None, []
+    for on in on_list:
+        st, offsets = ensemble_items(on, pre, post, window_size, hop)
+        starts.append(st)
+        counts.append(len(st))
+    if min(counts) < 1:
+        raise ValueError(f"recording {int(np.argmin(counts))} has no onsets: every group needs at least one trial")
+    return single, n_rec, np.repeat(np.arange(n_rec, dtype=np.int64), counts), np.concatenate(starts), counts, offsets
+
+
+def _recordings_to_device(eng, x, single):
+    if isinstance(x, torch.Tensor):
+        return (x[None] if single else x).to(device=eng.device, dtype=torch.float64).contiguous()
+    return eng.to_device(np.asarray(x, dtype=np.float64)[None] if single else np.asarray(x, dtype=np.float64))
 
 
 def sliding_ensemble(x, onsets, window_size, p, freqs, fs, *, pre, post, hop, measure="ffdtf", bands=None, spectra=False,
@@ -350,36 +387,16 @@ def sliding_ensemble(x, onsets, window_size, p, freqs, fs, *, pre, post, hop, me
     reference's `mvar_criterion` does not take 3-D input, so there is no automatic order to reproduce."""
     if p is None:
         raise ValueError("sliding_ensemble needs an integer model order p (no automatic order for ensembles)")
-    single = np.ndim(x) == 2
-    on_list = [onsets] if single else list(onsets)
-    n_rec = 1 if single else int(np.shape(x)[0])
-    if len(on_list) != n_rec:
-        raise ValueError(f"{n_rec} recording(s) need {n_rec} onset array(s), got {len(on_list)}")
-    starts, offsets, counts = [], None, []
-    for on in on_list:
-        st, offsets = ensemble_items(on, pre, post, window_size, hop)
-        starts.append(st)
-        counts.append(len(st))
-    if min(counts) < 1:
-        raise ValueError(f"recording {int(np.argmin(counts))} has no onsets: every group needs at least one trial")
+    single, n_rec, trial_rec, trial_start, counts, offsets = _onset_trials(x, onsets, pre, post, window_size, hop)
     eng = engine or default_engine()
-    if isinstance(x, torch.Tensor):
-        xd = (x[None] if single else x).to(device=eng.device, dtype=torch.float64).contiguous()
-    else:
-        xd = eng.to_device(np.asarray(x, dtype=np.float64)[None] if single else np.asarray(x, dtype=np.float64))
-    trial_rec = np.repeat(np.arange(n_rec, dtype=np.int64), counts)
-    res = _ensemble_run(eng, xd, trial_rec, np.concatenate(starts), counts, offsets, window_size, p, freqs, fs, measure, bands,
+    xd = _recordings_to_device(eng, x, single)
+    res = _ensemble_run(eng, xd, trial_rec, trial_start, counts, offsets, window_size, p, freqs, fs, measure, bands,
                         spectra, check, share_overlap)
     return _to_host(res, single)
 
 
-def sliding_ensemble_epochs(epochs, window_size, hop, p, freqs, fs, *, measure="ffdtf", bands=None, spectra=False,
-                            check=True, share_overlap=True, engine: Engine | None = None):
-    """`sliding_ensemble` for epochs that are already cut, in the reference's own layout (m, L, trials): windows of
-    `window_size` samples every `hop` samples of the L-sample epoch, each fitted from all trials -> (n_windows, m, m, F |
-    n_bands).  A list of such arrays (same m and L, any numbers of trials) -> (n_groups, n_windows, ...)."""
-    if p is None:
-        raise ValueError("sliding_ensemble_epochs needs an integer model order p (no automatic order for ensembles)")
+def _epoch_groups(epochs):
+    """The groups of `sliding_ensemble_epochs`'s input, checked: (single, list of (m, L, trials) arrays, counts)."""
     single = not isinstance(epochs, (list, tuple))
     groups = [np.asarray(e, dtype=np.float64) for e in ([epochs] if single else epochs)]
     if any(e.ndim != 3 for e in groups):
@@ -390,6 +407,18 @@ def sliding_ensemble_epochs(epochs, window_size, hop, p, freqs, fs, *, measure="
     counts = [e.shape[2] for e in groups]
     if min(counts) < 1:
         raise ValueError(f"group {int(np.argmin(counts))} has no trials: every group needs at least one trial")
+    return single, groups, counts
+
+
+def sliding_ensemble_epochs(epochs, window_size, hop, p, freqs, fs, *, measure="ffdtf", bands=None, spectra=False,
+                            check=True, share_overlap=True, engine: Engine | None = None):
+    """`sliding_ensemble` for epochs that are already cut, in the reference's own layout (m, L, trials): windows of
+    `window_size` samples every `hop` samples of the L-sample epoch, each fitted from all trials -> (n_windows, m, m, F |
+    n_bands).  A list of such arrays (same m and L, any numbers of trials) -> (n_groups, n_windows, ...)."""
+    if p is None:
+        raise ValueError("sliding_ensemble_epochs needs an integer model order p (no automatic order for ensembles)")
+    single, groups, counts = _epoch_groups(epochs)
+    L = groups[0].shape[1]
     eng = engine or default_engine()
     # every trial becomes one recording of L samples that starts at its own sample 0
     xd = eng.to_device(np.concatenate([np.moveaxis(e, 2, 0) for e in groups], axis=0))
@@ -398,3 +427,73 @@ def sliding_ensemble_epochs(epochs, window_size, hop, p, freqs, fs, *, measure="
                         hop_positions(L, window_size, hop).astype(np.int64), window_size, p, freqs, fs, measure, bands, spectra,
                         check, share_overlap)
     return _to_host(res, single)
+
+
+def _ensemble_significance_args(who, p, bands, measure, n_surrogates, m, L, window_size, split, counts, check):
+    """Everything about a trial-shuffle run that can be refused without a GPU."""
+    from . import surrogates as sg
+    if p is None:
+        raise ValueError(f"{who} needs an integer model order p (no automatic order for ensembles)")
+    sg.significance_args(measure, "trial", n_surrogates, m, L, window_size, split)
+    if check is not True and check != "nan":
+        raise ValueError(f"check must be True or 'nan', got {check!r}")
+    if bands is None or len(bands) != 2 or len(np.atleast_1d(bands[0])) < 1 or \
+            len(np.atleast_1d(bands[0])) != len(np.atleast_1d(bands[1])):
+        raise ValueError(f"{who} needs bands = (bin_lo, bin_hi) with at least one band")
+    small = [g for g, c in enumerate(counts) if c < 2]
+    if small:
+        raise ValueError(f"the trial shuffle needs at least 2 trials per group, group {small[0]} has {counts[small[0]]}")
+
+
+def _ensemble_significance_run(eng, xd, trial_rec, trial_start, counts, offsets, window_size, p, freqs, fs, bands, measure,
+                               n_surrogates, seed, split, check, chunk, share_overlap, single):
+    n_groups, n_win = len(counts), len(offsets)
+    dev = eng.device
+    group_ptr, item_group, item_offset, grid = _ensemble_index(eng, counts, offsets, window_size, share_overlap)
+    res = eng.ensemble_significance(xd, torch.as_tensor(trial_rec).to(dev), torch.as_tensor(trial_start).to(dev), group_ptr,
+                                    item_group, item_offset, int(window_size), p, freqs, fs, bands, measure=measure,
+                                    n_surrogates=n_surrogates, seed=seed, split=split, check=check, chunk=chunk, grid=grid)
+    out = {"tested": res["tested"].cpu().numpy()}
+    for k, v in res.items():
+        if k != "tested":
+            a = v.cpu().numpy().reshape((n_groups, n_win) + tuple(v.shape[1:]))
+            out[k] = a[0] if single else a
+    return out
+
+
+def sliding_ensemble_significance(x, onsets, window_size, p, freqs, fs, bands, *, pre, post, hop, measure, n_surrogates, seed,
+                                  split=None, check=True, chunk=None, share_overlap=True, engine: Engine | None = None):
+    """Trial-shuffle test of `sliding_ensemble(x, onsets, window_size, p, freqs, fs, pre=pre, post=post, hop=hop,
+    measure=measure, bands=bands)` (`Engine.ensemble_significance`): in every surrogate the epochs of the channels >=
+    split (the second participant) are permuted against those of the channels < split inside each recording's group of
+    trials, one permutation per surrogate and group for all windows.  Input as `sliding_ensemble`; bands = (bin_lo,
+    bin_hi) is required.  Returns a dict of NumPy arrays: observed, p, p_fwe, null_mean, null_std (n_windows, m, m,
+    n_bands) or (n_rec, n_windows, ...), n_valid (n_windows,) or (n_rec, n_windows), tested (m, m).  Every group needs
+    at least 2 trials.  The arguments are checked before the GPU is touched."""
+    single, n_rec, trial_rec, trial_start, counts, offsets = _onset_trials(x, onsets, pre, post, window_size, hop)
+    m = int(np.shape(x)[-2])
+    _ensemble_significance_args("sliding_ensemble_significance", p, bands, measure, n_surrogates, m, int(pre) + int(post),
+                                int(window_size), split, counts, check)
+    eng = engine or default_engine()
+    xd = _recordings_to_device(eng, x, single)
+    return _ensemble_significance_run(eng, xd, trial_rec, trial_start, counts, offsets, window_size, p, freqs, fs, bands, measure,
+                                      n_surrogates, seed, split, check, chunk, share_overlap, single)
+
+
+def sliding_ensemble_epochs_significance(epochs, window_size, hop, p, freqs, fs, bands, *, measure, n_surrogates, seed,
+                                         split=None, check=True, chunk=None, share_overlap=True,
+                                         engine: Engine | None = None):
+    """`sliding_ensemble_significance` for epochs that are already cut, (m, L, trials) or a list of such groups, as
+    `sliding_ensemble_epochs` takes them: trial e of the channels < split is paired with trial pi(e) of the channels >=
+    split.  Returns the same dict, shaped (n_windows, ...) or (n_groups, n_windows, ...)."""
+    single, groups, counts = _epoch_groups(epochs)
+    m, L = groups[0].shape[:2]
+    _ensemble_significance_args("sliding_ensemble_epochs_significance", p, bands, measure, n_surrogates, m, L,
+                                int(window_size), split, counts, check)
+    offsets = hop_positions(L, window_size, hop).astype(np.int64)
+    eng = engine or default_engine()
+    xd = eng.to_device(np.concatenate([np.moveaxis(e, 2, 0) for e in groups], axis=0))
+    n_tr = int(sum(counts))
+    return _ensemble_significance_run(eng, xd, np.arange(n_tr, dtype=np.int64), np.zeros(n_tr, dtype=np.int64), counts, offsets,
+                                      window_size, p, freqs, fs, bands, measure, n_surrogates, seed, split, check, chunk,
+                                      share_overlap, single)

@@ -1,19 +1,22 @@
-"""Host side of the surrogate significance tests (`Engine.sliding_significance`): argument checks, the random draws and
-the tested family.  Pure NumPy, so that every surrogate can be rebuilt on the host from the seed.
+"""Host side of the surrogate significance tests (`Engine.sliding_significance`, `Engine.ensemble_significance`): argument
+checks, the random draws and the tested family.  Pure NumPy, so that every surrogate can be rebuilt on the host from the seed.
 
 All randomness comes from `rng = numpy.random.default_rng(seed)`, in this order:
     null="shift":  d = rng.integers(min_shift, T - min_shift, size=(S, n_rec), endpoint=True)        (once)
     null="phase":  phi = 2 pi rng.random((S, m, n // 2 + 1)), phi[..., 0] = 0, phi[..., n // 2] = 0 for even n
                    (drawn in consecutive surrogate blocks: one double per draw, so the stream is the same)
+    null="trial":  for s = 0..S-1, then g = 0..G-1: pi[s][g] = rng.permutation(counts[g]), drawn again while it is the
+                   identity (`trial_permutations`; event-locked ensembles only)
 """
 from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["NULLS", "MEASURES", "significance_args", "shift_offsets", "phase_draws", "tested_mask",
-           "check_significance_dict"]
+__all__ = ["NULLS", "ENSEMBLE_NULLS", "MEASURES", "significance_args", "shift_offsets", "phase_draws",
+           "trial_permutations", "tested_mask", "check_significance_dict"]
 
-NULLS = ("shift", "phase")
+NULLS = ("shift", "phase")          # of continuous recordings (`sliding_significance`)
+ENSEMBLE_NULLS = ("trial",)         # of event-locked ensembles (`ensemble_significance`)
 MEASURES = ("ffdtf", "ddtf", "gpdc")
 
 
@@ -27,22 +30,23 @@ def significance_args(measure, null, n_surrogates, m, T, n, split=None, min_shif
     """Check the arguments of a significance run BEFORE anything is drawn or launched; returns (S, split, min_shift) with
     the defaults filled in: split = m // 2 for even m (odd m must pass it; the phase null does not use it), min_shift = n
     (the window length).  ValueError for an unknown measure or null, S < 1, a split outside 1..m-1 and, under the shift
-    null, T < 2 min_shift."""
+    null, T < 2 min_shift.  null="trial" (the trial shuffle of an event-locked ensemble) takes the split of the shift
+    null and uses neither T nor min_shift."""
     if measure not in MEASURES:
         raise ValueError(f"measure must be one of {MEASURES}, got {measure!r}")
-    if null not in NULLS:
-        raise ValueError(f"null must be one of {NULLS}, got {null!r}")
+    if null not in NULLS + ENSEMBLE_NULLS:
+        raise ValueError(f"null must be one of {NULLS + ENSEMBLE_NULLS}, got {null!r}")
     S = _int(n_surrogates, "n_surrogates")
     if S < 1:
         raise ValueError(f"n_surrogates must be >= 1, got {S}")
     m, T, n = int(m), int(T), int(n)
     if split is None:
-        if null == "shift" and m % 2:
+        if null in ("shift", "trial") and m % 2:
             raise ValueError(f"an odd channel count ({m}) needs an explicit split")
         split = m // 2
     else:
         split = _int(split, "split")
-    if null == "shift" and not 1 <= split <= m - 1:
+    if null in ("shift", "trial") and not 1 <= split <= m - 1:
         raise ValueError(f"split must be in 1..{m - 1}, got {split}")
     if null == "phase" and not 0 <= split <= m:
         raise ValueError(f"split must be in 0..{m}, got {split}")
@@ -68,10 +72,33 @@ def phase_draws(rng, S: int, m: int, n: int):
     return phi
 
 
+def trial_permutations(rng, S: int, counts):
+    """The trial shuffles of S surrogates: perms[s][g] = rng.permutation(counts[g]), drawn for s = 0..S-1 and inside a
+    surrogate for g = 0..G-1, in that order.  Trial e of group g (participant A, channels < split) is paired with trial
+    perms[s][g][e] of the same group (participant B).  A draw that is the identity is drawn again: it is the observed
+    arrangement, which the (1 + count) / (1 + n_valid) estimator already counts.  ValueError for a group of fewer than
+    2 trials, which has no other arrangement."""
+    counts = [int(c) for c in counts]
+    for g, c in enumerate(counts):
+        if c < 2:
+            raise ValueError(f"the trial shuffle needs at least 2 trials per group, group {g} has {c}")
+    perms = []
+    for _ in range(int(S)):
+        row = []
+        for c in counts:
+            pi = rng.permutation(c)
+            while np.array_equal(pi, np.arange(c)):
+                pi = rng.permutation(c)
+            row.append(np.asarray(pi, dtype=np.int64))
+        perms.append(row)
+    return perms
+
+
 def tested_mask(m: int, null: str, split: int):
-    """(m, m) bool: the pairs a null tests.  shift: exactly one index < split (the inter-brain pairs); phase: i != j."""
+    """(m, m) bool: the pairs a null tests.  shift and trial: exactly one index < split (the inter-brain pairs); phase:
+    i != j."""
     i, j = np.meshgrid(np.arange(m), np.arange(m), indexing="ij")
-    if null == "shift":
+    if null in ("shift", "trial"):
         return (i < split) != (j < split)
     return i != j
 

@@ -403,6 +403,46 @@ int hmv_sliding_ensemble_f64(int measure, const double* x, int64_t rec_stride, i
                              void* workspace, int64_t workspace_bytes, int64_t chunk, double pivot_tau, int64_t flags,
                              int64_t grid_hop, int64_t grid_nwin, void* stream, void* aux_stream);
 
+/* Trial-shuffle surrogates of an event-locked ensemble (csrc/lagcov_ensemble.hip, lagcov_ens_split_kernel).  A second
+ * trial table (trial_rec_b, trial_start_b), indexed through the same group_ptr, names the partner of every trial: trial
+ * step e of a group reads the channels < split from trial (trial_rec[e], trial_start[e]) and the channels >= split from
+ * trial (trial_rec_b[e], trial_start_b[e]),
+ *     x~_e = [a_e ; b_pi(e)],    R~_l(it) = (1/E_g) sum_e (1/n) X~_e[:, :n-l] X~_e[:, l:]^T
+ * -- the second participant's trials permuted against the first's inside the group; the permutation is the order of table
+ * B and nothing is written out.  Always the direct form (trial loop in the kernel, trials ascending, lagcov_kernel's order
+ * of products): table B = table A gives the bits of hmv_lagcov_ensemble_f64 with HMV_FLAG_DIRECT_LAGCOV.
+ *   R_base [n_base][p+1][MP][MP] with item_base int64 [n_items] (device; both or neither): an element (row, col) with both
+ *   indices < split or both >= split (padded rows and columns count as >= split) is a sum over all trials of one
+ *   participant, which no permutation changes.  Such an element is not computed but copied from
+ *   R_base[item_base[it]][lag], the padding's identity included, and an accumulator (4 rows x 16 columns of one wave) whose
+ *   real elements are all of this kind runs no MFMA.  Accumulators that straddle split are computed whole and their
+ *   within-participant elements then overwritten, so the result does not depend on the tiling.  Without R_base every
+ *   element is computed; the cross elements are the same bits either way.
+ *   The contents of table B and of item_base (0 <= item_base[it] < n_base) are checked by the caller like the other index
+ *   arrays (hyperscanning_signal_analysis_amd.engine.validate_trials): the kernel addresses with them.
+ * hmv_lagcov_ensemble_split_f64: K1 alone, arguments as hmv_lagcov_ensemble_f64 without workspace and grid (flags is
+ *   accepted and not looked at: there is one form).
+ * hmv_sliding_ensemble_split_f64: the fused path of hmv_sliding_ensemble_f64 with this K1; everything after K1 is the
+ *   existing path.  workspace: hmv_sliding_ensemble_workspace_bytes(..., grid_hop = 0, grid_nwin = 0).  item_base is
+ *   indexed by the item of the call, whatever the chunk.
+ * Refused before any launch, in addition to hmv_sliding_ensemble_f64's refusals: split outside 1..m-1 (-5), a null table
+ *   B (-4), R_base without item_base or the reverse (-4). */
+int hmv_lagcov_ensemble_split_f64(const double* x, int64_t rec_stride, int64_t ld, int64_t T,
+                                  const int64_t* trial_rec, const int64_t* trial_start, const int64_t* group_ptr,
+                                  int64_t n_groups, const int64_t* item_group, const int64_t* item_offset, int64_t n_items,
+                                  int m, int n, int p, double* R,
+                                  const int64_t* trial_rec_b, const int64_t* trial_start_b, int split,
+                                  const double* R_base, const int64_t* item_base, int64_t flags, void* stream);
+int hmv_sliding_ensemble_split_f64(int measure, const double* x, int64_t rec_stride, int64_t ld, int64_t T,
+                                   const int64_t* trial_rec, const int64_t* trial_start, const int64_t* group_ptr,
+                                   int64_t n_groups, const int64_t* item_group, const int64_t* item_offset, int64_t n_items,
+                                   int m, int n, int p, const double* freqs, int F, double fs,
+                                   double* out, const int32_t* bin_lo, const int32_t* bin_hi, int n_bands, double* S_out,
+                                   double* ar_out, double* V_out, int32_t* info_yw, int32_t* info_tf,
+                                   void* workspace, int64_t workspace_bytes, int64_t chunk, double pivot_tau, int64_t flags,
+                                   const int64_t* trial_rec_b, const int64_t* trial_start_b, int split,
+                                   const double* R_base, const int64_t* item_base, void* stream, void* aux_stream);
+
 /* FAD (frequency-amplitude-damping) decomposition of univariate AR models, batched over series.  Replaces
  * fad_decomposition (src/mtmvar.py:607-757): order selection as mvar_criterion at m = 1 (:551-601), the fit of ar_coeff
  * (:90-123, count_corr :35-87: biased 1/n autocovariance, no demeaning) by Levinson-Durbin, and the partial-fraction
