@@ -215,6 +215,48 @@ int hmv_lagcov_ensemble_split_f64(const double* x, int64_t rec_stride, int64_t l
   return hmv::launch_lagcov_ensemble_split(a, mp, S(stream));
 }
 
+// ---- K1 for pairs of recordings (lagcov_ensemble.hip, lagcov_pairs_kernel) ---------------------------------------------
+namespace {
+// what the two pair entries refuse about their extra arguments; 0 when they are fine
+int pairs_check(const char* who, int m, const int64_t* rec_b, int split, const double* R_base, const int64_t* base_a,
+                const int64_t* base_b) {
+  char buf[160];
+  const char* msg = nullptr;
+  int code = -4;
+  if (split < 1 || split >= m) { code = -5; msg = "split must be in 1..m-1"; }
+  else if (!rec_b) msg = "null pointer (rec_b)";
+  else if ((R_base != nullptr) != (base_a != nullptr) || (R_base != nullptr) != (base_b != nullptr))
+    msg = "R_base, base_a and base_b go together";
+  if (!msg) return 0;
+  snprintf(buf, sizeof(buf), "%s: %s", who, msg);
+  return fail(code, buf);
+}
+}  // namespace
+
+int hmv_lagcov_pairs_f64(const double* x, int64_t rec_stride, int64_t ld, int64_t T, const int64_t* rec_a,
+                         const int64_t* rec_b, const int64_t* item_start, int64_t n_items, int m, int n, int p, int split,
+                         double* R, const double* R_base, const int64_t* base_a, const int64_t* base_b, int64_t flags,
+                         void* stream) {
+  (void)flags;                                           // the direct form is the only one: nothing to choose
+  (void)T;                                               // the caller has checked the windows against it
+  const int mp = pad_of(m);
+  if (mp < 0) return fail(-1, "hmv_lagcov_pairs_f64: channel count must be in 1..64");
+  if (p < 1 || p > HMV_MAX_ORDER) return fail(-2, "hmv_lagcov_pairs_f64: model order must be in 1..32");
+  if (n <= p) return fail(-3, "hmv_lagcov_pairs_f64: window shorter than the model order");
+  if (!x || !rec_a || !item_start || !R || n_items < 0) return fail(-4, "hmv_lagcov_pairs_f64: null pointer");
+  if (int rc = pairs_check("hmv_lagcov_pairs_f64", m, rec_b, split, R_base, base_a, base_b)) return rc;
+  hmv::LagcovPairsArgs a{};
+  a.x = x; a.rec_stride = rec_stride; a.ld = ld;
+  a.rec_a = reinterpret_cast<const long long*>(rec_a);
+  a.rec_b = reinterpret_cast<const long long*>(rec_b);
+  a.item_start = reinterpret_cast<const long long*>(item_start);
+  a.n_items = n_items; a.m = m; a.n = n; a.p = p; a.split = split; a.R = R;
+  a.R_base = R_base;
+  a.base_a = reinterpret_cast<const long long*>(base_a);
+  a.base_b = reinterpret_cast<const long long*>(base_b);
+  return hmv::launch_lagcov_pairs(a, mp, S(stream));
+}
+
 int hmv_yw_solve_f64(const double* R, int64_t n_items, int m, int p, double* ws, double* ar, double* V,
                      double* vq_logdet, int32_t* info, int64_t flags, void* stream) {
   const int mp = pad_of(m);
@@ -627,6 +669,15 @@ struct EnsDesc {
   const double* R_base = nullptr;
   const int64_t* item_base = nullptr;
 };
+// Pairs of recordings in place of single windows (hmv_sliding_pairs_f64): item_rec / item_start of sliding_impl carry
+// rec_a / item_start, the channels >= split are read from recording rec_b, and only K1 differs (lagcov_pairs_kernel).
+struct PairDesc {
+  const int64_t* rec_b;
+  int split;
+  const double* R_base;
+  const int64_t* base_a;
+  const int64_t* base_b;
+};
 // Everything sliding_impl is told, by name; a field left alone means "not asked for".  The exported entries below fill in
 // what they have.  `ffdtf` receives the full (m, m, F) arrays, `band_out` (with bin_lo / bin_hi / n_bands) the band sums.
 struct SlidingArgs {
@@ -663,6 +714,7 @@ struct SlidingArgs {
   int32_t* order_out = nullptr;
   double* crit_out = nullptr;
   const EnsDesc* ens = nullptr;
+  const PairDesc* pairs = nullptr;
 };
 int sliding_impl(const SlidingArgs& a) {
   // crit >= 0: automatic order (hmv_sliding_auto_f64) -- p is the largest order tried, K1 sums p + 1 lags, K2 selects every
@@ -699,11 +751,12 @@ int sliding_impl(const SlidingArgs& a) {
     ens_shared = !a.ens->split && ens_shared_form(a.n, a.p, a.grid_hop, a.flags);
   }
   const SlidingWs w = sliding_layout(a.chunk, mp, a.p, a.F, bands, a.S_out != nullptr, a.measure,
-                                     a.ens ? (ens_shared ? ens_q_tiles(a.chunk, a.n, a.p, a.grid_hop, a.grid_nwin) : 0) : -1);
+                                     a.ens ? (ens_shared ? ens_q_tiles(a.chunk, a.n, a.p, a.grid_hop, a.grid_nwin) : 0)
+                                           : (a.pairs ? 0 : -1));
   if ((int64_t)w.total > a.workspace_bytes) return fail(-7, "hmv_sliding_ffdtf_f64: workspace too small");
   // Regular grid (the caller vouches: item = rec * grid_nwin + w starts at grid_first + w * grid_hop of recording rec,
   // recordings are grid_T samples long): K1 sums every hop block once and assembles the windows from the blocks.
-  bool regular = !a.ens && a.grid_hop > 0 && !(a.flags & HMV_FLAG_DIRECT_LAGCOV);
+  bool regular = !a.ens && !a.pairs && a.grid_hop > 0 && !(a.flags & HMV_FLAG_DIRECT_LAGCOV);
   if (regular) {
     if (a.grid_nwin < 1 || a.grid_first < 0 || a.n_items % a.grid_nwin != 0 ||
         a.grid_first + (a.grid_nwin - 1) * a.grid_hop + a.n > a.grid_T || a.ld < a.grid_T)
@@ -765,6 +818,17 @@ int sliding_impl(const SlidingArgs& a) {
       } else {
         rc = hmv::launch_lagcov_ensemble(ea, mp, ens_shared, st0);
       }
+    } else if (a.pairs) {
+      hmv::LagcovPairsArgs pa{};
+      pa.x = a.x; pa.rec_stride = a.rec_stride; pa.ld = a.ld;
+      pa.rec_a = reinterpret_cast<const long long*>(a.item_rec + i0);
+      pa.rec_b = reinterpret_cast<const long long*>(a.pairs->rec_b + i0);
+      pa.item_start = reinterpret_cast<const long long*>(a.item_start + i0);
+      pa.n_items = c; pa.m = a.m; pa.n = a.n; pa.p = a.p; pa.split = a.pairs->split; pa.R = R;
+      pa.R_base = a.pairs->R_base;
+      pa.base_a = a.pairs->R_base ? reinterpret_cast<const long long*>(a.pairs->base_a + i0) : nullptr;
+      pa.base_b = a.pairs->R_base ? reinterpret_cast<const long long*>(a.pairs->base_b + i0) : nullptr;
+      rc = hmv::launch_lagcov_pairs(pa, mp, st0);
     } else if (regular) {
       // items i0 .. i0+c-1 as runs of consecutive windows of one recording each (item = rec * grid_nwin + w)
       for (int64_t it = i0; it < i0 + c && rc == 0;) {
@@ -1080,6 +1144,46 @@ int hmv_sliding_ensemble_split_f64(int measure, const double* x, int64_t rec_str
   return sliding_ensemble_entry("hmv_sliding_ensemble_split_f64", measure, x, rec_stride, ld, ens, item_group, item_offset,
                                 n_items, m, n, p, freqs, F, fs, out, bin_lo, bin_hi, n_bands, S_out, ar_out, V_out, info_yw,
                                 info_tf, workspace, workspace_bytes, chunk, pivot_tau, flags, 0, 0, stream, aux_stream);
+}
+
+// ---- pairs of recordings: the fused path with the pair K1 (pseudo-dyad surrogates) -------------------------------------
+int64_t hmv_pairs_workspace_bytes(int measure, int64_t chunk, int m, int n, int p, int F, int n_bands) {
+  // n_bands = -1: the full ffDTF together with S_out, as hmv_sliding_auto_workspace_bytes
+  const bool spectra = (n_bands == -1 && measure == HMV_MEASURE_FFDTF);
+  if (n <= p) return -1;
+  return sliding_bytes(chunk, m, p, F, spectra ? 0 : n_bands, spectra, measure, 0);
+}
+
+int hmv_sliding_pairs_f64(int measure, const double* x, int64_t rec_stride, int64_t ld, int64_t T, const int64_t* rec_a,
+                          const int64_t* rec_b, const int64_t* item_start, int64_t n_items, int m, int n, int p,
+                          const double* freqs, int F, double fs, double* out, const int32_t* bin_lo, const int32_t* bin_hi,
+                          int n_bands, double* S_out, double* ar_out, double* V_out, int32_t* info_yw, int32_t* info_tf,
+                          void* workspace, int64_t workspace_bytes, int64_t chunk, double pivot_tau, int64_t flags, int split,
+                          const double* R_base, const int64_t* base_a, const int64_t* base_b, void* stream,
+                          void* aux_stream) {
+  const char* who = "hmv_sliding_pairs_f64";
+  (void)T;                                               // the caller has checked the windows against it
+  if (pad_of(m) >= 0)                                    // (a bad channel count is sliding_impl's -1)
+    if (int rc = pairs_check(who, m, rec_b, split, R_base, base_a, base_b)) return rc;
+  if (measure < HMV_MEASURE_FFDTF || measure > HMV_MEASURE_GPDC)
+    return fail(-4, "hmv_sliding_pairs_f64: measure must be HMV_MEASURE_FFDTF, _DDTF or _GPDC");
+  if (n_bands < 0) return fail(-4, "hmv_sliding_pairs_f64: n_bands must be >= 0");
+  if (S_out && (measure != HMV_MEASURE_FFDTF || n_bands != 0))
+    return fail(-4, "hmv_sliding_pairs_f64: spectra come with the full ffDTF only");
+  if (pad_of(m) >= 0 && p >= 1 && p <= HMV_MAX_ORDER && n > p && !out && n_items != 0)
+    return fail(-4, "hmv_sliding_pairs_f64: null pointer / empty grid");
+  const PairDesc pairs{rec_b, split, R_base, base_a, base_b};
+  SlidingArgs a{who};
+  a.measure = measure; a.pairs = &pairs;
+  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.item_rec = rec_a; a.item_start = item_start; a.n_items = n_items;
+  a.m = m; a.n = n; a.p = p; a.freqs = freqs; a.F = F; a.fs = fs;
+  if (n_bands > 0) a.band_out = out; else a.ffdtf = out;
+  a.bin_lo = bin_lo; a.bin_hi = bin_hi; a.n_bands = n_bands; a.S_out = S_out;
+  a.ar_out = ar_out; a.V_out = V_out; a.info_yw = info_yw; a.info_tf = info_tf;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.pivot_tau = pivot_tau; a.flags = flags;
+  if (measure == HMV_MEASURE_GPDC) { a.info_tf = nullptr; a.pivot_tau = 1.0; }
+  a.stream = stream; a.aux_stream = aux_stream;
+  return sliding_impl(a);
 }
 
 int64_t hmv_fad_workspace_bytes(int64_t n_series, int pmax) {

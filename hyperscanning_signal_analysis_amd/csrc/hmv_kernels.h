@@ -68,6 +68,26 @@ bool lagcov_ensemble_shared_ok(int n, long long hop, int p, int max_k);      // 
 long long lagcov_ensemble_q_tiles(long long n_items, long long nwin, int k);  // in stacks of (p+1) tiles
 int launch_lagcov_ensemble(const LagcovEnsArgs& a, int m_pad, bool shared, hipStream_t st);
 int launch_lagcov_ensemble_split(const LagcovEnsArgs& a, int m_pad, hipStream_t st);   // direct form, two trial tables
+// K1 for pairs of recordings (lagcov_ensemble.hip, lagcov_pairs_kernel): item `it` is the window of n samples starting at
+// item_start[it], its channels < split read from recording rec_a[it] and its channels >= split from recording rec_b[it].
+// lagcov_kernel's mapping, chunks and order of products; optionally the two within-participant blocks are copied from two
+// different base stacks and only the cross elements are computed.
+struct LagcovPairsArgs {
+  const double* x;          // [n_rec][m][ld]
+  long long rec_stride, ld;
+  const long long* rec_a;       // [n_items]  } of the items of THIS launch (device)
+  const long long* rec_b;       // [n_items]  }
+  const long long* item_start;  // [n_items]  }
+  long long n_items;
+  int m, n, p, split;       // split: 1 .. m - 1
+  double* R;                // [n_items][p+1][MP][MP]
+  // optional, all three or none: elements with both indices < split are copied from R_base[base_a[it]], elements with both
+  // indices >= split (padding included) from R_base[base_b[it]]
+  const double* R_base;     // [n_base][p+1][MP][MP]
+  const long long* base_a;  // [n_items], of the items of THIS launch
+  const long long* base_b;  // [n_items]
+};
+int launch_lagcov_pairs(const LagcovPairsArgs& a, int m_pad, hipStream_t st);
 
 // ---- K2 Yule-Walker solve (block LDL^T of the block-Toeplitz normal equations) ------------------
 struct YwArgs {

@@ -266,6 +266,98 @@ __global__ void __launch_bounds__(256, 2) lagcov_ens_split_kernel(LagcovEnsArgs 
   });
 }
 
+// ---- pairs of recordings (pseudo-dyad surrogates) -------------------------------------------------------------------------
+// Item `it` stages the channels < split from recording rec_a[it] and the channels >= split from recording rec_b[it], both at
+// item_start[it]: participant A of one dyad beside participant B of another, time-locked.  One window per item, so there is
+// no trial loop and no division by a trial count: the chunks, the k-steps, the order of products per accumulator and the
+// final scaling are lagcov_kernel's, and every computed element has the bits hmv_lagcov_f64 gives for the same window
+// written out as one recording.  With R_base the elements with both indices < split come from R_base[base_a[it]] and the
+// elements with both indices >= split (padding and its lag-0 identity included) from R_base[base_b[it]] -- two different
+// stacks, where lagcov_ens_split_kernel has one; the `need` mask, its place in an SGPR and the rule for accumulators that
+// straddle split are that kernel's.
+template <int NT, int LG>
+__global__ void __launch_bounds__(256, 2) lagcov_pairs_kernel(LagcovPairsArgs a) {
+  constexpr int MP = 16 * NT;
+  __shared__ double xs[MP * LE_S];
+  const int l = lane_id();
+  const int wv = uni(threadIdx.x >> 6);
+  const long long item = blockIdx.x;
+  const int lag0 = blockIdx.y * LG;
+  const int nl = min(LG, a.p + 1 - lag0);
+  const int i = l >> 4, cc = l & 15;
+  const int n = a.n, m = a.m, split = a.split;
+  const bool based = a.R_base != nullptr;
+  const long long start = a.item_start[item];
+  const double* xA = a.x + a.rec_a[item] * a.rec_stride + start;
+  const double* xB = a.x + a.rec_b[item] * a.rec_stride + start;
+
+  unsigned need = 0;
+#pragma unroll
+  for (int I = 0; I < NT; ++I)
+#pragma unroll
+    for (int J = 0; J < NT; ++J) {
+      const int r0 = 4 * (NT * wv + I), c0 = 16 * J;     // rows r0 .. r0 + 3, columns c0 .. c0 + 15
+      const bool rows_a = r0 < split, rows_b = max(r0, split) <= min(r0 + 3, m - 1);
+      const bool cols_a = c0 < split, cols_b = max(c0, split) <= min(c0 + 15, m - 1);
+      if (!based || (rows_a && cols_b) || (rows_b && cols_a)) need |= 1u << (I * NT + J);
+    }
+  need = (unsigned)uni((int)need);
+
+  double acc[LG][NT][NT];
+#pragma unroll
+  for (int q = 0; q < LG; ++q)
+#pragma unroll
+    for (int I = 0; I < NT; ++I)
+#pragma unroll
+      for (int J = 0; J < NT; ++J) acc[q][I][J] = 0.0;
+
+  constexpr int NLD = (MP * LE_W + 255) / 256;
+  const double* xa = xs + (4 * NT * wv + (l & 3)) * LE_S + (l >> 4);
+  const double* xb = xs + cc * LE_S + lag0 + (l >> 4);
+  for (int t0 = 0; t0 < n; t0 += LE_TC) {
+    double stg[NLD];
+#pragma unroll
+    for (int r = 0; r < NLD; ++r) {                     // all loads of the chunk in flight, then the LDS stores
+      const int idx = threadIdx.x + 256 * r;
+      const int ch = idx / LE_W, tt = idx - ch * LE_W;
+      const int t = t0 + tt;
+      const double* x = ch < split ? xA : xB;
+      stg[r] = (idx < MP * LE_W && ch < m && t < n) ? x[(size_t)ch * a.ld + t] : 0.0;
+    }
+    __syncthreads();                                    // the k-steps of the previous chunk have read xs
+#pragma unroll
+    for (int r = 0; r < NLD; ++r) {
+      const int idx = threadIdx.x + 256 * r;
+      const int ch = idx / LE_W, tt = idx - ch * LE_W;
+      if (idx < MP * LE_W) xs[ch * LE_S + tt] = stg[r];
+    }
+    __syncthreads();
+    le_ksteps_masked<NT, LG>(xa, xb, min(LE_TC, n - t0 + 3) >> 2, nl, need, acc);
+  }
+  const double scale = 1.0 / (double)n;                 // `corr_scale = 1 / n`, multiplied (mtmvar.py:57-59)
+  static_for<LG>([&](auto gc) __attribute__((always_inline)) {
+    constexpr int q = decltype(gc)::value;
+    if (q < nl) {
+      const int lag = lag0 + q;
+      const size_t tile = (size_t)MP * MP, stack = (size_t)(a.p + 1) * tile;
+      double* R = a.R + (size_t)item * stack + lag * tile;
+      const double* Ra = based ? a.R_base + (size_t)a.base_a[item] * stack + lag * tile : nullptr;
+      const double* Rb = based ? a.R_base + (size_t)a.base_b[item] * stack + lag * tile : nullptr;
+#pragma unroll
+      for (int I = 0; I < NT; ++I)
+#pragma unroll
+        for (int J = 0; J < NT; ++J) {
+          const int row = 4 * (NT * wv + I) + i, col = 16 * J + cc;
+          double v = acc[q][I][J] * scale;
+          if (lag == 0 && row == col && row >= m) v = 1.0;   // padded channels: identity block keeps G SPD
+          if (based && (row < split) == (col < split))        // (split < m: padding is >= split)
+            v = (row < split ? Ra : Rb)[(size_t)row * MP + col];
+          R[(size_t)row * MP + col] = v;
+        }
+    }
+  });
+}
+
 // ---- shared-overlap form --------------------------------------------------------------------------------------------
 // Items it0 .. it0 + n_items - 1 of the grid (item = g * nwin + w) touch the groups g0 .. g0 + ngc - 1; group g0 + gi owns
 // the Q slots gi * nblk .. + nblk - 1 (nblk = nwin + k - 1 hop blocks), of which only those under a window of the chunk
@@ -511,6 +603,24 @@ int launch_lagcov_ensemble_split(const LagcovEnsArgs& a, int m_pad, hipStream_t 
     case 32: hipLaunchKernelGGL((lagcov_ens_split_kernel<2, LG>), grid, block, 0, st, a); break;
     case 48: hipLaunchKernelGGL((lagcov_ens_split_kernel<3, LG>), grid, block, 0, st, a); break;
     case 64: hipLaunchKernelGGL((lagcov_ens_split_kernel<4, LG>), grid, block, 0, st, a); break;
+    default: return -1;
+  }
+  return (int)hipGetLastError();
+}
+
+int launch_lagcov_pairs(const LagcovPairsArgs& a, int m_pad, hipStream_t st) {
+  if (a.n_items == 0) return 0;
+  if (a.p > LE_HALO) return -2;
+  if (!a.rec_a || !a.rec_b || !a.item_start || a.split < 1 || a.split >= a.m ||
+      (a.R_base != nullptr) != (a.base_a != nullptr) || (a.R_base != nullptr) != (a.base_b != nullptr))
+    return -4;
+  constexpr int LG = 3;
+  const dim3 block(256), grid((unsigned)a.n_items, (a.p + LG) / LG);
+  switch (m_pad) {
+    case 16: hipLaunchKernelGGL((lagcov_pairs_kernel<1, LG>), grid, block, 0, st, a); break;
+    case 32: hipLaunchKernelGGL((lagcov_pairs_kernel<2, LG>), grid, block, 0, st, a); break;
+    case 48: hipLaunchKernelGGL((lagcov_pairs_kernel<3, LG>), grid, block, 0, st, a); break;
+    case 64: hipLaunchKernelGGL((lagcov_pairs_kernel<4, LG>), grid, block, 0, st, a); break;
     default: return -1;
   }
   return (int)hipGetLastError();

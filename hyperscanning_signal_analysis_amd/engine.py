@@ -1013,6 +1013,207 @@ class Engine:
                 res[k][obs_bad] = float("nan")
         return res
 
+    # ------------------------------------------------------------------ pairs of recordings, pseudo-dyad significance
+    def _check_pairs(self, x, n_items, p, split, R_base, base_a, base_b):
+        """The arguments of the pair K1 that `validate_items` does not see, before anything is launched."""
+        m, mp = x.shape[1], self.pad(x.shape[1])
+        if isinstance(split, bool) or int(split) != split or not 1 <= int(split) <= m - 1:
+            raise ValueError(f"split must be an integer in 1..{m - 1}, got {split!r}")
+        if len({R_base is None, base_a is None, base_b is None}) != 1:
+            raise ValueError("R_base, base_a and base_b go together")
+        if R_base is None:
+            return
+        if not (isinstance(R_base, torch.Tensor) and R_base.dtype == torch.float64 and R_base.device == x.device
+                and R_base.dim() == 4 and tuple(R_base.shape[1:]) == (int(p) + 1, mp, mp) and R_base.is_contiguous()):
+            raise ValueError(f"R_base must be a contiguous float64 tensor (n_base, {int(p) + 1}, {mp}, {mp}) on {x.device}")
+        for name, t in (("base_a", base_a), ("base_b", base_b)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.int64 and t.device == x.device and t.dim() == 1
+                    and t.numel() == n_items and t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous 1-D int64 tensor of {n_items} entries on {x.device}")
+            if n_items:
+                lo, hi = int(t.min()), int(t.max())
+                if lo < 0 or hi >= R_base.shape[0]:
+                    raise ValueError(f"{name} must lie in [0, {R_base.shape[0]}), got [{lo}, {hi}]")
+
+    def _validate_pairs(self, x, rec_a, rec_b, item_start, n, p, split, R_base, base_a, base_b):
+        validate_items(x, rec_a, item_start, n, p)
+        validate_items(x, rec_b, item_start, n, p)
+        self._check_pairs(x, int(rec_a.numel()), p, split, R_base, base_a, base_b)
+
+    def lagcov_pairs(self, x: torch.Tensor, rec_a: torch.Tensor, rec_b: torch.Tensor, item_start: torch.Tensor, n: int, p: int,
+                     split: int, R_base: torch.Tensor | None = None, base_a: torch.Tensor | None = None,
+                     base_b: torch.Tensor | None = None, out: torch.Tensor | None = None, validate: bool = True):
+        """K1 for pairs of recordings (`hmv_lagcov_pairs_f64`): x (n_rec, m, T) -> R (items, p+1, MP, MP) of the window of n
+        samples at item_start[it] whose channels < split come from recording rec_a[it] and whose channels >= split come
+        from recording rec_b[it].  Every computed element has the bits of `lagcov` on that window written out as one
+        recording.  With R_base (n_base, p+1, MP, MP), base_a and base_b (items,) the elements with both indices < split
+        are copied from R_base[base_a[it]], those with both indices >= split (padding included) from R_base[base_b[it]],
+        and only the cross blocks are computed.  Both recording tables are checked with `validate_items`.  `out`, if given,
+        is the contiguous (items, p+1, MP, MP) tensor the result is written to."""
+        no_auto_order(p, "lagcov_pairs")
+        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
+        x = x if x.stride(2) == 1 else x.contiguous()
+        if validate:
+            self._validate_pairs(x, rec_a, rec_b, item_start, n, p, split, R_base, base_a, base_b)
+        n_rec, m, T = x.shape
+        mp = self.pad(m)
+        n_items = int(rec_a.numel())
+        R = self.empty(n_items, int(p) + 1, mp, mp) if out is None else out
+        assert R.is_contiguous() and R.dtype == torch.float64 and tuple(R.shape) == (n_items, int(p) + 1, mp, mp)
+        if n_items == 0:
+            return R
+        with torch.cuda.device(self.device):
+            rc = self.lib.hmv_lagcov_pairs_f64(
+                x.data_ptr(), x.stride(0), x.stride(1), T, rec_a.data_ptr(), rec_b.data_ptr(), item_start.data_ptr(), n_items,
+                m, int(n), int(p), int(split), R.data_ptr(), _ptr(R_base), _ptr(base_a), _ptr(base_b), 0, self.stream())
+        _lib.check(rc, "hmv_lagcov_pairs_f64")
+        return R
+
+    def _pairs_route(self, measure, n, p, rec_b, split, R_base, base_a, base_b):
+        """Route of `sliding_pairs` (`hmv_sliding_pairs_f64`): the items are (rec_a, item_start), the second recording table
+        and the bases ride along, there is no grid, and a failed fit is reported with its pair of recordings."""
+        lib, n, p, code = self.lib, int(n), int(p), _MEASURES[measure]
+
+        def blame(err, items):       # say which pair of recordings and which window
+            idx = torch.as_tensor(err.items, dtype=torch.int64, device=items[0].device)
+            err.rec_a, err.rec_b = items[0][idx].cpu().numpy(), rec_b[idx].cpu().numpy()
+            err.starts = items[1][idx].cpu().numpy()
+            err.args = (err.args[0], err.args[1] + f" (channels < {int(split)} of recording {int(err.rec_a[0])} with channels "
+                        f">= {int(split)} of recording {int(err.rec_b[0])}, window at sample {int(err.starts[0])})")
+
+        def call(a):
+            return "hmv_sliding_pairs_f64", (
+                code, *a.x, a.T, a.items[0], rec_b.data_ptr(), a.items[1], a.n_items, a.m, n, p, a.f, a.F, a.fs, a.out, a.lo,
+                a.hi, a.nb, a.S, a.ar, a.V, a.info_yw, a.info_tf, a.ws, a.nbytes, a.chunk, a.tau, a.flags, int(split),
+                _ptr(R_base), _ptr(base_a), _ptr(base_b), a.stream, a.aux)
+        return _Route(
+            name="sliding_pairs", measure=measure, p=p, order_text=f"n={n}, p={p}", blame=blame,
+            yw_text="ar_coeff (Yule-Walker solve; a negative info: residual covariance not positive definite)",
+            validate=lambda x, items: self._validate_pairs(x, items[0], rec_b, items[1], n, p, split, R_base, base_a, base_b),
+            grid=lambda x, items, n_items, grid, compare: (),
+            ws_bytes=lambda chunk, m, F, nb, g: lib.hmv_pairs_workspace_bytes(code, chunk, m, n, p, F, nb),
+            call=call)
+
+    def sliding_pairs(self, x: torch.Tensor, rec_a: torch.Tensor, rec_b: torch.Tensor, item_start: torch.Tensor, n: int,
+                      p: int, freqs, fs: float, *, measure: str = "ffdtf", split: int, bands=None,
+                      R_base: torch.Tensor | None = None, base_a: torch.Tensor | None = None,
+                      base_b: torch.Tensor | None = None, out: torch.Tensor | None = None, return_ar: bool = False,
+                      check=True, chunk: int | None = None, flags: int = 0, validate: bool = True):
+        """Connectivity of pairs of recordings: `measure` ("ffdtf", "ddtf", "gpdc") of the window at item_start[it] whose
+        channels < split are those of recording rec_a[it] and whose channels >= split are those of recording rec_b[it] --
+        what `sliding_<measure>` gives for the two halves written out as one recording, bit for bit, without writing it.
+        x (n_rec, m, T) -> (items, m, m, F), or the band sums (items, m, m, n_bands) with `bands=(bin_lo, bin_hi)`.  One
+        C-ABI call (`hmv_sliding_pairs_f64`); only K1 differs from the single-recording calls.  R_base / base_a / base_b
+        as in `lagcov_pairs`.  out, return_ar, check, chunk, flags as in `sliding_ffdtf`; the SingularMatrixError of
+        check=True names the pair.  p=None raises ValueError (no automatic order here)."""
+        if measure not in _MEASURES:
+            raise ValueError(f"measure must be 'ffdtf', 'ddtf' or 'gpdc', got {measure!r}")
+        no_auto_order(p, "sliding_pairs")
+        rt = self._pairs_route(measure, n, p, rec_b, split, R_base, base_a, base_b)
+        return self._sliding_call(rt, x, (rec_a, item_start), freqs, fs, bands=bands, out=out, return_ar=return_ar,
+                                  check=check, chunk=chunk, flags=flags, validate=validate)
+
+    def pseudo_dyad_significance(self, x: torch.Tensor, item_start: torch.Tensor, n: int, p: int, freqs, fs: float, bands, *,
+                                 measure: str, split=None, n_surrogates=None, seed=None, check=True,
+                                 chunk: int | None = None):
+        """Pseudo-dyad (shuffled-partner) test of the band values of `sliding_<measure>(..., bands=bands)`.
+
+        x (D, m, T): recording d is dyad d, its channels < split participant A, the others participant B; every dyad went
+        through the same stimulus, and item_start (W,) names the windows common to all of them.  Surrogate s analyses A of
+        dyad d with B of dyad pi[s][d] != d at the same time points (`surrogates.partner_derangements`: n_surrogates=None
+        is the exhaustive set of the D - 1 cyclic offsets and uses no seed; an integer draws that many derangements from
+        numpy.random.default_rng(seed)).  What the real dyads share with the pseudo dyads is the stimulus; what they do not
+        share is the interaction.  No pseudo recording is written: K1 reads the two halves in place
+        (`hmv_sliding_pairs_f64`) and copies both within-participant covariance blocks from the observed fits.
+        Per dyad ("window" = (d, w)): surrogate s gives dyad d two null values, index 2s A-anchored (A_d with B_pi(d)) and
+        index 2s+1 B-anchored (A_{pi^-1(d)} with B_d); p, p_fwe, null_mean, null_std as in `sliding_significance` over the
+        n_valid of them whose fit succeeded.  Group ("window" = w): the observed value is the mean over the D dyads,
+        surrogate s the mean over its D pseudo dyads, invalid for a window where any of the D fits failed; the observed
+        group value is NaN where an observed fit of the window failed.  Tests the pairs with exactly one index < split.
+        check: True raises LinAlgError for a failed observed window, "nan" gives NaN statistics for it.  chunk: items per
+        fused call (default: a whole surrogate, as far as the workspace allows); the results are the same bits for any chunk.
+        Returns a dict of device tensors: observed, p, p_fwe, null_mean, null_std (D, W, m, m, n_bands), n_valid (D, W) int32,
+        tested (m, m) bool, partners (S, D) int64 and group = {observed, p, p_fwe, null_mean, null_std (W, m, m, n_bands),
+        n_valid (W,)}."""
+        from . import surrogates as sg
+        no_auto_order(p, "pseudo_dyad_significance")
+        D, m, T = x.shape
+        n, p = int(n), int(p)
+        S, split = sg.pseudo_dyad_args(measure, D, m, n_surrogates, seed, split, check)
+        lo, hi = (np.asarray(b, dtype=np.int32) for b in (bands if bands is not None else ((), ())))
+        nb = int(lo.size)
+        if nb < 1:
+            raise ValueError("pseudo_dyad_significance needs at least one band")
+        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
+        x = x if x.stride(2) == 1 else x.contiguous()
+        self.pad(m)
+        W = int(item_start.numel())
+        i64 = dict(dtype=torch.int64, device=self.device)
+        dy = torch.arange(D, **i64).repeat_interleave(W)                  # item (d, w) = d * W + w: its dyad ...
+        starts = item_start.repeat(D) if isinstance(item_start, torch.Tensor) else item_start
+        self.check_items(x, dy, starts, n, p)
+        f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
+        F = int(f.numel())
+        self.band_tables(lo, hi, F)
+        partners = sg.partner_derangements(None if S is None else np.random.default_rng(seed), S, D)
+        S = int(partners.shape[0])
+        tested_h = sg.tested_mask(m, "shift", split)
+        tested = torch.as_tensor(tested_h.astype(np.uint8)).to(self.device)
+        res = {"tested": torch.as_tensor(tested_h).to(self.device), "partners": torch.as_tensor(partners).to(self.device)}
+        stats = ("p", "p_fwe", "null_mean", "null_std")
+        if W == 0:
+            res.update({k: self.empty(D, 0, m, m, nb) for k in ("observed",) + stats}, n_valid=self.empty(D, 0, dtype=torch.int32))
+            res["group"] = dict({k: self.empty(0, m, m, nb) for k in ("observed",) + stats},
+                                n_valid=self.empty(0, dtype=torch.int32))
+            return res
+        N = D * W
+        run = {"ffdtf": self.sliding_ffdtf, "ddtf": self.sliding_ddtf, "gpdc": self.sliding_gpdc}[measure]
+        obs = run(x, dy, starts, n, p, f, fs, bands=(lo, hi), check=True if check is True else "mask", validate=False)
+        obs, obs_bad = (obs, None) if check is True else obs
+        # (K1 over the D W real windows a second time -- the fused call above does not hand its R out; a few per cent of it)
+        R_base = self.lagcov(x, dy, starts, n, p)
+        base_a = torch.arange(N, **i64)
+        wrep = torch.arange(W, **i64).repeat(D)
+        blk = N if chunk is None else max(1, min(N, int(chunk)))
+        st = self.null_state(N, m, nb)
+        gmean = self.empty(S, W, m, m, nb)
+        gbad = torch.empty(S, W, dtype=torch.bool, device=self.device)
+        both = self.empty(2, N, m, m, nb)                                   # the two surrogates one s gives every dyad
+        both_bad = torch.empty(2, N, dtype=torch.bool, device=self.device)
+        for s in range(S):
+            pi = torch.as_tensor(partners[s]).to(self.device)
+            inv = torch.empty_like(pi)
+            inv[pi] = torch.arange(D, **i64)
+            rec_b = pi[dy].contiguous()
+            base_b = (rec_b * W + wrep).contiguous()
+            for i0 in range(0, N, blk):
+                sl = slice(i0, min(N, i0 + blk))
+                _, bad = self.sliding_pairs(x, dy[sl], rec_b[sl], starts[sl], n, p, f, fs, measure=measure, split=split,
+                                            bands=(lo, hi), R_base=R_base, base_a=base_a[sl], base_b=base_b[sl],
+                                            out=both[0, sl], check="mask", validate=False)
+                both_bad[0, sl] = bad
+            # whole surrogates only: the B-anchored value of dyad d is the item of dyad pi^-1(d), wherever its block was
+            both[1] = both[0].view(D, W, m, m, nb)[inv].view(N, m, m, nb)
+            both_bad[1] = both_bad[0].view(D, W)[inv].view(N)
+            self.null_accumulate(obs, both.view(2 * N, m, m, nb), both_bad.view(2 * N), tested, st, s == S - 1, 2)
+            gmean[s] = both[0].view(D, W, m, m, nb).mean(dim=0)
+            gbad[s] = both_bad[0].view(D, W).any(dim=0)
+        gobs = obs.view(D, W, m, m, nb).mean(dim=0)
+        gst = self.null_state(W, m, nb)
+        self.null_accumulate(gobs, gmean.view(S * W, m, m, nb), gbad.view(S * W), tested, gst, True, S)
+        res.update(observed=obs.view(D, W, m, m, nb), n_valid=st["n_valid"].view(D, W))
+        group = {"observed": gobs, "n_valid": gst["n_valid"]}
+        for k in stats:
+            res[k] = st[k].view(D, W, m, m, nb)
+            group[k] = gst[k]
+        if obs_bad is not None and bool(obs_bad.any()):
+            bad_dw, bad_w = obs_bad.view(D, W), obs_bad.view(D, W).any(dim=0)
+            for k in ("observed",) + stats:
+                res[k][bad_dw] = float("nan")
+                group[k][bad_w] = float("nan")
+        res["group"] = group
+        return res
+
     # ------------------------------------------------------------------ surrogate significance (surrogate.hip)
     def surrogate_shift(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, shift: torch.Tensor,
                         split: int, out: torch.Tensor | None = None):

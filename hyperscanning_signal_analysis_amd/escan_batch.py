@@ -37,7 +37,8 @@ from .eeg_io import filter_eeg
 from .engine import default_engine
 from .sliding import hop_positions, regular_grid, window_items
 
-__all__ = ["discover_dyads", "decode_events", "segment_block", "prepare_dyad", "run", "savez_fast", "xarray_reader"]
+__all__ = ["discover_dyads", "decode_events", "segment_block", "prepare_dyad", "run", "run_pseudo_dyads", "savez_fast",
+           "xarray_reader"]
 
 ROLES = (("ch", "child"), ("cg", "caregiver"))
 MEASURES = ("ffdtf", "ddtf", "gpdc")          # what run(measures=...) can compute per window; ffDTF always
@@ -407,3 +408,125 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
             for dyad, err in failed:
                 log.write(f"  - {dyad}: {err}\n")
     return {"done": done, "skipped": skipped, "failed": failed, "timing": tm}
+
+
+def _event_block(files, reader, event, low_cutoff_hz, high_cutoff_hz, channel_subset):
+    """Host part of one dyad of `run_pseudo_dyads`: the named event of the task, through `segment_block`.  Returns
+    (block, names, fs), or the reason there is none."""
+    if "ch" not in files or "cg" not in files:
+        return f"missing {'child' if 'ch' not in files else 'caregiver'} file"
+    child, caregiver = reader(files["ch"]), reader(files["cg"])
+    for name, start, dur in decode_events(child["attrs"]):
+        if name == event:
+            return segment_block(child, caregiver, start, dur, low_cutoff_hz, high_cutoff_hz, channel_subset)
+    return f"no event {event!r}"
+
+
+def run_pseudo_dyads(root, out_dir, task, event, window_s=2.0, overlap=0.5, model_order=8, freqs=None,
+                     bands=hdist.DEFAULT_BANDS, low_cutoff_hz=None, high_cutoff_hz=None, channel_subset=None,
+                     measures=("ffdtf",), n_surrogates=None, seed=None, min_common_fraction=0.9, reader=None, engine=None,
+                     verbose=True, prefetch=2, compresslevel=0):
+    """Pseudo-dyad (shuffled-partner) test of one event across every dyad under <root>/EEG: all dyads saw the same film, so
+    the child of one dyad beside the caregiver of another shares the stimulus and nothing else
+    (`Engine.pseudo_dyad_significance`; split = the child's channel count).  The event `event` of task `task` of every
+    dyad is prepared as in `run` (`segment_block`, in a pool of `prefetch` worker threads), the segments are cropped to
+    the shortest one, and windows of `window_s` seconds slide over the common length with `run`'s hop rule.  A dyad without
+    both files or without the event gets a `[SKIP]` line, and so does one whose segment is shorter than
+    `min_common_fraction` of the longest (it would shorten everybody's); sampling rates and channel names must agree; at
+    least 2 dyads must remain.  n_surrogates=None: the exhaustive cyclic partner set, no seed; an integer: seeded draws.
+    Writes `<out_dir>/pseudo_dyads_<task>_<event>.npz`:
+        <measure>_bands, _p, _p_fwe, _null_mean, _null_std   (dyads, windows, n, n, n_bands)     per dyad
+        <measure>_n_valid                                    (dyads, windows)
+        group_<measure>_bands, _p, _p_fwe, _null_mean, _null_std  (windows, n, n, n_bands)       across dyads
+        group_<measure>_n_valid                              (windows,)
+        dyads, channels, freqs, starts, partners (S, dyads), meta (JSON)
+    A window whose observed fit is singular has NaN statistics.  A dyad whose files cannot be read or prepared
+    is reported with a `[FAILED]` line and listed under "failed", as in `run`; it is not one of the skipped.
+    Returns {"path", "dyads", "skipped": [(dyad, reason)], "failed": [(dyad, error)]}."""
+    import concurrent.futures as cf
+
+    from .engine import no_auto_order
+    from .surrogates import partner_count
+    measures = tuple(measures)
+    unknown = [m_ for m_ in measures if m_ not in MEASURES]
+    if unknown or not measures or len(set(measures)) != len(measures):
+        raise ValueError(f"measures must list any of {MEASURES} once each, got {measures}")
+    no_auto_order(model_order, "escan_batch.run_pseudo_dyads")
+    if not 0.0 < float(min_common_fraction) <= 1.0:
+        raise ValueError(f"min_common_fraction must be in (0, 1], got {min_common_fraction!r}")
+    partner_count(n_surrogates, seed)                                   # the surrogate count and its seed, before any file
+    reader = reader or xarray_reader
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    say = print if verbose else (lambda *a, **k: None)
+    tree = discover_dyads(root, [task])
+    skipped, failed, blocks = [], [], {}
+    with cf.ThreadPoolExecutor(max_workers=max(1, int(prefetch))) as pool:
+        futures = {dyad: pool.submit(_event_block, tree[dyad].get(task, {}), reader, event, low_cutoff_hz,
+                                     high_cutoff_hz, channel_subset) for dyad in sorted(tree)}
+        for dyad, fut in futures.items():
+            try:
+                got = fut.result()
+            except Exception as e:                      # one bad dyad does not stop the others; reported, as in `run`
+                failed.append((dyad, f"{type(e).__name__}: {e}"))
+                say(f"[FAILED] {dyad} {task}/{event}: {failed[-1][1]}")
+                continue
+            if isinstance(got, str):
+                say(f"[SKIP] {dyad} {task}/{event}: {got}")
+                skipped.append((dyad, got))
+            else:
+                blocks[dyad] = got
+    if blocks:
+        first = next(iter(blocks))
+        _, names, fs = blocks[first]
+        for dyad, (_, nm, f_) in blocks.items():
+            if f_ != fs:
+                raise ValueError(f"sampling rates differ: {first} has {fs}, {dyad} has {f_}")
+            if nm != names:
+                raise ValueError(f"channel names differ between {first} and {dyad}")
+        longest = max(b.shape[1] for b, _, _ in blocks.values())
+        for dyad in [d_ for d_, (b, _, _) in blocks.items() if b.shape[1] < float(min_common_fraction) * longest]:
+            why = f"{blocks[dyad][0].shape[1]} samples < {min_common_fraction} of the longest segment ({longest})"
+            say(f"[SKIP] {dyad} {task}/{event}: {why}")
+            skipped.append((dyad, why))
+            del blocks[dyad]
+    if len(blocks) < 2:
+        raise ValueError(f"the pseudo-dyad test needs at least 2 dyads with {task}/{event}, found {len(blocks)}" +
+                         (f" ({len(failed)} failed: " + "; ".join(f"{d_}: {e_}" for d_, e_ in failed) + ")" if failed else ""))
+    dyads = sorted(blocks)
+    T = min(blocks[d_][0].shape[1] for d_ in dyads)
+    x = np.stack([blocks[d_][0][:, :T] for d_ in dyads])               # cropped to the shortest segment
+    split = sum(1 for nm in names if nm.endswith("_ch"))               # the child block comes first (segment_block)
+    W = int(round(window_s * fs))
+    hop = max(1, int(round(W * (1.0 - overlap))))
+    if T < W:
+        raise ValueError(f"{task}/{event}: the common length ({T} samples) is shorter than one window ({W})")
+    pos = hop_positions(T, W, hop)
+    f = np.asarray(freqs if freqs is not None else np.arange(0.5, min(fs / 2.0, 128.0) + 1e-9, 0.5))
+    lo, hi = hdist.band_bins(f, bands)
+    eng = engine or default_engine()
+    import torch
+    xd = eng.to_device(x)
+    starts = torch.as_tensor(np.asarray(pos, dtype=np.int64)).to(eng.device)
+    result, partners = {}, None
+    for meas in measures:
+        sig = eng.pseudo_dyad_significance(xd, starts, W, int(model_order), f, fs, (lo, hi), measure=meas, split=split,
+                                           n_surrogates=n_surrogates, seed=seed, check="nan")
+        for level, d_ in (("", sig), ("group_", sig["group"])):
+            result[f"{level}{meas}_bands"] = d_["observed"].cpu().numpy()
+            for k_ in ("p", "p_fwe", "null_mean", "null_std", "n_valid"):
+                result[f"{level}{meas}_{k_}"] = d_[k_].cpu().numpy()
+        partners = sig["partners"].cpu().numpy()
+        say(f"[OK] {task}/{event} {meas}: {len(dyads)} dyads x {len(pos)} windows, {partners.shape[0]} partner sets")
+    meta = {"task": task, "event": event, "dyads": dyads, "skipped": [list(s_) for s_ in skipped],
+            "failed": [list(s_) for s_ in failed], "model_order": int(model_order),
+            "window_s": window_s, "overlap": overlap, "window": W, "fs": fs, "samples": int(T), "split": int(split),
+            "measures": list(measures), "n_surrogates": None if n_surrogates is None else int(n_surrogates), "seed": seed,
+            "min_common_fraction": float(min_common_fraction), "created": time.strftime("%Y-%m-%dT%H:%M:%S")}
+    target = out_dir / f"pseudo_dyads_{task}_{event}.npz"
+    tmp = target.with_suffix(".tmp.npz")
+    savez_fast(tmp, compresslevel, dyads=np.asarray(dyads), channels=np.asarray(names), freqs=f, starts=np.asarray(pos),
+               partners=partners, bands=np.asarray(bands, dtype=np.float64), meta=np.asarray(json.dumps(meta)), **result)
+    tmp.replace(target)
+    say(f"[SAVED] {target}")
+    return {"path": target, "dyads": dyads, "skipped": skipped, "failed": failed}

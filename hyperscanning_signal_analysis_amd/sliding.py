@@ -9,6 +9,7 @@ optimal_model_order=p)` (/root/reference/src/mtmvar.py:237-284) on every window 
 With `p=None` every window gets the order `mvar_criterion(window, max_model_order, crit_type)` (mtmvar.py:551-601)
 picks for it -- the reference's own default, `optimal_model_order=None` -- selected on the device in the same call.
 `sliding_significance` adds a surrogate test (shift or phase null) to the band values of any of the three.
+`sliding_pseudo_dyad_significance` tests them against shuffled partners: participant A of one dyad with participant B of another.
 `sliding_fad` is `fad_decomposition` (mtmvar.py:607-757) of every channel of every window.
 `sliding_ensemble` / `sliding_ensemble_epochs` are the event-locked form: the reference's functions take `signals` of shape
 (channels, samples, trials) and fit ONE model to the trial-averaged covariances (`count_corr`, mtmvar.py:54-85); here a
@@ -24,7 +25,7 @@ from .engine import Engine, default_engine
 __all__ = ["window_positions", "hop_positions", "create_windows", "sliding_ffdtf", "sliding_ffdtf_device", "window_items",
            "regular_grid", "sliding_ddtf", "sliding_ddtf_device", "sliding_gpdc", "sliding_gpdc_device", "sliding_fad",
            "sliding_significance", "ensemble_items", "sliding_ensemble", "sliding_ensemble_epochs",
-           "sliding_ensemble_significance", "sliding_ensemble_epochs_significance"]
+           "sliding_ensemble_significance", "sliding_ensemble_epochs_significance", "sliding_pseudo_dyad_significance"]
 
 
 def window_positions(T: int, n_windows: int = 3, window_size=None):
@@ -274,6 +275,38 @@ def sliding_significance(x, window_size, n_windows, p, freqs, fs, bands, *, meas
             continue
         a = v.cpu().numpy().reshape((n_rec, nw) + tuple(v.shape[1:]))
         out[k] = a[0] if single else a
+    return out
+
+
+def sliding_pseudo_dyad_significance(x, window_size, n_windows, p, freqs, fs, bands, *, measure, split=None, n_surrogates=None,
+                                     seed=None, hop=None, check=True, chunk=None, engine: Engine | None = None):
+    """NumPy (or tensor) in / NumPy out: the pseudo-dyad test of `Engine.pseudo_dyad_significance` for the band values
+    `sliding_<measure>(x, window_size, n_windows, p, freqs, fs, hop=hop, bands=bands)`.  x: (D, m, T), one recording per
+    dyad, all of them time-locked to the same stimulus; channels < split are participant A (default split = m // 2).
+    Windows and bands as for `sliding_significance`.  n_surrogates=None: every other dyad's partner once on each side (the
+    D - 1 cyclic offsets, no seed); an integer: that many seeded derangements.  Returns a dict of NumPy arrays: observed, p,
+    p_fwe, null_mean, null_std (D, n_windows, m, m, n_bands), n_valid (D, n_windows), tested (m, m), partners (S, D) and
+    group = {observed, p, p_fwe, null_mean, null_std (n_windows, m, m, n_bands), n_valid (n_windows,)}.  The arguments are
+    checked before the GPU is touched (`surrogates.pseudo_dyad_args`)."""
+    from . import surrogates as sg
+    from .engine import no_auto_order
+    no_auto_order(p, "sliding_pseudo_dyad_significance")
+    shape = tuple(np.shape(x))
+    if len(shape) != 3:
+        raise ValueError("x must have shape (dyads, channels, samples)")
+    D, m, T = shape
+    sg.pseudo_dyad_args(measure, D, m, n_surrogates, seed, split, check)
+    if bands is None or len(bands) != 2 or len(np.atleast_1d(bands[0])) < 1 or \
+            len(np.atleast_1d(bands[0])) != len(np.atleast_1d(bands[1])):
+        raise ValueError("sliding_pseudo_dyad_significance needs bands = (bin_lo, bin_hi) with at least one band")
+    positions, w = _positions(T, window_size, n_windows, hop)
+    eng = engine or default_engine()
+    xd = _recordings_to_device(eng, x, False)
+    item_start = torch.as_tensor(np.asarray(positions, dtype=np.int64)).to(eng.device)
+    res = eng.pseudo_dyad_significance(xd, item_start, w, p, freqs, fs, bands, measure=measure, split=split,
+                                       n_surrogates=n_surrogates, seed=seed, check=check, chunk=chunk)
+    out = {k: v.cpu().numpy() for k, v in res.items() if k != "group"}
+    out["group"] = {k: v.cpu().numpy() for k, v in res["group"].items()}
     return out
 
 

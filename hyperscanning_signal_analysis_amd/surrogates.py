@@ -1,5 +1,6 @@
-"""Host side of the surrogate significance tests (`Engine.sliding_significance`, `Engine.ensemble_significance`): argument
-checks, the random draws and the tested family.  Pure NumPy, so that every surrogate can be rebuilt on the host from the seed.
+"""Host side of the surrogate significance tests (`Engine.sliding_significance`, `Engine.ensemble_significance`,
+`Engine.pseudo_dyad_significance`): argument checks, the random draws and the tested family.  Pure NumPy, so that every
+surrogate can be rebuilt on the host from the seed.
 
 All randomness comes from `rng = numpy.random.default_rng(seed)`, in this order:
     null="shift":  d = rng.integers(min_shift, T - min_shift, size=(S, n_rec), endpoint=True)        (once)
@@ -7,13 +8,16 @@ All randomness comes from `rng = numpy.random.default_rng(seed)`, in this order:
                    (drawn in consecutive surrogate blocks: one double per draw, so the stream is the same)
     null="trial":  for s = 0..S-1, then g = 0..G-1: pi[s][g] = rng.permutation(counts[g]), drawn again while it is the
                    identity (`trial_permutations`; event-locked ensembles only)
+    pseudo dyads:  for s = 0..S-1: pi[s] = rng.permutation(D), drawn again while any pi[s][d] == d (`partner_derangements`
+                   with an integer S; `Engine.pseudo_dyad_significance` only).  S = None draws nothing: the exhaustive set is
+                   the D - 1 cyclic offsets pi[k-1][d] = (d + k) mod D, k = 1..D-1, and no seed is used
 """
 from __future__ import annotations
 
 import numpy as np
 
 __all__ = ["NULLS", "ENSEMBLE_NULLS", "MEASURES", "significance_args", "shift_offsets", "phase_draws",
-           "trial_permutations", "tested_mask", "check_significance_dict"]
+           "trial_permutations", "partner_count", "partner_derangements", "pseudo_dyad_args", "tested_mask", "check_significance_dict"]
 
 NULLS = ("shift", "phase")          # of continuous recordings (`sliding_significance`)
 ENSEMBLE_NULLS = ("trial",)         # of event-locked ensembles (`ensemble_significance`)
@@ -92,6 +96,72 @@ def trial_permutations(rng, S: int, counts):
             row.append(np.asarray(pi, dtype=np.int64))
         perms.append(row)
     return perms
+
+
+def _n_dyads(D):
+    D = _int(D, "the number of dyads")
+    if D < 2:
+        raise ValueError(f"the pseudo-dyad test needs at least 2 dyads, got {D}")
+    return D
+
+
+def partner_count(n_surrogates, seed=None, *, seeded=True):
+    """The number of partner sets asked for: None for the exhaustive set, else the integer S >= 1.  ValueError for S < 1 and,
+    with `seeded`, for an integer S without a seed."""
+    if n_surrogates is None:
+        return None
+    S = _int(n_surrogates, "n_surrogates")
+    if S < 1:
+        raise ValueError(f"n_surrogates must be >= 1, got {S}")
+    if seeded and seed is None:
+        raise ValueError("seeded partner draws (an integer n_surrogates) need a seed; n_surrogates=None takes the "
+                         "exhaustive set of cyclic offsets")
+    return S
+
+
+def partner_derangements(rng, S, D: int):
+    """(S, D) int64 partners of the pseudo-dyad test: in surrogate s participant A of dyad d is analysed with participant
+    B of dyad pi[s][d] != d.  S = None: the exhaustive set of the D - 1 cyclic offsets pi[k-1][d] = (d + k) mod D -- every
+    ordered pair (d, j != d) exactly once, every other partner once on each side; `rng` is not used.  An integer S >= 1:
+    pi[s] = rng.permutation(D) for s = 0..S-1 in that order, drawn again while it has a fixed point (a dyad paired with
+    itself is the observed arrangement).  ValueError for D < 2, which has no other partner, and for S < 1."""
+    D = _n_dyads(D)
+    d = np.arange(D, dtype=np.int64)
+    S = partner_count(S, seeded=False)
+    if S is None:
+        return np.stack([(d + k) % D for k in range(1, D)])
+    if rng is None:
+        raise ValueError("seeded partner draws need a random generator")
+    out = np.empty((S, D), dtype=np.int64)
+    for s in range(S):
+        pi = rng.permutation(D)
+        while np.any(pi == d):
+            pi = rng.permutation(D)
+        out[s] = pi
+    return out
+
+
+def pseudo_dyad_args(measure, D, m, n_surrogates, seed, split=None, check=True):
+    """Check the arguments of a pseudo-dyad run BEFORE anything is drawn or launched; returns (S or None, split) with the
+    default split = m // 2 for even m filled in.  ValueError for an unknown measure, fewer than 2 dyads, an odd channel
+    count without a split, a split outside 1..m-1, an integer n_surrogates < 1 or without a seed, a `check` other than
+    True / "nan"."""
+    if measure not in MEASURES:
+        raise ValueError(f"measure must be one of {MEASURES}, got {measure!r}")
+    _n_dyads(int(D))
+    S = partner_count(n_surrogates, seed)
+    m = int(m)
+    if split is None:
+        if m % 2:
+            raise ValueError(f"an odd channel count ({m}) needs an explicit split")
+        split = m // 2
+    else:
+        split = _int(split, "split")
+    if not 1 <= split <= m - 1:
+        raise ValueError(f"split must be in 1..{m - 1}, got {split}")
+    if check is not True and check != "nan":
+        raise ValueError(f"check must be True or 'nan', got {check!r}")
+    return S, split
 
 
 def tested_mask(m: int, null: str, split: int):

@@ -443,6 +443,46 @@ int hmv_sliding_ensemble_split_f64(int measure, const double* x, int64_t rec_str
                                    const int64_t* trial_rec_b, const int64_t* trial_start_b, int split,
                                    const double* R_base, const int64_t* item_base, void* stream, void* aux_stream);
 
+/* Pairs of recordings: the pseudo-dyad (shuffled-partner) surrogates of hyperscanning data (csrc/lagcov_ensemble.hip,
+ * lagcov_pairs_kernel).  Item `it` is the window of n samples starting at item_start[it] whose channels < split are read
+ * from recording rec_a[it] and whose channels >= split are read from recording rec_b[it] (x: [n_rec][m][ld], T samples per
+ * recording) -- participant A of one dyad beside participant B of another at the same time points; nothing is written out:
+ *     x~(it) = [x[rec_a[it]][:split] ; x[rec_b[it]][split:]][:, item_start[it] : + n],   R_l(it) = (1/n) X~[:, :n-l] X~[:, l:]^T
+ * (count_corr's estimator, src/mtmvar.py:35-87: biased 1/n, not demeaned).  One form, lagcov_kernel's mapping, chunks and
+ * order of products: every computed element has the bits hmv_lagcov_f64 gives for the same window written out as one
+ * recording, and rec_b = rec_a without R_base gives hmv_lagcov_f64's whole result.
+ *   R_base [n_base][p+1][MP][MP] with base_a, base_b int64 [n_items] (device; all three or none): an element (row, col) with
+ *   both indices < split belongs to participant A alone and is copied from R_base[base_a[it]][lag]; one with both indices
+ *   >= split (padded rows and columns count as >= split, their lag-0 identity included) is copied from
+ *   R_base[base_b[it]][lag].  Only the cross elements are computed: an accumulator (4 rows x 16 columns of one wave) with no
+ *   cross element among its real elements runs no MFMA, one that straddles split is computed whole and its
+ *   within-participant elements then overwritten, so the result does not depend on the tiling.  Without R_base every
+ *   element is computed; the cross elements are the same bits either way.
+ *   rec_a, rec_b, item_start, base_a and base_b are int64 DEVICE arrays whose contents the caller has checked (0 <= rec <
+ *   n_rec, 0 <= start, start + n <= T, 0 <= base < n_base; hyperscanning_signal_analysis_amd.engine.validate_items on
+ *   both recording tables): the kernel addresses with them.
+ * hmv_lagcov_pairs_f64: K1 alone, R [n_items][p+1][MP][MP].  flags is accepted and not looked at: there is one form.
+ * hmv_sliding_pairs_f64: the fused path K1 -> K2 -> K3 (-> K5) / dDTF / GPDC with this K1; everything after K1 is the
+ *   existing path.  The arguments are those of hmv_sliding_ensemble_split_f64 with (rec_a, rec_b, item_start) in place of
+ *   the trial and group tables.  workspace: hmv_pairs_workspace_bytes(measure, chunk, m, n, p, F, n_bands), n_bands
+ *   = -1 for the full ffDTF together with S_out (the same number as hmv_sliding_ensemble_workspace_bytes without a grid).
+ *   base_a and base_b are indexed by the item of the call, whatever the chunk.
+ * Refused before any launch: channel count (-1), order (-2), n <= p (-3), null pointers, R_base without both base tables or
+ *   the reverse (-4), split outside 1..m-1 (-5), workspace too small (-7). */
+int hmv_lagcov_pairs_f64(const double* x, int64_t rec_stride, int64_t ld, int64_t T,
+                         const int64_t* rec_a, const int64_t* rec_b, const int64_t* item_start, int64_t n_items,
+                         int m, int n, int p, int split, double* R,
+                         const double* R_base, const int64_t* base_a, const int64_t* base_b, int64_t flags, void* stream);
+int64_t hmv_pairs_workspace_bytes(int measure, int64_t chunk, int m, int n, int p, int F, int n_bands);
+int hmv_sliding_pairs_f64(int measure, const double* x, int64_t rec_stride, int64_t ld, int64_t T,
+                          const int64_t* rec_a, const int64_t* rec_b, const int64_t* item_start, int64_t n_items,
+                          int m, int n, int p, const double* freqs, int F, double fs,
+                          double* out, const int32_t* bin_lo, const int32_t* bin_hi, int n_bands, double* S_out,
+                          double* ar_out, double* V_out, int32_t* info_yw, int32_t* info_tf,
+                          void* workspace, int64_t workspace_bytes, int64_t chunk, double pivot_tau, int64_t flags,
+                          int split, const double* R_base, const int64_t* base_a, const int64_t* base_b,
+                          void* stream, void* aux_stream);
+
 /* FAD (frequency-amplitude-damping) decomposition of univariate AR models, batched over series.  Replaces
  * fad_decomposition (src/mtmvar.py:607-757): order selection as mvar_criterion at m = 1 (:551-601), the fit of ar_coeff
  * (:90-123, count_corr :35-87: biased 1/n autocovariance, no demeaning) by Levinson-Durbin, and the partial-fraction
