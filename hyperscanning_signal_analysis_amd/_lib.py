@@ -119,6 +119,14 @@ SIGNATURES = {
                                         c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "hmv_surrogate_phase_c128": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "hmv_null_accumulate_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int] + [c_void_p] * 12),
+    "hmv_residuals_workspace_bytes": (c_int64, [c_int64, c_int, c_int]),
+    "hmv_residuals_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p,
+                                  c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "hmv_whiteness_f64": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_double] + [c_void_p] * 6),
+    "hmv_model_validation_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int, c_int]),
+    "hmv_model_validation_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
+                                         c_void_p, c_int, c_double] + [c_void_p] * 7 + [c_int64, c_void_p, c_int64, c_int64,
+                                                                                       c_void_p]),
 }
 
 # option bits of the fused entry points (include/hypermvar.h)

@@ -1282,4 +1282,130 @@ int hmv_null_accumulate_f64(const double* observed, const double* surr, const ui
   return hmv::launch_null_accumulate(a, S(stream));
 }
 
+// ---- model validation (validate.hip) ---------------------------------------------------------------------------
+namespace {
+// workspace of hmv_model_validation_f64 for a chunk: packed coefficients | E | C | item_rec, item_start of the residuals
+struct ValidationLayout {
+  size_t arp, E, C, idx, total;
+  int64_t ldE;
+};
+ValidationLayout validation_layout(int64_t chunk, int mp, int m, int n, int p, int h) {
+  ValidationLayout L{};
+  L.ldE = ((int64_t)(n - p) + 3) & ~int64_t(3);
+  size_t off = 0;
+  L.arp = off; off += align256(sizeof(double) * (size_t)hmv::resid_pack_doubles(chunk, mp, p));
+  L.E = off;   off += align256(sizeof(double) * (size_t)chunk * m * L.ldE);
+  L.C = off;   off += align256(sizeof(double) * (size_t)chunk * (h + 1) * mp * mp);
+  L.idx = off; off += align256(sizeof(int64_t) * 2 * (size_t)chunk);
+  L.total = off;
+  return L;
+}
+}  // namespace
+
+int64_t hmv_residuals_workspace_bytes(int64_t chunk_items, int m, int p) {
+  const int mp = pad_of(m);
+  if (mp < 0 || p < 1 || p > HMV_MAX_ORDER || chunk_items < 1) return -1;
+  return (int64_t)sizeof(double) * hmv::resid_pack_doubles(chunk_items, mp, p);
+}
+
+int hmv_residuals_f64(const double* x, int64_t rec_stride, int64_t ld, const int64_t* item_rec, const int64_t* item_start,
+                      int64_t n_items, int m, int n, int p, const double* ar, double* E, int64_t ldE, void* workspace,
+                      int64_t workspace_bytes, void* stream) {
+  const int mp = pad_of(m);
+  if (mp < 0) return fail(-1, "hmv_residuals_f64: channel count must be in 1..64");
+  if (p < 1 || p > HMV_MAX_ORDER) return fail(-2, "hmv_residuals_f64: model order must be in 1..32");
+  if (n <= p) return fail(-3, "hmv_residuals_f64: window shorter than the model order");
+  if (!x || !item_rec || !item_start || !ar || !E || !workspace || n_items < 0)
+    return fail(-4, "hmv_residuals_f64: null pointer");
+  const int64_t per_item = hmv_residuals_workspace_bytes(1, m, p);
+  if (workspace_bytes < per_item) return fail(-7, "hmv_residuals_f64: workspace too small");
+  if (ldE < n - p) return fail(-8, "hmv_residuals_f64: ldE is smaller than n - p");
+  const int64_t chunk = workspace_bytes / per_item;
+  for (int64_t i0 = 0; i0 < n_items; i0 += chunk) {
+    hmv::ResidArgs a{};
+    a.x = x; a.rec_stride = rec_stride; a.ld = ld;
+    a.item_rec = reinterpret_cast<const long long*>(item_rec) + i0;
+    a.item_start = reinterpret_cast<const long long*>(item_start) + i0;
+    a.n_items = n_items - i0 < chunk ? n_items - i0 : chunk;
+    a.m = m; a.n = n; a.p = p;
+    a.ar = ar + (size_t)i0 * mp * mp * p;
+    a.arp = static_cast<double*>(workspace);
+    a.E = E + (size_t)i0 * m * ldE; a.ldE = ldE;
+    const int rc = hmv::launch_residuals(a, mp, S(stream));
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+int hmv_whiteness_f64(const double* C, int64_t n_items, int m, int N, int h, double acf_thr, double* s, double* q,
+                      double* q_ch, int32_t* acf_count, int32_t* info, void* stream) {
+  const int mp = pad_of(m);
+  if (mp < 0) return fail(-1, "hmv_whiteness_f64: channel count must be in 1..64");
+  if (h < 1 || h > HMV_MAX_ORDER) return fail(-6, "hmv_whiteness_f64: number of tested lags must be in 1..32");
+  if (N <= h) return fail(-3, "hmv_whiteness_f64: no more residuals than tested lags");
+  if (!C || !s || !q || !q_ch || !acf_count || !info || n_items < 0) return fail(-4, "hmv_whiteness_f64: null pointer");
+  hmv::WhiteArgs a{};
+  a.C = C; a.n_items = n_items; a.m = m; a.N = N; a.h = h; a.acf_thr = acf_thr;
+  a.s = s; a.q = q; a.q_ch = q_ch; a.acf_count = acf_count; a.info = info;
+  return hmv::launch_whiteness(a, mp, S(stream));
+}
+
+int64_t hmv_model_validation_workspace_bytes(int64_t chunk, int m, int n, int p, int h) {
+  const int mp = pad_of(m);
+  if (mp < 0 || p < 1 || p > HMV_MAX_ORDER || h < 1 || h > HMV_MAX_ORDER || (int64_t)n - p <= h || chunk < 1) return -1;
+  return (int64_t)validation_layout(chunk, mp, m, n, p, h).total;
+}
+
+int hmv_model_validation_f64(const double* x, int64_t rec_stride, int64_t ld, const int64_t* item_rec,
+                             const int64_t* item_start, int64_t n_items, int m, int n, int p, const double* ar, int h,
+                             double acf_thr, double* s, double* q, double* q_ch, int32_t* acf_count, int32_t* info,
+                             double* resid_cov, double* E_out, int64_t ldE, void* workspace, int64_t workspace_bytes,
+                             int64_t chunk, void* stream) {
+  const int mp = pad_of(m);
+  if (mp < 0) return fail(-1, "hmv_model_validation_f64: channel count must be in 1..64");
+  if (p < 1 || p > HMV_MAX_ORDER) return fail(-2, "hmv_model_validation_f64: model order must be in 1..32");
+  if (h < 1 || h > HMV_MAX_ORDER) return fail(-6, "hmv_model_validation_f64: number of tested lags must be in 1..32");
+  if ((int64_t)n - p <= h) return fail(-3, "hmv_model_validation_f64: no more residuals than tested lags");
+  if (!x || !item_rec || !item_start || !ar || !s || !q || !q_ch || !acf_count || !info || !workspace || n_items < 0)
+    return fail(-4, "hmv_model_validation_f64: null pointer");
+  if (chunk < 1 || workspace_bytes < hmv_model_validation_workspace_bytes(chunk, m, n, p, h))
+    return fail(-7, "hmv_model_validation_f64: workspace too small");
+  if (E_out && ldE < n - p) return fail(-8, "hmv_model_validation_f64: ldE is smaller than n - p");
+  const ValidationLayout L = validation_layout(chunk, mp, m, n, p, h);
+  char* ws = static_cast<char*>(workspace);
+  const int N = n - p;
+  long long* rec_e = reinterpret_cast<long long*>(ws + L.idx);
+  long long* start_e = rec_e + chunk;
+  for (int64_t i0 = 0; i0 < n_items; i0 += chunk) {
+    const int64_t cnt = n_items - i0 < chunk ? n_items - i0 : chunk;
+    hmv::ResidArgs r{};
+    r.x = x; r.rec_stride = rec_stride; r.ld = ld;
+    r.item_rec = reinterpret_cast<const long long*>(item_rec) + i0;
+    r.item_start = reinterpret_cast<const long long*>(item_start) + i0;
+    r.n_items = cnt; r.m = m; r.n = n; r.p = p;
+    r.ar = ar + (size_t)i0 * mp * mp * p;
+    r.arp = reinterpret_cast<double*>(ws + L.arp);
+    r.E = E_out ? E_out + (size_t)i0 * m * ldE : reinterpret_cast<double*>(ws + L.E);
+    r.ldE = E_out ? ldE : L.ldE;
+    int rc = hmv::launch_residuals(r, mp, S(stream));
+    if (rc) return rc;
+    // K1 over the residuals: `cnt` recordings of N samples, h lags
+    rc = hmv::launch_iota_items(rec_e, start_e, cnt, S(stream));
+    if (rc) return rc;
+    hmv::LagcovArgs c{};
+    c.x = r.E; c.rec_stride = (long long)m * r.ldE; c.ld = r.ldE; c.item_rec = rec_e; c.item_start = start_e;
+    c.n_items = cnt; c.m = m; c.n = N; c.p = h; c.R = reinterpret_cast<double*>(ws + L.C);
+    rc = hmv::launch_lagcov(c, mp, S(stream));
+    if (rc) return rc;
+    hmv::WhiteArgs w{};
+    w.C = c.R; w.n_items = cnt; w.m = m; w.N = N; w.h = h; w.acf_thr = acf_thr;
+    w.s = s + (size_t)i0 * h; w.q = q + (size_t)i0 * 3; w.q_ch = q_ch + (size_t)i0 * m;
+    w.acf_count = acf_count + i0; w.info = info + i0;
+    w.resid_cov = resid_cov ? resid_cov + (size_t)i0 * mp * mp : nullptr;
+    rc = hmv::launch_whiteness(w, mp, S(stream));
+    if (rc) return rc;
+  }
+  return 0;
+}
+
 }  // extern "C"

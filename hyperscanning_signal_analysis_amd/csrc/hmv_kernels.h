@@ -283,4 +283,35 @@ struct NullAccArgs {
 };
 int launch_null_accumulate(const NullAccArgs& a, hipStream_t st);
 
+// ---- model validation: residuals and whiteness statistics (validate.hip) ----------------------------------------
+struct ResidArgs {
+  const double* x;          // [n_rec][m][ld]; windows addressed as LagcovArgs
+  long long rec_stride, ld;
+  const long long* item_rec;
+  const long long* item_start;
+  long long n_items;
+  int m, n, p;
+  const double* ar;         // [n_items][MP][MP][p]  (K2's layout; read by the packing kernel only)
+  double* arp;              // scratch, resid_pack_doubles(): the coefficients in the A-operand order of resid_kernel
+  double* E;                // [n_items][m][ldE], columns 0 .. n - p - 1 written
+  long long ldE;
+};
+long long resid_pack_doubles(long long n_items, int m_pad, int p);
+int launch_residuals(const ResidArgs& a, int m_pad, hipStream_t st);
+// item_rec[i] = i, item_start[i] = 0: the residuals of a chunk as n recordings for launch_lagcov
+int launch_iota_items(long long* item_rec, long long* item_start, long long n, hipStream_t st);
+struct WhiteArgs {
+  const double* C;          // [n_items][h+1][MP][MP]
+  long long n_items;
+  int m, N, h;
+  double acf_thr;
+  double* s;                // [n_items][h]
+  double* q;                // [n_items][3]
+  double* q_ch;             // [n_items][m]
+  int* acf_count;           // [n_items]
+  int* info;                // [n_items]
+  double* resid_cov;        // optional [n_items][MP][MP]: a copy of C_0
+};
+int launch_whiteness(const WhiteArgs& a, int m_pad, hipStream_t st);
+
 }  // namespace hmv

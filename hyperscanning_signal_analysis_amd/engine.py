@@ -1619,6 +1619,106 @@ class Engine:
         _lib.check(rc, "hmv_fad_decompose_f64")
         return self._fad_finish(o)
 
+    # ------------------------------------------------------------------ model validation (csrc/validate.hip)
+    def _validation_inputs(self, x, item_rec, item_start, n, ar, validate):
+        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
+        x = x if x.stride(2) == 1 else x.contiguous()
+        m = x.shape[1]
+        mp = self.pad(m)
+        assert ar.dim() == 4 and ar.dtype == torch.float64 and ar.is_cuda and ar.is_contiguous()
+        p = int(ar.shape[3])
+        if validate:
+            self.check_items(x, item_rec, item_start, n, p)
+        n_items = int(item_rec.numel())
+        if tuple(ar.shape) != (n_items, mp, mp, p) or not 1 <= p <= MAX_ORDER:
+            raise ValueError(f"ar must have shape (items, MP, MP, p) = ({n_items}, {mp}, {mp}, 1..{MAX_ORDER}), "
+                             f"got {tuple(ar.shape)}")
+        return x, m, mp, p, n_items
+
+    def residuals(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, ar: torch.Tensor,
+                  validate: bool = True):
+        """Residuals of every window's fit (`hmv_residuals_f64`): x (n_rec, m, T), ar (items, MP, MP, p) from `yw_solve`
+        (or `yw_solve_auto`: zero-padded to pmax lags, p = pmax) -> E (items, m, n - p), E[:, :, c] the residual at
+        sample p + c of the window:  E = X[:, p:] - sum_k ar[:, :, k-1] X[:, p-k : n-k].  The products run in a fixed
+        order, so a window's residuals do not depend on the batch it is computed in."""
+        x, m, mp, p, n_items = self._validation_inputs(x, item_rec, item_start, n, ar, validate)
+        N = int(n) - p
+        E = self.empty(n_items, m, N)
+        if n_items == 0:
+            return E
+        per_item = int(self.lib.hmv_residuals_workspace_bytes(1, m, p))
+        nbytes = per_item * self._chunk(n_items, per_item, self.max_workspace_bytes)
+        ws = self._workspace(nbytes)
+        with torch.cuda.device(self.device):
+            rc = self.lib.hmv_residuals_f64(x.data_ptr(), x.stride(0), x.stride(1), item_rec.data_ptr(),
+                                            item_start.data_ptr(), n_items, m, int(n), p, ar.data_ptr(), E.data_ptr(), N,
+                                            ws.data_ptr(), nbytes, self.stream())
+        _lib.check(rc, "hmv_residuals_f64")
+        return E
+
+    def whiteness(self, C: torch.Tensor, m: int, N: int, acf_thr: float):
+        """The whiteness statistics (`hmv_whiteness_f64`) of lag covariances C (items, h+1, MP, MP) of residuals -- `lagcov`
+        over E as `items` recordings of N samples.  Returns the dict of `model_validation` without resid_cov."""
+        assert C.dim() == 4 and C.dtype == torch.float64 and C.is_cuda and C.is_contiguous()
+        n_items, h = int(C.shape[0]), int(C.shape[1]) - 1
+        o = dict(s=self.empty(n_items, h), q=self.empty(n_items, 3), q_channel=self.empty(n_items, m),
+                 acf_count=self.empty(n_items, dtype=torch.int32), info=self.empty(n_items, dtype=torch.int32))
+        if n_items == 0:
+            return o
+        with torch.cuda.device(self.device):
+            rc = self.lib.hmv_whiteness_f64(C.data_ptr(), n_items, int(m), int(N), h, float(acf_thr), o["s"].data_ptr(),
+                                            o["q"].data_ptr(), o["q_channel"].data_ptr(), o["acf_count"].data_ptr(),
+                                            o["info"].data_ptr(), self.stream())
+        _lib.check(rc, "hmv_whiteness_f64")
+        return o
+
+    def model_validation(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, ar: torch.Tensor,
+                         max_lag: int, *, acf_z: float = 1.96, return_residuals: bool = False, chunk: int | None = None,
+                         validate: bool = True):
+        """Residual whiteness of every window's fit in one call (`hmv_model_validation_f64`): the residuals E of `residuals`,
+        their lag covariances C_l = E[:, :N-l] E[:, l:]^T / N (K1 itself, l = 0..max_lag, N = n - p) and from them, with
+        C_0 = L L^T,
+            s (items, h)            s_l = ||L^-1 C_l L^-T||_F^2, l = 1..h = max_lag
+            q (items, 3)            Box-Pierce N sum s_l, Li-McLeod + m^2 h (h+1) / (2N), Hosking N^2 sum s_l / (N - l)
+            q_channel (items, m)    per-channel Ljung-Box N (N+2) sum_l r_l[i,i]^2 / (N - l)
+            acf_count (items,)      residual correlations r_l[i,j] = C_l[i,j] / sqrt(C_0[i,i] C_0[j,j]) beyond acf_z / sqrt(N)
+            info (items,)           0, or c + 1 where C_0 is not positive definite at column c (statistics NaN, count -1)
+            resid_cov (items, m, m) C_0
+        and with return_residuals `residuals` (items, m, N).  All device tensors; the chi-square tails are the caller's
+        (`sliding.sliding_model_validation`).  The windows are processed `chunk` at a time (default: what
+        `max_workspace_bytes` allows)."""
+        x, m, mp, p, n_items = self._validation_inputs(x, item_rec, item_start, n, ar, validate)
+        h, N = int(max_lag), int(n) - p
+        if isinstance(max_lag, bool) or h != max_lag or not 1 <= h <= MAX_ORDER:
+            raise ValueError(f"max_lag must be an integer in 1..{MAX_ORDER}, got {max_lag!r}")
+        if N <= h:
+            raise ValueError(f"n - p ({N}) residuals must exceed max_lag ({h})")
+        o = dict(s=self.empty(n_items, h), q=self.empty(n_items, 3), q_channel=self.empty(n_items, m),
+                 acf_count=self.empty(n_items, dtype=torch.int32), info=self.empty(n_items, dtype=torch.int32))
+        cov = self.empty(n_items, mp, mp)
+        E = self.empty(n_items, m, N) if return_residuals else None
+        o["resid_cov"] = cov[:, :m, :m]
+        if return_residuals:
+            o["residuals"] = E
+        if n_items == 0:
+            return o
+        if chunk is None:
+            per_item = int(self.lib.hmv_model_validation_workspace_bytes(1, m, int(n), p, h))
+            chunk = self._chunk(n_items, per_item, self.max_workspace_bytes)
+        chunk = int(chunk)
+        nbytes = int(self.lib.hmv_model_validation_workspace_bytes(chunk, m, int(n), p, h))
+        if nbytes < 0:
+            raise ValueError(f"model_validation: bad sizes (m={m}, n={n}, p={p}, max_lag={h}, chunk={chunk})")
+        ws = self._workspace(nbytes)
+        with torch.cuda.device(self.device):
+            rc = self.lib.hmv_model_validation_f64(
+                x.data_ptr(), x.stride(0), x.stride(1), item_rec.data_ptr(), item_start.data_ptr(), n_items, m, int(n), p,
+                ar.data_ptr(), h, float(acf_z) / float(np.sqrt(N)), o["s"].data_ptr(), o["q"].data_ptr(),
+                o["q_channel"].data_ptr(), o["acf_count"].data_ptr(), o["info"].data_ptr(), cov.data_ptr(), _ptr(E), N,
+                ws.data_ptr(), nbytes, chunk, self.stream())
+        _lib.check(rc, "hmv_model_validation_f64")
+        return o
+
 
 _default = None
 

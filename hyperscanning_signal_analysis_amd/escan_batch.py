@@ -35,7 +35,7 @@ import numpy as np
 from . import distributed as hdist
 from .eeg_io import filter_eeg
 from .engine import default_engine
-from .sliding import hop_positions, regular_grid, window_items
+from .sliding import hop_positions, regular_grid, validation_p_values, window_items
 
 __all__ = ["discover_dyads", "decode_events", "segment_block", "prepare_dyad", "run", "run_pseudo_dyads", "savez_fast",
            "xarray_reader"]
@@ -177,7 +177,7 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
         low_cutoff_hz=None, high_cutoff_hz=None, channel_subset=None, with_psd=False, psd_fmin=1.0, psd_fmax=30.0,
         psd_bandwidth=2.0, save_full=False, skip_existing=True, reader=None, engine=None, world=1, rank=0,
         verbose=True, prefetch=2, timing=None, save_workers=4, compresslevel=0, measures=("ffdtf",), significance=None,
-        max_model_order=20, crit_type="AIC"):
+        max_model_order=20, crit_type="AIC", validation_lags=None):
     """Process every dyad under <root>/EEG.  Per dyad one `<out_dir>/<dyad>_ffdtf.npz` with, per segment `<task>/<event>`:
         <seg>/ffdtf_bands   (windows, n, n, n_bands)   band-integrated ffDTF of every window
         <seg>/ffdtf         (windows, n, n, F)         only with save_full=True (8.4 MB per window at 64 channels)
@@ -197,6 +197,13 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                                                        window); meta then says "model_order": "auto" and carries
                                                        `max_model_order` and `crit_type`.  Every measure of a window uses
                                                        that window's order.  Not offered together with `significance`.
+        <seg>/whiteness_q, <seg>/whiteness_p   (windows, 3)   only with validation_lags=h (an integer): Box-Pierce, Li-McLeod and
+                                                       Hosking portmanteau statistics of every window's residuals over h
+                                                       lags and their chi-square tails (`Engine.model_validation`; the
+                                                       segment's own windows and order -- `model_order`, or the per-window
+                                                       automatic one), NaN for a singular window
+        <seg>/acf_fraction  (windows,)                 with validation_lags: share of the residual correlations beyond
+                                                       1.96 / sqrt(N)
       plus `channels`, `freqs`, `meta` (JSON, its `measures` field lists what was computed, `significance` the test).  Returns {"done": [...], "skipped": [...], "failed": [(dyad, error)],
       "timing": {...}}.
     A window whose fit is singular is NaN-filled, not fatal (the reference would raise and lose the dyad); a segment that
@@ -325,6 +332,21 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                                                      bands=(lo, hi), **order_kw)
                             red_m.masked_fill_(bad_m.view(-1, 1, 1, 1), float("nan"))
                             extra[f"{meas}_bands"] = red_m
+                        if validation_lags is not None:          # K1 + K2 once more, then residuals and whiteness
+                            fit_p = pmax if auto else order
+                            R_v = eng.lagcov(xd, rec_i, st_i, W, fit_p)
+                            if auto:
+                                ar_v, _, ord_v, _, info_v = eng.yw_solve_auto(R_v, block.shape[0], W, crit_type)
+                            else:
+                                ar_v, _, _, info_v = eng.yw_solve(R_v, block.shape[0])
+                                ord_v = torch.full_like(info_v, fit_p)
+                            val = eng.model_validation(xd, rec_i, st_i, W, ar_v, validation_lags, validate=False)
+                            bad_v = (info_v != 0) | (val["info"] != 0)
+                            extra["whiteness_q"] = val["q"].masked_fill(bad_v.view(-1, 1), float("nan"))
+                            extra["acf_fraction"] = (val["acf_count"].to(torch.float64)
+                                                     / float(int(validation_lags) * block.shape[0] ** 2)
+                                                     ).masked_fill(bad_v, float("nan"))
+                            extra["_whiteness_orders"] = ord_v
                         if significance is not None:             # the child block comes first (segment_block)
                             split = sum(1 for nm in seg["names"] if nm.endswith("_ch"))
                             for meas in measures:
@@ -346,8 +368,14 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                     result[f"{key}/ffdtf_bands"] = bsum.cpu().numpy()
                     if ff is not None:
                         result[f"{key}/ffdtf"] = ff.cpu().numpy()
+                    ord_v = extra.pop("_whiteness_orders", None)
                     for name, arr in extra.items():
                         result[f"{key}/{name}"] = arr.cpu().numpy()
+                    if ord_v is not None:
+                        q_v = result[f"{key}/whiteness_q"]
+                        _, result[f"{key}/whiteness_p"], _ = validation_p_values(
+                            q_v, np.zeros((len(q_v), 1)), ord_v.cpu().numpy(), seg["block"].shape[0], int(validation_lags),
+                            np.isnan(q_v[:, 0]))
                     result[f"{key}/starts"] = np.asarray(pos)
                     if psd_dev is not None:
                         result[f"{key}/psd"], result[f"{key}/psd_freqs"] = psd_dev.cpu().numpy(), pf

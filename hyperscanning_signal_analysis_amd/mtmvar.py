@@ -25,7 +25,8 @@ from .engine import Engine, SingularMatrixError, default_engine
 
 __all__ = ["count_corr", "ar_coeff", "mvar_transfer_function", "multivariate_spectra", "dtf_multivariate",
            "full_freq_dtf", "mvar_criterion", "mvar_analysis", "lag_covariances", "compute_and_plot_mvar",
-           "mvar_plot", "fad_decomposition", "fad_decomposition_batch", "fad_components_table"]
+           "mvar_plot", "fad_decomposition", "fad_decomposition_batch", "fad_components_table", "mvar_residuals",
+           "mvar_whiteness"]
 
 
 # ----------------------------------------------------------------------------- internals
@@ -244,6 +245,54 @@ def mvar_criterion(data, max_model_order, crit_type='AIC', plot=False, engine: E
     if plot:
         _criterion_figure(model_order_range, crit, best, crit_type)
     return crit, model_order_range, p_opt
+
+
+def _one_window(signals, who):
+    signals = np.asarray(signals, dtype=np.float64)
+    if signals.ndim != 2:
+        raise ValueError(f"{who}: signals must have shape (channels, samples); trials are not offered here")
+    return signals
+
+
+def mvar_residuals(signals, model_order):
+    """Residuals of the order-`model_order` Yule-Walker fit of one window signals (channels, samples):
+    E = X[:, p:] - sum_k A_k X[:, p-k : n-k], shape (channels, samples - model_order), with A_k = ar_coeff(signals,
+    model_order)[0][:, :, k-1].  Beyond the reference, which stops at the residual covariance (mtmvar.py:119)."""
+    signals = _one_window(signals, "mvar_residuals")
+    eng = default_engine()
+    p = int(model_order)
+    ar, _, _, m, n = _fit(signals, p, eng)
+    x = _as_trials(signals, eng)
+    zero = torch.zeros(1, dtype=torch.int64, device=eng.device)
+    return eng.residuals(x, zero, zero, n, ar)[0].cpu().numpy()
+
+
+def mvar_whiteness(signals, max_lag, max_model_order=20, optimal_model_order=None, crit_type='AIC'):
+    """Residual whiteness of one window's MVAR model (Luetkepohl 2005, section 4.4.3; Hosking 1980; Li & McLeod 1981).
+    signals (channels, samples); the order is `optimal_model_order`, or with None the one `mvar_criterion(signals,
+    max_model_order, crit_type)` selects.  Returns a dict: model_order, q and p_value (3: Box-Pierce, Li-McLeod, Hosking),
+    df = m^2 (max_lag - model_order), q_channel and p_channel (m: per-channel Ljung-Box), acf_fraction (share of the
+    residual correlations r_l[i,j], l = 1..max_lag, beyond 1.96 / sqrt(N)), s (max_lag: the per-lag terms) and resid_cov
+    (m, m).  Raises LinAlgError('Singular matrix') where the fit or the residual covariance is singular.  The chi-square
+    approximation needs samples >> channels^2 max_lag."""
+    from .sliding import validation_p_values
+    signals = _one_window(signals, "mvar_whiteness")
+    eng = default_engine()
+    if optimal_model_order is None:
+        _, _, optimal_model_order = mvar_criterion(signals, max_model_order, crit_type)
+    p = int(optimal_model_order)
+    ar, _, _, m, n = _fit(signals, p, eng)
+    x = _as_trials(signals, eng)
+    zero = torch.zeros(1, dtype=torch.int64, device=eng.device)
+    res = eng.model_validation(x, zero, zero, n, ar, max_lag)
+    eng.raise_on_info(res["info"], "mvar_whiteness (Cholesky of the residual covariance)")
+    h = int(max_lag)
+    out = {"model_order": p, "q": res["q"][0].cpu().numpy(), "q_channel": res["q_channel"][0].cpu().numpy(),
+           "s": res["s"][0].cpu().numpy(), "resid_cov": res["resid_cov"][0].cpu().numpy(),
+           "acf_fraction": float(res["acf_count"][0].item()) / float(h * m * m)}
+    df, out["p_value"], out["p_channel"] = validation_p_values(out["q"], out["q_channel"], np.asarray(p), m, h)
+    out["df"] = int(df)
+    return out
 
 
 def _criterion_figure(orders, crit, best, crit_type):

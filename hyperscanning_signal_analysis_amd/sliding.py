@@ -25,7 +25,8 @@ from .engine import Engine, default_engine
 __all__ = ["window_positions", "hop_positions", "create_windows", "sliding_ffdtf", "sliding_ffdtf_device", "window_items",
            "regular_grid", "sliding_ddtf", "sliding_ddtf_device", "sliding_gpdc", "sliding_gpdc_device", "sliding_fad",
            "sliding_significance", "ensemble_items", "sliding_ensemble", "sliding_ensemble_epochs",
-           "sliding_ensemble_significance", "sliding_ensemble_epochs_significance", "sliding_pseudo_dyad_significance"]
+           "sliding_ensemble_significance", "sliding_ensemble_epochs_significance", "sliding_pseudo_dyad_significance",
+           "sliding_model_validation", "validation_p_values"]
 
 
 def window_positions(T: int, n_windows: int = 3, window_size=None):
@@ -340,6 +341,79 @@ def sliding_fad(signals, fs, window_size=None, n_windows=3, hop=None, model_orde
         return v.reshape((nw, m) + v.shape[1:]) if isinstance(v, np.ndarray) else v
     out = {k: ({kk: split(vv) for kk, vv in v.items()} if isinstance(v, dict) else split(v)) for k, v in out.items()}
     return out
+
+
+# ---- model validation -----------------------------------------------------------------------------------------------------
+def validation_p_values(q, q_channel, orders, m: int, max_lag: int, bad=None):
+    """Host side of the whiteness tests: degrees of freedom and chi-square tails of the device's statistics.
+    q (..., 3), q_channel (..., m), orders (...) the model order of every window.  Returns (df, p_value (..., 3),
+    p_channel (..., m)) with df = m^2 (max_lag - order); the p-values are NaN where df <= 0 or `bad`."""
+    from scipy.special import chdtrc
+    q, q_channel, orders = np.asarray(q, dtype=np.float64), np.asarray(q_channel, dtype=np.float64), np.asarray(orders)
+    df_ch = int(max_lag) - orders.astype(np.int64)
+    df = int(m) * int(m) * df_ch
+    ok = df_ch > 0 if bad is None else (df_ch > 0) & ~np.asarray(bad, dtype=bool)
+    safe = np.where(ok, df_ch, 1).astype(np.float64)
+    p_value = np.where(ok[..., None], chdtrc(safe[..., None] * m * m, q), np.nan)
+    p_channel = np.where(ok[..., None], chdtrc(safe[..., None], q_channel), np.nan)
+    return df, p_value, p_channel
+
+
+def sliding_model_validation(x, window_size, n_windows, p, *, max_lag, hop=None, max_model_order=20, crit_type="AIC",
+                             acf_z=1.96, engine: Engine | None = None):
+    """Is every window's MVAR model adequate?  NumPy (or tensor) in / NumPy out.  x: (m, T) or (n_rec, m, T); windows as
+    `sliding_ddtf` (`window_positions`, or every `hop` samples).  Every window is fitted by Yule-Walker (K1 + K2) at the
+    order p, or with p=None at the order `mvar_criterion(window, max_model_order, crit_type)` picks for it; then
+    `Engine.model_validation` computes the residuals and their whiteness statistics over h = max_lag lags.  With p=None
+    the coefficients are zero-padded to max_model_order lags, so every window has N = window_size - max_model_order
+    residuals and its own order enters the degrees of freedom only.
+    Returns a dict with leading shape (n_windows,) or (n_rec, n_windows):
+        q, p_value (..., 3)      Box-Pierce, Li-McLeod, Hosking portmanteau statistics and their chi-square tails
+        df                       m^2 (h - order)
+        q_channel, p_channel (..., m)   per-channel Ljung-Box, h - order degrees of freedom
+        acf_fraction             share of the h m^2 residual correlations beyond acf_z / sqrt(N) (white: about 5 %)
+        s (..., h)               the per-lag terms;  orders;  resid_cov (..., m, m)
+        bad                      True where the fit or the Cholesky of the residual covariance failed: every statistic NaN.
+    The chi-square approximation needs N >> m^2 h: the p-values are for few channels ("Model validation")."""
+    from .engine import auto_order_args
+    single = np.ndim(x) == 2
+    shape = tuple(np.shape(x))
+    if len(shape) not in (2, 3):
+        raise ValueError("x must have shape (channels, samples) or (recordings, channels, samples)")
+    n_rec, m, T = (1,) + shape if single else shape
+    positions, w = _positions(T, window_size, n_windows, hop)
+    if p is None:
+        fit_p, _ = auto_order_args(max_model_order, crit_type, w)
+    else:
+        fit_p = int(p)
+        if not 1 <= fit_p <= 32:
+            raise ValueError(f"p must be None or an integer in 1..32, got {p!r}")
+    h = int(max_lag)
+    if isinstance(max_lag, bool) or h != max_lag or not 1 <= h <= 32:
+        raise ValueError(f"max_lag must be an integer in 1..32, got {max_lag!r}")
+    if w - fit_p <= h:
+        raise ValueError(f"window_size - order ({w - fit_p}) residuals must exceed max_lag ({h})")
+    eng = engine or default_engine()
+    xd = _recordings_to_device(eng, x, single)
+    item_rec, item_start = window_items(n_rec, positions, eng.device)
+    R = eng.lagcov(xd, item_rec, item_start, w, fit_p)
+    if p is None:
+        ar, _, orders, _, info_yw = eng.yw_solve_auto(R, m, w, crit_type)
+    else:
+        ar, _, _, info_yw = eng.yw_solve(R, m)
+        orders = torch.full_like(info_yw, fit_p)
+    res = eng.model_validation(xd, item_rec, item_start, w, ar, h, acf_z=acf_z, validate=False)
+    bad = ((info_yw != 0) | (res["info"] != 0)).cpu().numpy()
+    nw = len(positions)
+    nan = float("nan")
+    out = {k: np.where(bad.reshape((-1,) + (1,) * (res[k].dim() - 1)), nan, res[k].cpu().numpy())
+           for k in ("q", "q_channel", "s", "resid_cov")}
+    out["acf_fraction"] = np.where(bad, nan, res["acf_count"].cpu().numpy() / float(h * m * m))
+    out["orders"] = orders.cpu().numpy()
+    out["bad"] = bad
+    out["df"], out["p_value"], out["p_channel"] = validation_p_values(out["q"], out["q_channel"], out["orders"], m, h, bad)
+    out = {k: v.reshape((n_rec, nw) + v.shape[1:]) for k, v in out.items()}
+    return {k: v[0] for k, v in out.items()} if single else out
 
 
 # ---- event-locked ensembles ---------------------------------------------------------------------------------------------

@@ -545,6 +545,46 @@ int hmv_null_accumulate_f64(const double* observed, const double* surr, const ui
                             int32_t* count_fwe, int32_t* n_cell, double* mean, double* m2, double* p, double* p_fwe,
                             double* null_mean, double* null_std, void* stream);
 
+/* Model validation: residuals and whiteness statistics of every window's MVAR fit (csrc/validate.hip).  Beyond the
+ * reference, which computes the residual covariance (ar_coeff, src/mtmvar.py:119) but never the residuals; definitions
+ * after Luetkepohl, New Introduction to Multiple Time Series Analysis, section 4.4.3; Hosking 1980; Li & McLeod 1981.
+ * For a window X (m x n), coefficients A_k = ar[:, :, k-1] (k = 1..p), N = n - p and h tested lags:
+ *     E        = X[:, p:] - sum_k A_k X[:, p-k : n-k]                 (m x N; column c is the residual at sample p + c)
+ *     C_l      = E[:, :N-l] E[:, l:]^T / N,  l = 0..h                  (K1's estimator: biased, residuals not demeaned)
+ *     s_l      = || L^-1 C_l L^-T ||_F^2,  C_0 = L L^T,  l = 1..h
+ *     Q_BP     = N sum_l s_l;   Q_LM = Q_BP + m^2 h (h+1) / (2N);   Q_H = N^2 sum_l s_l / (N - l)
+ *     r_l[i,j] = C_l[i,j] / sqrt(C_0[i,i] C_0[j,j]);   acf_count = #{(l,i,j): |r_l[i,j]| > acf_thr}
+ *     q_ch[i]  = N (N+2) sum_l r_l[i,i]^2 / (N - l)
+ * The degrees of freedom (m^2 (h - q) with q the window's model order) and the chi-square tails are the caller's.
+ * hmv_residuals_f64: E[item][c][t] for c < m, t < n - p;  E: [n_items][m][ldE], ldE >= n - p; columns >= n - p are not
+ *   written.  Products in a fixed order (lags ascending, then source channel ascending): the bits of a window's residuals
+ *   do not depend on the batch.  workspace: hmv_residuals_workspace_bytes(chunk_items, m, p) bytes for any chunk_items >= 1
+ *   (the coefficients re-ordered once per item into the operand order; the call walks the items in chunks of what fits).
+ * hmv_whiteness_f64: the statistics from C [n_items][h+1][MP][MP] (hmv_lagcov_f64 over the residuals as n_items
+ *   recordings of N samples, p = h).  s [items][h], q [items][3] (BP, LM, H), q_ch [items][m], acf_count int32 [items], info
+ *   int32 [items]: a non-positive Cholesky pivot of C_0 at column c sets info = c + 1, NaN statistics and acf_count = -1.
+ *   Fixed reduction trees, no atomics: run-to-run bit-identical.
+ * hmv_model_validation_f64: the three stages, `chunk` items at a time so E and C stay bounded.  resid_cov (optional):
+ *   [items][MP][MP] = C_0;  E_out (optional): [n_items][m][ldE].  workspace:
+ *   hmv_model_validation_workspace_bytes(chunk, m, n, p, h) bytes (-1 for bad arguments).
+ * Refused before any launch: channel count (-1), p outside 1..HMV_MAX_ORDER (-2), h outside 1..HMV_MAX_ORDER (-6),
+ *   n - p <= h (-3; hmv_residuals_f64: n <= p, hmv_whiteness_f64: N <= h), null required pointer (-4), workspace too small
+ *   (-7), ldE < n - p (-8). */
+int64_t hmv_residuals_workspace_bytes(int64_t chunk_items, int m, int p);
+int hmv_residuals_f64(const double* x, int64_t rec_stride, int64_t ld,
+                      const int64_t* item_rec, const int64_t* item_start, int64_t n_items,
+                      int m, int n, int p, const double* ar, double* E, int64_t ldE,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+int hmv_whiteness_f64(const double* C, int64_t n_items, int m, int N, int h, double acf_thr,
+                      double* s, double* q, double* q_ch, int32_t* acf_count, int32_t* info, void* stream);
+int64_t hmv_model_validation_workspace_bytes(int64_t chunk, int m, int n, int p, int h);
+int hmv_model_validation_f64(const double* x, int64_t rec_stride, int64_t ld,
+                             const int64_t* item_rec, const int64_t* item_start, int64_t n_items,
+                             int m, int n, int p, const double* ar, int h, double acf_thr,
+                             double* s, double* q, double* q_ch, int32_t* acf_count, int32_t* info,
+                             double* resid_cov, double* E_out, int64_t ldE,
+                             void* workspace, int64_t workspace_bytes, int64_t chunk, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
