@@ -111,6 +111,11 @@ SIGNATURES = {
                                       c_int, c_int, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int] +
                               [c_void_p] * 6 + [c_int64, c_int64, c_double, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                                 c_void_p, c_void_p]),
+    "hmv_lagcov_mix_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
+    "hmv_mix_workspace_bytes": (c_int64, [c_int, c_int64, c_int, c_int, c_int, c_int]),
+    "hmv_sliding_mix_f64": (c_int, [c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
+                                    c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 6 +
+                            [c_int64, c_int64, c_double, c_int64, c_void_p, c_void_p]),
     "hmv_fad_workspace_bytes": (c_int64, [c_int64, c_int]),
     "hmv_fad_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int,
                             c_double, c_double, c_int] + [c_void_p] * 17),

@@ -678,6 +678,14 @@ struct PairDesc {
   const int64_t* base_a;
   const int64_t* base_b;
 };
+// A weighted sum over the trials of a per-trial stack in place of single windows (hmv_sliding_mix_f64): item k * n_win + w
+// is mix row k at window w, there are no samples and no item tables, and only K1 differs (lagcov_mix_kernel).
+struct MixDesc {
+  const double* Rt;
+  const double* W;
+  const double* scale;
+  int64_t n_trials, n_win, n_mix;
+};
 // Everything sliding_impl is told, by name; a field left alone means "not asked for".  The exported entries below fill in
 // what they have.  `ffdtf` receives the full (m, m, F) arrays, `band_out` (with bin_lo / bin_hi / n_bands) the band sums.
 struct SlidingArgs {
@@ -715,6 +723,7 @@ struct SlidingArgs {
   double* crit_out = nullptr;
   const EnsDesc* ens = nullptr;
   const PairDesc* pairs = nullptr;
+  const MixDesc* mix = nullptr;
 };
 int sliding_impl(const SlidingArgs& a) {
   // crit >= 0: automatic order (hmv_sliding_auto_f64) -- p is the largest order tried, K1 sums p + 1 lags, K2 selects every
@@ -735,9 +744,14 @@ int sliding_impl(const SlidingArgs& a) {
   if (automatic && a.crit > 2) return fail(-5, "hmv_sliding_ffdtf_f64: criterion must be 0 (AIC), 1 (HQ) or 2 (SC)");
   if (automatic && (a.flags & (HMV_FLAG_YW_TILED | HMV_FLAG_YW_ONE_LAUNCH)))
     return fail(-6, "hmv_sliding_ffdtf_f64: the LDL^T forms of K2 have no automatic order");
+  if (a.mix && (a.mix->n_trials < 1 || a.mix->n_win < 1 || a.mix->n_mix < 1))
+    return fail(-10, "hmv_sliding_ffdtf_f64: n_trials, n_win and n_mix must be >= 1");
   if (a.n_items == 0) return 0;                                    // empty batch: nothing to do, nothing to check
   if (automatic && !a.order_out) return fail(-4, "hmv_sliding_ffdtf_f64: null pointer / empty grid");
-  if (!a.x || !a.item_rec || !a.item_start || !a.freqs || (!a.ffdtf && !bands) || !a.info_yw ||
+  if (a.mix ? (!a.mix->Rt || !a.mix->W || reinterpret_cast<uintptr_t>(a.mix->Rt) % 16 != 0)
+            : (!a.x || !a.item_rec || !a.item_start))
+    return fail(-4, "hmv_sliding_ffdtf_f64: null pointer / empty grid");
+  if (!a.freqs || (!a.ffdtf && !bands) || !a.info_yw ||
       (!a.info_tf && a.measure != MEAS_GPDC) || !a.workspace || a.F < 1 || a.chunk < 1)
     return fail(-4, "hmv_sliding_ffdtf_f64: null pointer / empty grid");
   if (bands && (!a.bin_lo || !a.bin_hi || a.n_bands < 1)) return fail(-4, "hmv_sliding_ffdtf_f64: band bins missing");
@@ -752,11 +766,11 @@ int sliding_impl(const SlidingArgs& a) {
   }
   const SlidingWs w = sliding_layout(a.chunk, mp, a.p, a.F, bands, a.S_out != nullptr, a.measure,
                                      a.ens ? (ens_shared ? ens_q_tiles(a.chunk, a.n, a.p, a.grid_hop, a.grid_nwin) : 0)
-                                           : (a.pairs ? 0 : -1));
+                                           : ((a.pairs || a.mix) ? 0 : -1));
   if ((int64_t)w.total > a.workspace_bytes) return fail(-7, "hmv_sliding_ffdtf_f64: workspace too small");
   // Regular grid (the caller vouches: item = rec * grid_nwin + w starts at grid_first + w * grid_hop of recording rec,
   // recordings are grid_T samples long): K1 sums every hop block once and assembles the windows from the blocks.
-  bool regular = !a.ens && !a.pairs && a.grid_hop > 0 && !(a.flags & HMV_FLAG_DIRECT_LAGCOV);
+  bool regular = !a.ens && !a.pairs && !a.mix && a.grid_hop > 0 && !(a.flags & HMV_FLAG_DIRECT_LAGCOV);
   if (regular) {
     if (a.grid_nwin < 1 || a.grid_first < 0 || a.n_items % a.grid_nwin != 0 ||
         a.grid_first + (a.grid_nwin - 1) * a.grid_hop + a.n > a.grid_T || a.ld < a.grid_T)
@@ -829,6 +843,11 @@ int sliding_impl(const SlidingArgs& a) {
       pa.base_a = a.pairs->R_base ? reinterpret_cast<const long long*>(a.pairs->base_a + i0) : nullptr;
       pa.base_b = a.pairs->R_base ? reinterpret_cast<const long long*>(a.pairs->base_b + i0) : nullptr;
       rc = hmv::launch_lagcov_pairs(pa, mp, st0);
+    } else if (a.mix) {
+      hmv::LagcovMixArgs ma{};
+      ma.Rt = a.mix->Rt; ma.W = a.mix->W; ma.scale = a.mix->scale; ma.n_trials = a.mix->n_trials; ma.n_win = a.mix->n_win;
+      ma.it0 = i0; ma.n_items = c; ma.m = a.m; ma.m_pad = mp; ma.p = a.p; ma.R = R;
+      rc = hmv::launch_lagcov_mix(ma, st0);
     } else if (regular) {
       // items i0 .. i0+c-1 as runs of consecutive windows of one recording each (item = rec * grid_nwin + w)
       for (int64_t it = i0; it < i0 + c && rc == 0;) {
@@ -1176,6 +1195,55 @@ int hmv_sliding_pairs_f64(int measure, const double* x, int64_t rec_stride, int6
   SlidingArgs a{who};
   a.measure = measure; a.pairs = &pairs;
   a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.item_rec = rec_a; a.item_start = item_start; a.n_items = n_items;
+  a.m = m; a.n = n; a.p = p; a.freqs = freqs; a.F = F; a.fs = fs;
+  if (n_bands > 0) a.band_out = out; else a.ffdtf = out;
+  a.bin_lo = bin_lo; a.bin_hi = bin_hi; a.n_bands = n_bands; a.S_out = S_out;
+  a.ar_out = ar_out; a.V_out = V_out; a.info_yw = info_yw; a.info_tf = info_tf;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.pivot_tau = pivot_tau; a.flags = flags;
+  if (measure == HMV_MEASURE_GPDC) { a.info_tf = nullptr; a.pivot_tau = 1.0; }
+  a.stream = stream; a.aux_stream = aux_stream;
+  return sliding_impl(a);
+}
+
+// ---- weighted trial sums: the fused path with the mix K1 (label permutations of the condition contrast) ----------------
+int hmv_lagcov_mix_f64(const double* Rt, int64_t n_trials, int64_t n_win, const double* W, const double* scale,
+                       int64_t n_mix, int m, int p, double* R, void* stream) {
+  const int mp = pad_of(m);
+  if (mp < 0) return fail(-1, "hmv_lagcov_mix_f64: channel count must be in 1..64");
+  if (p < 1 || p > HMV_MAX_ORDER) return fail(-2, "hmv_lagcov_mix_f64: model order must be in 1..32");
+  if (n_trials < 1 || n_win < 1 || n_mix < 1) return fail(-10, "hmv_lagcov_mix_f64: n_trials, n_win and n_mix must be >= 1");
+  if (!Rt || !W || !R || reinterpret_cast<uintptr_t>(Rt) % 16 != 0 || reinterpret_cast<uintptr_t>(R) % 16 != 0)
+    return fail(-4, "hmv_lagcov_mix_f64: null or misaligned pointer");
+  hmv::LagcovMixArgs ma{};
+  ma.Rt = Rt; ma.W = W; ma.scale = scale; ma.n_trials = n_trials; ma.n_win = n_win;
+  ma.it0 = 0; ma.n_items = n_mix * n_win; ma.m = m; ma.m_pad = mp; ma.p = p; ma.R = R;
+  return hmv::launch_lagcov_mix(ma, S(stream));
+}
+
+int64_t hmv_mix_workspace_bytes(int measure, int64_t chunk, int m, int p, int F, int n_bands) {
+  // n_bands = -1: the full ffDTF together with S_out, as hmv_sliding_auto_workspace_bytes
+  const bool spectra = (n_bands == -1 && measure == HMV_MEASURE_FFDTF);
+  return sliding_bytes(chunk, m, p, F, spectra ? 0 : n_bands, spectra, measure, 0);
+}
+
+int hmv_sliding_mix_f64(int measure, const double* Rt, int64_t n_trials, int64_t n_win, const double* W, const double* scale,
+                        int64_t n_mix, int m, int n, int p, const double* freqs, int F, double fs, double* out,
+                        const int32_t* bin_lo, const int32_t* bin_hi, int n_bands, double* S_out, double* ar_out,
+                        double* V_out, int32_t* info_yw, int32_t* info_tf, void* workspace, int64_t workspace_bytes,
+                        int64_t chunk, double pivot_tau, int64_t flags, void* stream, void* aux_stream) {
+  const char* who = "hmv_sliding_mix_f64";
+  if (measure < HMV_MEASURE_FFDTF || measure > HMV_MEASURE_GPDC)
+    return fail(-4, "hmv_sliding_mix_f64: measure must be HMV_MEASURE_FFDTF, _DDTF or _GPDC");
+  if (n_bands < 0) return fail(-4, "hmv_sliding_mix_f64: n_bands must be >= 0");
+  if (S_out && (measure != HMV_MEASURE_FFDTF || n_bands != 0))
+    return fail(-4, "hmv_sliding_mix_f64: spectra come with the full ffDTF only");
+  const bool sizes_ok = n_trials >= 1 && n_win >= 1 && n_mix >= 1;
+  if (pad_of(m) >= 0 && p >= 1 && p <= HMV_MAX_ORDER && n > p && sizes_ok && !out)
+    return fail(-4, "hmv_sliding_mix_f64: null pointer / empty grid");
+  const MixDesc mix{Rt, W, scale, n_trials, n_win, n_mix};
+  SlidingArgs a{who};
+  a.measure = measure; a.mix = &mix;
+  a.n_items = sizes_ok ? n_mix * n_win : 0;
   a.m = m; a.n = n; a.p = p; a.freqs = freqs; a.F = F; a.fs = fs;
   if (n_bands > 0) a.band_out = out; else a.ffdtf = out;
   a.bin_lo = bin_lo; a.bin_hi = bin_hi; a.n_bands = n_bands; a.S_out = S_out;

@@ -88,6 +88,18 @@ struct LagcovPairsArgs {
   const long long* base_b;  // [n_items]
 };
 int launch_lagcov_pairs(const LagcovPairsArgs& a, int m_pad, hipStream_t st);
+// K1 as a weighted sum over trials (lagcov_mix.hip): item k * n_win + w of the whole call is mix row k at window w,
+// R = scale[k] * sum_e W[k][e] * Rt[e][w], trials ascending; the padding is written, not read.
+struct LagcovMixArgs {
+  const double* Rt;         // [n_trials][n_win][p+1][MP][MP], 16-byte aligned
+  const double* W;          // [n_mix][n_trials]
+  const double* scale;      // [n_mix], or null for 1
+  long long n_trials, n_win;
+  long long it0, n_items;   // the items of THIS launch: it0 .. it0 + n_items - 1 (may start or end inside a row)
+  int m, m_pad, p;
+  double* R;                // [n_items][p+1][MP][MP] of the items of this launch, 16-byte aligned
+};
+int launch_lagcov_mix(const LagcovMixArgs& a, hipStream_t st);
 
 // ---- K2 Yule-Walker solve (block LDL^T of the block-Toeplitz normal equations) ------------------
 struct YwArgs {

@@ -178,6 +178,7 @@ class _Route:
     automatic: bool = False     # the order is selected per window: `orders` and `crit` exist
     per_item: Callable | None = None    # (m, F, n_bands) -> bytes that size the chunk, where not ws_bytes(1, ...)
     blame: Callable | None = None       # (SingularMatrixError, items): what the route adds to the error
+    m: int | None = None                # the channel count, where x does not carry it (the mix route: x is the stack)
 
     @property
     def has_tf(self) -> bool:           # GPDC never inverts A(f): the Yule-Walker info is all it reports
@@ -631,9 +632,12 @@ class Engine:
         """The one driver of the fused entries; `rt` (a `_Route`) carries what differs between them.  Top to bottom: the
         inputs, the empty batch, the grid, where the C call writes, chunk and workspace, the outputs, the call, the band
         sums of the two-step form, `check`, the result `(out[, S][, bad][, ar, V, infos][, orders, crit])`."""
-        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
-        x = x if x.stride(2) == 1 else x.contiguous()
-        n_rec, m, T = x.shape
+        if rt.m is None:
+            assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
+            x = x if x.stride(2) == 1 else x.contiguous()
+            n_rec, m, T = x.shape
+        else:                                 # the mix route: x is the per-trial stack, there are no samples
+            m, T = rt.m, 0
         mp = self.pad(m)
         if validate:
             rt.validate(x, items)
@@ -1011,6 +1015,264 @@ class Engine:
         if obs_bad is not None and bool(obs_bad.any()):
             for k in ("observed", "p", "p_fwe", "null_mean", "null_std"):
                 res[k][obs_bad] = float("nan")
+        return res
+
+    # ------------------------------------------------------------------ condition contrast of ensembles (lagcov_mix.hip)
+    def lagcov_trials(self, x: torch.Tensor, trial_rec: torch.Tensor, trial_start: torch.Tensor, offsets: torch.Tensor, n: int,
+                      p: int, grid=None, validate: bool = True):
+        """The per-trial stack of an event-locked ensemble: x (n_rec, m, T) -> Rt (E, W, p+1, MP, MP), the lag covariances of
+        the window offsets[w] samples after the start of trial e, every trial on its own -- `lagcov_ensemble` with E groups
+        of one trial, items group-major.  grid = (hop, n_win) declares offsets[w] = w * hop and lets the library share the
+        overlap between the windows of a trial where `lagcov_ensemble`'s rule allows it."""
+        if p is None:
+            raise ValueError(_NO_ENSEMBLE_ORDER)
+        E, W = int(trial_rec.numel()), int(offsets.numel())
+        i64 = dict(dtype=torch.int64, device=self.device)
+        R = self.lagcov_ensemble(x, trial_rec, trial_start, torch.arange(E + 1, **i64), torch.arange(E, **i64).repeat_interleave(W),
+                                 offsets.repeat(E), n, p, grid=grid, validate=validate)
+        return R.view(E, W, int(p) + 1, R.shape[-1], R.shape[-1])
+
+    def _check_mix(self, Rt, W, scale, m):
+        """Stack, weights and scales of the mix K1 against one another, before anything is launched."""
+        mp = self.pad(m)
+        if not (isinstance(Rt, torch.Tensor) and Rt.dtype == torch.float64 and Rt.device == self.device and Rt.dim() == 5
+                and Rt.is_contiguous() and tuple(Rt.shape[3:]) == (mp, mp) and Rt.shape[2] >= 2):
+            raise ValueError(f"Rt must be a contiguous float64 tensor (trials, windows, p + 1, {mp}, {mp}) on {self.device}")
+        if not (isinstance(W, torch.Tensor) and W.dtype == torch.float64 and W.device == self.device and W.dim() == 2
+                and W.is_contiguous() and W.shape[1] == Rt.shape[0]):
+            raise ValueError(f"W must be a contiguous float64 tensor (rows, {Rt.shape[0]}) on {self.device}")
+        if scale is not None and not (isinstance(scale, torch.Tensor) and scale.dtype == torch.float64
+                                      and scale.device == self.device and tuple(scale.shape) == (W.shape[0],)
+                                      and scale.is_contiguous()):
+            raise ValueError(f"scale must be a contiguous float64 tensor of {W.shape[0]} entries on {self.device}")
+
+    def lagcov_mix(self, Rt: torch.Tensor, W: torch.Tensor, scale: torch.Tensor | None = None, *, m: int):
+        """K1 as a weighted sum over trials (`hmv_lagcov_mix_f64`): Rt (E, n_win, p+1, MP, MP) from `lagcov_trials`, W (rows,
+        E), scale (rows,) or None -> R (rows * n_win, p+1, MP, MP), item k * n_win + w = scale[k] * sum_e W[k, e] Rt[e, w] on
+        the m x m real elements, trials in ascending order; the padding is written (zero, identity at lag 0), not read.
+        m: the channel count, which the padded stack does not carry."""
+        self._check_mix(Rt, W, scale, m)
+        E, n_win, p1, mp, _ = Rt.shape
+        rows = int(W.shape[0])
+        R = self.empty(rows * n_win, p1, mp, mp)
+        if rows == 0 or n_win == 0 or E == 0:
+            if E == 0 and R.numel():
+                raise ValueError("lagcov_mix needs at least one trial")
+            return R
+        with torch.cuda.device(self.device):
+            rc = self.lib.hmv_lagcov_mix_f64(Rt.data_ptr(), E, n_win, W.data_ptr(), _ptr(scale), rows, int(m), p1 - 1,
+                                             R.data_ptr(), self.stream())
+        _lib.check(rc, "hmv_lagcov_mix_f64")
+        return R
+
+    def _mix_route(self, measure, n, m, Rt, W, scale, spectra=False):
+        """Route of `sliding_mix` (`hmv_sliding_mix_f64`): the driver's x is the per-trial stack, which carries the order but
+        not the channel count; the items are (mix row, window) pairs that only name a failed fit; there is no grid."""
+        lib, n, code = self.lib, int(n), _MEASURES[measure]
+        E, n_win, p1 = (int(v) for v in Rt.shape[:3])
+        p, rows = p1 - 1, int(W.shape[0])
+
+        def blame(err, items):       # say which mix row and which window
+            idx = torch.as_tensor(err.items, dtype=torch.int64, device=items[0].device)
+            err.rows, err.windows = items[0][idx].cpu().numpy(), items[1][idx].cpu().numpy()
+            err.args = (err.args[0], err.args[1] + f" (mix row {int(err.rows[0])}, window {int(err.windows[0])})")
+
+        def call(a):
+            return "hmv_sliding_mix_f64", (
+                code, a.x[0], E, n_win, W.data_ptr(), _ptr(scale), rows, a.m, n, p, a.f, a.F, a.fs, a.out, a.lo, a.hi, a.nb, a.S,
+                a.ar, a.V, a.info_yw, a.info_tf, a.ws, a.nbytes, a.chunk, a.tau, a.flags, a.stream, a.aux)
+        return _Route(
+            name="sliding_mix", measure=measure, p=p, order_text=f"n={n}, p={p}", spectra=spectra, blame=blame, m=int(m),
+            yw_text="ar_coeff (Yule-Walker solve of the mixed covariances; a negative info: residual covariance not positive "
+                    "definite)",
+            validate=lambda x, items: self._check_mix(x, W, scale, m), grid=lambda x, items, n_items, grid, compare: (),
+            ws_bytes=lambda chunk, m_, F, nb, g: lib.hmv_mix_workspace_bytes(code, chunk, m_, p, F, -1 if spectra else nb),
+            call=call)
+
+    def sliding_mix(self, Rt: torch.Tensor, W: torch.Tensor, scale: torch.Tensor | None, n: int, freqs, fs: float, *, m: int,
+                    measure: str = "ffdtf", bands=None, spectra: bool = False, out: torch.Tensor | None = None,
+                    return_ar: bool = False, check=True, chunk: int | None = None, flags: int = 0, validate: bool = True):
+        """Connectivity of weighted trial sums: for every mix row k and window w ONE model of the stack's order is fitted to
+        scale[k] * sum_e W[k, e] Rt[e, w] and `measure` is computed from it -- with 0 / 1 label rows and scale = 1 / E_c what
+        `sliding_ensemble` gives for the trials labelled c, to rounding.  Rt (E, n_win, p+1, MP, MP) from `lagcov_trials` at
+        window length n (K1 does not use n; the C entry checks it against the order) -> (rows * n_win, m, m, F), item k *
+        n_win + w, or the band sums with `bands=(bin_lo, bin_hi)`.  One C-ABI call (`hmv_sliding_mix_f64`); only K1
+        differs from `sliding_ensemble`, whose conventions for spectra, out, return_ar, check and chunk hold; the
+        SingularMatrixError of check=True names the mix row and the window.  m: the channel count, which the padded stack
+        does not carry.  validate=False skips the shape checks of Rt, W and scale."""
+        if measure not in _MEASURES:
+            raise ValueError(f"measure must be 'ffdtf', 'ddtf' or 'gpdc', got {measure!r}")
+        if spectra and (measure != "ffdtf" or bands is not None):
+            raise ValueError("spectra come with the full ffDTF only")
+        if validate:
+            self._check_mix(Rt, W, scale, m)
+        rows, n_win = int(W.shape[0]), int(Rt.shape[1])
+        if Rt.shape[0] == 0 and rows * n_win:
+            raise ValueError("sliding_mix needs at least one trial")
+        rt = self._mix_route(measure, n, m, Rt, W, scale, spectra)
+        i64 = dict(dtype=torch.int64, device=self.device)
+        items = (torch.arange(rows, **i64).repeat_interleave(n_win), torch.arange(n_win, **i64).repeat(rows))
+        return self._sliding_call(rt, Rt, items, freqs, fs, bands=bands, out=out, return_ar=return_ar, check=check, chunk=chunk,
+                                  flags=flags, validate=False)
+
+    def ensemble_contrast_chunk(self, measure: str, m: int, p: int, F: int, nb: int) -> int:
+        """Items (mix row x window) per block of `ensemble_contrast`: half of `max_workspace_bytes` (the other half is the
+        per-trial stack's) over what one item needs -- the fused call's workspace and the item's band values."""
+        ws = int(self.lib.hmv_mix_workspace_bytes(_MEASURES[measure], 1, m, p, F, nb))
+        return max(1, (self.max_workspace_bytes // 2) // (ws + 3 * 8 * m * m * nb + 8 * nb + 2))
+
+    def ensemble_contrast(self, x: torch.Tensor, trial_rec: torch.Tensor, trial_start: torch.Tensor, group_ptr: torch.Tensor,
+                          cond: torch.Tensor, offsets: torch.Tensor, n: int, p: int, freqs, fs: float, bands, *, measure: str,
+                          n_surrogates: int, seed, tail: str = "two-sided", split=None, group=None, check=True,
+                          chunk: int | None = None, grid=None):
+        """Label-permutation test of the difference between two conditions of an event-locked ensemble (Maris & Oostenveld
+        2007): does the band value of `sliding_ensemble(..., measure=measure, bands=bands)` differ between the trials
+        labelled A (cond == 0) and those labelled B (cond == 1)?
+
+        x (n_rec, m, T); trial e is the epoch starting at trial_start[e] of recording trial_rec[e]; group g (a dyad) owns the
+        trials group_ptr[g] .. group_ptr[g+1]-1 and needs at least one of each condition; offsets (W,) int64 are the window
+        offsets, common to all groups (grid = (hop, W) declares offsets[w] = w * hop, as for `lagcov_ensemble`).  The pool of
+        a group is its A trials in their order, then its B trials.  Surrogate s relabels the pool keeping both sizes
+        (`surrogates.label_draws` from numpy.random.default_rng(seed)); one relabelling per (s, g) serves every window.
+        The samples are read once per group: `lagcov_trials` gives the per-trial stack and every relabelling -- the observed
+        labels included, as two weight rows -- is a row of `sliding_mix`.
+        Per group and window: D = band(A) - band(B); T = |D| (tail="two-sided"), D ("greater") or -D ("less"); p, p_fwe
+        (maximum over the tested pairs), null_mean, null_std of T as in `sliding_significance`, over the n_valid surrogates
+        both of whose fits succeeded.  Tested pairs: i != j without a split, the pairs with exactly one index < split with
+        one; NaN elsewhere.  group (G >= 2, or group=True): the observed value is the mean of D over the groups, surrogate s
+        the mean of its D over the groups (summed in ascending group order), invalid for a window where any group's fit
+        failed; conventions of `pseudo_dyad_significance`.
+        check: True raises LinAlgError for a failed observed fit, naming group and window; "nan" gives NaN statistics for
+        it.  chunk: items (mix row x window) per block; the results are the same bits for any chunk.  Where the stack of a
+        group would exceed half of `max_workspace_bytes` it is built per block of windows.  p=None raises ValueError.
+        Returns a dict of device tensors: observed (= D), observed_a, observed_b, p, p_fwe, null_mean, null_std (G, W, m, m,
+        n_bands), n_valid (G, W) int32, tested (m, m) bool and, where built, group = {observed, p, p_fwe, null_mean,
+        null_std (W, m, m, n_bands), n_valid (W,)}."""
+        from . import surrogates as sg
+        if p is None:
+            raise ValueError(_NO_ENSEMBLE_ORDER)
+        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
+        x = x if x.stride(2) == 1 else x.contiguous()
+        n_rec, m, T = x.shape
+        n, p = int(n), int(p)
+        mp = self.pad(m)
+        i64 = dict(dtype=torch.int64, device=self.device)
+        if not (isinstance(cond, torch.Tensor) and cond.dim() == 1 and cond.numel() == trial_rec.numel()
+                and not cond.dtype.is_floating_point):
+            raise ValueError("cond must be a 1-D integer tensor with one entry per trial")
+        gp = group_ptr.cpu().numpy()
+        G, W = len(gp) - 1, int(offsets.numel())
+        validate_trials(x, trial_rec, trial_start, group_ptr, torch.arange(G, **i64).repeat_interleave(W), offsets.repeat(G), n, p)
+        cond_h = cond.cpu().numpy().astype(np.int64)
+        if ((cond_h != 0) & (cond_h != 1)).any():
+            raise ValueError("cond must hold 0 (condition A) or 1 (condition B)")
+        counts_a = [int((cond_h[gp[g]:gp[g + 1]] == 0).sum()) for g in range(G)]
+        counts_b = [int((cond_h[gp[g]:gp[g + 1]] == 1).sum()) for g in range(G)]
+        S, split = sg.contrast_args(measure, n_surrogates, m, tail, split, check, bands, counts_a, counts_b)
+        self._ensemble_grid(1, (torch.zeros(W, **i64), offsets), W, grid, True)
+        f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
+        F = int(f.numel())
+        lo, hi = (np.asarray(b, dtype=np.int32) for b in bands)
+        nb = int(lo.size)
+        self.band_tables(lo, hi, F)
+        draws = sg.label_draws(np.random.default_rng(seed), S, counts_a, counts_b)
+        tested_h = sg.tested_mask(m, "phase" if split is None else "shift", 0 if split is None else split)
+        tested = torch.as_tensor(tested_h.astype(np.uint8)).to(self.device)
+        res = {"tested": torch.as_tensor(tested_h).to(self.device)}
+        stats = ("p", "p_fwe", "null_mean", "null_std")
+        want_group = (G >= 2) if group is None else bool(group)
+        stat = {"two-sided": torch.abs, "greater": lambda d: d, "less": torch.neg}[tail]
+        if W == 0:
+            res.update({k: self.empty(G, 0, m, m, nb) for k in ("observed", "observed_a", "observed_b") + stats},
+                       n_valid=self.empty(G, 0, dtype=torch.int32))
+            if want_group:
+                res["group"] = dict({k: self.empty(0, m, m, nb) for k in ("observed",) + stats},
+                                    n_valid=self.empty(0, dtype=torch.int32))
+            return res
+        chunk = self.ensemble_contrast_chunk(measure, m, p, F, nb) if chunk is None else max(1, int(chunk))
+        st = self.null_state(G * W, m, nb)
+        obs_ab = self.empty(2, G, W, m, m, nb)
+        obs_bad = torch.zeros(G, W, dtype=torch.bool, device=self.device)
+        if want_group:
+            gsum = self.empty(S, W, m, m, nb)
+            gbad = torch.zeros(S, W, dtype=torch.bool, device=self.device)
+        per_window = (p + 1) * mp * mp * 8
+        for g in range(G):
+            e0, e1, EA, EB = int(gp[g]), int(gp[g + 1]), counts_a[g], counts_b[g]
+            E = EA + EB
+            pool = torch.as_tensor(e0 + np.argsort(cond_h[e0:e1], kind="stable")).to(self.device)      # A's trials, then B's
+            rec_g, start_g = trial_rec[pool].contiguous(), trial_start[pool].contiguous()
+            # weight rows: 2 s = the trials relabelled A in surrogate s, 2 s + 1 = the others; the observed labels alike
+            Wh = np.zeros((2 * S + 2, E))
+            for s in range(S + 1):
+                a = np.arange(EA) if s == S else draws[s][g]
+                Wh[2 * s, a] = 1.0
+                Wh[2 * s + 1] = 1.0 - Wh[2 * s]
+            Wd = self.to_device(Wh)
+            sc = self.to_device(np.tile([1.0 / EA, 1.0 / EB], S + 1))
+            Wb = W if E * W * per_window <= self.max_workspace_bytes // 2 else \
+                max(1, (self.max_workspace_bytes // 2) // (E * per_window))
+            for w0 in range(0, W, Wb):
+                w1 = min(W, w0 + Wb)
+                wb = w1 - w0
+                if grid is not None:        # a block of a regular grid is a regular grid that starts offsets[w0] later
+                    Rt = self.lagcov_trials(x, rec_g, start_g + int(grid[0]) * w0, offsets[:wb], n, p, grid=(int(grid[0]), wb),
+                                            validate=False)
+                else:
+                    Rt = self.lagcov_trials(x, rec_g, start_g, offsets[w0:w1].contiguous(), n, p, validate=False)
+                run = dict(m=m, measure=measure, bands=(lo, hi), validate=False)
+                try:
+                    o = self.sliding_mix(Rt, Wd[2 * S:], sc[2 * S:], n, f, fs, check=True if check is True else "mask",
+                                         chunk=min(chunk, 2 * wb), **run)
+                except SingularMatrixError as err:
+                    err.group, err.windows = g, err.windows + w0
+                    err.args = (err.args[0], err.args[1] + f" (group {g}, condition {'AB'[int(err.rows[0])]}, window "
+                                f"{int(err.windows[0])} of the observed labels)")
+                    raise
+                if check is not True:
+                    o, bad = o
+                    obs_bad[g, w0:w1] = bad.view(2, wb).any(dim=0)
+                obs_ab[:, g, w0:w1] = o.view(2, wb, m, m, nb)
+                obs_d = o[:wb] - o[wb:]
+                obs_t = stat(obs_d)
+                sub = {k: v[g * W + w0:g * W + w1] for k, v in st.items()}         # contiguous views
+                Sb = max(1, min(S, chunk // (2 * wb)))
+                for s0 in range(0, S, Sb):
+                    sb = min(Sb, S - s0)
+                    vals, bad = self.sliding_mix(Rt, Wd[2 * s0:2 * (s0 + sb)], sc[2 * s0:2 * (s0 + sb)], n, f, fs, check="mask",
+                                                 chunk=min(chunk, 2 * sb * wb), **run)
+                    vals, bad = vals.view(sb, 2, wb, m, m, nb), bad.view(sb, 2, wb).any(dim=1)
+                    d = vals[:, 0] - vals[:, 1]
+                    self.null_accumulate(obs_t, stat(d).view(sb * wb, m, m, nb), bad.reshape(sb * wb), tested, sub,
+                                         s0 + sb >= S, sb)
+                    if want_group:
+                        if g == 0:
+                            gsum[s0:s0 + sb, w0:w1] = d
+                        else:
+                            gsum[s0:s0 + sb, w0:w1] += d
+                        gbad[s0:s0 + sb, w0:w1] |= bad
+        res.update(observed=obs_ab[0] - obs_ab[1], observed_a=obs_ab[0], observed_b=obs_ab[1], n_valid=st["n_valid"].view(G, W))
+        for k in stats:
+            res[k] = st[k].view(G, W, m, m, nb)
+        any_bad = check is not True and bool(obs_bad.any())
+        if any_bad:
+            for k in ("observed", "observed_a", "observed_b") + stats:
+                res[k][obs_bad] = float("nan")
+        if want_group:
+            gobs = obs_ab[0, 0] - obs_ab[1, 0]
+            for g in range(1, G):                           # the order of the surrogates' sums
+                gobs = gobs + (obs_ab[0, g] - obs_ab[1, g])
+            gobs = gobs / G
+            gst = self.null_state(W, m, nb)
+            self.null_accumulate(stat(gobs), stat(gsum / G).view(S * W, m, m, nb), gbad.view(S * W), tested, gst, True, S)
+            grp = {"observed": gobs, "n_valid": gst["n_valid"]}
+            for k in stats:
+                grp[k] = gst[k]
+            if any_bad:
+                bad_w = obs_bad.any(dim=0)
+                for k in ("observed",) + stats:
+                    grp[k][bad_w] = float("nan")
+            res["group"] = grp
         return res
 
     # ------------------------------------------------------------------ pairs of recordings, pseudo-dyad significance

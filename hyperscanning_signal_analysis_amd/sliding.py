@@ -14,6 +14,8 @@ picks for it -- the reference's own default, `optimal_model_order=None` -- selec
 `sliding_ensemble` / `sliding_ensemble_epochs` are the event-locked form: the reference's functions take `signals` of shape
 (channels, samples, trials) and fit ONE model to the trial-averaged covariances (`count_corr`, mtmvar.py:54-85); here a
 window slides through the epoch and every position is fitted from all repetitions of the event.
+`sliding_ensemble_contrast` / `sliding_ensemble_epochs_contrast` test whether such event-locked band values differ between
+two conditions, by permuting the condition labels of the pooled trials.
 """
 from __future__ import annotations
 
@@ -26,7 +28,7 @@ __all__ = ["window_positions", "hop_positions", "create_windows", "sliding_ffdtf
            "regular_grid", "sliding_ddtf", "sliding_ddtf_device", "sliding_gpdc", "sliding_gpdc_device", "sliding_fad",
            "sliding_significance", "ensemble_items", "sliding_ensemble", "sliding_ensemble_epochs",
            "sliding_ensemble_significance", "sliding_ensemble_epochs_significance", "sliding_pseudo_dyad_significance",
-           "sliding_model_validation", "validation_p_values"]
+           "sliding_model_validation", "validation_p_values", "sliding_ensemble_contrast", "sliding_ensemble_epochs_contrast"]
 
 
 def window_positions(T: int, n_windows: int = 3, window_size=None):
@@ -604,3 +606,86 @@ def sliding_ensemble_epochs_significance(epochs, window_size, hop, p, freqs, fs,
     return _ensemble_significance_run(eng, xd, np.arange(n_tr, dtype=np.int64), np.zeros(n_tr, dtype=np.int64), counts, offsets,
                                       window_size, p, freqs, fs, bands, measure, n_surrogates, seed, split, check, chunk,
                                       share_overlap, single)
+
+
+# ---- condition contrast of event-locked ensembles --------------------------------------------------------------------------
+def _contrast_args(who, p, bands, measure, n_surrogates, m, tail, split, counts_a, counts_b, check):
+    """Everything about a condition contrast that can be refused without a GPU."""
+    from . import surrogates as sg
+    if p is None:
+        raise ValueError(f"{who} needs an integer model order p (no automatic order for ensembles)")
+    if len(counts_a) != len(counts_b):
+        raise ValueError(f"{who}: conditions A and B must have the same number of groups, got {len(counts_a)} and {len(counts_b)}")
+    sg.contrast_args(measure, n_surrogates, m, tail, split, check, bands, counts_a, counts_b)
+
+
+def _contrast_run(eng, xd, rec_a, start_a, counts_a, rec_b, start_b, counts_b, offsets, window_size, p, freqs, fs, bands, measure,
+                  n_surrogates, seed, tail, split, check, chunk, share_overlap, single):
+    """Trial tables of the two conditions (group-major each) -> the pool of every group (A's trials, then B's), the engine's
+    test, and the result as NumPy arrays shaped (n_groups, n_windows, ...), or (n_windows, ...) for a single group."""
+    dev = eng.device
+    pa, pb = np.concatenate([[0], np.cumsum(counts_a)]), np.concatenate([[0], np.cumsum(counts_b)])
+    order = [(c, g) for g in range(len(counts_a)) for c in (0, 1)]
+    pick = lambda a, b: np.concatenate([(a, b)[c][(pa, pb)[c][g]:(pa, pb)[c][g + 1]] for c, g in order])  # noqa: E731
+    trial_rec, trial_start = pick(np.asarray(rec_a), np.asarray(rec_b)), pick(np.asarray(start_a), np.asarray(start_b))
+    cond = np.concatenate([np.full((counts_a, counts_b)[c][g], c, dtype=np.int64) for c, g in order])
+    counts = np.asarray(counts_a) + np.asarray(counts_b)
+    _, _, _, grid = _ensemble_index(eng, counts, offsets, window_size, share_overlap)
+    i64 = lambda a: torch.as_tensor(np.asarray(a, dtype=np.int64)).to(dev)  # noqa: E731
+    res = eng.ensemble_contrast(xd, i64(trial_rec), i64(trial_start), i64(np.concatenate([[0], np.cumsum(counts)])), i64(cond),
+                                i64(offsets), int(window_size), p, freqs, fs, bands, measure=measure, n_surrogates=n_surrogates,
+                                seed=seed, tail=tail, split=split, check=check, chunk=chunk, grid=grid)
+    out = {}
+    for k, v in res.items():
+        if k == "group":
+            out[k] = {kk: vv.cpu().numpy() for kk, vv in v.items()}
+        else:
+            a = v.cpu().numpy()
+            out[k] = a[0] if single and k != "tested" else a
+    return out
+
+
+def sliding_ensemble_contrast(x, onsets_a, onsets_b, window_size, p, freqs, fs, bands, *, pre, post, hop, measure, n_surrogates,
+                              seed, tail="two-sided", split=None, check=True, chunk=None, share_overlap=True,
+                              engine: Engine | None = None):
+    """Label-permutation test of the difference between two conditions of event-locked connectivity
+    (`Engine.ensemble_contrast`): does the band value of `sliding_ensemble(..., measure=measure, bands=bands)` differ between
+    the epochs at `onsets_a` and those at `onsets_b`?  x (m, T) with two 1-D onset arrays; or x (n_rec, m, T) with two lists
+    of onset arrays, one pair per recording (a dyad).  Every recording's epochs are pooled, A's first, then B's; surrogate s
+    relabels the pool keeping both sizes, one relabelling per surrogate and recording for all windows.  tail: "two-sided"
+    tests |A - B|, "greater" A - B, "less" B - A.  split=None tests every pair i != j, an integer the pairs with exactly one
+    index < split.  Returns a dict of NumPy arrays: observed (= A - B), observed_a, observed_b, p, p_fwe, null_mean, null_std
+    (n_windows, m, m, n_bands) or (n_rec, n_windows, ...), n_valid (n_windows,) or (n_rec, n_windows), tested (m, m) and, for
+    two or more recordings, group = {observed, p, p_fwe, null_mean, null_std (n_windows, m, m, n_bands), n_valid
+    (n_windows,)}: the same test on the mean of A - B over the recordings.  Every recording needs at least one onset of each
+    condition.  The arguments are checked before the GPU is touched."""
+    single, n_rec, rec_a, start_a, counts_a, offsets = _onset_trials(x, onsets_a, pre, post, window_size, hop)
+    _, _, rec_b, start_b, counts_b, _ = _onset_trials(x, onsets_b, pre, post, window_size, hop)
+    m = int(np.shape(x)[-2])
+    _contrast_args("sliding_ensemble_contrast", p, bands, measure, n_surrogates, m, tail, split, counts_a, counts_b, check)
+    eng = engine or default_engine()
+    xd = _recordings_to_device(eng, x, single)
+    return _contrast_run(eng, xd, rec_a, start_a, counts_a, rec_b, start_b, counts_b, offsets, window_size, p, freqs, fs, bands,
+                         measure, n_surrogates, seed, tail, split, check, chunk, share_overlap, single)
+
+
+def sliding_ensemble_epochs_contrast(epochs_a, epochs_b, window_size, hop, p, freqs, fs, bands, *, measure, n_surrogates, seed,
+                                     tail="two-sided", split=None, check=True, chunk=None, share_overlap=True,
+                                     engine: Engine | None = None):
+    """`sliding_ensemble_contrast` for epochs that are already cut: two (m, L, trials) arrays, or two lists of such groups
+    (one pair per dyad; same m and L, any numbers of trials), as `sliding_ensemble_epochs` takes them.  Returns the same dict,
+    shaped (n_windows, ...) or (n_groups, n_windows, ...)."""
+    single, groups_a, counts_a = _epoch_groups(epochs_a)
+    single_b, groups_b, counts_b = _epoch_groups(epochs_b)
+    if single != single_b or groups_a[0].shape[:2] != groups_b[0].shape[:2]:
+        raise ValueError("epochs_a and epochs_b must both be arrays or both be lists, with the same channels and samples")
+    m, L = groups_a[0].shape[:2]
+    _contrast_args("sliding_ensemble_epochs_contrast", p, bands, measure, n_surrogates, m, tail, split, counts_a, counts_b, check)
+    offsets = hop_positions(L, window_size, hop).astype(np.int64)
+    eng = engine or default_engine()
+    # every trial becomes one recording of L samples that starts at its own sample 0: A's groups, then B's
+    xd = eng.to_device(np.concatenate([np.moveaxis(e, 2, 0) for e in groups_a + groups_b], axis=0))
+    na, nb_ = int(sum(counts_a)), int(sum(counts_b))
+    return _contrast_run(eng, xd, np.arange(na, dtype=np.int64), np.zeros(na, dtype=np.int64), counts_a,
+                         na + np.arange(nb_, dtype=np.int64), np.zeros(nb_, dtype=np.int64), counts_b, offsets, window_size, p,
+                         freqs, fs, bands, measure, n_surrogates, seed, tail, split, check, chunk, share_overlap, single)

@@ -1,5 +1,5 @@
 """Host side of the surrogate significance tests (`Engine.sliding_significance`, `Engine.ensemble_significance`,
-`Engine.pseudo_dyad_significance`): argument checks, the random draws and the tested family.  Pure NumPy, so that every
+`Engine.pseudo_dyad_significance`, `Engine.ensemble_contrast`): argument checks, the random draws and the tested family.  Pure NumPy, so that every
 surrogate can be rebuilt on the host from the seed.
 
 All randomness comes from `rng = numpy.random.default_rng(seed)`, in this order:
@@ -11,17 +11,22 @@ All randomness comes from `rng = numpy.random.default_rng(seed)`, in this order:
     pseudo dyads:  for s = 0..S-1: pi[s] = rng.permutation(D), drawn again while any pi[s][d] == d (`partner_derangements`
                    with an integer S; `Engine.pseudo_dyad_significance` only).  S = None draws nothing: the exhaustive set is
                    the D - 1 cyclic offsets pi[k-1][d] = (d + k) mod D, k = 1..D-1, and no seed is used
+    contrast:      for s = 0..S-1, then g = 0..G-1: a[s][g] = sort(rng.permutation(E_g)[:EA_g]), the positions of the pooled
+                   trials of group g (its EA_g trials of condition A, then its EB_g of condition B; E_g = EA_g + EB_g) that
+                   surrogate s labels A, drawn again while it is the observed set 0..EA_g-1 (`label_draws`;
+                   `Engine.ensemble_contrast` only)
 """
 from __future__ import annotations
 
 import numpy as np
 
 __all__ = ["NULLS", "ENSEMBLE_NULLS", "MEASURES", "significance_args", "shift_offsets", "phase_draws",
-           "trial_permutations", "partner_count", "partner_derangements", "pseudo_dyad_args", "tested_mask", "check_significance_dict"]
+           "trial_permutations", "label_draws", "contrast_args", "TAILS", "partner_count", "partner_derangements", "pseudo_dyad_args", "tested_mask", "check_significance_dict"]
 
 NULLS = ("shift", "phase")          # of continuous recordings (`sliding_significance`)
 ENSEMBLE_NULLS = ("trial",)         # of event-locked ensembles (`ensemble_significance`)
 MEASURES = ("ffdtf", "ddtf", "gpdc")
+TAILS = ("two-sided", "greater", "less")    # of the condition contrast: T = |D|, D, -D with D = band(A) - band(B)
 
 
 def _int(v, name):
@@ -96,6 +101,63 @@ def trial_permutations(rng, S: int, counts):
             row.append(np.asarray(pi, dtype=np.int64))
         perms.append(row)
     return perms
+
+
+def label_draws(rng, S: int, counts_a, counts_b):
+    """The relabellings of S surrogates of the condition contrast: draws[s][g] = np.sort(rng.permutation(E_g)[:EA_g]) with
+    E_g = counts_a[g] + counts_b[g], drawn for s = 0..S-1 and inside a surrogate for g = 0..G-1, in that order -- the
+    positions in group g's pool (A's trials, then B's) that surrogate s labels A; the others are labelled B, so both group
+    sizes are kept.  A draw equal to the observed set 0..EA_g-1 is drawn again: it is the observed labelling, which the
+    (1 + count) / (1 + n_valid) estimator already counts.  ValueError for a group with an empty condition."""
+    counts_a, counts_b = [int(c) for c in counts_a], [int(c) for c in counts_b]
+    if len(counts_a) != len(counts_b):
+        raise ValueError("counts_a and counts_b must have one entry per group each")
+    for g, (ea, eb) in enumerate(zip(counts_a, counts_b)):
+        if ea < 1 or eb < 1:
+            raise ValueError(f"the condition contrast needs at least one trial of each condition per group, group {g} has "
+                             f"{ea} of A and {eb} of B")
+    draws = []
+    for _ in range(int(S)):
+        row = []
+        for ea, eb in zip(counts_a, counts_b):
+            a = np.sort(rng.permutation(ea + eb)[:ea])
+            while np.array_equal(a, np.arange(ea)):
+                a = np.sort(rng.permutation(ea + eb)[:ea])
+            row.append(np.asarray(a, dtype=np.int64))
+        draws.append(row)
+    return draws
+
+
+def contrast_args(measure, n_surrogates, m, tail, split, check, bands, counts_a, counts_b):
+    """Check the arguments of a condition contrast BEFORE anything is drawn or launched; returns (S, split), split None
+    (every pair i != j is tested) or the integer in 1..m-1 (the inter-brain pairs are).  ValueError for an unknown measure
+    or tail, S < 1, a split outside 1..m-1, a `check` other than True / "nan", bands that are not (bin_lo, bin_hi) with at
+    least one band, no group, and a group with an empty condition."""
+    if measure not in MEASURES:
+        raise ValueError(f"measure must be one of {MEASURES}, got {measure!r}")
+    if tail not in TAILS:
+        raise ValueError(f"tail must be one of {TAILS}, got {tail!r}")
+    S = _int(n_surrogates, "n_surrogates")
+    if S < 1:
+        raise ValueError(f"n_surrogates must be >= 1, got {S}")
+    m = int(m)
+    if split is not None:
+        split = _int(split, "split")
+        if not 1 <= split <= m - 1:
+            raise ValueError(f"split must be in 1..{m - 1}, got {split}")
+    if check is not True and check != "nan":
+        raise ValueError(f"check must be True or 'nan', got {check!r}")
+    if bands is None or len(bands) != 2 or len(np.atleast_1d(bands[0])) < 1 or \
+            len(np.atleast_1d(bands[0])) != len(np.atleast_1d(bands[1])):
+        raise ValueError("the condition contrast needs bands = (bin_lo, bin_hi) with at least one band")
+    counts_a, counts_b = list(counts_a), list(counts_b)
+    if len(counts_a) != len(counts_b) or len(counts_a) < 1:
+        raise ValueError("the condition contrast needs at least one group, with both conditions")
+    for g, (ea, eb) in enumerate(zip(counts_a, counts_b)):
+        if int(ea) < 1 or int(eb) < 1:
+            raise ValueError(f"the condition contrast needs at least one trial of each condition per group, group {g} has "
+                             f"{int(ea)} of A and {int(eb)} of B")
+    return S, split
 
 
 def _n_dyads(D):

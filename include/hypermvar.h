@@ -483,6 +483,40 @@ int hmv_sliding_pairs_f64(int measure, const double* x, int64_t rec_stride, int6
                           int split, const double* R_base, const int64_t* base_a, const int64_t* base_b,
                           void* stream, void* aux_stream);
 
+/* Weighted trial sums of an event-locked ensemble: the label permutations of the condition contrast (csrc/lagcov_mix.hip).
+ * The trial-averaged lag covariances are linear in the per-trial ones, R_l(condition c, window w) = (1/E_c) sum_{e in c}
+ * R_l(trial e, window w), so every relabelling of a pool of trials is a weighted sum over the trial axis of ONE per-trial
+ * stack, and the samples are read once:
+ *     R[k][w] = scale[k] * sum_{e = 0..n_trials-1} W[k][e] * Rt[e][w]
+ *   Rt [n_trials][n_win][p+1][MP][MP]: the per-trial stack, exactly what hmv_lagcov_ensemble_f64 writes for n_trials groups
+ *   of one trial with the items group-major (16-byte aligned).  W [n_mix][n_trials]: the weights, general doubles (0 / 1
+ *   label rows with scale = 1 / E_c give the ensemble estimator to rounding).  scale [n_mix], or NULL for 1.
+ *   R [n_mix][n_win][p+1][MP][MP]: item k * n_win + w is mix row k at window w.  All are DEVICE arrays.
+ *   Every real element (row, col < m) of every lag is one chain acc = fma(W[k][e], Rt[e], acc) over the trials in
+ *   ascending order, then one multiplication by scale[k]; no atomics, no split of the trial sum.  The bits of element
+ *   (k, w) depend on row k of W, on scale[k] and on the stack, and on nothing else: not on the other rows of the call, on
+ *   n_mix, or on how a caller chunks rows or windows.  The padding is written by the kernel, whatever Rt holds there:
+ *   zero, with the lag-0 identity on the padded diagonal.
+ * hmv_lagcov_mix_f64: K1 alone.
+ * hmv_sliding_mix_f64: the fused path K1 -> K2 -> K3 (-> K5) / dDTF / GPDC with this K1; everything after K1 is the
+ *   existing path, with measure, out, bin_lo / bin_hi / n_bands, S_out, ar_out, V_out, info_yw, info_tf, chunk, pivot_tau
+ *   and flags as in hmv_sliding_ensemble_f64 (fixed order p; n is the window length the stack was computed with, which K1
+ *   itself does not use).  A chunk is a contiguous range of items and may start or end inside a row.  workspace:
+ *   hmv_mix_workspace_bytes(measure, chunk, m, p, F, n_bands), n_bands = -1 for the full ffDTF together with S_out
+ *   (the same number as hmv_pairs_workspace_bytes).
+ * Refused before any launch: channel count (-1), order (-2), n <= p (-3; hmv_sliding_mix_f64 only), null or misaligned
+ *   pointers (-4), workspace too small (-7), n_trials, n_win or n_mix < 1 (-10). */
+int hmv_lagcov_mix_f64(const double* Rt, int64_t n_trials, int64_t n_win, const double* W, const double* scale,
+                       int64_t n_mix, int m, int p, double* R, void* stream);
+int64_t hmv_mix_workspace_bytes(int measure, int64_t chunk, int m, int p, int F, int n_bands);
+int hmv_sliding_mix_f64(int measure, const double* Rt, int64_t n_trials, int64_t n_win,
+                        const double* W, const double* scale, int64_t n_mix,
+                        int m, int n, int p, const double* freqs, int F, double fs,
+                        double* out, const int32_t* bin_lo, const int32_t* bin_hi, int n_bands, double* S_out,
+                        double* ar_out, double* V_out, int32_t* info_yw, int32_t* info_tf,
+                        void* workspace, int64_t workspace_bytes, int64_t chunk, double pivot_tau, int64_t flags,
+                        void* stream, void* aux_stream);
+
 /* FAD (frequency-amplitude-damping) decomposition of univariate AR models, batched over series.  Replaces
  * fad_decomposition (src/mtmvar.py:607-757): order selection as mvar_criterion at m = 1 (:551-601), the fit of ar_coeff
  * (:90-123, count_corr :35-87: biased 1/n autocovariance, no demeaning) by Levinson-Durbin, and the partial-fraction
