@@ -22,7 +22,7 @@ inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 // Tuning knobs: the environment is parsed once, at load time, with range checks; hmv_set_tuning overrides.
 constexpr int N_TUNE = 6;
 struct TuneRange { long long lo, hi; };
-constexpr TuneRange kTuneRange[N_TUNE] = {{0, 0}, {0, 1 << 20}, {0, 3}, {0, 2}, {0, 3}, {0, 140000}};
+constexpr TuneRange kTuneRange[N_TUNE] = {{0, 0}, {0, 1 << 20}, {0, 3}, {0, 2}, {0, 4}, {0, 140000}};
 long long env_knob(const char* name, int key) {
   const char* e = getenv(name);
   if (!e || !*e) return 0;
@@ -501,10 +501,11 @@ int64_t hmv_tf_ffdtf_workspace_bytes(int64_t n_items, int m, int p, int F) {
 
 namespace {
 // ffdtf != NULL: the full array.  band_out != NULL: its band sums only (see hmv_tf_ffdtf_bands_f64).
+// yw_ws (fused sliding path only): K2's scratch, where a recursion that did not emit left the model (launch_tf_inv).
 int tf_ffdtf_impl(const char* who, const double* ar, int64_t n_items, int m, int p, const double* tw, int F, double* ffdtf,
                   double* band_out, const int32_t* bin_lo, const int32_t* bin_hi, int n_bands, double* den, double* H,
                   int32_t* info, double pivot_tau, void* workspace, int64_t workspace_bytes, int64_t flags,
-                  void* ev_k3_start, void* ev_k3_stop, void* stream) {
+                  void* ev_k3_start, void* ev_k3_stop, void* stream, const double* yw_ws = nullptr) {
   auto failw = [&](int code, const char* msg) {
     char buf[200];
     snprintf(buf, sizeof(buf), "%s: %s", who, msg);
@@ -553,7 +554,8 @@ int tf_ffdtf_impl(const char* who, const double* ar, int64_t n_items, int m, int
   a.stamps = g_tf_stamps;
 #endif
   hipStream_t st = S(stream);
-  int rc = hmv::launch_tf_inv(a, mp, st, reinterpret_cast<hipEvent_t>(ev_k3_start), reinterpret_cast<hipEvent_t>(ev_k3_stop));
+  int rc = hmv::launch_tf_inv(a, mp, st, reinterpret_cast<hipEvent_t>(ev_k3_start), reinterpret_cast<hipEvent_t>(ev_k3_stop),
+                              yw_ws);
   if (rc) return rc;
   if (n_fused < n_items) {
     const int64_t n_tail = n_items - n_fused;
@@ -895,7 +897,19 @@ int sliding_impl(const SlidingArgs& a) {
       }
       if (rc) break;
     }
-    if (!automatic) rc = hmv_yw_solve_f64(R, c0, a.m, a.p, ws, ar_c, V_c, nullptr, a.info_yw + i0, yw_flags, st0);
+    // Nobody but K3's packing kernel reads the model when the caller does not ask for it and the measure is the ffDTF:
+    // the default recursion then leaves it in its scratch tiles, which the packing kernel reads directly (windows that
+    // the conditioning guard hands to the LDL^T re-solve come through `ar` as before).
+    const int64_t yw_form = hmv::tuning(HMV_TUNE_YW_FORM);
+    const bool from_tiles = !automatic && !a.ar_out && !ldl && (yw_form == 0 || yw_form == 2) && a.measure == MEAS_FFDTF;
+    if (!automatic && from_tiles) {
+      hmv::YwArgs ya{};
+      ya.R = R; ya.n_items = c0; ya.m = a.m; ya.p = a.p; ya.ws = ws; ya.ar = ar_c; ya.V = V_c; ya.info = a.info_yw + i0;
+      ya.tiled = -1; ya.no_emit = 1;
+      rc = hmv::launch_yw(ya, mp, st0);
+    } else if (!automatic) {
+      rc = hmv_yw_solve_f64(R, c0, a.m, a.p, ws, ar_c, V_c, nullptr, a.info_yw + i0, yw_flags, st0);
+    }
     if (rc) break;
     const bool last = (ci == n_chunks - 1);
     double* Hc = a.S_out ? reinterpret_cast<double*>(base + w.off_H) : nullptr;
@@ -909,7 +923,7 @@ int sliding_impl(const SlidingArgs& a) {
                          k3_bands ? nullptr : (full_c ? full_c : a.ffdtf + (size_t)i0 * a.m * a.m * a.F),
                          k3_bands ? a.band_out + (size_t)i0 * a.m * a.m * a.n_bands : nullptr, a.bin_lo, a.bin_hi,
                          a.n_bands, den, Hc, a.info_tf + (size_t)i0 * a.F, a.pivot_tau, tfws, tfws_bytes, a.flags,
-                         last ? a.ev_k3_start : nullptr, last ? a.ev_k3_stop : nullptr, st0);
+                         last ? a.ev_k3_start : nullptr, last ? a.ev_k3_stop : nullptr, st0, from_tiles ? ws : nullptr);
     }
     if (!rc && a.measure == MEAS_DDTF) {     // |kappa| from W(f) = A^T V^-1 A, multiplied into K3's ffDTF in place
       hmv::DdtfArgs da{};

@@ -119,6 +119,10 @@ struct YwArgs {
   // <= p from the first order[item] + 1 lag blocks of its [p+1]-strided R, in its ws_tiles(p)-strided scratch, and its
   // [MP][MP][p] coefficients are written with the lags >= order[item] as +0.0.
   const int* order;
+  // internal (fused sliding path, default recursion only): the recursion does not write `ar`; the model stays in the final
+  // A generation's tiles of `ws` ([k][row][col] at tile (p & 1) * p), where the packing kernel of K3 reads it.  Windows
+  // re-solved by the LDL^T kernel still get their `ar` (their scratch is overwritten), flagged by the guard word.
+  int no_emit;
 };
 // automatic model order (yw_auto.hip only; a struct of its own so that the fixed-order kernels' arguments stay as they
 // were): YwArgs::p is the largest order tried, criterion of order q = log det Vf_q + crit_c * q * m^2 / n
@@ -175,7 +179,11 @@ struct TfArgs {
   unsigned long long* stamps;   // diagnostic builds (-DHMV_STAMP) only: [wave][8] phase cycle sums; else null
 };
 int launch_twiddles(const double* freqs, int F, double fs, int p, double* tw, hipStream_t st);
-int launch_tf_inv(const TfArgs& a, int m_pad, hipStream_t st, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+// yw_ws (optional): K2's scratch of the same items, left by a recursion that did not emit (YwArgs::no_emit).  The packing
+// kernel then takes window `item` from its final A generation's tiles, or from `ar` if its guard word says that the LDL^T
+// re-solve wrote it.
+int launch_tf_inv(const TfArgs& a, int m_pad, hipStream_t st, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
+                  const double* yw_ws = nullptr);
 int launch_cinv(const TfArgs& a, int m_pad, hipStream_t st);
 long long tf_workspace_doubles(long long n_items, int m_pad, int p);
 int tf_band_max_F(int m_pad);

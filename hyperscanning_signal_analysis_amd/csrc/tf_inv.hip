@@ -1058,8 +1058,13 @@ __global__ void __launch_bounds__(256, HMV_K3A_WGS) tf_inv64_asm_kernel(TfArgs a
 // lane (i, b, j) of wave w finds lags (2h, 2h+1) of element (16*Ig + 4*b + i, 4*(Jl*NT + w) + j) at its own
 // 16-byte slot (zero for the padding lag of an odd order).  262 KB per item, once per item instead of once
 // per (item, frequency).
-template <int NT>
-__global__ void __launch_bounds__(256) ar_pack_kernel(const double* ar, double* arx, long long n_items, int p) {
+// TILES: the second source form.  `ws` is K2's scratch, ws_item doubles per item, left by a recursion that did not emit:
+// lag k of the model is tile (p & 1) * p + k of the item ([row][col]: the final A generation of yw_lwr_core.h), unless the
+// item's guard word (the last int of its scratch) says that the LDL^T re-solve took it -- that kernel overwrote the tiles
+// and wrote `ar`.  Same values either way: emit copies those tiles into `ar`.
+template <int NT, bool TILES>
+__global__ void __launch_bounds__(256) ar_pack_kernel(const double* ar, const double* ws, long long ws_item, double* arx,
+                                                      long long n_items, int p) {
   constexpr int MP = 16 * NT;
   const int P2 = (p + 1) >> 1;
   const long long per_item = (long long)MP * MP * P2;       // double2 slots
@@ -1073,10 +1078,16 @@ __global__ void __launch_bounds__(256) ar_pack_kernel(const double* ar, double* 
   const int Ig = (int)(r % NT);
   const int w = (int)(r / NT);
   const int row = 16 * Ig + 4 * ((lane >> 2) & 3) + (lane >> 4), col = 4 * (Jl * NT + w) + (lane & 3);
-  const double* e = ar + ((size_t)item * MP * MP + (size_t)row * MP + col) * p;
   double2 v;
-  v.x = e[2 * h];
-  v.y = (2 * h + 1 < p) ? e[2 * h + 1] : 0.0;
+  if (TILES && reinterpret_cast<const int*>(ws + (size_t)(item + 1) * ws_item)[-1] == 0) {
+    const double* e = ws + (size_t)item * ws_item + ((size_t)(p & 1) * p + 2 * h) * (MP * MP) + (size_t)row * MP + col;
+    v.x = e[0];
+    v.y = (2 * h + 1 < p) ? e[MP * MP] : 0.0;
+  } else {
+    const double* e = ar + ((size_t)item * MP * MP + (size_t)row * MP + col) * p;
+    v.x = e[2 * h];
+    v.y = (2 * h + 1 < p) ? e[2 * h + 1] : 0.0;
+  }
   reinterpret_cast<double2*>(arx)[idx] = v;
 }
 
@@ -1115,7 +1126,8 @@ long long tf_workspace_doubles(long long n_items, int m_pad, int p) {
   return n_items * (long long)m_pad * m_pad * 2 * ((p + 1) / 2);
 }
 
-int launch_tf_inv(const TfArgs& a_in, int m_pad, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop) {
+int launch_tf_inv(const TfArgs& a_in, int m_pad, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop,
+                  const double* yw_ws) {
   TfArgs a = a_in;
   if (a.n_items == 0 || a.F == 0) return 0;
   const bool fused = ((a.ff != nullptr || a.bands != nullptr) && a.fuse_items > 0);
@@ -1133,13 +1145,18 @@ int launch_tf_inv(const TfArgs& a_in, int m_pad, hipStream_t st, hipEvent_t ev_s
   const long long slots = a.n_items * (long long)m_pad * m_pad * ((a.p + 1) / 2);
   const dim3 pgrid((unsigned)((slots + 255) / 256));
   double* arx = const_cast<double*>(a.arx);
+  const long long ws_item = yw_ws_tiles(a.p) * (long long)m_pad * m_pad;
+#define HMV_AR_PACK(NT)                                                                                                  \
+  if (yw_ws) hipLaunchKernelGGL((ar_pack_kernel<NT, true>), pgrid, dim3(256), 0, st, a.ar, yw_ws, ws_item, arx, a.n_items, a.p); \
+  else hipLaunchKernelGGL((ar_pack_kernel<NT, false>), pgrid, dim3(256), 0, st, a.ar, yw_ws, ws_item, arx, a.n_items, a.p)
   switch (m_pad) {
-    case 16: hipLaunchKernelGGL(ar_pack_kernel<1>, pgrid, dim3(256), 0, st, a.ar, arx, a.n_items, a.p); break;
-    case 32: hipLaunchKernelGGL(ar_pack_kernel<2>, pgrid, dim3(256), 0, st, a.ar, arx, a.n_items, a.p); break;
-    case 48: hipLaunchKernelGGL(ar_pack_kernel<3>, pgrid, dim3(256), 0, st, a.ar, arx, a.n_items, a.p); break;
-    case 64: hipLaunchKernelGGL(ar_pack_kernel<4>, pgrid, dim3(256), 0, st, a.ar, arx, a.n_items, a.p); break;
+    case 16: HMV_AR_PACK(1); break;
+    case 32: HMV_AR_PACK(2); break;
+    case 48: HMV_AR_PACK(3); break;
+    case 64: HMV_AR_PACK(4); break;
     default: return -1;
   }
+#undef HMV_AR_PACK
   // the caller's events bracket the K3 kernel alone: not the packing kernel in front of it, not norm_missed_kernel behind it
   // (what rocprofv3 reports as the kernel's duration must be what bench.py prices against the roofline)
   if (ev_start)

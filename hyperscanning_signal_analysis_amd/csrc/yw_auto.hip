@@ -32,9 +32,9 @@
 
 namespace hmv {
 
-template <int NT>
+template <int NT, bool LEGACY = false>
 __global__ void __launch_bounds__(256, 3) yw_auto_kernel(YwArgs a, YwAutoArgs sel) {
-  yw_lwr_body<NT, true, true>(a, sel);
+  yw_lwr_body<NT, true, true, LEGACY>(a, sel);
 }
 
 int launch_yw_auto(const YwArgs& a_in, const YwAutoArgs& sel, int m_pad, hipStream_t st) {
@@ -42,12 +42,18 @@ int launch_yw_auto(const YwArgs& a_in, const YwAutoArgs& sel, int m_pad, hipStre
   if (a.n_items == 0) return 0;
   a.order = nullptr;
   a.only_guarded = 0;
+  a.no_emit = 0;                              // (the selecting form always writes its snapshots)
   const dim3 grid((unsigned)a.n_items), block(256);
+  const bool legacy = tuning(4 /* HMV_TUNE_YW_FORM */) == 4;      // the walk kept for the tests (LEGACY in yw_lwr_core.h)
   switch (m_pad) {
-    case 16: hipLaunchKernelGGL((yw_auto_kernel<1>), grid, block, 0, st, a, sel); break;
-    case 32: hipLaunchKernelGGL((yw_auto_kernel<2>), grid, block, 0, st, a, sel); break;
-    case 48: hipLaunchKernelGGL((yw_auto_kernel<3>), grid, block, 0, st, a, sel); break;
-    case 64: hipLaunchKernelGGL((yw_auto_kernel<4>), grid, block, 0, st, a, sel); break;
+    case 16: if (legacy) hipLaunchKernelGGL((yw_auto_kernel<1, true>), grid, block, 0, st, a, sel);
+             else hipLaunchKernelGGL((yw_auto_kernel<1>), grid, block, 0, st, a, sel); break;
+    case 32: if (legacy) hipLaunchKernelGGL((yw_auto_kernel<2, true>), grid, block, 0, st, a, sel);
+             else hipLaunchKernelGGL((yw_auto_kernel<2>), grid, block, 0, st, a, sel); break;
+    case 48: if (legacy) hipLaunchKernelGGL((yw_auto_kernel<3, true>), grid, block, 0, st, a, sel);
+             else hipLaunchKernelGGL((yw_auto_kernel<3>), grid, block, 0, st, a, sel); break;
+    case 64: if (legacy) hipLaunchKernelGGL((yw_auto_kernel<4, true>), grid, block, 0, st, a, sel);
+             else hipLaunchKernelGGL((yw_auto_kernel<4>), grid, block, 0, st, a, sel); break;
     default: return -1;
   }
   if (const int rc = (int)hipGetLastError()) return rc;

@@ -10,8 +10,10 @@
 //     Vf_{q+1} = Vf_q - A_{q+1}^(q+1) D_q^T                    Vb_{q+1} = Vb_q - B_{q+1}^(q+1) D_q
 // ar[:, :, k] = A_{k+1}^(p), V = Vf_p, and the Vf_q of every lower order (the model-order criterion,
 // mtmvar.py:551-601) come out on the way.  Per window: 115 tile products and 16 tile inverses at p = 8 against 184 + 8
-// for the block LDL^T, and the state is 2p coefficient tiles instead of a (p+1)(p+2)/2-tile factor: ~170 tile moves
-// instead of ~360.
+// for the block LDL^T, and the state is 2p coefficient tiles instead of a (p+1)(p+2)/2-tile factor.  Tile moves per
+// window at p = 8, counted from the loop structure: 367 (265 reads, 102 writes) with the model
+// left in its tiles, 383 with it emitted; 388 (275 + 113) for the walk kept as form 4.  The LDL^T form moves ~360 and
+// does 184 + 8 products and inverses for them.
 //
 // Numerics.  Levinson-type recursions are only weakly stable: the error grows with the condition of the lag-0 blocks'
 // Schur complements (Vf_q, Vb_q), where the LDL^T of the whole Gram matrix loses cond * eps.  Measured against the
@@ -27,9 +29,28 @@
 
 namespace hmv {
 
-template <int NT, bool VQ>
+template <int NT, bool VQ, bool LEGACY = false>
 __global__ void __launch_bounds__(256, 3) yw_lwr_kernel(YwArgs a) {
-  yw_lwr_body<NT, VQ, false>(a, YwAutoArgs{});        // the recursion itself: yw_lwr_core.h
+  yw_lwr_body<NT, VQ, false, LEGACY>(a, YwAutoArgs{});        // the recursion itself: yw_lwr_core.h
+}
+
+// HMV_TUNE_YW_FORM = 4: the walk before the lower-lag updates were paired (LEGACY in yw_lwr_core.h), same bits; the
+// tests hold the default walk against it
+static int launch_yw_lwr_legacy(const YwArgs& a, int m_pad, hipStream_t st) {
+  const dim3 grid((unsigned)a.n_items), block(256);
+  const bool vq = (a.Vq_logdet != nullptr);
+  switch (m_pad) {
+    case 16: if (vq) hipLaunchKernelGGL((yw_lwr_kernel<1, true, true>), grid, block, 0, st, a);
+             else hipLaunchKernelGGL((yw_lwr_kernel<1, false, true>), grid, block, 0, st, a); break;
+    case 32: if (vq) hipLaunchKernelGGL((yw_lwr_kernel<2, true, true>), grid, block, 0, st, a);
+             else hipLaunchKernelGGL((yw_lwr_kernel<2, false, true>), grid, block, 0, st, a); break;
+    case 48: if (vq) hipLaunchKernelGGL((yw_lwr_kernel<3, true, true>), grid, block, 0, st, a);
+             else hipLaunchKernelGGL((yw_lwr_kernel<3, false, true>), grid, block, 0, st, a); break;
+    case 64: if (vq) hipLaunchKernelGGL((yw_lwr_kernel<4, true, true>), grid, block, 0, st, a);
+             else hipLaunchKernelGGL((yw_lwr_kernel<4, false, true>), grid, block, 0, st, a); break;
+    default: return -1;
+  }
+  return (int)hipGetLastError();
 }
 
 // HMV_TUNE_YW_FORM = 3 takes the software-pipelined form of the same recursion (yw_lwr2.hip): measured equal in time
@@ -37,6 +58,7 @@ __global__ void __launch_bounds__(256, 3) yw_lwr_kernel(YwArgs a) {
 int launch_yw_lwr(const YwArgs& a, int m_pad, hipStream_t st) {
   if (a.n_items == 0) return 0;
   if (tuning(4 /* HMV_TUNE_YW_FORM */) == 3) return launch_yw_lwr2(a, m_pad, st);
+  if (tuning(4) == 4) return launch_yw_lwr_legacy(a, m_pad, st);
   const dim3 grid((unsigned)a.n_items), block(256);
   const bool vq = (a.Vq_logdet != nullptr);
   switch (m_pad) {

@@ -3,6 +3,11 @@
 // arg-min and a snapshot of the best model taken on the way).  The algebra, the numerics and the conditioning guard are
 // described at the head of yw_lwr.hip; what AUTO adds is described at the head of yw_auto.hip.  AUTO is a compile-time
 // switch: the fixed-order instantiations contain none of it.
+//
+// LEGACY is the second compile-time switch: the walk as it was before the lower-lag updates were paired (backward update
+// indexed by k, so that every A_k / B_k tile is read twice several iterations apart; Vf_0 = Vb_0 = R_0 stored, loaded back
+// and inverted twice; the model always emitted).  It computes the same bits and is kept, behind HMV_TUNE_YW_FORM = 4, as
+// the reference the tests hold the default walk against.
 #pragma once
 #include "yw_common.h"
 
@@ -12,12 +17,15 @@ namespace hmv {
 #define HMV_LWR_GUARD 1e-7
 #endif
 
-template <int NT, bool VQ, bool AUTO>
+template <int NT, bool VQ, bool AUTO, bool LEGACY = false>
 __device__ __forceinline__ void yw_lwr_body(const YwArgs& a, const YwAutoArgs& sel) {
   static_assert(VQ || !AUTO, "the selecting form needs every log det Vf_q");
   constexpr int MP = 16 * NT, KH = MP / 2, SH = KH + 6, NIW = NT, NJ = NT, TILE = MP * MP;
   constexpr int NV = (MP * KH / 2 + 255) / 256;
   constexpr int SI = YwCfg<NT>::S;
+  // one inverse at order 0.  Not in the selecting form: there it cost two more spilled VGPRs at 64 channels, in every
+  // arrangement tried (pointer selects, branches, the inverse ahead of the loop), and that kernel has none to give.
+  constexpr bool ONE0 = !LEGACY && !AUTO;
   constexpr int GEMM_D = 2 * MP * SH, INV_D = MP * SI, BUF_D = GEMM_D > INV_D ? GEMM_D : INV_D;
   __shared__ __attribute__((aligned(16))) double buf[BUF_D];
   __shared__ double Pb[2 * MP * 4];            // two panel and four N buffers: both inverses of an order at once
@@ -321,12 +329,18 @@ __device__ __forceinline__ void yw_lwr_body(const YwArgs& a, const YwAutoArgs& s
 
   double g[NIW][NJ], acc[NIW][NJ], dacc[NIW][NJ];
   const double (&none)[NIW][NJ] = g;
-  // ---- order 0: Vf = Vb = C(0) = R_0 (symmetric), D_0 = C(1) = R_1^T
-  load_tile(g, R, false);
-  store_tile(Vf, g);
-  store_tile(Vb, g);
-  load_tile(g, R + TILE, true);
-  store_tile(Dq, g);
+  // ---- order 0: Vf = Vb = C(0) = R_0 (symmetric), D_0 = C(1) = R_1^T.  With one inverse at order 0 nothing is stored for
+  // them: the inverse and the Vf / Vb updates of order 0 read R_0, and Vf and Vb are first written by those updates.
+  if (!ONE0) {
+    load_tile(g, R, false);
+    store_tile(Vf, g);
+    store_tile(Vb, g);
+    load_tile(g, R + TILE, true);
+    store_tile(Dq, g);
+  } else {
+    load_tile(g, R + TILE, true);
+    store_tile(Dq, g);
+  }
   __syncthreads();
   for (int q = 0; q < p; ++q) {
     const double* Ao = Agen[q & 1];
@@ -334,10 +348,12 @@ __device__ __forceinline__ void yw_lwr_body(const YwArgs& a, const YwAutoArgs& s
     double* An = Agen[(q + 1) & 1];
     double* Bn = Bgen[(q + 1) & 1];
     const bool last = (q == p - 1);
-    // ---- inverses of the two error covariances of order q (log det Vf_q is the criterion's term of order q)
-    load_tile(g, Vb, false);
+    // ---- inverses of the two error covariances of order q (log det Vf_q is the criterion's term of order q).
+    // Order 0 has one (ONE0): Vf_0 = Vb_0 = R_0, so Vf_0^-1 is read from where Vb_0^-1 is written.
+    const bool one0 = ONE0 && q == 0;
+    load_tile(g, one0 ? R : Vb, false);
 #ifndef HMV_LWR_SINGLE_INVERSES
-    if (!last || (VQ && q >= 1)) {       // (the last order needs Vf^-1 only for its log det)
+    if (!one0 && (!last || (VQ && q >= 1))) {       // (the last order needs Vf^-1 only for its log det)
       load_tile(acc, Vf, false);
       invert2(g, acc, VbI, VfI, (VQ && q >= 1) ? ld_dst(q) : nullptr, q);
     } else {
@@ -345,7 +361,7 @@ __device__ __forceinline__ void yw_lwr_body(const YwArgs& a, const YwAutoArgs& s
     }
 #else
     invert(g, VbI, nullptr, q);
-    if (!last || (VQ && q >= 1)) {
+    if (!one0 && (!last || (VQ && q >= 1))) {
       load_tile(g, Vf, false);
       invert(g, VfI, (VQ && q >= 1) ? ld_dst(q) : nullptr, q);
     }
@@ -357,25 +373,30 @@ __device__ __forceinline__ void yw_lwr_body(const YwArgs& a, const YwAutoArgs& s
     store_tile(An + (size_t)q * TILE, acc);
     zero(dacc);
     product(dacc, nullptr, false, acc, Dq, false);       // A_{q+1} D^T
-    load_tile(g, Vf, false);
+    load_tile(g, one0 ? R : Vf, false);
     sub(g, dacc);
     store_tile(Vf, g);
     if (!last) {
       // ---- B_{q+1} = D^T Vf^-1;  Vb <- Vb - B_{q+1} D
       zero(acc);
-      product(acc, Dq, true, none, VfI, false);
+      product(acc, Dq, true, none, one0 ? VbI : VfI, false);
       store_tile(Bn + (size_t)q * TILE, acc);
       zero(dacc);
       product(dacc, nullptr, false, acc, Dq, true);      // B_{q+1} D
-      load_tile(g, Vb, false);
+      load_tile(g, one0 ? R : Vb, false);
       sub(g, dacc);
       store_tile(Vb, g);
     }
     __syncthreads();                                     // A_{q+1} / B_{q+1} are in global memory
     // ---- lower lags: A'_k = A_k - A_{q+1} B_{q-1-k},  B'_j = B_j - B_{q+1} A_{q-1-j}   (k, j = 0 .. q-1: lag k + 1)
-    // and the next partial correlation D' = C(q+2) - sum_{k=0..q} A'_k C(q+1-k), C(l) = R_l^T
+    // and the next partial correlation D' = C(q+2) - sum_{k=0..q} A'_k C(q+1-k), C(l) = R_l^T.
+    // The pair (A_k, B_{q-1-k}) is closed under the update, so iteration k takes the backward update of j = q-1-k: both
+    // uses of either tile (operand of one product, seed of the other) fall inside one iteration, one or three products
+    // apart, and the second finds the tile in the last-level cache instead of HBM.  Every product keeps its own sum
+    // order and dacc still runs over ascending k: the same bits as the walk that indexed both updates by k.
     zero(dacc);
     for (int k = 0; k < q; ++k) {
+      const int j = LEGACY ? k : q - 1 - k;             // backward lag updated in this iteration
       zero(acc);
       product(acc, An + (size_t)q * TILE, false, none, Bo + (size_t)(q - 1 - k) * TILE, true);
       load_tile(g, Ao + (size_t)k * TILE, false);
@@ -384,10 +405,10 @@ __device__ __forceinline__ void yw_lwr_body(const YwArgs& a, const YwAutoArgs& s
       if (!last) {
         product(dacc, nullptr, false, g, R + (size_t)(q + 1 - k) * TILE, false);       // A'_k R_{q+1-k}^T
         zero(acc);
-        product(acc, Bn + (size_t)q * TILE, false, none, Ao + (size_t)(q - 1 - k) * TILE, true);
-        load_tile(g, Bo + (size_t)k * TILE, false);
+        product(acc, Bn + (size_t)q * TILE, false, none, Ao + (size_t)(q - 1 - j) * TILE, true);
+        load_tile(g, Bo + (size_t)j * TILE, false);
         sub(g, acc);
-        store_tile(Bn + (size_t)k * TILE, g);
+        store_tile(Bn + (size_t)j * TILE, g);
       }
     }
     if (!last) {
@@ -435,7 +456,8 @@ __device__ __forceinline__ void yw_lwr_body(const YwArgs& a, const YwAutoArgs& s
     // (a singular window stays singular: nothing to re-solve)
     *yw_guard_ptr(a.ws, item, p, TILE) = (s_info == 0) ? s_guard : 0;
   }
-  emit(Agen[p & 1], p);
+  // (no_emit: the fused path's packing kernel reads the final generation's tiles where they are)
+  if (LEGACY || !a.no_emit) emit(Agen[p & 1], p);
 }
 
 }  // namespace hmv

@@ -423,6 +423,7 @@ int launch_yw(const YwArgs& a_in, int m_pad, hipStream_t st) {
   // the one-launch LDL^T over the windows whose tile inverses tripped the conditioning guard (normally none: every other
   // workgroup of that launch reads one int and exits).
   const long long form = tuning(4 /* HMV_TUNE_YW_FORM */);
+  if (a.tiled >= 0 || (form != 0 && form != 2)) a.no_emit = 0;       // only the default recursion can leave its tiles
   if (a.tiled < 0 && form != 1) {
     int rc = launch_yw_lwr(a, m_pad, st);
     if (rc) return rc;
