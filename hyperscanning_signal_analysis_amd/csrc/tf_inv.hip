@@ -576,6 +576,7 @@ __global__ void __launch_bounds__(64 * NT, (NT == 4) ? HMV_K3_WGS : 2) tf_inv_ke
   double* rsum = reinterpret_cast<double*>(Srow + L::SROW + L::SWAPB);
 
   double re[NG][4], im[NG][4];
+  [[maybe_unused]] double zscale = 1.0;         // GEN: the power of two the real block of Z was multiplied by
 #ifdef HMV_STAMP
   unsigned long long tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast;
   asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tlast)::"memory");
@@ -592,6 +593,38 @@ __global__ void __launch_bounds__(64 * NT, (NT == 4) ? HMV_K3_WGS : 2) tf_inv_ke
         re[Ig][Jl] = v.x;
         im[Ig][Jl] = v.y;
       }
+    // The inversion below updates its pivot rows as U + (N - I) U, which is exact to rounding only for matrices of order
+    // one (A(f) is; a spectral matrix of samples in ADC counts, |S| ~ 1e12, came back 4e-4 off).  So the real m x m
+    // block is brought to [0.5, 1) in max-norm by an EXACT power of two and the inverse is multiplied by the same
+    // power on the way out: Z * 2**k gives Z^-1 * 2**-k bit for bit, and the padded identity block, which is decoupled,
+    // is left as it is.  (Non-negative doubles order like their bit patterns: the maximum is taken on those.)
+    __shared__ unsigned long long s_mx[4];
+    double mx = 0.0;
+#pragma unroll
+    for (int Ig = 0; Ig < NG; ++Ig)
+#pragma unroll
+      for (int Jl = 0; Jl < 4; ++Jl)
+        if (16 * Ig + rowl < a.m && 4 * NT * Jl + colw < a.m) mx = fmax(mx, fmax(fabs(re[Ig][Jl]), fabs(im[Ig][Jl])));
+    unsigned long long key = wave_max_u64((unsigned long long)__double_as_longlong(mx));
+    if (l == 0) s_mx[wv] = key;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NT; ++k) key = s_mx[k] > key ? s_mx[k] : key;
+    mx = __longlong_as_double((long long)key);
+    if (mx > 0.0 && mx < __builtin_inf()) {
+      int e;
+      (void)frexp(mx, &e);
+      e = e > 1000 ? 1000 : (e < -1000 ? -1000 : e);
+      zscale = ldexp(1.0, -e);
+    }
+#pragma unroll
+    for (int Ig = 0; Ig < NG; ++Ig)
+#pragma unroll
+      for (int Jl = 0; Jl < 4; ++Jl)
+        if (16 * Ig + rowl < a.m && 4 * NT * Jl + colw < a.m) {
+          re[Ig][Jl] *= zscale;
+          im[Ig][Jl] *= zscale;
+        }
   } else {
     // Coefficients in the packed layout written by ar_pack_kernel: for wave w, register (Ig, Jl) and lag pair
     // h the 64 lanes' (a[2h], a[2h+1]) are 1 KB contiguous, so every load instruction is one fully coalesced
@@ -964,6 +997,16 @@ __global__ void __launch_bounds__(64 * NT, (NT == 4) ? HMV_K3_WGS : 2) tf_inv_ke
   });
 
   HMV_T(3);
+  if constexpr (GEN) {       // (Z 2**-e)^-1 2**-e = Z^-1 on the real block; stored column c is output column s_orig[c]
+#pragma unroll
+    for (int Ig = 0; Ig < NG; ++Ig)
+#pragma unroll
+      for (int Jl = 0; Jl < 4; ++Jl)
+        if (16 * Ig + rowl < a.m && s_orig[4 * (Jl * NT + w) + j] < a.m) {
+          re[Ig][Jl] *= zscale;
+          im[Ig][Jl] *= zscale;
+        }
+  }
   tf_outputs<NT, GEN, (NT < 4)>(a, item, f, gw, w, wv, re, im, smem, rsum, s_orig, &s_info, s_det
 #ifdef HMV_STAMP
                       , tsum, tlast

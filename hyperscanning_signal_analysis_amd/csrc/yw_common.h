@@ -40,10 +40,19 @@ struct YwCfg {
 // dinv_out (global, may be null): the inverse;  logdet_out (global, may be null): log det of the tile;
 // pm (LDS, 8 doubles, may be null): on return pm[0] = smallest and pm[1] = largest pivot met (the conditioning guard of
 // the Levinson-Whittle solver), valid for every thread after the call (it ends with a barrier then).
+// mreal: the number of real channels, MP - 16 < mreal <= MP.  The pivots of the padded columns (col >= mreal) are
+// exactly 1.0 -- K1's identity block, decoupled from the real block -- and say nothing about the window's conditioning,
+// so pm leaves them out: with them in, the guard compared the data's variance with 1.0 and tripped on every window of
+// a recording in volts.  Only the last 16 columns can be padding; the others are not asked.
+// The rank-4 update of block step s writes the pivot rows as N_SS U (accumulator zero), U the pivot rows before the step
+// and N_SS the inverse of the pivot block.  They used to be U + (N_SS - I) U: the same in exact arithmetic, but N_SS is
+// an inverse variance and I is not -- for samples of amplitude 2**k the difference kept 53 + 2 k bits of N_SS at k < 0
+// ... and only 53 - 2 k at k > 0: 1e-4 relative at ADC counts of 1e6.  Without the constant the whole routine is
+// homogeneous: X * 4**k gives the inverse times 4**-k bit for bit.
 template <int NT, int S>
 __device__ __forceinline__ void spd_inverse_coop(const double* Xs, double* Pb, double* Nb2, int* s_info,
                                                  double* s_ld, double* dinv_out, double* logdet_out, int info_base,
-                                                 double* pm = nullptr) {
+                                                 double* pm = nullptr, int mreal = 16 * NT) {
   constexpr int MP = 16 * NT, NI = 4 * NT, NSTEP = MP / 4;
   const int l = lane_id();
   const int w = uni(threadIdx.x >> 6);
@@ -78,8 +87,10 @@ __device__ __forceinline__ void spd_inverse_coop(const double* Xs, double* Pb, d
         const double piv = readlane_f64(x[jj], col);
         if (!(piv > 0.0) && l == 0 && *s_info == 0) *s_info = info_base + col + 1;
         mypiv = (l == col) ? piv : mypiv;
-        pmin = fmin(pmin, piv);
-        pmax = fmax(pmax, piv);
+        if (col < MP - 16 || col < mreal) {      // (the first term is known at compile time, the second is uniform)
+          pmin = fmin(pmin, piv);
+          pmax = fmax(pmax, piv);
+        }
         double inv = __builtin_amdgcn_rcp(piv);                  // v_rcp_f64 seed + 2 Newton steps
         inv = __builtin_fma(__builtin_fma(-piv, inv, 1.0), inv, inv);
         inv = __builtin_fma(__builtin_fma(-piv, inv, 1.0), inv, inv);
@@ -105,9 +116,8 @@ __device__ __forceinline__ void spd_inverse_coop(const double* Xs, double* Pb, d
       const double u = m[s];
 #pragma unroll
       for (int I = 0; I < NI; ++I) {
-        double nv = Nb[(4 * I + (l & 3)) * 4 + (l >> 4)];
-        if (I == s) nv -= ((l & 3) == (l >> 4)) ? 1.0 : 0.0;
-        m[I] = mfma4(nv, u, m[I]);
+        const double nv = Nb[(4 * I + (l & 3)) * 4 + (l >> 4)];
+        m[I] = mfma4(nv, u, (I == s) ? 0.0 : m[I]);          // the pivot rows: N_SS U, see the note above
       }
       if (w == ws && (cc >> 2) == q) {
 #pragma unroll
@@ -154,11 +164,12 @@ __device__ __forceinline__ void spd_inverse_coop(const double* Xs, double* Pb, d
 // its column blocks of both tiles (2 x 4 NT MFMAs).  ga / gb: the tiles in the D layout (row strips per wave); `img`: an
 // LDS image buffer of MP x S doubles used for one tile after the other; Pb2 / Nb4: two panel and four N buffers.
 // out_a / out_b (global): the inverses; logdet_b (may be null): log det of B; pm (LDS, >= 4 + 16 doubles): on return
-// pm[0..1] = smallest / largest pivot of A, pm[2..3] of B.  Must be called by all 256 threads.
+// pm[0..1] = smallest / largest pivot of A, pm[2..3] of B, over the real columns (col < mreal) as in spd_inverse_coop.
+// Must be called by all 256 threads.
 template <int NT, int S>
 __device__ __forceinline__ void spd_inverse_coop2(const double (&ga)[NT][NT], const double (&gb)[NT][NT], double* img,
                                                   double* Pb2, double* Nb4, int* s_info, double* s_ld, double* out_a,
-                                                  double* out_b, double* logdet_b, int info_base, double* pm) {
+                                                  double* out_b, double* logdet_b, int info_base, double* pm, int mreal) {
   constexpr int MP = 16 * NT, NI = 4 * NT, NSTEP = MP / 4, ROT = NT / 2;
   const int l = lane_id();
   const int w = uni(threadIdx.x >> 6);
@@ -210,8 +221,10 @@ __device__ __forceinline__ void spd_inverse_coop2(const double (&ga)[NT][NT], co
       const double piv = readlane_f64(x[jj], col);
       if (!(piv > 0.0) && l == 0 && *s_info == 0) *s_info = info_base + col + 1;
       if (mypiv) *mypiv = (l == col) ? piv : *mypiv;
-      pmin = fmin(pmin, piv);
-      pmax = fmax(pmax, piv);
+      if (col < MP - 16 || col < mreal) {
+        pmin = fmin(pmin, piv);
+        pmax = fmax(pmax, piv);
+      }
       double inv = __builtin_amdgcn_rcp(piv);                  // v_rcp_f64 seed + 2 Newton steps
       inv = __builtin_fma(__builtin_fma(-piv, inv, 1.0), inv, inv);
       inv = __builtin_fma(__builtin_fma(-piv, inv, 1.0), inv, inv);
@@ -237,9 +250,8 @@ __device__ __forceinline__ void spd_inverse_coop2(const double (&ga)[NT][NT], co
     const double u = m[s];
 #pragma unroll
     for (int I = 0; I < NI; ++I) {
-      double nv = Nb[(4 * I + (l & 3)) * 4 + (l >> 4)];
-      if (I == s) nv -= ((l & 3) == (l >> 4)) ? 1.0 : 0.0;
-      m[I] = mfma4(nv, u, m[I]);
+      const double nv = Nb[(4 * I + (l & 3)) * 4 + (l >> 4)];
+      m[I] = mfma4(nv, u, (I == s) ? 0.0 : m[I]);            // the pivot rows: N_SS U
     }
     if (owner && (cc >> 2) == q) {
 #pragma unroll

@@ -22,6 +22,15 @@
 // in which any inverse met min / max < HMV_LWR_GUARD is flagged in `guard[item]`; the launcher then re-solves exactly
 // the flagged windows with the LDL^T kernel (one more launch whose other workgroups exit at once).  Well-conditioned
 // windows (every window of the synthetic benchmark; cond ~ 1e4) never take that path.
+// The ratio is taken over the pivots of the REAL channels only (yw_common.h): the padded channels' pivots are K1's unit
+// diagonal, and with them in, a 19-channel recording in volts (variance 1e-10) or in ADC counts (1e8) had every window
+// flagged.  Nothing in the recursion or in the tile inverse holds an absolute constant: samples times 2**k give the same
+// coefficient bits, V times 4**k and the same guard decision (tests/test_gpu_amplitude.py).
+//
+// What the LDL^T delivers where it is the fallback (tests/test_gpu_high_order.py prints it; well-conditioned windows, cond
+// 6e3 .. 8e4, against the oracle's dense solve): 5e-11 at p = 9, 2e-9 at p = 12, 6e-7 at p = 16, 1e-7 at p = 17, 5e-7 at
+// p = 20, 2e-3 at p = 24 and 2e-1 at p = 32, where this recursion stays at ~1e-12 at every order up to 32.  Beyond p ~ 20 a
+// guarded window therefore comes back OUTSIDE the 1e-5 contract.
 //
 // One workgroup of four waves per window walks the whole recursion in ONE launch; the tile products are the same
 // MFMA kernel body as yw_solve.hip (operands staged through LDS in two k-halves, 39 KB, three workgroups per CU).

@@ -276,7 +276,7 @@ __global__ void __launch_bounds__(256, 3) yw_lwr2_kernel(YwArgs a) {
 #pragma unroll
       for (int J = 0; J < NJ; ++J) buf[(4 * (wv * NT + ii) + i) * SI + 16 * J + cc] = g[ii][J];
     __syncthreads();
-    spd_inverse_coop<NT, SI>(buf, Pb, Nb, &s_info, s_ld, out, logdet, info_base, s_pm);
+    spd_inverse_coop<NT, SI>(buf, Pb, Nb, &s_info, s_ld, out, logdet, info_base, s_pm, a.m);
     if (threadIdx.x == 0 && !(s_pm[0] >= HMV_LWR_GUARD * s_pm[1])) s_guard = 1;      // also catches NaN
     __syncthreads();            // the inverse is in global memory for the whole workgroup
   };

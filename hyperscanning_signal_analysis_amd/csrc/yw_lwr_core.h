@@ -260,7 +260,7 @@ __device__ __forceinline__ void yw_lwr_body(const YwArgs& a, const YwAutoArgs& s
 #pragma unroll
       for (int J = 0; J < NJ; ++J) buf[(4 * (wv * NT + ii) + i) * SI + 16 * J + cc] = g[ii][J];
     __syncthreads();
-    spd_inverse_coop<NT, SI>(buf, Pb, Nb, &s_info, s_ld, out, logdet, info_base, s_pm);
+    spd_inverse_coop<NT, SI>(buf, Pb, Nb, &s_info, s_ld, out, logdet, info_base, s_pm, a.m);
     if (threadIdx.x == 0 && !(s_pm[0] >= HMV_LWR_GUARD * s_pm[1])) {                 // also catches NaN
       if (!AUTO) s_guard = 1;
       else if (s_guard == 0) s_guard = q + 1;
@@ -273,7 +273,7 @@ __device__ __forceinline__ void yw_lwr_body(const YwArgs& a, const YwAutoArgs& s
   auto invert2 = [&](const double (&ga)[NIW][NJ], const double (&gb)[NIW][NJ], double* out_a, double* out_b, double* logdet_b,
                      int q) __attribute__((always_inline)) {
     const int info_base = q * MP;
-    spd_inverse_coop2<NT, SI>(ga, gb, buf, Pb, Nb, &s_info, s_ld, out_a, out_b, logdet_b, info_base, s_pm);
+    spd_inverse_coop2<NT, SI>(ga, gb, buf, Pb, Nb, &s_info, s_ld, out_a, out_b, logdet_b, info_base, s_pm, a.m);
     if (threadIdx.x == 0 && (!(s_pm[0] >= HMV_LWR_GUARD * s_pm[1]) || !(s_pm[2] >= HMV_LWR_GUARD * s_pm[3]))) {
       if (!AUTO) s_guard = 1;
       else if (s_guard == 0) s_guard = q + 1;

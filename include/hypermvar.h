@@ -126,6 +126,8 @@ int hmv_spectra_mmf_f64(const double* H, const double* V, double* S, int64_t n_i
  *   [item][f][MP][MP] with the identity on the padding (inverse of hmv_transpose_c128).
  * hmv_cinv_c128: Zinv[item][f] = inv(Z[item][f]) by K3's blocked Gauss-Jordan (same pivoting rule);
  *   detph (optional): [item*F + f][2] = det / |det| (product of the pivots, sign of the interchanges).
+ *   Z may have any magnitude: the kernel brings the real m x m block to order one by an exact power of two and undoes
+ *   it on the way out, so Z * 2^k returns Zinv * 2^-k bit for bit (the padding is expected to hold the identity).
  * hmv_partial_coherence_c128: kappa from Sinv = inverse spectral matrix and its detph; replaces
  *   partial_coherence (src/mtmvar.py:287-338: minors by np.linalg.det) through M_ij = (-1)^(i+j) det (S^-1)_ji;
  *   kappa: complex [item][f][MP][MP] (hmv_transpose_c128 brings it to (m, m, F)).
