@@ -150,6 +150,7 @@ TUNE_LAG_GROUP = 2
 TUNE_K3_FORM = 3
 TUNE_YW_FORM = 4
 TUNE_K3_LDS_PAD = 5
+TUNE_K3_SPLIT = 6
 
 
 _lib = None

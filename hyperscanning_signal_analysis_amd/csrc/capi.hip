@@ -20,9 +20,9 @@ inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 
 // Tuning knobs: the environment is parsed once, at load time, with range checks; hmv_set_tuning overrides.
-constexpr int N_TUNE = 6;
+constexpr int N_TUNE = 7;
 struct TuneRange { long long lo, hi; };
-constexpr TuneRange kTuneRange[N_TUNE] = {{0, 0}, {0, 1 << 20}, {0, 3}, {0, 2}, {0, 4}, {0, 140000}};
+constexpr TuneRange kTuneRange[N_TUNE] = {{0, 0}, {0, 1 << 20}, {0, 3}, {0, 2}, {0, 4}, {0, 140000}, {-1, 1 << 20}};
 long long env_knob(const char* name, int key) {
   const char* e = getenv(name);
   if (!e || !*e) return 0;
@@ -37,7 +37,7 @@ long long env_knob(const char* name, int key) {
 }
 std::atomic<long long> g_tune[N_TUNE] = {{0}, {env_knob("HYPERMVAR_NORM_LAG", 1)}, {env_knob("HYPERMVAR_LAG_GROUP", 2)},
                                          {env_knob("HYPERMVAR_K3_FORM", 3)}, {env_knob("HYPERMVAR_YW_FORM", 4)},
-                                         {env_knob("HYPERMVAR_K3_LDS_PAD", 5)}};
+                                         {env_knob("HYPERMVAR_K3_LDS_PAD", 5)}, {env_knob("HYPERMVAR_K3_SPLIT", 6)}};
 }  // namespace
 
 namespace hmv {
@@ -505,7 +505,8 @@ namespace {
 int tf_ffdtf_impl(const char* who, const double* ar, int64_t n_items, int m, int p, const double* tw, int F, double* ffdtf,
                   double* band_out, const int32_t* bin_lo, const int32_t* bin_hi, int n_bands, double* den, double* H,
                   int32_t* info, double pivot_tau, void* workspace, int64_t workspace_bytes, int64_t flags,
-                  void* ev_k3_start, void* ev_k3_stop, void* stream, const double* yw_ws = nullptr) {
+                  void* ev_k3_start, void* ev_k3_stop, void* stream, const double* yw_ws = nullptr,
+                  hmv::TfSplit* k3_split = nullptr) {
   auto failw = [&](int code, const char* msg) {
     char buf[200];
     snprintf(buf, sizeof(buf), "%s: %s", who, msg);
@@ -555,7 +556,7 @@ int tf_ffdtf_impl(const char* who, const double* ar, int64_t n_items, int m, int
 #endif
   hipStream_t st = S(stream);
   int rc = hmv::launch_tf_inv(a, mp, st, reinterpret_cast<hipEvent_t>(ev_k3_start), reinterpret_cast<hipEvent_t>(ev_k3_stop),
-                              yw_ws);
+                              yw_ws, k3_split);
   if (rc) return rc;
   if (n_fused < n_items) {
     const int64_t n_tail = n_items - n_fused;
@@ -650,6 +651,36 @@ ForkJoin* fork_join_events() {
     if (hipEventCreateWithFlags(&e.join, hipEventDisableTiming) != hipSuccess) return nullptr;
   }
   return &e;
+}
+// Where a chunk of c windows is handed from K2 to K3 in two parts (HMV_TUNE_K3_SPLIT), or 0 for one part.  K2 runs one
+// workgroup per window, all of them resident at once while c < occupancy * CUs, and lasts as long as the fullest compute
+// unit's windows take: with k = c / CUs full rounds and r = c % CUs windows over, r units carry k + 1 windows and the others
+// wait for them.  The r windows over are then solved on the second stream while K3 starts on the first c0 = c - r.  Chunks of
+// several rounds (k >= occupancy) are not split, nor are chunks whose first part is shorter than K3's normalisation lag.
+// CUs and occupancy come from the runtime, once per (host thread, device, padded size).
+int64_t k3_split_point(int64_t c, int mp, int64_t lag) {
+  const int64_t t = hmv::tuning(HMV_TUNE_K3_SPLIT);
+  int64_t c0 = t;
+  if (t < 0) return 0;
+  if (t == 0) {
+    constexpr int MAXDEV = 64;
+    struct Shape { int cus = 0, occ[4] = {0, 0, 0, 0}; };
+    thread_local Shape tl[MAXDEV];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV || mp < 16 || mp > 64) return 0;
+    Shape& d = tl[dev];
+    int& occ = d.occ[mp / 16 - 1];
+    if (d.cus == 0 && hipDeviceGetAttribute(&d.cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) d.cus = -1;
+    if (occ == 0 && (occ = hmv::yw_lwr_occupancy(mp)) == 0) occ = -1;
+    if (d.cus < 1 || occ < 1) {
+      (void)hipGetLastError();                           // (a failed query must not surface as a later launch's error)
+      return 0;
+    }
+    const int64_t k = c / d.cus, r = c % d.cus;
+    if (k < 1 || k >= occ || r == 0) return 0;
+    c0 = c - r;
+  }
+  return (c0 >= lag && c0 < c) ? c0 : 0;
 }
 }  // namespace
 
@@ -785,10 +816,19 @@ int sliding_impl(const SlidingArgs& a) {
   // whose launches interleave on the device (fork after K1, join before K3).  The default one-launch form of K2
   // needs none of this.  Chunk pipelining (K1/K2 of chunk c+1 under K3 of chunk c) was measured and does NOT
   // work: K3 holds every wave slot and starves the other stream.
+  // What the default form does with the second stream is a different thing (k3_split_point, profiles/k3_split_notes.md):
+  // the work put beside K3 is the few windows of the SAME chunk that K2's last, partly filled round would make the whole
+  // chip wait for, and it is placed before K3 arrives -- forked behind K2's first part, with only the light packing kernel
+  // between the fork and K3, so its workgroups land on an almost empty chip and K3 fills in around them.  It is zero-sum
+  // in chip time like the others; what it removes is the idle tail of K2 from the critical path.  Only where nobody but
+  // K3's packing kernel reads the model (from_tiles below) and no output beyond the ffDTF is asked for.
   hipStream_t st0 = S(a.stream), st1 = S(a.aux_stream);
-  const bool split = (a.aux_stream && a.aux_stream != a.stream) && !(a.flags & HMV_FLAG_YW_ONE_LAUNCH);
+  const bool two = (a.aux_stream && a.aux_stream != a.stream);
+  const bool split = two && !(a.flags & HMV_FLAG_YW_ONE_LAUNCH);
+  const bool k3_split = two && !automatic && a.measure == MEAS_FFDTF && !a.S_out && !a.ar_out && !a.V_out &&
+                        !(a.flags & (HMV_FLAG_YW_TILED | HMV_FLAG_YW_ONE_LAUNCH));
   ForkJoin* fj = nullptr;
-  if (split) {
+  if (split || k3_split) {
     fj = fork_join_events();
     if (!fj) return fail(-8, "hmv_sliding_ffdtf_f64: cannot create fork/join events");
   }
@@ -808,6 +848,12 @@ int sliding_impl(const SlidingArgs& a) {
   const int64_t tfws_bytes = (int64_t)tf_ff_layout(a.chunk, mp, a.p, a.F, k3_bands).total;
   rc = hmv_twiddles_f64(a.freqs, a.F, a.fs, a.p, tw, st0);
   const size_t ws_item = (size_t)hmv_yw_workspace_doubles(a.m, a.p);
+  hmv::TfSplit sp{};                         // the chunk's K2 -> K3 hand-over in two parts, if any
+  auto join_k3_split = [&]() {               // st0 joins st1 unless K3's launcher already made it wait
+    if (sp.join && !sp.joined)
+      if (hipStreamWaitEvent(st0, sp.join, 0) != hipSuccess) (void)hipStreamSynchronize(st1);
+    sp.joined = true;
+  };
   for (int64_t ci = 0; ci < n_chunks && rc == 0; ++ci) {
     const int64_t i0 = ci * a.chunk;
     const int64_t c = (a.n_items - i0 < a.chunk) ? (a.n_items - i0) : a.chunk;
@@ -902,11 +948,31 @@ int sliding_impl(const SlidingArgs& a) {
     // the conditioning guard hands to the LDL^T re-solve come through `ar` as before).
     const int64_t yw_form = hmv::tuning(HMV_TUNE_YW_FORM);
     const bool from_tiles = !automatic && !a.ar_out && !ldl && (yw_form == 0 || yw_form == 2) && a.measure == MEAS_FFDTF;
+    sp = hmv::TfSplit{};
     if (!automatic && from_tiles) {
+      const int64_t s0 = k3_split ? k3_split_point(c, mp, norm_lag_items(mp, a.F)) : 0;
       hmv::YwArgs ya{};
-      ya.R = R; ya.n_items = c0; ya.m = a.m; ya.p = a.p; ya.ws = ws; ya.ar = ar_c; ya.V = V_c; ya.info = a.info_yw + i0;
+      ya.R = R; ya.n_items = s0 ? s0 : c0; ya.m = a.m; ya.p = a.p; ya.ws = ws; ya.ar = ar_c; ya.V = V_c; ya.info = a.info_yw + i0;
       ya.tiled = -1; ya.no_emit = 1;
       rc = hmv::launch_yw(ya, mp, st0);
+      if (!rc && s0) {
+        // fork behind K2's first part (the remainder never shares a compute unit with it); the join is waited for inside
+        // K3's launcher, between its two launches, or below on every path that did not get that far
+        int hrc = (int)hipEventRecord(fj->fork, st0);
+        if (!hrc) hrc = (int)hipStreamWaitEvent(st1, fj->fork, 0);
+        if (hrc) { rc = hrc; break; }                    // nothing was put on st1
+        hmv::YwArgs yb = ya;
+        yb.R = R + (size_t)s0 * (a.p + 1) * t; yb.n_items = c - s0; yb.ws = ws + (size_t)s0 * ws_item;
+        yb.ar = ar_c + (size_t)s0 * t * a.p; yb.V = V_c + (size_t)s0 * t; yb.info = a.info_yw + i0 + s0;
+        rc = hmv::launch_yw(yb, mp, st1);
+        hrc = (int)hipEventRecord(fj->join, st1);
+        if (hrc) {                                       // cannot express the join as an event: join on the host, one K3 launch
+          (void)hipStreamSynchronize(st1);
+          if (!rc) rc = hrc;
+        } else {
+          sp.c0 = s0; sp.join = fj->join;
+        }
+      }
     } else if (!automatic) {
       rc = hmv_yw_solve_f64(R, c0, a.m, a.p, ws, ar_c, V_c, nullptr, a.info_yw + i0, yw_flags, st0);
     }
@@ -923,8 +989,9 @@ int sliding_impl(const SlidingArgs& a) {
                          k3_bands ? nullptr : (full_c ? full_c : a.ffdtf + (size_t)i0 * a.m * a.m * a.F),
                          k3_bands ? a.band_out + (size_t)i0 * a.m * a.m * a.n_bands : nullptr, a.bin_lo, a.bin_hi,
                          a.n_bands, den, Hc, a.info_tf + (size_t)i0 * a.F, a.pivot_tau, tfws, tfws_bytes, a.flags,
-                         last ? a.ev_k3_start : nullptr, last ? a.ev_k3_stop : nullptr, st0, from_tiles ? ws : nullptr);
+                         last ? a.ev_k3_start : nullptr, last ? a.ev_k3_stop : nullptr, st0, from_tiles ? ws : nullptr, &sp);
     }
+    join_k3_split();                         // (K3's launcher did not get to its second part)
     if (!rc && a.measure == MEAS_DDTF) {     // |kappa| from W(f) = A^T V^-1 A, multiplied into K3's ffDTF in place
       hmv::DdtfArgs da{};
       da.ar = ar_c; da.V = V_c; da.info_yw = a.info_yw + i0;
@@ -944,6 +1011,7 @@ int sliding_impl(const SlidingArgs& a) {
       rc = hmv::launch_spectra(sa, mp, st0);
     }
   }
+  join_k3_split();                           // a chunk that ended on an error between the fork and K3
   return rc;
 }
 }  // namespace

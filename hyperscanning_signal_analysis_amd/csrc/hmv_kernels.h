@@ -136,6 +136,8 @@ struct YwAutoArgs {
 long long yw_ws_tiles(int p);
 int launch_yw(const YwArgs& a, int m_pad, hipStream_t st);
 int launch_yw_lwr(const YwArgs& a, int m_pad, hipStream_t st);
+// how many workgroups (= windows) of the default recursion one compute unit holds at once, from the runtime; 0: unknown
+int yw_lwr_occupancy(int m_pad);
 int launch_yw_lwr2(const YwArgs& a, int m_pad, hipStream_t st);
 // K2 with on-device order selection: the recursion to order p with criterion, first arg-min and snapshot, then the LDL^T
 // re-solve of the guarded windows at their own orders
@@ -177,13 +179,25 @@ struct TfArgs {
   const int* band_hi;       // [nb] device
   int nb;
   unsigned long long* stamps;   // diagnostic builds (-DHMV_STAMP) only: [wave][8] phase cycle sums; else null
+  // K3 of one batch in two launches (launch_tf_inv with a TfSplit): workgroup b of a launch is (item, frequency)
+  // item0 * F + b of the batch.  Every array, n_items, fuse_items and lag stay those of the whole batch.
+  int item0;
+};
+// K3 of one batch in two launches on `st`: items [0, c0), then -- once `join` has happened (the event behind whatever
+// produces the model of the items >= c0 on another stream) -- items [c0, n_items).  One protocol: one memset ahead of the
+// first launch, the second launch's first workgroups normalise the first launch's last windows (complete by stream
+// order), one set of tail windows, one norm_missed_kernel.  `joined` comes back true once `st` waits for `join`.
+struct TfSplit {
+  long long c0 = 0;
+  hipEvent_t join = nullptr;
+  bool joined = false;
 };
 int launch_twiddles(const double* freqs, int F, double fs, int p, double* tw, hipStream_t st);
 // yw_ws (optional): K2's scratch of the same items, left by a recursion that did not emit (YwArgs::no_emit).  The packing
 // kernel then takes window `item` from its final A generation's tiles, or from `ar` if its guard word says that the LDL^T
 // re-solve wrote it.
 int launch_tf_inv(const TfArgs& a, int m_pad, hipStream_t st, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
-                  const double* yw_ws = nullptr);
+                  const double* yw_ws = nullptr, TfSplit* split = nullptr);
 int launch_cinv(const TfArgs& a, int m_pad, hipStream_t st);
 long long tf_workspace_doubles(long long n_items, int m_pad, int p);
 int tf_band_max_F(int m_pad);

@@ -556,11 +556,13 @@ __global__ void __launch_bounds__(64 * NT, (NT == 4) ? HMV_K3_WGS : 2) tf_inv_ke
   // Column blocks owned by this wave, rotated per workgroup by a hash of the block id: co-resident
   // workgroups run in near lockstep and wave k of every workgroup tends to sit on the same SIMD, so without
   // the rotation the resident panel factorisations (one wave each) pile up on one SIMD.
-  const int w = (wv + (int)((blockIdx.x * 2654435761u) >> 20)) % NT;
+  // (bid: this workgroup's number in the batch -- a batch may come as two launches, TfArgs::item0)
+  const unsigned bid = blockIdx.x + (unsigned)a.item0 * (unsigned)a.F;
+  const int w = (wv + (int)((bid * 2654435761u) >> 20)) % NT;
   // One workgroup = one (window, frequency) matrix.  (A runtime loop over several frequencies per workgroup
   // was tried to amortise the publish step below: the loop-carried state costs 525 spilled VGPRs.)
-  const int item = uni((int)(blockIdx.x / (unsigned)a.F));   // wave-uniform: keep it in SGPRs
-  const int f = uni((int)(blockIdx.x - (unsigned)item * (unsigned)a.F));
+  const int item = uni((int)(bid / (unsigned)a.F));   // wave-uniform: keep it in SGPRs
+  const int f = uni((int)(bid - (unsigned)item * (unsigned)a.F));
   const long long gw = (long long)item * a.F + f;
   const int p = a.p;
   // "X layout" (hmv_common.h lane maps with the four MFMA blocks on four ROW blocks): lane (i, b, j) holds
@@ -1042,9 +1044,10 @@ __global__ void __launch_bounds__(256, HMV_K3A_WGS) tf_inv64_asm_kernel(TfArgs a
   int* s_orig = reinterpret_cast<int*>(lds + K3A_SORIG);
   int* s_flag = reinterpret_cast<int*>(lds + K3A_SINFO);
   const int wv = uni(threadIdx.x >> 6);
-  const int w = (wv + (int)((blockIdx.x * 2654435761u) >> 20)) % NT;      // same rotation as tf_inv_kernel
-  const int item = uni((int)(blockIdx.x / (unsigned)a.F));
-  const int f = uni((int)(blockIdx.x - (unsigned)item * (unsigned)a.F));
+  const unsigned bid = blockIdx.x + (unsigned)a.item0 * (unsigned)a.F;    // as in tf_inv_kernel
+  const int w = (wv + (int)((bid * 2654435761u) >> 20)) % NT;             // same rotation as tf_inv_kernel
+  const int item = uni((int)(bid / (unsigned)a.F));
+  const int f = uni((int)(bid - (unsigned)item * (unsigned)a.F));
   const long long gw = (long long)item * a.F + f;
   if (w == 0) {
     const int l = lane_id();
@@ -1170,9 +1173,10 @@ long long tf_workspace_doubles(long long n_items, int m_pad, int p) {
 }
 
 int launch_tf_inv(const TfArgs& a_in, int m_pad, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop,
-                  const double* yw_ws) {
+                  const double* yw_ws, TfSplit* split) {
   TfArgs a = a_in;
   if (a.n_items == 0 || a.F == 0) return 0;
+  if (m_pad != 16 && m_pad != 32 && m_pad != 48 && m_pad != 64) return -1;
   const bool fused = ((a.ff != nullptr || a.bands != nullptr) && a.fuse_items > 0);
   if (fused) {
     if (!a.P || !a.den || !a.wcount || !a.ready || !a.missed || a.lag < 1) return -3;
@@ -1183,45 +1187,57 @@ int launch_tf_inv(const TfArgs& a_in, int m_pad, hipStream_t st, hipEvent_t ev_s
     a.ff = nullptr;
     a.bands = nullptr;
   }
-  const long long n = a.n_items * (long long)a.F;
-  const dim3 grid((unsigned)n);
-  const long long slots = a.n_items * (long long)m_pad * m_pad * ((a.p + 1) / 2);
-  const dim3 pgrid((unsigned)((slots + 255) / 256));
-  double* arx = const_cast<double*>(a.arx);
+  // one launch over the whole batch, or two: items [0, c0) and, behind the join, [c0, n_items)
+  const long long c0 = (split && split->join && split->c0 > 0 && split->c0 < a.n_items) ? split->c0 : a.n_items;
+  const long long per_item = (long long)m_pad * m_pad * ((a.p + 1) / 2);      // double2 slots of arx
   const long long ws_item = yw_ws_tiles(a.p) * (long long)m_pad * m_pad;
-#define HMV_AR_PACK(NT)                                                                                                  \
-  if (yw_ws) hipLaunchKernelGGL((ar_pack_kernel<NT, true>), pgrid, dim3(256), 0, st, a.ar, yw_ws, ws_item, arx, a.n_items, a.p); \
-  else hipLaunchKernelGGL((ar_pack_kernel<NT, false>), pgrid, dim3(256), 0, st, a.ar, yw_ws, ws_item, arx, a.n_items, a.p)
-  switch (m_pad) {
-    case 16: HMV_AR_PACK(1); break;
-    case 32: HMV_AR_PACK(2); break;
-    case 48: HMV_AR_PACK(3); break;
-    case 64: HMV_AR_PACK(4); break;
-    default: return -1;
-  }
+  for (long long i0 = 0, ni = c0; i0 < a.n_items; i0 += ni, ni = a.n_items - i0) {
+    if (i0 > 0) {
+      if (const hipError_t e = hipStreamWaitEvent(st, split->join, 0)) return (int)e;
+      split->joined = true;
+    }
+    const dim3 pgrid((unsigned)((ni * per_item + 255) / 256));
+    const double* ar = a.ar + (size_t)i0 * m_pad * m_pad * a.p;
+    const double* wsp = yw_ws ? yw_ws + (size_t)i0 * ws_item : nullptr;
+    double* arx = const_cast<double*>(a.arx) + (size_t)i0 * per_item * 2;
+#define HMV_AR_PACK(NT)                                                                                             \
+  if (yw_ws) hipLaunchKernelGGL((ar_pack_kernel<NT, true>), pgrid, dim3(256), 0, st, ar, wsp, ws_item, arx, ni, a.p); \
+  else hipLaunchKernelGGL((ar_pack_kernel<NT, false>), pgrid, dim3(256), 0, st, ar, wsp, ws_item, arx, ni, a.p)
+    switch (m_pad) {
+      case 16: HMV_AR_PACK(1); break;
+      case 32: HMV_AR_PACK(2); break;
+      case 48: HMV_AR_PACK(3); break;
+      case 64: HMV_AR_PACK(4); break;
+    }
 #undef HMV_AR_PACK
-  // the caller's events bracket the K3 kernel alone: not the packing kernel in front of it, not norm_missed_kernel behind it
-  // (what rocprofv3 reports as the kernel's duration must be what bench.py prices against the roofline)
-  if (ev_start)
-    if (const hipError_t e = hipEventRecord(ev_start, st)) return (int)e;
-  switch (m_pad) {
-    case 16: hipLaunchKernelGGL((tf_inv_kernel<1, false>), grid, dim3(64), 0, st, a); break;
-    case 32: hipLaunchKernelGGL((tf_inv_kernel<2, false>), grid, dim3(128), 0, st, a); break;
-    case 48: hipLaunchKernelGGL((tf_inv_kernel<3, false>), grid, dim3(192), 0, st, a); break;
-    case 64:
-      if (tuning(5) > 0) {        // measurement knob: dynamic LDS nobody uses, to hold fewer workgroups per CU
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tf_inv64_asm_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)tuning(5));
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tf_inv_kernel<4, false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)tuning(5));
-      }
-      // the hand-scheduled body has no A(f) output (asked for by the staged API only)
-      if ((tuning(3 /* HMV_TUNE_K3_FORM */) != 1 || a.bands != nullptr) && a.A == nullptr)
-        hipLaunchKernelGGL(tf_inv64_asm_kernel, grid, dim3(256), (unsigned)tuning(5 /* HMV_TUNE_K3_LDS_PAD */), st, a);
-      else
-        hipLaunchKernelGGL((tf_inv_kernel<4, false>), grid, dim3(256), (unsigned)tuning(5), st, a);
-      break;
+    // the caller's events bracket the K3 kernel alone (both launches of a split batch, and what lies between them): not the
+    // packing kernel in front of it, not norm_missed_kernel behind it (what rocprofv3 reports as the kernel's duration must
+    // be what bench.py prices against the roofline)
+    if (ev_start && i0 == 0)
+      if (const hipError_t e = hipEventRecord(ev_start, st)) return (int)e;
+    a.item0 = (int)i0;
+    const dim3 grid((unsigned)(ni * (long long)a.F));
+    switch (m_pad) {
+      case 16: hipLaunchKernelGGL((tf_inv_kernel<1, false>), grid, dim3(64), 0, st, a); break;
+      case 32: hipLaunchKernelGGL((tf_inv_kernel<2, false>), grid, dim3(128), 0, st, a); break;
+      case 48: hipLaunchKernelGGL((tf_inv_kernel<3, false>), grid, dim3(192), 0, st, a); break;
+      case 64:
+        if (tuning(5) > 0) {        // measurement knob: dynamic LDS nobody uses, to hold fewer workgroups per CU
+          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tf_inv64_asm_kernel),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)tuning(5));
+          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tf_inv_kernel<4, false>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)tuning(5));
+        }
+        // the hand-scheduled body has no A(f) output (asked for by the staged API only)
+        if ((tuning(3 /* HMV_TUNE_K3_FORM */) != 1 || a.bands != nullptr) && a.A == nullptr)
+          hipLaunchKernelGGL(tf_inv64_asm_kernel, grid, dim3(256), (unsigned)tuning(5 /* HMV_TUNE_K3_LDS_PAD */), st, a);
+        else
+          hipLaunchKernelGGL((tf_inv_kernel<4, false>), grid, dim3(256), (unsigned)tuning(5), st, a);
+        break;
+    }
+    if (const hipError_t e = hipGetLastError()) return (int)e;
   }
+  a.item0 = 0;
   if (ev_stop)
     if (const hipError_t e = hipEventRecord(ev_stop, st)) return (int)e;
   if (fused) {          // rows whose window was not complete in time (normally none) and the rows of the last `lag` windows

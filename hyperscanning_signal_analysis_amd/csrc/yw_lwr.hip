@@ -84,4 +84,20 @@ int launch_yw_lwr(const YwArgs& a, int m_pad, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
+// Windows of the default form that one compute unit holds at once, asked of the runtime (registers and LDS of the build in
+// use decide it, not a constant here); the sliding step sizes its K2 -> K3 hand-over by it (capi.hip).  0: not known.
+int yw_lwr_occupancy(int m_pad) {
+  if (tuning(4 /* HMV_TUNE_YW_FORM */) == 3 || tuning(4) == 4) return 0;
+  int occ = 0;
+  hipError_t e = hipErrorInvalidValue;
+  switch (m_pad) {
+    case 16: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, yw_lwr_kernel<1, false>, 256, 0); break;
+    case 32: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, yw_lwr_kernel<2, false>, 256, 0); break;
+    case 48: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, yw_lwr_kernel<3, false>, 256, 0); break;
+    case 64: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, yw_lwr_kernel<4, false>, 256, 0); break;
+    default: return 0;
+  }
+  return (e == hipSuccess && occ > 0) ? occ : 0;
+}
+
 }  // namespace hmv

@@ -38,7 +38,7 @@ int hmv_pad(int m);
 /* Tuning knobs (process-wide; never needed for correct results -- every setting gives the same numbers up to the
  * documented bit-identity classes).  They replace the environment variables that earlier builds read inside the
  * launch path: the environment is looked at ONCE, when the library is loaded (HYPERMVAR_NORM_LAG,
- * HYPERMVAR_LAG_GROUP, HYPERMVAR_K3_FORM, HYPERMVAR_YW_FORM), and hmv_set_tuning overrides it afterwards.
+ * HYPERMVAR_LAG_GROUP, HYPERMVAR_K3_FORM, HYPERMVAR_YW_FORM, HYPERMVAR_K3_SPLIT), and hmv_set_tuning overrides it afterwards.
  *   HMV_TUNE_NORM_LAG   windows between a K3 workgroup and the window whose rows it normalises (0 = built-in rule, >= 8)
  *   HMV_TUNE_LAG_GROUP  lags per K1 workgroup (1..3; 0 = default 3)
  *   HMV_TUNE_K3_FORM    0 = default, 1 = compiler-scheduled K3 body, 2 = hand-scheduled 64-channel K3 body
@@ -48,12 +48,17 @@ int hmv_pad(int m);
  *                       always emitted (same bits; the form the tests hold the default against)
  *   HMV_TUNE_K3_LDS_PAD bytes of unused dynamic LDS added to every K3 workgroup (measurement only: fewer resident
  *                       workgroups per CU, to separate latency from throughput; 0 = none)
+ *   HMV_TUNE_K3_SPLIT   the fused ffDTF calls with a second stream: where a chunk's K2 -> K3 hand-over is split, so that K3
+ *                       starts on the chunk's first windows while K2 finishes the rest on the second stream.  0 = by rule
+ *                       (the windows past the last full round of one K2 workgroup per compute unit), -1 = never,
+ *                       n > 0 = after the chunk's first n windows (same bits at every setting)
  * Returns 0, or -1 for an unknown key / value out of range.  hmv_get_tuning returns the value in force (-1: unknown key). */
 #define HMV_TUNE_NORM_LAG 1
 #define HMV_TUNE_LAG_GROUP 2
 #define HMV_TUNE_K3_FORM 3
 #define HMV_TUNE_YW_FORM 4
 #define HMV_TUNE_K3_LDS_PAD 5
+#define HMV_TUNE_K3_SPLIT 6
 int hmv_set_tuning(int key, int64_t value);
 int64_t hmv_get_tuning(int key);
 /* Number of doubles of K2 scratch per item. */
@@ -228,12 +233,14 @@ int hmv_tf_ffdtf_bands_f64(const double* ar, int64_t n_items, int m, int p, cons
  * (item_rec / item_start must say the same; they are still what every other stage and the direct form read) and
  * that recordings are grid_T samples long.  Taken when n is 2..8 whole hops; grid_hop = 0: arbitrary windows.
  * ev_k3_start / ev_k3_stop (optional hipEvent_t, NULL to skip) are recorded on `stream` right before
- * and after the LAST chunk's K3 launch, so a caller can time the dominant kernel inside its own timed
- * region without an extra synchronisation.
- * aux_stream (optional second hipStream_t, NULL to disable; used by the tiled form of K2 only): a chain of dependent
+ * and after the LAST chunk's K3 launch (both launches and what lies between them where K3 comes in two, see
+ * aux_stream), so a caller can time the dominant kernel inside its own timed region without an extra synchronisation.
+ * aux_stream (optional second hipStream_t, NULL to disable).  The tiled form of K2 is a chain of dependent
  * launches that cannot fill the chip -- it runs as two half-batches, one per stream (fork
- * after K1, join before K3), so their launches interleave on the device; the call still behaves as one
- * operation on `stream`. */
+ * after K1, join before K3), so their launches interleave on the device.  The default form of K2, when only the
+ * ffDTF is asked for (no ar_out / V_out), uses it for the windows of its last, partly filled round: they are solved
+ * on aux_stream while K3 already runs on the windows before them (HMV_TUNE_K3_SPLIT; same bits).  Either way the
+ * call still behaves as one operation on `stream`. */
 int64_t hmv_sliding_workspace_bytes(int64_t chunk, int m, int p, int F);
 int hmv_sliding_ffdtf_f64(const double* x, int64_t rec_stride, int64_t ld,
                           const int64_t* item_rec, const int64_t* item_start, int64_t n_items,
