@@ -20,7 +20,7 @@ from typing import Callable
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, significance
 
 __all__ = ["Engine", "default_engine", "SingularMatrixError", "validate_items", "validate_trials"]
 
@@ -928,94 +928,9 @@ class Engine:
         one entry per item.  chunk: items (surrogate x item) per block (default `ensemble_significance_chunk`); where
         the items of one surrogate exceed it, a block holds whole groups of one surrogate.  The results are the same
         bits for any chunk.  p=None raises ValueError (no automatic order for ensembles)."""
-        from . import surrogates as sg
-        if p is None:
-            raise ValueError(_NO_ENSEMBLE_ORDER)
-        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
-        x = x if x.stride(2) == 1 else x.contiguous()
-        n_rec, m, T = x.shape
-        n, p = int(n), int(p)
-        S, split, _ = sg.significance_args(measure, "trial", n_surrogates, m, T, n, split)
-        if check is not True and check != "nan":
-            raise ValueError(f"check must be True or 'nan', got {check!r}")
-        self.pad(m)
-        validate_trials(x, trial_rec, trial_start, group_ptr, item_group, item_offset, n, p)
-        gp = group_ptr.cpu().numpy()
-        counts = np.diff(gp)
-        G, N = len(counts), int(item_group.numel())
-        self._ensemble_grid(G, (item_group, item_offset), N, grid, True)       # checked once, for both observed calls
-        f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
-        F = int(f.numel())
-        lo, hi = (np.asarray(b, dtype=np.int32) for b in bands)
-        nb = int(lo.size)
-        if nb < 1:
-            raise ValueError("ensemble_significance needs at least one band")
-        self.band_tables(lo, hi, F)
-        perms = sg.trial_permutations(np.random.default_rng(seed), S, counts)     # (also: every group has >= 2 trials)
-        tested_h = sg.tested_mask(m, "trial", split)
-        tested = torch.as_tensor(tested_h.astype(np.uint8)).to(self.device)
-        res = {"tested": torch.as_tensor(tested_h).to(self.device)}
-        if N == 0:
-            for k in ("observed", "p", "p_fwe", "null_mean", "null_std"):
-                res[k] = self.empty(0, m, m, nb)
-            res["n_valid"] = self.empty(0, dtype=torch.int32)
-            return res
-        ens = (x, trial_rec, trial_start, group_ptr, item_group, item_offset, n, p)
-        obs = self.sliding_ensemble(*ens, f, fs, measure=measure, bands=(lo, hi), grid=grid, validate=False,
-                                    check=True if check is True else "mask")
-        obs, obs_bad = (obs, None) if check is True else obs
-        R_base = self.lagcov_ensemble(*ens, grid=grid, validate=False)
-        # table B of every surrogate: the trials of each group in the order of its permutation
-        rec_h, start_h = trial_rec.cpu().numpy(), trial_start.cpu().numpy()
-        src = np.stack([np.concatenate([gp[g] + perms[s][g] for g in range(G)]) for s in range(S)])       # (S, trials)
-        rec_b = torch.as_tensor(rec_h[src]).to(self.device)
-        start_b = torch.as_tensor(start_h[src]).to(self.device)
-        # the items group-major (a stable sort: nothing moves where they already are), so that a block of whole groups is
-        # a contiguous run of items and of the running state
-        order = torch.argsort(item_group, stable=True)
-        grp, offs = item_group[order].contiguous(), item_offset[order].contiguous()
-        first = np.searchsorted(grp.cpu().numpy(), np.arange(G + 1))           # items of group g: first[g] .. first[g+1]
-        obs_s = obs[order].contiguous()
-        chunk = self.ensemble_significance_chunk(measure, m, n, p, F, nb) if chunk is None else max(1, int(chunk))
-        if N <= chunk:
-            Sb, blocks = min(S, chunk // N), [(0, G)]
-        else:                                   # whole groups of one surrogate, as many as fit (at least one)
-            Sb, blocks, g0 = 1, [], 0
-            while g0 < G:
-                g1 = g0 + 1
-                while g1 < G and first[g1 + 1] - first[g0] <= chunk:
-                    g1 += 1
-                blocks.append((g0, g1))
-                g0 = g1
-        st = self.null_state(N, m, nb)
-        i64 = dict(dtype=torch.int64, device=self.device)
-        for s0 in range(0, S, Sb):
-            sb = min(Sb, S - s0)
-            for g0, g1 in blocks:
-                i0, i1, e0, e1 = int(first[g0]), int(first[g1]), int(gp[g0]), int(gp[g1])
-                wb, gb = i1 - i0, g1 - g0
-                if wb == 0:
-                    continue
-                srep = torch.arange(sb, **i64).repeat_interleave(wb)
-                d = dict(trial_rec=trial_rec[e0:e1].repeat(sb), trial_start=trial_start[e0:e1].repeat(sb),
-                         group_ptr=torch.as_tensor(np.concatenate([[0], np.cumsum(np.tile(counts[g0:g1], sb))]), **i64),
-                         item_group=(grp[i0:i1] - g0).repeat(sb) + srep * gb, item_offset=offs[i0:i1].repeat(sb))
-                shuffle = (rec_b[s0:s0 + sb, e0:e1].reshape(-1).contiguous(), start_b[s0:s0 + sb, e0:e1].reshape(-1).contiguous(),
-                           split, R_base, order[i0:i1].repeat(sb))
-                rt = self._ensemble_route(measure, n, p, d["trial_rec"], d["trial_start"], d["group_ptr"], shuffle=shuffle)
-                vals, bad = self._sliding_call(rt, x, (d["item_group"], d["item_offset"]), f, fs, bands=(lo, hi), check="mask",
-                                               chunk=min(sb * wb, chunk), validate=False)
-                sub = {k: v[i0:i1] for k, v in st.items()}                 # item-major: contiguous views
-                self.null_accumulate(obs_s[i0:i1], vals, bad, tested, sub, s0 + sb >= S, sb)
-        inv = torch.empty_like(order)
-        inv[order] = torch.arange(N, **i64)
-        res.update(observed=obs, n_valid=st["n_valid"][inv])
-        for k in ("p", "p_fwe", "null_mean", "null_std"):
-            res[k] = st[k][inv]
-        if obs_bad is not None and bool(obs_bad.any()):
-            for k in ("observed", "p", "p_fwe", "null_mean", "null_std"):
-                res[k][obs_bad] = float("nan")
-        return res
+        return significance.ensemble_significance(self, x, trial_rec, trial_start, group_ptr, item_group, item_offset, n, p,
+                                                  freqs, fs, bands, measure=measure, n_surrogates=n_surrogates, seed=seed,
+                                                  split=split, check=check, chunk=chunk, grid=grid)
 
     # ------------------------------------------------------------------ condition contrast of ensembles (lagcov_mix.hip)
     def lagcov_trials(self, x: torch.Tensor, trial_rec: torch.Tensor, trial_start: torch.Tensor, offsets: torch.Tensor, n: int,
@@ -1148,132 +1063,9 @@ class Engine:
         Returns a dict of device tensors: observed (= D), observed_a, observed_b, p, p_fwe, null_mean, null_std (G, W, m, m,
         n_bands), n_valid (G, W) int32, tested (m, m) bool and, where built, group = {observed, p, p_fwe, null_mean,
         null_std (W, m, m, n_bands), n_valid (W,)}."""
-        from . import surrogates as sg
-        if p is None:
-            raise ValueError(_NO_ENSEMBLE_ORDER)
-        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
-        x = x if x.stride(2) == 1 else x.contiguous()
-        n_rec, m, T = x.shape
-        n, p = int(n), int(p)
-        mp = self.pad(m)
-        i64 = dict(dtype=torch.int64, device=self.device)
-        if not (isinstance(cond, torch.Tensor) and cond.dim() == 1 and cond.numel() == trial_rec.numel()
-                and not cond.dtype.is_floating_point):
-            raise ValueError("cond must be a 1-D integer tensor with one entry per trial")
-        gp = group_ptr.cpu().numpy()
-        G, W = len(gp) - 1, int(offsets.numel())
-        validate_trials(x, trial_rec, trial_start, group_ptr, torch.arange(G, **i64).repeat_interleave(W), offsets.repeat(G), n, p)
-        cond_h = cond.cpu().numpy().astype(np.int64)
-        if ((cond_h != 0) & (cond_h != 1)).any():
-            raise ValueError("cond must hold 0 (condition A) or 1 (condition B)")
-        counts_a = [int((cond_h[gp[g]:gp[g + 1]] == 0).sum()) for g in range(G)]
-        counts_b = [int((cond_h[gp[g]:gp[g + 1]] == 1).sum()) for g in range(G)]
-        S, split = sg.contrast_args(measure, n_surrogates, m, tail, split, check, bands, counts_a, counts_b)
-        self._ensemble_grid(1, (torch.zeros(W, **i64), offsets), W, grid, True)
-        f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
-        F = int(f.numel())
-        lo, hi = (np.asarray(b, dtype=np.int32) for b in bands)
-        nb = int(lo.size)
-        self.band_tables(lo, hi, F)
-        draws = sg.label_draws(np.random.default_rng(seed), S, counts_a, counts_b)
-        tested_h = sg.tested_mask(m, "phase" if split is None else "shift", 0 if split is None else split)
-        tested = torch.as_tensor(tested_h.astype(np.uint8)).to(self.device)
-        res = {"tested": torch.as_tensor(tested_h).to(self.device)}
-        stats = ("p", "p_fwe", "null_mean", "null_std")
-        want_group = (G >= 2) if group is None else bool(group)
-        stat = {"two-sided": torch.abs, "greater": lambda d: d, "less": torch.neg}[tail]
-        if W == 0:
-            res.update({k: self.empty(G, 0, m, m, nb) for k in ("observed", "observed_a", "observed_b") + stats},
-                       n_valid=self.empty(G, 0, dtype=torch.int32))
-            if want_group:
-                res["group"] = dict({k: self.empty(0, m, m, nb) for k in ("observed",) + stats},
-                                    n_valid=self.empty(0, dtype=torch.int32))
-            return res
-        chunk = self.ensemble_contrast_chunk(measure, m, p, F, nb) if chunk is None else max(1, int(chunk))
-        st = self.null_state(G * W, m, nb)
-        obs_ab = self.empty(2, G, W, m, m, nb)
-        obs_bad = torch.zeros(G, W, dtype=torch.bool, device=self.device)
-        if want_group:
-            gsum = self.empty(S, W, m, m, nb)
-            gbad = torch.zeros(S, W, dtype=torch.bool, device=self.device)
-        per_window = (p + 1) * mp * mp * 8
-        for g in range(G):
-            e0, e1, EA, EB = int(gp[g]), int(gp[g + 1]), counts_a[g], counts_b[g]
-            E = EA + EB
-            pool = torch.as_tensor(e0 + np.argsort(cond_h[e0:e1], kind="stable")).to(self.device)      # A's trials, then B's
-            rec_g, start_g = trial_rec[pool].contiguous(), trial_start[pool].contiguous()
-            # weight rows: 2 s = the trials relabelled A in surrogate s, 2 s + 1 = the others; the observed labels alike
-            Wh = np.zeros((2 * S + 2, E))
-            for s in range(S + 1):
-                a = np.arange(EA) if s == S else draws[s][g]
-                Wh[2 * s, a] = 1.0
-                Wh[2 * s + 1] = 1.0 - Wh[2 * s]
-            Wd = self.to_device(Wh)
-            sc = self.to_device(np.tile([1.0 / EA, 1.0 / EB], S + 1))
-            Wb = W if E * W * per_window <= self.max_workspace_bytes // 2 else \
-                max(1, (self.max_workspace_bytes // 2) // (E * per_window))
-            for w0 in range(0, W, Wb):
-                w1 = min(W, w0 + Wb)
-                wb = w1 - w0
-                if grid is not None:        # a block of a regular grid is a regular grid that starts offsets[w0] later
-                    Rt = self.lagcov_trials(x, rec_g, start_g + int(grid[0]) * w0, offsets[:wb], n, p, grid=(int(grid[0]), wb),
-                                            validate=False)
-                else:
-                    Rt = self.lagcov_trials(x, rec_g, start_g, offsets[w0:w1].contiguous(), n, p, validate=False)
-                run = dict(m=m, measure=measure, bands=(lo, hi), validate=False)
-                try:
-                    o = self.sliding_mix(Rt, Wd[2 * S:], sc[2 * S:], n, f, fs, check=True if check is True else "mask",
-                                         chunk=min(chunk, 2 * wb), **run)
-                except SingularMatrixError as err:
-                    err.group, err.windows = g, err.windows + w0
-                    err.args = (err.args[0], err.args[1] + f" (group {g}, condition {'AB'[int(err.rows[0])]}, window "
-                                f"{int(err.windows[0])} of the observed labels)")
-                    raise
-                if check is not True:
-                    o, bad = o
-                    obs_bad[g, w0:w1] = bad.view(2, wb).any(dim=0)
-                obs_ab[:, g, w0:w1] = o.view(2, wb, m, m, nb)
-                obs_d = o[:wb] - o[wb:]
-                obs_t = stat(obs_d)
-                sub = {k: v[g * W + w0:g * W + w1] for k, v in st.items()}         # contiguous views
-                Sb = max(1, min(S, chunk // (2 * wb)))
-                for s0 in range(0, S, Sb):
-                    sb = min(Sb, S - s0)
-                    vals, bad = self.sliding_mix(Rt, Wd[2 * s0:2 * (s0 + sb)], sc[2 * s0:2 * (s0 + sb)], n, f, fs, check="mask",
-                                                 chunk=min(chunk, 2 * sb * wb), **run)
-                    vals, bad = vals.view(sb, 2, wb, m, m, nb), bad.view(sb, 2, wb).any(dim=1)
-                    d = vals[:, 0] - vals[:, 1]
-                    self.null_accumulate(obs_t, stat(d).view(sb * wb, m, m, nb), bad.reshape(sb * wb), tested, sub,
-                                         s0 + sb >= S, sb)
-                    if want_group:
-                        if g == 0:
-                            gsum[s0:s0 + sb, w0:w1] = d
-                        else:
-                            gsum[s0:s0 + sb, w0:w1] += d
-                        gbad[s0:s0 + sb, w0:w1] |= bad
-        res.update(observed=obs_ab[0] - obs_ab[1], observed_a=obs_ab[0], observed_b=obs_ab[1], n_valid=st["n_valid"].view(G, W))
-        for k in stats:
-            res[k] = st[k].view(G, W, m, m, nb)
-        any_bad = check is not True and bool(obs_bad.any())
-        if any_bad:
-            for k in ("observed", "observed_a", "observed_b") + stats:
-                res[k][obs_bad] = float("nan")
-        if want_group:
-            gobs = obs_ab[0, 0] - obs_ab[1, 0]
-            for g in range(1, G):                           # the order of the surrogates' sums
-                gobs = gobs + (obs_ab[0, g] - obs_ab[1, g])
-            gobs = gobs / G
-            gst = self.null_state(W, m, nb)
-            self.null_accumulate(stat(gobs), stat(gsum / G).view(S * W, m, m, nb), gbad.view(S * W), tested, gst, True, S)
-            grp = {"observed": gobs, "n_valid": gst["n_valid"]}
-            for k in stats:
-                grp[k] = gst[k]
-            if any_bad:
-                bad_w = obs_bad.any(dim=0)
-                for k in ("observed",) + stats:
-                    grp[k][bad_w] = float("nan")
-            res["group"] = grp
-        return res
+        return significance.ensemble_contrast(self, x, trial_rec, trial_start, group_ptr, cond, offsets, n, p, freqs, fs, bands,
+                                              measure=measure, n_surrogates=n_surrogates, seed=seed, tail=tail, split=split,
+                                              group=group, check=check, chunk=chunk, grid=grid)
 
     # ------------------------------------------------------------------ pairs of recordings, pseudo-dyad significance
     def _check_pairs(self, x, n_items, p, split, R_base, base_a, base_b):
@@ -1397,84 +1189,8 @@ class Engine:
         Returns a dict of device tensors: observed, p, p_fwe, null_mean, null_std (D, W, m, m, n_bands), n_valid (D, W) int32,
         tested (m, m) bool, partners (S, D) int64 and group = {observed, p, p_fwe, null_mean, null_std (W, m, m, n_bands),
         n_valid (W,)}."""
-        from . import surrogates as sg
-        no_auto_order(p, "pseudo_dyad_significance")
-        D, m, T = x.shape
-        n, p = int(n), int(p)
-        S, split = sg.pseudo_dyad_args(measure, D, m, n_surrogates, seed, split, check)
-        lo, hi = (np.asarray(b, dtype=np.int32) for b in (bands if bands is not None else ((), ())))
-        nb = int(lo.size)
-        if nb < 1:
-            raise ValueError("pseudo_dyad_significance needs at least one band")
-        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
-        x = x if x.stride(2) == 1 else x.contiguous()
-        self.pad(m)
-        W = int(item_start.numel())
-        i64 = dict(dtype=torch.int64, device=self.device)
-        dy = torch.arange(D, **i64).repeat_interleave(W)                  # item (d, w) = d * W + w: its dyad ...
-        starts = item_start.repeat(D) if isinstance(item_start, torch.Tensor) else item_start
-        self.check_items(x, dy, starts, n, p)
-        f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
-        F = int(f.numel())
-        self.band_tables(lo, hi, F)
-        partners = sg.partner_derangements(None if S is None else np.random.default_rng(seed), S, D)
-        S = int(partners.shape[0])
-        tested_h = sg.tested_mask(m, "shift", split)
-        tested = torch.as_tensor(tested_h.astype(np.uint8)).to(self.device)
-        res = {"tested": torch.as_tensor(tested_h).to(self.device), "partners": torch.as_tensor(partners).to(self.device)}
-        stats = ("p", "p_fwe", "null_mean", "null_std")
-        if W == 0:
-            res.update({k: self.empty(D, 0, m, m, nb) for k in ("observed",) + stats}, n_valid=self.empty(D, 0, dtype=torch.int32))
-            res["group"] = dict({k: self.empty(0, m, m, nb) for k in ("observed",) + stats},
-                                n_valid=self.empty(0, dtype=torch.int32))
-            return res
-        N = D * W
-        run = {"ffdtf": self.sliding_ffdtf, "ddtf": self.sliding_ddtf, "gpdc": self.sliding_gpdc}[measure]
-        obs = run(x, dy, starts, n, p, f, fs, bands=(lo, hi), check=True if check is True else "mask", validate=False)
-        obs, obs_bad = (obs, None) if check is True else obs
-        # (K1 over the D W real windows a second time -- the fused call above does not hand its R out; a few per cent of it)
-        R_base = self.lagcov(x, dy, starts, n, p)
-        base_a = torch.arange(N, **i64)
-        wrep = torch.arange(W, **i64).repeat(D)
-        blk = N if chunk is None else max(1, min(N, int(chunk)))
-        st = self.null_state(N, m, nb)
-        gmean = self.empty(S, W, m, m, nb)
-        gbad = torch.empty(S, W, dtype=torch.bool, device=self.device)
-        both = self.empty(2, N, m, m, nb)                                   # the two surrogates one s gives every dyad
-        both_bad = torch.empty(2, N, dtype=torch.bool, device=self.device)
-        for s in range(S):
-            pi = torch.as_tensor(partners[s]).to(self.device)
-            inv = torch.empty_like(pi)
-            inv[pi] = torch.arange(D, **i64)
-            rec_b = pi[dy].contiguous()
-            base_b = (rec_b * W + wrep).contiguous()
-            for i0 in range(0, N, blk):
-                sl = slice(i0, min(N, i0 + blk))
-                _, bad = self.sliding_pairs(x, dy[sl], rec_b[sl], starts[sl], n, p, f, fs, measure=measure, split=split,
-                                            bands=(lo, hi), R_base=R_base, base_a=base_a[sl], base_b=base_b[sl],
-                                            out=both[0, sl], check="mask", validate=False)
-                both_bad[0, sl] = bad
-            # whole surrogates only: the B-anchored value of dyad d is the item of dyad pi^-1(d), wherever its block was
-            both[1] = both[0].view(D, W, m, m, nb)[inv].view(N, m, m, nb)
-            both_bad[1] = both_bad[0].view(D, W)[inv].view(N)
-            self.null_accumulate(obs, both.view(2 * N, m, m, nb), both_bad.view(2 * N), tested, st, s == S - 1, 2)
-            gmean[s] = both[0].view(D, W, m, m, nb).mean(dim=0)
-            gbad[s] = both_bad[0].view(D, W).any(dim=0)
-        gobs = obs.view(D, W, m, m, nb).mean(dim=0)
-        gst = self.null_state(W, m, nb)
-        self.null_accumulate(gobs, gmean.view(S * W, m, m, nb), gbad.view(S * W), tested, gst, True, S)
-        res.update(observed=obs.view(D, W, m, m, nb), n_valid=st["n_valid"].view(D, W))
-        group = {"observed": gobs, "n_valid": gst["n_valid"]}
-        for k in stats:
-            res[k] = st[k].view(D, W, m, m, nb)
-            group[k] = gst[k]
-        if obs_bad is not None and bool(obs_bad.any()):
-            bad_dw, bad_w = obs_bad.view(D, W), obs_bad.view(D, W).any(dim=0)
-            for k in ("observed",) + stats:
-                res[k][bad_dw] = float("nan")
-                group[k][bad_w] = float("nan")
-        res["group"] = group
-        return res
+        return significance.pseudo_dyad_significance(self, x, item_start, n, p, freqs, fs, bands, measure=measure, split=split,
+                                                     n_surrogates=n_surrogates, seed=seed, check=check, chunk=chunk)
 
     # ------------------------------------------------------------------ surrogate significance (surrogate.hip)
     def surrogate_shift(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, shift: torch.Tensor,
@@ -1568,77 +1284,9 @@ class Engine:
         grid: (hop, first, n_win) for the OBSERVED call only (`sliding_ffdtf(grid=...)`); the surrogates are separate
         recordings.  Returns a dict of device tensors: observed, p, p_fwe, null_mean, null_std (W, m, m, n_bands),
         n_valid (W,) int32, tested (m, m) bool."""
-        from . import surrogates as sg
-        no_auto_order(p, "sliding_significance")
-        if null in sg.ENSEMBLE_NULLS:
-            raise ValueError(f"null={null!r} is the test of event-locked ensembles (ensemble_significance); "
-                             f"sliding_significance takes one of {sg.NULLS}")
-        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
-        x = x if x.stride(2) == 1 else x.contiguous()
-        n_rec, m, T = x.shape
-        n = int(n)
-        S, split, min_shift = sg.significance_args(measure, null, n_surrogates, m, T, n, split, min_shift)
-        if check is not True and check != "nan":
-            raise ValueError(f"check must be True or 'nan', got {check!r}")
-        self.pad(m)
-        self.check_items(x, item_rec, item_start, n, p)
-        W = int(item_rec.numel())
-        f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
-        F = int(f.numel())
-        lo, hi = (np.asarray(b, dtype=np.int32) for b in bands)
-        nb = int(lo.size)
-        if nb < 1:
-            raise ValueError("sliding_significance needs at least one band")
-        self.band_tables(lo, hi, F)
-        tested_h = sg.tested_mask(m, null, split)
-        tested = torch.as_tensor(tested_h.astype(np.uint8)).to(self.device)
-        run = {"ffdtf": self.sliding_ffdtf, "ddtf": self.sliding_ddtf, "gpdc": self.sliding_gpdc}[measure]
-        res = {"tested": torch.as_tensor(tested_h).to(self.device)}
-        if W == 0:
-            for k in ("observed", "p", "p_fwe", "null_mean", "null_std"):
-                res[k] = self.empty(0, m, m, nb)
-            res["n_valid"] = self.empty(0, dtype=torch.int32)
-            return res
-        if check is True:
-            obs = run(x, item_rec, item_start, n, p, f, fs, bands=(lo, hi), check=True, grid=grid)
-            obs_bad = None
-        else:
-            obs, obs_bad = run(x, item_rec, item_start, n, p, f, fs, bands=(lo, hi), check="mask", grid=grid)
-        rng = np.random.default_rng(seed)
-        if null == "shift":
-            d_all = torch.as_tensor(sg.shift_offsets(rng, S, n_rec, T, min_shift)).to(self.device)
-        else:
-            spec = self.window_spectra(x, item_rec, item_start, n)
-        chunk = self.significance_chunk(measure, null, W, m, n, p, F, nb) if chunk is None else max(1, int(chunk))
-        Wb = min(W, chunk)
-        Sb = min(S, max(1, chunk // W)) if Wb == W else 1
-        st = self.null_state(W, m, nb)
-        zeros = None
-        for s0 in range(0, S, Sb):
-            sb = min(Sb, S - s0)
-            if null == "phase":
-                phi = torch.as_tensor(sg.phase_draws(rng, sb, m, n)).to(self.device)
-            for w0 in range(0, W, Wb):
-                wb = min(Wb, W - w0)
-                ws = slice(w0, w0 + wb)
-                if null == "shift":
-                    xs = self.surrogate_shift(x, item_rec[ws], item_start[ws], n, d_all[s0:s0 + sb], split)
-                else:
-                    xs = self.surrogate_phase(spec[ws], phi, n)
-                items = sb * wb
-                if zeros is None or zeros.numel() < items:
-                    zeros = torch.zeros(items, dtype=torch.int64, device=self.device)
-                    ar_items = torch.arange(items, dtype=torch.int64, device=self.device)
-                vals, bad = run(xs.view(items, m, n), ar_items[:items], zeros[:items], n, p, f, fs, bands=(lo, hi),
-                                check="mask", validate=False)
-                sub = {k: v[ws] for k, v in st.items()}               # window-major: contiguous views
-                self.null_accumulate(obs[ws], vals, bad, tested, sub, s0 + sb >= S, sb)
-        res.update(observed=obs, p=st["p"], p_fwe=st["p_fwe"], null_mean=st["null_mean"], null_std=st["null_std"],
-                   n_valid=st["n_valid"])
-        if obs_bad is not None and bool(obs_bad.any()):
-            for k in ("observed", "p", "p_fwe", "null_mean", "null_std"):
-                res[k][obs_bad] = float("nan")
-        return res
+        return significance.sliding_significance(self, x, item_rec, item_start, n, p, freqs, fs, bands, measure=measure,
+                                                 null=null, n_surrogates=n_surrogates, seed=seed, split=split,
+                                                 min_shift=min_shift, check=check, chunk=chunk, grid=grid)
 
     # ------------------------------------------------------------------ recordings streamed from the host
     def stream_dyads(self, dyads, n: int, positions, p: int, freqs, fs: float, bands=None, reduce=None, depth: int = 3,

@@ -1,6 +1,7 @@
-"""Host side of the surrogate significance tests (`Engine.sliding_significance`, `Engine.ensemble_significance`,
-`Engine.pseudo_dyad_significance`, `Engine.ensemble_contrast`): argument checks, the random draws and the tested family.  Pure NumPy, so that every
-surrogate can be rebuilt on the host from the seed.
+"""Host side of the surrogate significance tests: argument checks, the random draws and the tested family.  Pure NumPy,
+so that every surrogate can be rebuilt on the host from the seed.  The draws are consumed by `significance.py`, which
+drives the four tests (`Engine.sliding_significance`, `.ensemble_significance`, `.pseudo_dyad_significance`,
+`.ensemble_contrast`); where and how often each is drawn relative to the others is part of the result's bits.
 
 All randomness comes from `rng = numpy.random.default_rng(seed)`, in this order:
     null="shift":  d = rng.integers(min_shift, T - min_shift, size=(S, n_rec), endpoint=True)        (once)
@@ -20,8 +21,9 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["NULLS", "ENSEMBLE_NULLS", "MEASURES", "significance_args", "shift_offsets", "phase_draws",
-           "trial_permutations", "label_draws", "contrast_args", "TAILS", "partner_count", "partner_derangements", "pseudo_dyad_args", "tested_mask", "check_significance_dict"]
+__all__ = ["NULLS", "ENSEMBLE_NULLS", "MEASURES", "TAILS", "significance_args", "shift_offsets", "phase_draws",
+           "trial_permutations", "label_draws", "contrast_args", "partner_count", "partner_derangements", "pseudo_dyad_args",
+           "tested_mask", "check_significance_dict"]
 
 NULLS = ("shift", "phase")          # of continuous recordings (`sliding_significance`)
 ENSEMBLE_NULLS = ("trial",)         # of event-locked ensembles (`ensemble_significance`)
