@@ -81,6 +81,13 @@ SIGNATURES = {
                                      c_int, c_double, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p,
                                      c_void_p]),
+    "hmv_block_gc_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int, c_int]),
+    "hmv_block_gc_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_double, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "hmv_block_gc_sliding_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int, c_int, c_int]),
+    "hmv_sliding_block_gc_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
+                                         c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 7 +
+                                 [c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p]),
     "hmv_yw_solve_auto_f64": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int] + [c_void_p] * 7 + [c_int64, c_void_p]),
     "hmv_sliding_auto_workspace_bytes": (c_int64, [c_int, c_int64, c_int, c_int, c_int, c_int]),
     "hmv_sliding_auto_f64": (c_int, [c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,

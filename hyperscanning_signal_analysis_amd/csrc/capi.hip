@@ -596,7 +596,9 @@ int hmv_tf_ffdtf_bands_f64(const double* ar, int64_t n_items, int m, int p, cons
 // ---- fused sliding-window path ----------------------------------------------------------------------
 namespace {
 // what the fused call computes on top of K1 / K2: ffDTF (K3), dDTF (K3 + sliding_conn.hip), GPDC (sliding_conn.hip only)
-enum Measure { MEAS_FFDTF = 0, MEAS_DDTF = 1, MEAS_GPDC = 2 };
+// (MEAS_BGC, block Granger causality, is internal to hmv_sliding_block_gc_f64: not one of the public HMV_MEASURE_* codes,
+// its output is not an (m, m, F) array)
+enum Measure { MEAS_FFDTF = 0, MEAS_DDTF = 1, MEAS_GPDC = 2, MEAS_BGC = 3 };
 struct SlidingWs {
   size_t off_R, off_Q, off_ws, off_ar, off_V, off_tf, off_den, off_tw, off_H, off_B, off_G, off_full, total;
 };
@@ -613,7 +615,7 @@ SlidingWs sliding_layout(int64_t chunk, int mp, int p, int F, bool bands = false
   w.off_ar = o;     o += align256(sizeof(double) * chunk * t * p);
   w.off_V = o;      o += align256(sizeof(double) * chunk * t);
   w.off_tf = o;
-  if (measure != MEAS_GPDC) o += tf_ff_layout(chunk, mp, p, F, bands && measure == MEAS_FFDTF).total;
+  if (measure == MEAS_FFDTF || measure == MEAS_DDTF) o += tf_ff_layout(chunk, mp, p, F, bands && measure == MEAS_FFDTF).total;
   w.off_den = o;    o += align256(sizeof(double) * chunk * mp);
   w.off_tw = o;     o += align256(sizeof(double) * F * p * 2);
   w.off_H = o;
@@ -623,7 +625,31 @@ SlidingWs sliding_layout(int64_t chunk, int mp, int p, int F, bool bands = false
   w.off_G = o;
   if (measure == MEAS_DDTF) o += align256(sizeof(double) * chunk * (2 * p + 1) * t);
   w.off_full = o;
-  if (measure != MEAS_FFDTF && bands) o += align256(sizeof(double) * chunk * (mp * mp) * F);
+  if ((measure == MEAS_DDTF || measure == MEAS_GPDC) && bands) o += align256(sizeof(double) * chunk * (mp * mp) * F);
+  w.total = o;
+  return w;
+}
+// What block Granger causality adds behind the shared front (K1 / K2 scratch, twiddles): the stage's own scratch, the two
+// restricted lag-covariance stacks and fits, and (band form) the chunk's full spectral array.  `front` = where it starts.
+struct BgcWs {
+  size_t off_B, off_C, off_D, off_cst, off_Ra, off_Rb, off_arr, off_Vra, off_Vrb, off_ir, off_full, total;
+};
+BgcWs bgc_layout(size_t front, int64_t chunk, int m, int p, int F, int split, bool bands, bool time) {
+  BgcWs w;
+  size_t o = front;
+  const hmv::BgcPads pd = hmv::bgc_pads(m, split);
+  const size_t mp = (size_t)pad_of(m), mpa = (size_t)pd.mpa, mpb = (size_t)pd.mpb, nsp = (size_t)pd.nsp, pp = (size_t)p + 1;
+  w.off_B = o;      o += align256(sizeof(double) * chunk * pp * mp * mp);
+  w.off_C = o;      o += align256(sizeof(double) * chunk * 2 * pp * nsp * nsp);
+  w.off_D = o;      o += align256(sizeof(double) * chunk * 2 * pp * nsp * nsp);
+  w.off_cst = o;    o += align256(sizeof(double) * chunk * 2);
+  w.off_Ra = o;     if (time) o += align256(sizeof(double) * chunk * pp * mpa * mpa);
+  w.off_Rb = o;     if (time) o += align256(sizeof(double) * chunk * pp * mpb * mpb);
+  w.off_arr = o;    if (time) o += align256(sizeof(double) * chunk * nsp * nsp * p);
+  w.off_Vra = o;    if (time) o += align256(sizeof(double) * chunk * mpa * mpa);
+  w.off_Vrb = o;    if (time) o += align256(sizeof(double) * chunk * mpb * mpb);
+  w.off_ir = o;     if (time) o += align256(sizeof(int32_t) * chunk * 2);
+  w.off_full = o;   if (bands) o += align256(sizeof(double) * chunk * 2 * F);
   w.total = o;
   return w;
 }
@@ -719,6 +745,14 @@ struct MixDesc {
   const double* scale;
   int64_t n_trials, n_win, n_mix;
 };
+// Block Granger causality in place of an (m, m, F) measure (hmv_sliding_block_gc_f64): K1 and K2 as for every entry, then
+// the two restricted fits from the same lag covariances and the kernels of block_gc.hip; there is no K3.
+struct BgcDesc {
+  int split;
+  double* time;                                     // [n_items][4]
+  int32_t* info_red;                                // [n_items][2]
+  int32_t* info_gc;                                 // [n_items*F]
+};
 // Everything sliding_impl is told, by name; a field left alone means "not asked for".  The exported entries below fill in
 // what they have.  `ffdtf` receives the full (m, m, F) arrays, `band_out` (with bin_lo / bin_hi / n_bands) the band sums.
 struct SlidingArgs {
@@ -757,6 +791,7 @@ struct SlidingArgs {
   const EnsDesc* ens = nullptr;
   const PairDesc* pairs = nullptr;
   const MixDesc* mix = nullptr;
+  const BgcDesc* bgc = nullptr;                     // measure == MEAS_BGC: `ffdtf` / `band_out` carry the spectral output
 };
 int sliding_impl(const SlidingArgs& a) {
   // crit >= 0: automatic order (hmv_sliding_auto_f64) -- p is the largest order tried, K1 sums p + 1 lags, K2 selects every
@@ -785,7 +820,7 @@ int sliding_impl(const SlidingArgs& a) {
             : (!a.x || !a.item_rec || !a.item_start))
     return fail(-4, "hmv_sliding_ffdtf_f64: null pointer / empty grid");
   if (!a.freqs || (!a.ffdtf && !bands) || !a.info_yw ||
-      (!a.info_tf && a.measure != MEAS_GPDC) || !a.workspace || a.F < 1 || a.chunk < 1)
+      (!a.info_tf && (a.measure == MEAS_FFDTF || a.measure == MEAS_DDTF)) || !a.workspace || a.F < 1 || a.chunk < 1)
     return fail(-4, "hmv_sliding_ffdtf_f64: null pointer / empty grid");
   if (bands && (!a.bin_lo || !a.bin_hi || a.n_bands < 1)) return fail(-4, "hmv_sliding_ffdtf_f64: band bins missing");
   bool ens_shared = false;
@@ -800,7 +835,9 @@ int sliding_impl(const SlidingArgs& a) {
   const SlidingWs w = sliding_layout(a.chunk, mp, a.p, a.F, bands, a.S_out != nullptr, a.measure,
                                      a.ens ? (ens_shared ? ens_q_tiles(a.chunk, a.n, a.p, a.grid_hop, a.grid_nwin) : 0)
                                            : ((a.pairs || a.mix) ? 0 : -1));
-  if ((int64_t)w.total > a.workspace_bytes) return fail(-7, "hmv_sliding_ffdtf_f64: workspace too small");
+  BgcWs gw{};
+  if (a.bgc) gw = bgc_layout(w.total, a.chunk, a.m, a.p, a.F, a.bgc->split, bands, true);
+  if ((int64_t)(a.bgc ? gw.total : w.total) > a.workspace_bytes) return fail(-7, "hmv_sliding_ffdtf_f64: workspace too small");
   // Regular grid (the caller vouches: item = rec * grid_nwin + w starts at grid_first + w * grid_hop of recording rec,
   // recordings are grid_T samples long): K1 sums every hop block once and assembles the windows from the blocks.
   bool regular = !a.ens && !a.pairs && !a.mix && a.grid_hop > 0 && !(a.flags & HMV_FLAG_DIRECT_LAGCOV);
@@ -980,9 +1017,42 @@ int sliding_impl(const SlidingArgs& a) {
     const bool last = (ci == n_chunks - 1);
     double* Hc = a.S_out ? reinterpret_cast<double*>(base + w.off_H) : nullptr;
     // dDTF / GPDC: the chunk's full array goes to the output, or (band form) to scratch ahead of its band sums
-    double* full_c = (a.measure == MEAS_FFDTF) ? nullptr
+    double* full_c = (a.measure == MEAS_FFDTF || a.measure == MEAS_BGC) ? nullptr
                      : bands ? reinterpret_cast<double*>(base + w.off_full) : a.ffdtf + (size_t)i0 * a.m * a.m * a.F;
-    if (a.measure == MEAS_GPDC) {
+    if (a.measure == MEAS_BGC) {
+      // the two restricted fits (K2 on the gathered blocks of the same lag covariances, in the scratch the full fit has
+      // left, in the form the caller's flags / HMV_TUNE_YW_FORM choose for the full fit -- the launch chain by each
+      // block's own padded size), then the stage; its full array goes to the output or (band form) to scratch ahead of
+      // its band sums
+      const int na = a.bgc->split, nb2 = a.m - na;
+      double* Ra = reinterpret_cast<double*>(base + gw.off_Ra);
+      double* Rb = reinterpret_cast<double*>(base + gw.off_Rb);
+      double* arr = reinterpret_cast<double*>(base + gw.off_arr);
+      int32_t* ir = reinterpret_cast<int32_t*>(base + gw.off_ir);
+      hmv::BgcArgs ga{};
+      ga.VrA = reinterpret_cast<double*>(base + gw.off_Vra); ga.VrB = reinterpret_cast<double*>(base + gw.off_Vrb);
+      ga.info_rA = ir; ga.info_rB = ir + c;
+      auto red_flags = [&](int nx) {
+        const bool chain = (a.flags & HMV_FLAG_YW_TILED) ||
+                           (ldl && !(a.flags & HMV_FLAG_YW_ONE_LAUNCH) && pad_of(nx) == 64 && c >= 128);
+        return (int64_t)(ldl ? (chain ? HMV_FLAG_YW_TILED : HMV_FLAG_YW_ONE_LAUNCH) : 0);
+      };
+      rc = hmv::launch_bgc_gather(R, Ra, Rb, c, a.m, mp, a.p, na, st0);
+      if (!rc) rc = hmv_yw_solve_f64(Ra, c, na, a.p, ws, arr, const_cast<double*>(ga.VrA), nullptr, ir, red_flags(na), st0);
+      if (!rc)
+        rc = hmv_yw_solve_f64(Rb, c, nb2, a.p, ws, arr, const_cast<double*>(ga.VrB), nullptr, ir + c, red_flags(nb2), st0);
+      double* spec_c = bands ? reinterpret_cast<double*>(base + gw.off_full) : a.ffdtf + (size_t)i0 * 2 * a.F;
+      ga.ar = ar_c; ga.V = V_c; ga.info_yw = a.info_yw + i0;
+      ga.B = reinterpret_cast<double*>(base + gw.off_B); ga.C = reinterpret_cast<double*>(base + gw.off_C);
+      ga.D = reinterpret_cast<double*>(base + gw.off_D); ga.cst = reinterpret_cast<double*>(base + gw.off_cst);
+      ga.tw = tw; ga.out = spec_c; ga.info_gc = a.bgc->info_gc + (size_t)i0 * a.F;
+      ga.time = a.bgc->time + (size_t)i0 * 4; ga.info_red = a.bgc->info_red + (size_t)i0 * 2;
+      ga.n_items = c; ga.F = a.F; ga.m = a.m; ga.p = a.p; ga.split = na;
+      if (!rc) rc = hmv::launch_bgc(ga, mp, st0);
+      if (!rc && bands)
+        rc = hmv::launch_band_sums(spec_c, reinterpret_cast<const int*>(a.bin_lo), reinterpret_cast<const int*>(a.bin_hi),
+                                   a.band_out + (size_t)i0 * 2 * a.n_bands, c * 2, a.F, a.n_bands, st0);
+    } else if (a.measure == MEAS_GPDC) {
       rc = hmv::launch_gpdc_sliding(ar_c, V_c, tw, full_c, c, a.F, a.m, mp, a.p, st0);
     } else {
       rc = tf_ffdtf_impl(a.who, ar_c, c, a.m, a.p, tw, a.F,
@@ -1000,7 +1070,7 @@ int sliding_impl(const SlidingArgs& a) {
       da.n_items = c; da.F = a.F; da.m = a.m; da.p = a.p;
       rc = hmv::launch_ddtf_sliding(da, mp, st0);
     }
-    if (!rc && a.measure != MEAS_FFDTF && bands)
+    if (!rc && (a.measure == MEAS_DDTF || a.measure == MEAS_GPDC) && bands)
       rc = hmv::launch_band_sums(full_c, reinterpret_cast<const int*>(a.bin_lo), reinterpret_cast<const int*>(a.bin_hi),
                                  a.band_out + (size_t)i0 * a.m * a.m * a.n_bands, c * (long long)a.m * a.m, a.F,
                                  a.n_bands, st0);
@@ -1131,6 +1201,89 @@ int hmv_sliding_gpdc_f64(const double* x, int64_t rec_stride, int64_t ld, const 
   a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.flags = flags;
   a.grid_hop = grid_hop; a.grid_first = grid_first; a.grid_nwin = grid_nwin; a.grid_T = grid_T;
   a.stream = stream; a.aux_stream = aux_stream;
+  return sliding_impl(a);
+}
+
+// ---- block Granger causality (block_gc.hip) ----------------------------------------------------------------------
+namespace {
+// the checks the three block Granger entries share; 0 or the refusal
+int bgc_check(const char* who, int m, int p, int split, int F) {
+  char buf[200];
+  auto refuse = [&](int code, const char* msg) {
+    snprintf(buf, sizeof(buf), "%s: %s", who, msg);
+    return fail(code, buf);
+  };
+  if (pad_of(m) < 0) return refuse(-1, "channel count must be in 1..64");
+  if (p < 1 || p > HMV_MAX_ORDER) return refuse(-2, "model order must be in 1..32");
+  if (split < 1 || split > m - 1) return refuse(-11, "split must be in 1..m-1 (both blocks need a channel)");
+  if (F < 1) return refuse(-12, "the frequency grid is empty (F must be >= 1)");
+  return 0;
+}
+}  // namespace
+
+int64_t hmv_block_gc_workspace_bytes(int64_t n_items, int m, int p, int split, int F) {
+  if (pad_of(m) < 0 || n_items < 1 || p < 1 || p > HMV_MAX_ORDER || split < 1 || split > m - 1 || F < 1) return -1;
+  return (int64_t)bgc_layout(align256(sizeof(double) * F * p * 2), n_items, m, p, F, split, false, false).total;
+}
+
+int hmv_block_gc_f64(const double* ar, const double* V, int64_t n_items, int m, int p, int split, const double* freqs, int F,
+                     double fs, double* spectral, int32_t* info_v, int32_t* info_gc, void* workspace,
+                     int64_t workspace_bytes, void* stream) {
+  if (int rc = bgc_check("hmv_block_gc_f64", m, p, split, F)) return rc;
+  if (n_items < 0) return fail(-4, "hmv_block_gc_f64: n_items must be >= 0");
+  if (n_items == 0) return 0;
+  if (!spectral) return fail(-13, "hmv_block_gc_f64: the spectral output is a null pointer");
+  if (!ar || !V || !freqs || !info_v || !info_gc || !workspace) return fail(-4, "hmv_block_gc_f64: null pointer");
+  const size_t front = align256(sizeof(double) * F * p * 2);
+  const BgcWs gw = bgc_layout(front, n_items, m, p, F, split, false, false);
+  if ((int64_t)gw.total > workspace_bytes) return fail(-7, "hmv_block_gc_f64: workspace too small");
+  char* base = static_cast<char*>(workspace);
+  double* tw = reinterpret_cast<double*>(base);
+  int rc = hmv_twiddles_f64(freqs, F, fs, p, tw, stream);
+  if (rc) return rc;
+  rc = (int)hipMemsetAsync(info_v, 0, sizeof(int32_t) * n_items, S(stream));
+  if (rc) return rc;
+  hmv::BgcArgs ga{};
+  ga.ar = ar; ga.V = V; ga.info_yw = info_v;
+  ga.B = reinterpret_cast<double*>(base + gw.off_B); ga.C = reinterpret_cast<double*>(base + gw.off_C);
+  ga.D = reinterpret_cast<double*>(base + gw.off_D); ga.cst = reinterpret_cast<double*>(base + gw.off_cst);
+  ga.tw = tw; ga.out = spectral; ga.info_gc = info_gc;
+  ga.n_items = n_items; ga.F = F; ga.m = m; ga.p = p; ga.split = split;
+  return hmv::launch_bgc(ga, pad_of(m), S(stream));
+}
+
+int64_t hmv_block_gc_sliding_workspace_bytes(int64_t chunk, int m, int p, int split, int F, int n_bands) {
+  const int mp = pad_of(m);
+  if (mp < 0 || chunk < 1 || p < 1 || p > HMV_MAX_ORDER || split < 1 || split > m - 1 || F < 1 || n_bands < 0) return -1;
+  const SlidingWs w = sliding_layout(chunk, mp, p, F, n_bands > 0, false, MEAS_BGC);
+  return (int64_t)bgc_layout(w.total, chunk, m, p, F, split, n_bands > 0, true).total;
+}
+
+int hmv_sliding_block_gc_f64(const double* x, int64_t rec_stride, int64_t ld, const int64_t* item_rec,
+                             const int64_t* item_start, int64_t n_items, int m, int n, int p, int split,
+                             const double* freqs, int F, double fs, double* spectral, const int32_t* bin_lo,
+                             const int32_t* bin_hi, int n_bands, double* time, double* ar_out, double* V_out,
+                             int32_t* info_yw, int32_t* info_red, int32_t* info_gc, void* workspace,
+                             int64_t workspace_bytes, int64_t chunk, int64_t flags, int64_t grid_hop, int64_t grid_first,
+                             int64_t grid_nwin, int64_t grid_T, void* stream) {
+  const char* who = "hmv_sliding_block_gc_f64";
+  if (int rc = bgc_check(who, m, p, split, F)) return rc;
+  if (n <= p) return fail(-3, "hmv_sliding_block_gc_f64: window shorter than the model order");
+  if (n_items < 0) return fail(-4, "hmv_sliding_block_gc_f64: n_items must be >= 0");
+  if (n_bands < 0) return fail(-14, "hmv_sliding_block_gc_f64: n_bands must be >= 0");
+  if (n_items != 0 && !spectral) return fail(-13, "hmv_sliding_block_gc_f64: the spectral output is a null pointer");
+  if (n_items != 0 && (!time || !info_red || !info_gc)) return fail(-4, "hmv_sliding_block_gc_f64: null pointer / empty grid");
+  BgcDesc g{split, time, info_red, info_gc};
+  SlidingArgs a{who};
+  a.measure = MEAS_BGC; a.bgc = &g;
+  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.item_rec = item_rec; a.item_start = item_start; a.n_items = n_items;
+  a.m = m; a.n = n; a.p = p; a.freqs = freqs; a.F = F; a.fs = fs;
+  if (n_bands > 0) a.band_out = spectral; else a.ffdtf = spectral;
+  a.bin_lo = bin_lo; a.bin_hi = bin_hi; a.n_bands = n_bands;
+  a.ar_out = ar_out; a.V_out = V_out; a.info_yw = info_yw;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.flags = flags;
+  a.grid_hop = grid_hop; a.grid_first = grid_first; a.grid_nwin = grid_nwin; a.grid_T = grid_T;
+  a.stream = stream;
   return sliding_impl(a);
 }
 

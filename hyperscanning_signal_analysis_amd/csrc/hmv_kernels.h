@@ -254,8 +254,48 @@ struct DdtfArgs {
   int F, m, p;
 };
 int launch_ddtf_sliding(const DdtfArgs& a, int m_pad, hipStream_t st);
+// ddtf_factor_kernel on its own: B [item][p+1][MP][MP] = L^-1 A_k with V = L L^T; info_yw as DdtfArgs
+int launch_ddtf_factor(const double* ar, const double* V, int* info_yw, double* B, long long n_items, int m, int m_pad, int p,
+                       hipStream_t st);
 int launch_gpdc_sliding(const double* ar, const double* V, const double* tw, double* out, long long n_items, int F, int m,
                         int m_pad, int p, hipStream_t st);
+
+// ---- block Granger causality between the channels < split and the channels >= split (block_gc.hip) -------------------
+// the two restricted lag-covariance stacks, each in the MP layout of its own block size, with K1's padding
+int launch_bgc_gather(const double* R, double* Ra, double* Rb, long long n_items, int m, int m_pad, int p, int split,
+                      hipStream_t st);
+// The one layout rule of the stage, for the workspace layout and both launchers: the blocks' own MP (padded to 16, as
+// hmv_pad) and NSP, the larger of the two, the row length of C and D.  1 <= split <= m - 1 <= 63 is the caller's check.
+struct BgcPads {
+  int mpa, mpb, nsp;
+};
+inline BgcPads bgc_pads(int m, int split) {
+  const int mpa = ((split + 15) / 16) * 16, mpb = ((m - split + 15) / 16) * 16;
+  return BgcPads{mpa, mpb, mpa > mpb ? mpa : mpb};
+}
+struct BgcArgs {
+  const double* ar;         // [n_items][MP][MP][p]   K2
+  const double* V;          // [n_items][MP][MP]      K2 (symmetric)
+  int* info_yw;             // [n_items]: set to -(column + 1) where V, one of its diagonal blocks or a Schur complement
+                            // Sigma_{s|d} is not positive definite (and the entry was 0); column counted in V
+  double* B;                // scratch [n_items][p+1][MP][MP]
+  double* C;                // scratch [n_items][2][p+1][NSP][NSP]: coefficients of W_ss(f), per direction
+  double* D;                // scratch [n_items][2][p+1][NSP][NSP]: coefficients of At_ss(f), per direction
+  double* cst;              // scratch [n_items][2]: ln det Sigma_{s|d}
+  const double* tw;         // [F][p][2]
+  double* out;              // [n_items][2][F]: 0 = A -> B, 1 = B -> A
+  int* info_gc;             // [n_items*F]
+  // time domain (VrA == nullptr: none of it): the restricted fits' residual covariances and K2 infos
+  const double* VrA;        // [n_items][MPa][MPa]
+  const double* VrB;        // [n_items][MPb][MPb]
+  const int* info_rA;       // [n_items]
+  const int* info_rB;       // [n_items]
+  double* time;             // [n_items][4]
+  int* info_red;            // [n_items][2]
+  long long n_items;
+  int F, m, p, split;
+};
+int launch_bgc(const BgcArgs& a, int m_pad, hipStream_t st);
 
 // ---- multitaper PSD (psd.hip; hipFFT for the transforms) -------------------------------------------------
 long long psd_workspace_bytes(long long ch_chunk, long long n, int K);

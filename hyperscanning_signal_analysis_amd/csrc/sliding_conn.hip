@@ -287,6 +287,13 @@ __global__ void __launch_bounds__(256) gpdc_sliding_kernel(const double* ar, con
   }
 }
 
+int launch_ddtf_factor(const double* ar, const double* V, int* info_yw, double* B, long long n_items, int m, int m_pad, int p,
+                       hipStream_t st) {
+  if (n_items == 0) return 0;
+  hipLaunchKernelGGL(ddtf_factor_kernel, dim3((unsigned)n_items), dim3(256), 0, st, ar, V, info_yw, B, m, m_pad, p);
+  return (int)hipGetLastError();
+}
+
 int launch_ddtf_sliding(const DdtfArgs& a, int m_pad, hipStream_t st) {
   if (a.n_items == 0 || a.F == 0) return 0;
   const int D = 2 * a.p + 1;

@@ -22,7 +22,7 @@ import torch
 
 from . import _lib, significance
 
-__all__ = ["Engine", "default_engine", "SingularMatrixError", "validate_items", "validate_trials"]
+__all__ = ["Engine", "default_engine", "SingularMatrixError", "validate_items", "validate_trials", "check_block_split"]
 
 
 # Pivot threshold of the per-frequency inverses of A(f) (K3): a row interchange happens only when some row's |re| + |im|
@@ -154,6 +154,25 @@ def no_auto_order(p, where: str):
     if p is None:
         raise ValueError(f"{where}: the automatic model order (p=None) is not offered here yet; pass an integer p "
                          "(sliding_ffdtf / sliding_ddtf / sliding_gpdc / sliding_ffdtf_spectra select it per window)")
+
+
+def check_block_split(split, m: int, where: str) -> int:
+    """`split` of the block measures, checked before the GPU is touched: an integer with 1 <= split <= m - 1 (channels
+    < split are block A, the others block B; both need a channel)."""
+    if isinstance(split, (bool, float)) or not isinstance(split, (int, np.integer)):
+        raise ValueError(f"{where}: split must be an integer in 1..m-1, got {split!r}")
+    if not 1 <= int(split) <= int(m) - 1:
+        raise ValueError(f"{where}: split must be an integer in 1..m-1 = 1..{int(m) - 1}, got {int(split)}")
+    return int(split)
+
+
+def no_block_auto_order(p, where: str):
+    """`p=None` of the block Granger calls: the restricted fits need the full fit's order, which is fixed."""
+    if p is None:
+        raise ValueError(f"{where}: the automatic model order (p=None) is not available for this call; pass an integer p")
+    if isinstance(p, (bool, float)) or int(p) != p or not 1 <= int(p) <= MAX_ORDER:
+        raise ValueError(f"{where}: p must be an integer in 1..{MAX_ORDER}, got {p!r}")
+    return int(p)
 
 
 _MEASURES = {"ffdtf": _lib.MEASURE_FFDTF, "ddtf": _lib.MEASURE_DDTF, "gpdc": _lib.MEASURE_GPDC}
@@ -794,6 +813,123 @@ class Engine:
         return self._sliding_call(rt, x, (item_rec, item_start), freqs, fs, bands=bands, out=out, return_ar=return_ar,
                                   return_orders=return_orders, check=check, chunk=chunk, overlap=overlap, flags=flags,
                                   grid=grid, validate=validate)
+
+    # ------------------------------------------------------------------ block Granger causality (block_gc.hip)
+    def block_granger(self, ar: torch.Tensor, V: torch.Tensor, m: int, split: int, freqs, fs: float, check=True):
+        """Geweke's spectral block Granger causality of fitted models: ar (items, MP, MP, p), V (items, MP, MP) in K2's
+        layouts -> (items, 2, F); index 0 is A -> B (channels < split drive the others), 1 is B -> A.  The stage of
+        `sliding_block_granger` on its own (`hmv_block_gc_f64`), the same kernels and the same bits.  The spectrum behind
+        it is S(f) = H V H^H with the CONJUGATE transpose, not the plain transpose of `spectra` / `multivariate_spectra`.
+        check: True raises SingularMatrixError where V is not positive definite or a per-frequency pivot fails; False
+        returns (out, info_v, info_gc)."""
+        split = check_block_split(split, m, "block_granger")
+        n_items, mp, _, p = ar.shape
+        assert mp == self.pad(m) and tuple(V.shape) == (n_items, mp, mp) and ar.is_contiguous() and V.is_contiguous()
+        f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
+        F = int(f.numel())
+        out = self.empty(n_items, 2, F)
+        info_v = torch.zeros(n_items, dtype=torch.int32, device=self.device)
+        info_gc = torch.zeros(n_items * F, dtype=torch.int32, device=self.device)
+        if n_items:
+            nbytes = int(self.lib.hmv_block_gc_workspace_bytes(n_items, m, p, split, F))
+            if nbytes < 0:
+                raise ValueError(f"block_granger: bad sizes (m={m}, p={p}, split={split}, F={F})")
+            ws = self._workspace(nbytes)
+            with torch.cuda.device(self.device):
+                rc = self.lib.hmv_block_gc_f64(ar.data_ptr(), V.data_ptr(), n_items, m, p, split, f.data_ptr(), F, float(fs),
+                                               out.data_ptr(), info_v.data_ptr(), info_gc.data_ptr(), ws.data_ptr(), nbytes,
+                                               self.stream())
+            _lib.check(rc, "hmv_block_gc_f64")
+        if not check:
+            return out, info_v, info_gc
+        self.raise_on_info(info_v, "block_granger (residual covariance not positive definite)")
+        self.raise_on_info(info_gc, "block_granger (per-frequency factorisation)", per_item=F)
+        return out
+
+    def sliding_block_granger(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, p: int, freqs,
+                              fs: float, *, split: int, bands=None, out=None, return_ar: bool = False, check=True,
+                              chunk: int | None = None, flags: int = 0, grid=None, validate: bool = True):
+        """Block (multivariate) Granger causality between the channels < split (block A) and the channels >= split
+        (block B) of every window: x (n_rec, m, T) -> (spectral, time).  One C-ABI call (`hmv_sliding_block_gc_f64`): K1 and
+        K2 once per window, the two restricted fits from the same lag covariances, then the kernels of block_gc.hip.
+            spectral (items, 2, F)   Geweke's spectral decomposition, index 0 = A -> B, 1 = B -> A; with
+                                     `bands=(bin_lo, bin_hi)` its band sums (items, 2, n_bands), the bits of `band_sums` of
+                                     the full output.  Defined on S(f) = H V H^H (conjugate transpose -- not the plain
+                                     transpose of `sliding_ffdtf_spectra`).
+            time (items, 4)          (F_{A->B}, F_{B->A}, F_{A.B} instantaneous, F_{A,B} total): log-determinant ratios of
+                                     the residual covariances of the full fit and of the order-p Yule-Walker fits of each
+                                     block alone -- the classical Geweke estimator, which differs from the state-space /
+                                     spectral-factorisation estimators.
+        `out`, if given, receives `spectral`.  check / chunk / flags / grid / validate mean what they mean for
+        `sliding_ffdtf`: check=True raises SingularMatrixError naming the failed windows, "nan" NaN-fills them, "mask"
+        appends the boolean device mask, False skips the check.  return_ar appends (ar, V, (info_yw, info_red, info_gc)).
+        An integer p is required: the automatic order (p=None) is not available for this call."""
+        p = no_block_auto_order(p, "sliding_block_granger")
+        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
+        x = x if x.stride(2) == 1 else x.contiguous()
+        n_rec, m, T = x.shape
+        split = check_block_split(split, m, "sliding_block_granger")
+        mp, n = self.pad(m), int(n)
+        items = (item_rec, item_start)
+        if validate:
+            self.check_items(x, item_rec, item_start, n, p)
+        n_items = int(item_rec.numel())
+        f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
+        F = int(f.numel())
+        nb = 0
+        if bands is not None:
+            b_lo, b_hi = self.band_tables(bands[0], bands[1], F)
+            nb = int(b_lo.numel())
+        two_step = bands is not None and nb == 0          # an empty band set: the full array, then its (empty) band sums
+        knb = 0 if two_step else nb
+        last = knb or F
+        spectral = self.empty(n_items, 2, last) if out is None or two_step else out
+        assert spectral.is_contiguous() and tuple(spectral.shape) == (n_items, 2, last)
+        time = self.empty(n_items, 4)
+        ar = self.empty(n_items, mp, mp, p) if return_ar else None
+        V = self.empty(n_items, mp, mp) if return_ar else None
+        info_yw = torch.zeros(n_items, dtype=torch.int32, device=self.device)
+        info_red = torch.zeros(n_items, 2, dtype=torch.int32, device=self.device)
+        info_gc = torch.zeros(n_items * F, dtype=torch.int32, device=self.device)
+        if n_items:
+            g = self._window_grid(x, items, n_items, grid, validate)
+            ws_bytes = self.lib.hmv_block_gc_sliding_workspace_bytes
+            if chunk is None:
+                chunk = self._chunk(n_items, int(ws_bytes(1, m, p, split, F, knb)), self.max_workspace_bytes)
+            chunk = int(chunk)
+            nbytes = int(ws_bytes(chunk, m, p, split, F, knb))
+            if nbytes < 0:
+                raise ValueError(f"sliding_block_granger: bad sizes (m={m}, p={p}, split={split}, F={F}, chunk={chunk})")
+            ws = self._workspace(nbytes)
+            with torch.cuda.device(self.device):
+                rc = self.lib.hmv_sliding_block_gc_f64(
+                    x.data_ptr(), x.stride(0), x.stride(1), item_rec.data_ptr(), item_start.data_ptr(), n_items, m, n, p, split,
+                    f.data_ptr(), F, float(fs), spectral.data_ptr(), b_lo.data_ptr() if knb else 0,
+                    b_hi.data_ptr() if knb else 0, knb, time.data_ptr(), _ptr(ar), _ptr(V), info_yw.data_ptr(),
+                    info_red.data_ptr(), info_gc.data_ptr(), ws.data_ptr(), nbytes, chunk, int(flags), *g, T, self.stream())
+            _lib.check(rc, "hmv_sliding_block_gc_f64")
+        if two_step:
+            spectral = self.band_sums(spectral, bands[0], bands[1])
+            if out is not None:
+                out.copy_(spectral)
+                spectral = out
+        r = (spectral, time)
+        if check == "nan" or check == "mask":
+            bad = (info_yw != 0) | (info_red != 0).any(dim=1) | (info_gc.view(n_items, F) != 0).any(dim=1)
+            if check == "nan":
+                if bool(bad.any()):
+                    spectral[bad] = float("nan")
+                    time[bad] = float("nan")
+            else:
+                r += (bad,)
+        elif check:
+            self.raise_on_info(info_yw, "ar_coeff (Yule-Walker solve; a negative info: residual covariance not positive "
+                                        "definite)")
+            self.raise_on_info(info_red.view(-1), "block Granger causality (Yule-Walker solve of one block alone)", per_item=2)
+            self.raise_on_info(info_gc, "block Granger causality (per-frequency factorisation)", per_item=F)
+        if return_ar:
+            r += (ar, V, (info_yw, info_red, info_gc))
+        return r
 
     # ------------------------------------------------------------------ event-locked ensembles (lagcov_ensemble.hip)
     def lagcov_ensemble(self, x: torch.Tensor, trial_rec: torch.Tensor, trial_start: torch.Tensor, group_ptr: torch.Tensor,

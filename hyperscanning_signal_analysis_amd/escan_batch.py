@@ -177,7 +177,7 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
         low_cutoff_hz=None, high_cutoff_hz=None, channel_subset=None, with_psd=False, psd_fmin=1.0, psd_fmax=30.0,
         psd_bandwidth=2.0, save_full=False, skip_existing=True, reader=None, engine=None, world=1, rank=0,
         verbose=True, prefetch=2, timing=None, save_workers=4, compresslevel=0, measures=("ffdtf",), significance=None,
-        max_model_order=20, crit_type="AIC", validation_lags=None):
+        max_model_order=20, crit_type="AIC", validation_lags=None, block_granger=False):
     """Process every dyad under <root>/EEG.  Per dyad one `<out_dir>/<dyad>_ffdtf.npz` with, per segment `<task>/<event>`:
         <seg>/ffdtf_bands   (windows, n, n, n_bands)   band-integrated ffDTF of every window
         <seg>/ffdtf         (windows, n, n, F)         only with save_full=True (8.4 MB per window at 64 channels)
@@ -202,6 +202,12 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                                                        lags and their chi-square tails (`Engine.model_validation`; the
                                                        segment's own windows and order -- `model_order`, or the per-window
                                                        automatic one), NaN for a singular window
+        <seg>/block_gc_bands (windows, 2, n_bands), <seg>/block_gc_time (windows, 4)
+                                                       only with block_granger=True: band-summed spectral block Granger
+                                                       causality child -> caregiver (index 0) and caregiver -> child
+                                                       (index 1) and the time-domain values (`Engine.sliding_block_granger`;
+                                                       split = the child's channel count); meta then says
+                                                       "block_granger": true.  Needs an integer model_order.
         <seg>/acf_fraction  (windows,)                 with validation_lags: share of the residual correlations beyond
                                                        1.96 / sqrt(N)
       plus `channels`, `freqs`, `meta` (JSON, its `measures` field lists what was computed, `significance` the test).  Returns {"done": [...], "skipped": [...], "failed": [(dyad, error)],
@@ -222,6 +228,9 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
         from .surrogates import check_significance_dict
         significance = check_significance_dict(significance)
     auto = model_order is None
+    if block_granger and auto:
+        raise ValueError("escan_batch.run(block_granger=True): the automatic model order (model_order=None) is not "
+                         "available for block Granger causality; pass an integer model_order")
     if auto:
         from .engine import auto_order_args, no_auto_order
         pmax, _ = auto_order_args(max_model_order, crit_type, 1 << 62)     # (the window length is checked per segment)
@@ -279,6 +288,8 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                     meta["max_model_order"], meta["crit_type"] = pmax, crit_type
                 if significance is not None:
                     meta["significance"] = dict(significance)
+                if block_granger:
+                    meta["block_granger"] = True
                 names_out, freqs_out = None, None
                 tg = time.perf_counter()
                 pending = []                                       # device results of this dyad, fetched after the last launch
@@ -347,6 +358,12 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                                                      / float(int(validation_lags) * block.shape[0] ** 2)
                                                      ).masked_fill(bad_v, float("nan"))
                             extra["_whiteness_orders"] = ord_v
+                        if block_granger:                        # the child block comes first (segment_block)
+                            gc_f, gc_t, gc_bad = eng.sliding_block_granger(
+                                xd, rec_i, st_i, W, order, f, fs, bands=(lo, hi), check="mask", grid=grid_w,
+                                split=sum(1 for nm in seg["names"] if nm.endswith("_ch")))
+                            extra["block_gc_bands"] = gc_f.masked_fill_(gc_bad.view(-1, 1, 1), float("nan"))
+                            extra["block_gc_time"] = gc_t.masked_fill_(gc_bad.view(-1, 1), float("nan"))
                         if significance is not None:             # the child block comes first (segment_block)
                             split = sum(1 for nm in seg["names"] if nm.endswith("_ch"))
                             for meas in measures:

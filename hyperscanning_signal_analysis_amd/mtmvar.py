@@ -26,7 +26,7 @@ from .engine import Engine, SingularMatrixError, default_engine
 __all__ = ["count_corr", "ar_coeff", "mvar_transfer_function", "multivariate_spectra", "dtf_multivariate",
            "full_freq_dtf", "mvar_criterion", "mvar_analysis", "lag_covariances", "compute_and_plot_mvar",
            "mvar_plot", "fad_decomposition", "fad_decomposition_batch", "fad_components_table", "mvar_residuals",
-           "mvar_whiteness"]
+           "mvar_whiteness", "block_granger_causality"]
 
 
 # ----------------------------------------------------------------------------- internals
@@ -384,6 +384,26 @@ def compute_and_plot_mvar(ncdf_path, channel_subset=None, max_model_order=20, op
 
 # ----------------------------------------------------------------------------- FAD decomposition (mtmvar.py:607-845)
 _FAD_POLE_KEYS = ("poles", "C", "alpha", "freq_hz", "omega_rad_s", "beta", "bandwidth_hz", "phi", "B")
+
+
+def block_granger_causality(signals, freqs, fs, split, max_model_order=20, optimal_model_order=None, crit_type='AIC'):
+    """Block (multivariate) Granger causality between the channels < split (block A) and the channels >= split (block B)
+    of one window signals (channels, samples) -- Geweke (1982); beyond the reference, in its signature style.  The order is
+    `optimal_model_order`, or with None the one `mvar_criterion(signals, max_model_order, crit_type)` selects first.
+    Returns (spectral (2, F), time (4,)): spectral[0] = f_{A->B}(f), spectral[1] = f_{B->A}(f) on the spectrum
+    S = H V H^H (CONJUGATE transpose: not the plain transpose that `multivariate_spectra` reproduces); time =
+    (F_{A->B}, F_{B->A}, F_{A.B}, F_{A,B}) from the residual covariances of the full fit and of the same-order Yule-Walker
+    fits of each block alone (the classical Geweke estimator, not the state-space / spectral-factorisation one)."""
+    from .engine import check_block_split
+    signals = _one_window(signals, "block_granger_causality")
+    split = check_block_split(split, signals.shape[0], "block_granger_causality")
+    p = _order(signals, max_model_order, optimal_model_order, crit_type, False, None, "dtf")
+    eng = default_engine()
+    x = _as_trials(signals, eng)
+    zero = torch.zeros(1, dtype=torch.int64, device=eng.device)
+    spectral, time = eng.sliding_block_granger(x, zero, zero, signals.shape[1], p, np.asarray(freqs, dtype=np.float64), fs,
+                                               split=split)
+    return spectral[0].cpu().numpy(), time[0].cpu().numpy()
 
 
 def _fad_orders(model_order, max_model_order, crit_type, n):

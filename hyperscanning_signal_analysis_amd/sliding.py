@@ -241,6 +241,30 @@ def sliding_gpdc(x, window_size, n_windows, p, freqs, fs, engine: Engine | None 
                               max_model_order, crit_type, return_orders)
 
 
+def sliding_block_granger(x, window_size, n_windows, p, freqs, fs, *, split, hop=None, bands=None, check=True,
+                          engine: Engine | None = None):
+    """NumPy (or tensor) in / NumPy out: block Granger causality between the channels < split and the channels >= split of
+    every window (`Engine.sliding_block_granger`).  x: (m, T) or (n_rec, m, T) -> (spectral, time) shaped
+    (n_rec, n_windows, 2, F | n_bands) and (n_rec, n_windows, 4), without the leading axis for a single recording.
+    Windows from `window_positions`, or every `hop` samples when `hop` is given.  An integer p is required."""
+    from .engine import check_block_split, no_block_auto_order
+    p = no_block_auto_order(p, "sliding_block_granger")
+    x = np.asarray(x, dtype=np.float64) if not isinstance(x, torch.Tensor) else x
+    single = x.ndim == 2
+    split = check_block_split(split, x.shape[-2], "sliding_block_granger")
+    eng = engine or default_engine()
+    if isinstance(x, torch.Tensor):
+        xd = (x[None] if single else x).to(device=eng.device, dtype=torch.float64)
+    else:
+        xd = eng.to_device(x[None] if single else x)
+    n_rec, m, T = xd.shape
+    positions, w = _positions(T, window_size, n_windows, hop)
+    item_rec, item_start = window_items(n_rec, positions, eng.device)
+    spectral, time = eng.sliding_block_granger(xd, item_rec, item_start, w, p, freqs, fs, split=split, bands=bands,
+                                               check=check, grid=regular_grid(positions, w, p))
+    return _to_host((spectral.view(n_rec, len(positions), 2, -1), time.view(n_rec, len(positions), 4)), single)
+
+
 def sliding_significance(x, window_size, n_windows, p, freqs, fs, bands, *, measure, null, n_surrogates, seed, split=None,
                          min_shift=None, check=True, chunk=None, hop=None, share_overlap: bool = True,
                          engine: Engine | None = None):

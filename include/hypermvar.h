@@ -318,6 +318,51 @@ int hmv_sliding_gpdc_f64(const double* x, int64_t rec_stride, int64_t ld,
                          int64_t grid_hop, int64_t grid_first, int64_t grid_nwin, int64_t grid_T,
                          void* stream, void* aux_stream);
 
+/* Block (multivariate) Granger causality between two groups of channels, per window (csrc/block_gc.hip): channels
+ * 0 .. split-1 are block A, split .. m-1 block B, 1 <= split <= m-1.  Geweke (1982); not a function of the reference.
+ * From the window's order-p Yule-Walker fit (ar, V =: Sigma), A(f) = I - sum_k ar_k z^k (z: hmv_twiddles_f64), H = A^-1 and
+ *   S(f) = H Sigma H^H  -- the CONJUGATE transpose, NOT the plain transpose that hmv_spectra_f64 reproduces from the
+ *   reference --
+ * spectral, src -> dst:  f(f) = ln det S_dd - ln det(S_dd - H_ds Sigma_{s|d} H_ds^H),  Sigma_{s|d} = Sigma_ss - Sigma_sd Sigma_dd^-1 Sigma_ds,
+ * evaluated as ln det Sigma_{s|d} + ln det W_ss(f) - 2 ln|det At_ss(f)| with W = A^H Sigma^-1 A and
+ * At_ss = A_ss - Sigma_sd Sigma_dd^-1 A_ds: no inverse of A(f), no S (equal to the definition to rounding);
+ * time domain:  F_{A->B} = ln det Sr_BB - ln det Sigma_BB,  F_{B->A} = ln det Sr_AA - ln det Sigma_AA,
+ *   F_{A.B} = ln(det Sigma_AA det Sigma_BB / det Sigma),  F_{A,B} = their sum;  Sr_XX is the residual covariance of the
+ *   order-p Yule-Walker fit of block X alone from the same lag covariances (the classical Geweke estimator with the same
+ *   order in the restricted fit; it differs from the state-space / spectral-factorisation estimators).
+ *
+ * hmv_block_gc_f64: the spectral stage on its own.  ar [item][MP][MP][p], V [item][MP][MP] (K2's layouts), freqs [F] ->
+ *   spectral [item][2][F], index 0 = A -> B, 1 = B -> A.  info_v [item] (written): -(c + 1) where V, one of its two
+ *   diagonal blocks or a Schur complement Sigma_{s|d} is not positive definite (c the column of V; the window's spectral
+ *   rows are then NaN); info_gc [item*F + f]: -(c + 1) a non-positive pivot of W_ss(f), +(c + 1) a zero pivot of At_ss(f), either
+ *   direction.  workspace: hmv_block_gc_workspace_bytes(n_items, m, p, split, F) bytes (-1 for bad arguments).
+ * hmv_sliding_block_gc_f64: from samples to outputs, with the conventions of hmv_sliding_ddtf_f64 (device pointers,
+ *   caller-owned buffers, `chunk` items at a time, grid_hop / grid_first / grid_nwin / grid_T for the shared-overlap K1,
+ *   optional ar_out / V_out, flags).  One K1 and one K2 per window serve both directions and the time-domain values; the
+ *   two restricted fits run in the form of K2 that `flags` (HMV_FLAG_YW_TILED / _ONE_LAUNCH) and HMV_TUNE_YW_FORM select
+ *   for the full fit.
+ *   spectral: [item][2][F] (n_bands = 0) or [item][2][n_bands], band b the sum over the bins bin_lo[b] <= f < bin_hi[b] --
+ *   the bits of hmv_band_sums_f64 on the full output.  time: [item][4] = (F_{A->B}, F_{B->A}, F_{A.B}, F_{A,B}).
+ *   info_yw [item]: K2's info of the full fit, or what info_v reports above;  info_red [item][2]: the restricted fits of block A and block B (K2's info, or
+ *   -(c + 1) where the restricted residual covariance is not positive definite);  info_gc [item*F]: as above.
+ *   workspace: hmv_block_gc_sliding_workspace_bytes(chunk, m, p, split, F, n_bands) bytes (-1 for bad arguments).
+ * Refused before any launch, each with its own code: channel count (-1), p outside 1..HMV_MAX_ORDER (-2), n <= p (-3), a
+ * null pointer, n_items < 0 or chunk < 1 (-4), workspace too small (-7), an inconsistent grid (-9), split outside 1..m-1 (-11), F < 1
+ * (-12), a null spectral output (-13), n_bands < 0 (-14). */
+int64_t hmv_block_gc_workspace_bytes(int64_t n_items, int m, int p, int split, int F);
+int hmv_block_gc_f64(const double* ar, const double* V, int64_t n_items, int m, int p, int split,
+                     const double* freqs, int F, double fs, double* spectral, int32_t* info_v, int32_t* info_gc,
+                     void* workspace, int64_t workspace_bytes, void* stream);
+int64_t hmv_block_gc_sliding_workspace_bytes(int64_t chunk, int m, int p, int split, int F, int n_bands);
+int hmv_sliding_block_gc_f64(const double* x, int64_t rec_stride, int64_t ld,
+                             const int64_t* item_rec, const int64_t* item_start, int64_t n_items,
+                             int m, int n, int p, int split, const double* freqs, int F, double fs,
+                             double* spectral, const int32_t* bin_lo, const int32_t* bin_hi, int n_bands,
+                             double* time, double* ar_out, double* V_out,
+                             int32_t* info_yw, int32_t* info_red, int32_t* info_gc,
+                             void* workspace, int64_t workspace_bytes, int64_t chunk, int64_t flags,
+                             int64_t grid_hop, int64_t grid_first, int64_t grid_nwin, int64_t grid_T, void* stream);
+
 /* Automatic model order, window by window (csrc/yw_auto.hip).  Every connectivity function of the reference takes
  * `max_model_order=20, optimal_model_order=None, crit_type='AIC'`: with no order given it calls mvar_criterion
  * (src/mtmvar.py:551-601), which fits EVERY order 1..pmax with ar_coeff (:90-123) and returns the first arg-min of
