@@ -131,6 +131,48 @@ int64_t ens_q_tiles(int64_t n_items, int n, int p, int64_t grid_hop, int64_t gri
   if (grid_hop <= 0 || grid_nwin < 1 || !ens_shared_form(n, p, grid_hop, 0)) return 0;
   return hmv::lagcov_ensemble_q_tiles(n_items, grid_nwin, (int)(n / grid_hop));
 }
+// The samples and the two per-item tables of a K1 call, as a stage entry or sliding_impl received them: item_rec /
+// item_start, for an ensemble item_group / item_offset, for pairs rec_a / item_start.
+struct K1In {
+  const double* x;
+  int64_t rec_stride, ld;
+  const int64_t* item_a;
+  const int64_t* item_b;
+  int m, n, p;
+};
+const long long* ll(const int64_t* v) { return reinterpret_cast<const long long*>(v); }
+// An event-locked ensemble in place of single windows (hmv_sliding_ensemble_f64): item_rec / item_start of sliding_impl
+// then carry item_group / item_offset, grid_hop / grid_nwin describe the offsets, and only K1 differs.
+struct EnsDesc {
+  const int64_t* trial_rec;
+  const int64_t* trial_start;
+  const int64_t* group_ptr;
+  int64_t n_groups, T;
+  // hmv_sliding_ensemble_split_f64 only: the second trial table, the first channel read through it, and the stacks the
+  // within-participant elements are copied from (lagcov_ens_split_kernel; always the direct form)
+  const int64_t* trial_rec_b = nullptr;
+  const int64_t* trial_start_b = nullptr;
+  int split = 0;
+  const double* R_base = nullptr;
+  const int64_t* item_base = nullptr;
+};
+// K1's arguments for the items i0 .. i0 + c - 1 of the call.  Q: the scratch of the shared-overlap form on the grid
+// (hop, nwin), or null for the direct form.
+hmv::LagcovEnsArgs ens_args(const K1In& in, const EnsDesc& e, int64_t i0, int64_t c, double* R, double* Q, int64_t hop,
+                            int64_t nwin) {
+  hmv::LagcovEnsArgs a{};
+  a.x = in.x; a.rec_stride = in.rec_stride; a.ld = in.ld; a.T = e.T;
+  a.trial_rec = ll(e.trial_rec); a.trial_start = ll(e.trial_start); a.group_ptr = ll(e.group_ptr);
+  a.item_group = ll(in.item_a + i0); a.item_offset = ll(in.item_b + i0);
+  a.n_items = c; a.m = in.m; a.n = in.n; a.p = in.p; a.R = R;
+  if (Q) { a.it0 = i0; a.nwin = nwin; a.hop = hop; a.k = (int)(in.n / hop); a.Q = Q; }
+  if (e.split) {
+    a.trial_rec_b = ll(e.trial_rec_b); a.trial_start_b = ll(e.trial_start_b);
+    a.split = e.split; a.R_base = e.R_base;
+    a.item_base = e.item_base ? ll(e.item_base + i0) : nullptr;
+  }
+  return a;
+}
 }  // namespace
 
 int64_t hmv_lagcov_ensemble_workspace_doubles(int64_t n_items, int m, int n, int p, int64_t grid_hop, int64_t grid_nwin) {
@@ -158,16 +200,10 @@ int hmv_lagcov_ensemble_f64(const double* x, int64_t rec_stride, int64_t ld, int
     const int64_t need = ens_q_tiles(n_items, n, p, grid_hop, grid_nwin) * (int64_t)(p + 1) * mp * mp;
     if (!workspace || workspace_doubles < need) return fail(-7, "hmv_lagcov_ensemble_f64: workspace too small");
   }
-  hmv::LagcovEnsArgs a{};
-  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.T = T;
-  a.trial_rec = reinterpret_cast<const long long*>(trial_rec);
-  a.trial_start = reinterpret_cast<const long long*>(trial_start);
-  a.group_ptr = reinterpret_cast<const long long*>(group_ptr);
-  a.item_group = reinterpret_cast<const long long*>(item_group);
-  a.item_offset = reinterpret_cast<const long long*>(item_offset);
-  a.n_items = n_items; a.m = m; a.n = n; a.p = p; a.R = R;
-  if (shared) { a.it0 = 0; a.nwin = grid_nwin; a.hop = grid_hop; a.k = (int)(n / grid_hop); a.Q = workspace; }
-  return hmv::launch_lagcov_ensemble(a, mp, shared, S(stream));
+  const EnsDesc ens{trial_rec, trial_start, group_ptr, n_groups, T};
+  const K1In in{x, rec_stride, ld, item_group, item_offset, m, n, p};
+  return hmv::launch_lagcov_ensemble(ens_args(in, ens, 0, n_items, R, shared ? workspace : nullptr, grid_hop, grid_nwin), mp,
+                                     shared, S(stream));
 }
 
 namespace {
@@ -201,18 +237,11 @@ int hmv_lagcov_ensemble_split_f64(const double* x, int64_t rec_stride, int64_t l
   if (n_groups < 1) return fail(-10, "hmv_lagcov_ensemble_split_f64: n_groups must be >= 1");
   if (int rc = ens_split_check("hmv_lagcov_ensemble_split_f64", m, trial_rec_b, trial_start_b, split, R_base, item_base))
     return rc;
-  hmv::LagcovEnsArgs a{};
-  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.T = T;
-  a.trial_rec = reinterpret_cast<const long long*>(trial_rec);
-  a.trial_start = reinterpret_cast<const long long*>(trial_start);
-  a.group_ptr = reinterpret_cast<const long long*>(group_ptr);
-  a.item_group = reinterpret_cast<const long long*>(item_group);
-  a.item_offset = reinterpret_cast<const long long*>(item_offset);
-  a.n_items = n_items; a.m = m; a.n = n; a.p = p; a.R = R;
-  a.trial_rec_b = reinterpret_cast<const long long*>(trial_rec_b);
-  a.trial_start_b = reinterpret_cast<const long long*>(trial_start_b);
-  a.split = split; a.R_base = R_base; a.item_base = reinterpret_cast<const long long*>(item_base);
-  return hmv::launch_lagcov_ensemble_split(a, mp, S(stream));
+  EnsDesc ens{trial_rec, trial_start, group_ptr, n_groups, T};
+  ens.trial_rec_b = trial_rec_b; ens.trial_start_b = trial_start_b; ens.split = split;
+  ens.R_base = R_base; ens.item_base = item_base;
+  const K1In in{x, rec_stride, ld, item_group, item_offset, m, n, p};
+  return hmv::launch_lagcov_ensemble_split(ens_args(in, ens, 0, n_items, R, nullptr, 0, 0), mp, S(stream));
 }
 
 // ---- K1 for pairs of recordings (lagcov_ensemble.hip, lagcov_pairs_kernel) ---------------------------------------------
@@ -231,6 +260,26 @@ int pairs_check(const char* who, int m, const int64_t* rec_b, int split, const d
   snprintf(buf, sizeof(buf), "%s: %s", who, msg);
   return fail(code, buf);
 }
+// Pairs of recordings in place of single windows (hmv_sliding_pairs_f64): item_rec / item_start of sliding_impl carry
+// rec_a / item_start, the channels >= split are read from recording rec_b, and only K1 differs (lagcov_pairs_kernel).
+struct PairDesc {
+  const int64_t* rec_b;
+  int split;
+  const double* R_base;
+  const int64_t* base_a;
+  const int64_t* base_b;
+};
+// K1's arguments for the items i0 .. i0 + c - 1 of the call
+hmv::LagcovPairsArgs pairs_args(const K1In& in, const PairDesc& d, int64_t i0, int64_t c, double* R) {
+  hmv::LagcovPairsArgs a{};
+  a.x = in.x; a.rec_stride = in.rec_stride; a.ld = in.ld;
+  a.rec_a = ll(in.item_a + i0); a.rec_b = ll(d.rec_b + i0); a.item_start = ll(in.item_b + i0);
+  a.n_items = c; a.m = in.m; a.n = in.n; a.p = in.p; a.split = d.split; a.R = R;
+  a.R_base = d.R_base;
+  a.base_a = d.R_base ? ll(d.base_a + i0) : nullptr;
+  a.base_b = d.R_base ? ll(d.base_b + i0) : nullptr;
+  return a;
+}
 }  // namespace
 
 int hmv_lagcov_pairs_f64(const double* x, int64_t rec_stride, int64_t ld, int64_t T, const int64_t* rec_a,
@@ -245,16 +294,9 @@ int hmv_lagcov_pairs_f64(const double* x, int64_t rec_stride, int64_t ld, int64_
   if (n <= p) return fail(-3, "hmv_lagcov_pairs_f64: window shorter than the model order");
   if (!x || !rec_a || !item_start || !R || n_items < 0) return fail(-4, "hmv_lagcov_pairs_f64: null pointer");
   if (int rc = pairs_check("hmv_lagcov_pairs_f64", m, rec_b, split, R_base, base_a, base_b)) return rc;
-  hmv::LagcovPairsArgs a{};
-  a.x = x; a.rec_stride = rec_stride; a.ld = ld;
-  a.rec_a = reinterpret_cast<const long long*>(rec_a);
-  a.rec_b = reinterpret_cast<const long long*>(rec_b);
-  a.item_start = reinterpret_cast<const long long*>(item_start);
-  a.n_items = n_items; a.m = m; a.n = n; a.p = p; a.split = split; a.R = R;
-  a.R_base = R_base;
-  a.base_a = reinterpret_cast<const long long*>(base_a);
-  a.base_b = reinterpret_cast<const long long*>(base_b);
-  return hmv::launch_lagcov_pairs(a, mp, S(stream));
+  const PairDesc pairs{rec_b, split, R_base, base_a, base_b};
+  const K1In in{x, rec_stride, ld, rec_a, item_start, m, n, p};
+  return hmv::launch_lagcov_pairs(pairs_args(in, pairs, 0, n_items, R), mp, S(stream));
 }
 
 int hmv_yw_solve_f64(const double* R, int64_t n_items, int m, int p, double* ws, double* ar, double* V,
@@ -713,30 +755,6 @@ int64_t k3_split_point(int64_t c, int mp, int64_t lag) {
 int64_t hmv_sliding_workspace_bytes(int64_t chunk, int m, int p, int F) { return sliding_bytes(chunk, m, p, F); }
 
 namespace {
-// An event-locked ensemble in place of single windows (hmv_sliding_ensemble_f64): item_rec / item_start of sliding_impl
-// then carry item_group / item_offset, grid_hop / grid_nwin describe the offsets, and only K1 differs.
-struct EnsDesc {
-  const int64_t* trial_rec;
-  const int64_t* trial_start;
-  const int64_t* group_ptr;
-  int64_t n_groups, T;
-  // hmv_sliding_ensemble_split_f64 only: the second trial table, the first channel read through it, and the stacks the
-  // within-participant elements are copied from (lagcov_ens_split_kernel; always the direct form)
-  const int64_t* trial_rec_b = nullptr;
-  const int64_t* trial_start_b = nullptr;
-  int split = 0;
-  const double* R_base = nullptr;
-  const int64_t* item_base = nullptr;
-};
-// Pairs of recordings in place of single windows (hmv_sliding_pairs_f64): item_rec / item_start of sliding_impl carry
-// rec_a / item_start, the channels >= split are read from recording rec_b, and only K1 differs (lagcov_pairs_kernel).
-struct PairDesc {
-  const int64_t* rec_b;
-  int split;
-  const double* R_base;
-  const int64_t* base_a;
-  const int64_t* base_b;
-};
 // A weighted sum over the trials of a per-trial stack in place of single windows (hmv_sliding_mix_f64): item k * n_win + w
 // is mix row k at window w, there are no samples and no item tables, and only K1 differs (lagcov_mix_kernel).
 struct MixDesc {
@@ -793,6 +811,34 @@ struct SlidingArgs {
   const MixDesc* mix = nullptr;
   const BgcDesc* bgc = nullptr;                     // measure == MEAS_BGC: `ffdtf` / `band_out` carry the spectral output
 };
+// K1 of the chunk i0 .. i0 + c - 1 into R, on st: whichever form the entry's descriptors and the grid call for
+int sliding_k1(const SlidingArgs& a, int mp, bool ens_shared, bool regular, int64_t i0, int64_t c, double* R, double* Qb,
+               hipStream_t st) {
+  const K1In in{a.x, a.rec_stride, a.ld, a.item_rec, a.item_start, a.m, a.n, a.p};
+  if (a.ens) {
+    const hmv::LagcovEnsArgs ea = ens_args(in, *a.ens, i0, c, R, ens_shared ? Qb : nullptr, a.grid_hop, a.grid_nwin);
+    return a.ens->split ? hmv::launch_lagcov_ensemble_split(ea, mp, st) : hmv::launch_lagcov_ensemble(ea, mp, ens_shared, st);
+  }
+  if (a.pairs) return hmv::launch_lagcov_pairs(pairs_args(in, *a.pairs, i0, c, R), mp, st);
+  if (a.mix) {
+    hmv::LagcovMixArgs ma{};
+    ma.Rt = a.mix->Rt; ma.W = a.mix->W; ma.scale = a.mix->scale; ma.n_trials = a.mix->n_trials; ma.n_win = a.mix->n_win;
+    ma.it0 = i0; ma.n_items = c; ma.m = a.m; ma.m_pad = mp; ma.p = a.p; ma.R = R;
+    return hmv::launch_lagcov_mix(ma, st);
+  }
+  if (!regular) return hmv_lagcov_f64(a.x, a.rec_stride, a.ld, a.item_rec + i0, a.item_start + i0, c, a.m, a.n, a.p, R, st);
+  // items i0 .. i0+c-1 as runs of consecutive windows of one recording each (item = rec * grid_nwin + w)
+  const size_t stack = (size_t)(a.p + 1) * mp * mp;
+  int rc = 0;
+  for (int64_t it = i0; it < i0 + c && rc == 0;) {
+    const int64_t rec = it / a.grid_nwin, w0 = it - rec * a.grid_nwin;
+    const int64_t run = ((a.grid_nwin - w0) < (i0 + c - it)) ? (a.grid_nwin - w0) : (i0 + c - it);
+    rc = hmv_lagcov_regular_f64(a.x + rec * a.rec_stride, a.ld, a.grid_T, a.grid_first + w0 * a.grid_hop, a.grid_hop, run,
+                                a.m, a.n, a.p, R + (size_t)(it - i0) * stack, Qb, st);
+    it += run;
+  }
+  return rc;
+}
 int sliding_impl(const SlidingArgs& a) {
   // crit >= 0: automatic order (hmv_sliding_auto_f64) -- p is the largest order tried, K1 sums p + 1 lags, K2 selects every
   // window's order and leaves its coefficients zero-padded to p lags, and every later stage runs at p on those (the
@@ -896,55 +942,7 @@ int sliding_impl(const SlidingArgs& a) {
     const int64_t c = (a.n_items - i0 < a.chunk) ? (a.n_items - i0) : a.chunk;
     double* ar_c = a.ar_out ? a.ar_out + (size_t)i0 * t * a.p : ar;
     double* V_c = a.V_out ? a.V_out + (size_t)i0 * t : V;
-    if (a.ens) {
-      hmv::LagcovEnsArgs ea{};
-      ea.x = a.x; ea.rec_stride = a.rec_stride; ea.ld = a.ld; ea.T = a.ens->T;
-      ea.trial_rec = reinterpret_cast<const long long*>(a.ens->trial_rec);
-      ea.trial_start = reinterpret_cast<const long long*>(a.ens->trial_start);
-      ea.group_ptr = reinterpret_cast<const long long*>(a.ens->group_ptr);
-      ea.item_group = reinterpret_cast<const long long*>(a.item_rec + i0);
-      ea.item_offset = reinterpret_cast<const long long*>(a.item_start + i0);
-      ea.n_items = c; ea.m = a.m; ea.n = a.n; ea.p = a.p; ea.R = R;
-      if (ens_shared) {
-        ea.it0 = i0; ea.nwin = a.grid_nwin; ea.hop = a.grid_hop; ea.k = (int)(a.n / a.grid_hop); ea.Q = Qb;
-      }
-      if (a.ens->split) {
-        ea.trial_rec_b = reinterpret_cast<const long long*>(a.ens->trial_rec_b);
-        ea.trial_start_b = reinterpret_cast<const long long*>(a.ens->trial_start_b);
-        ea.split = a.ens->split; ea.R_base = a.ens->R_base;
-        ea.item_base = a.ens->item_base ? reinterpret_cast<const long long*>(a.ens->item_base + i0) : nullptr;
-        rc = hmv::launch_lagcov_ensemble_split(ea, mp, st0);
-      } else {
-        rc = hmv::launch_lagcov_ensemble(ea, mp, ens_shared, st0);
-      }
-    } else if (a.pairs) {
-      hmv::LagcovPairsArgs pa{};
-      pa.x = a.x; pa.rec_stride = a.rec_stride; pa.ld = a.ld;
-      pa.rec_a = reinterpret_cast<const long long*>(a.item_rec + i0);
-      pa.rec_b = reinterpret_cast<const long long*>(a.pairs->rec_b + i0);
-      pa.item_start = reinterpret_cast<const long long*>(a.item_start + i0);
-      pa.n_items = c; pa.m = a.m; pa.n = a.n; pa.p = a.p; pa.split = a.pairs->split; pa.R = R;
-      pa.R_base = a.pairs->R_base;
-      pa.base_a = a.pairs->R_base ? reinterpret_cast<const long long*>(a.pairs->base_a + i0) : nullptr;
-      pa.base_b = a.pairs->R_base ? reinterpret_cast<const long long*>(a.pairs->base_b + i0) : nullptr;
-      rc = hmv::launch_lagcov_pairs(pa, mp, st0);
-    } else if (a.mix) {
-      hmv::LagcovMixArgs ma{};
-      ma.Rt = a.mix->Rt; ma.W = a.mix->W; ma.scale = a.mix->scale; ma.n_trials = a.mix->n_trials; ma.n_win = a.mix->n_win;
-      ma.it0 = i0; ma.n_items = c; ma.m = a.m; ma.m_pad = mp; ma.p = a.p; ma.R = R;
-      rc = hmv::launch_lagcov_mix(ma, st0);
-    } else if (regular) {
-      // items i0 .. i0+c-1 as runs of consecutive windows of one recording each (item = rec * grid_nwin + w)
-      for (int64_t it = i0; it < i0 + c && rc == 0;) {
-        const int64_t rec = it / a.grid_nwin, w0 = it - rec * a.grid_nwin;
-        const int64_t run = ((a.grid_nwin - w0) < (i0 + c - it)) ? (a.grid_nwin - w0) : (i0 + c - it);
-        rc = hmv_lagcov_regular_f64(a.x + rec * a.rec_stride, a.ld, a.grid_T, a.grid_first + w0 * a.grid_hop, a.grid_hop,
-                                    run, a.m, a.n, a.p, R + (size_t)(it - i0) * (a.p + 1) * t, Qb, st0);
-        it += run;
-      }
-    } else {
-      rc = hmv_lagcov_f64(a.x, a.rec_stride, a.ld, a.item_rec + i0, a.item_start + i0, c, a.m, a.n, a.p, R, st0);
-    }
+    rc = sliding_k1(a, mp, ens_shared, regular, i0, c, R, Qb, st0);
     if (rc) break;
     if (automatic) {
       hmv::YwArgs ya{};

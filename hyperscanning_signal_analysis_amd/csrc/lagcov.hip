@@ -4,37 +4,27 @@
 // 1/n scaling for every lag (mtmvar.py:57,72), data NOT demeaned (quirk Q1).  The block-Toeplitz
 // r_left / r_right of the reference are never materialised -- K2 consumes the p+1 blocks directly.
 //
-// Mapping: one workgroup = one window x a group of LG = 3 consecutive lags; wave w owns a strip of MP/4 rows of
-// each lag's MP x MP accumulator (D layout, hmv_common.h).  The window is streamed through LDS in chunks of TC samples plus
-// a halo of 32 lagged samples (all global loads of a chunk in flight before the LDS stores); samples past
-// the window end and channels past m are staged as zeros, so every lag runs the same t-loop (the products
-// with t + l >= n vanish).  Per 4-sample k-step a wave issues NT A-operand reads + NT B-operand reads
-// (ds_read_b64, conflict-free because the row stride is 6 mod 32 doubles) for NT*NT v_mfma_f64_4x4x4_4b_f64.
+// The direct form below is lagcov_core.h's (mapping, chunks, k-steps): the window itself is the source, and in block mode
+// the hop block with everything behind it up to the end of the recording.
 #include "hmv_common.h"
 #include "hmv_kernels.h"
+#include "lagcov_core.h"
 #include <cstdlib>
 
 namespace hmv {
 
-constexpr int LC_TC = 64;      // samples per chunk
-constexpr int LC_HALO = 32;    // max lag
-constexpr int LC_S = LC_TC + LC_HALO + 6;   // 102 = 6 (mod 32)
-
-// grid (items, ceil((p+1) / LG)): one workgroup = one window x LG consecutive lags; wave w owns the row strip
-// 4*NT*w .. of each lag's MP x MP accumulator (LG * NT * NT accumulators per lane).  The staged chunk (the costly
-// part: global loads, two barriers, LDS stores) is shared by the LG lags -- per 4-sample k-step a wave reads NT
-// A operands once and NT B operands per lag for LG*NT*NT MFMAs -- and the window is fetched ceil((p+1)/LG) times
-// instead of p+1 times (round 1, LG = 1: 21x over-fetch, 0.53 of the f64 peak).
+// grid (items, ceil((p+1) / LG)).  The staged chunk (the costly part: global loads, two barriers, LDS stores) is shared by
+// the LG lags, and the window is fetched ceil((p+1)/LG) times instead of p+1 times (round 1, LG = 1: 21x over-fetch, 0.53
+// of the f64 peak).
 template <int NT, int LG>
 __global__ void __launch_bounds__(256, 2) lagcov_kernel(LagcovArgs a) {
-  constexpr int MP = 16 * NT, NIW = NT, NJ = NT;
-  __shared__ double xs[MP * LC_S];
+  constexpr int MP = 16 * NT;
+  __shared__ double xs[MP * k1::S];
   const int l = lane_id();
   const int wv = uni(threadIdx.x >> 6);
   const long long item = blockIdx.x;
   const int lag0 = blockIdx.y * LG;
   const int nl = min(LG, a.p + 1 - lag0);          // lags of this workgroup (the last group may be short)
-  const int i = l >> 4, cc = l & 15;
   const int n = a.n, m = a.m;            // n: samples summed over (window length, or hop in block mode)
   const bool blk = a.blocks != 0;
   const long long start = blk ? a.blk_first + item * (long long)n : a.item_start[item];
@@ -44,75 +34,22 @@ __global__ void __launch_bounds__(256, 2) lagcov_kernel(LagcovArgs a) {
   const long long vlen = blk ? a.blk_T - start : (long long)n;
   const bool mask_a = blk && (n & 3) != 0;  // block mode: the A operand must end at n even if real samples follow
 
-  double acc[LG][NIW][NJ];
-#pragma unroll
-  for (int g = 0; g < LG; ++g)
-#pragma unroll
-    for (int I = 0; I < NIW; ++I)
-#pragma unroll
-      for (int J = 0; J < NJ; ++J) acc[g][I][J] = 0.0;
-
-  constexpr int W = LC_TC + LC_HALO;   // 96 staged samples per channel
-  constexpr int NLD = (MP * W + 255) / 256;
-  for (int t0 = 0; t0 < n; t0 += LC_TC) {
-    double stg[NLD];
-#pragma unroll
-    for (int r = 0; r < NLD; ++r) {                     // all loads of the chunk in flight, then the LDS stores
-      const int idx = threadIdx.x + 256 * r;
-      const int ch = idx / W, tt = idx - ch * W;
-      const int t = t0 + tt;
-      stg[r] = (idx < MP * W && ch < m && t < vlen) ? x[(size_t)ch * a.ld + t] : 0.0;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < NLD; ++r) {
-      const int idx = threadIdx.x + 256 * r;
-      const int ch = idx / W, tt = idx - ch * W;
-      if (idx < MP * W) xs[ch * LC_S + tt] = stg[r];
-    }
-    __syncthreads();
-    const int steps = min(LC_TC, n - t0 + 3) >> 2;
-    const double* xa = xs + (4 * NT * wv + (l & 3)) * LC_S + (l >> 4);
-    const double* xb = xs + cc * LC_S + lag0 + (l >> 4);
-    for (int ts = 0; ts < steps; ++ts) {
-      double av[NIW];
-#pragma unroll
-      for (int I = 0; I < NIW; ++I) av[I] = xa[4 * I * LC_S + 4 * ts];
-      if (mask_a && t0 + 4 * ts + 3 >= n) {             // uniform: only the last k-step of a block
-        const bool in = t0 + 4 * ts + (l >> 4) < n;
-#pragma unroll
-        for (int I = 0; I < NIW; ++I) av[I] = in ? av[I] : 0.0;
-      }
-      static_for<LG>([&](auto gc) __attribute__((always_inline)) {
-        constexpr int g = decltype(gc)::value;
-        if (g < nl) {                                   // workgroup-uniform
-          double bv[NJ];
-#pragma unroll
-          for (int J = 0; J < NJ; ++J) bv[J] = xb[16 * J * LC_S + 4 * ts + g];
-#pragma unroll
-          for (int I = 0; I < NIW; ++I)
-#pragma unroll
-            for (int J = 0; J < NJ; ++J) acc[g][I][J] = mfma4(av[I], bv[J], acc[g][I][J]);
-        }
-      });
-    }
+  double acc[LG][NT][NT];
+  k1::zero_acc(acc);
+  for (int t0 = 0; t0 < n; t0 += k1::TC) {
+    k1::stage_chunk<NT>(xs, t0, [&](int ch, int t) __attribute__((always_inline)) {
+      return (ch < m && t < vlen) ? x[(size_t)ch * a.ld + t] : 0.0;
+    });
+    k1::ksteps<NT, LG>(k1::a_operand<NT>(xs, wv, l), k1::b_operand(xs, lag0, l), min(k1::TC, n - t0 + 3) >> 2, nl, mask_a,
+                       n - t0, l, acc);
   }
   const double scale = blk ? 1.0 : 1.0 / (double)n;   // `corr_scale = 1 / n`, multiplied (mtmvar.py:57-59)
-  static_for<LG>([&](auto gc) __attribute__((always_inline)) {
-    constexpr int g = decltype(gc)::value;
-    if (g < nl) {
-      const int lag = lag0 + g;
-      double* R = a.R + ((size_t)item * (a.p + 1) + lag) * MP * MP;
-#pragma unroll
-      for (int I = 0; I < NIW; ++I)
-#pragma unroll
-        for (int J = 0; J < NJ; ++J) {
-          const int row = 4 * (NT * wv + I) + i, col = 16 * J + cc;
-          double v = acc[g][I][J] * scale;
-          if (!blk && lag == 0 && row == col && row >= m) v = 1.0;   // padded channels: identity block keeps G SPD
-          R[(size_t)row * MP + col] = v;
-        }
-    }
+  k1::store_acc(acc, a.R + (size_t)item * (a.p + 1) * MP * MP, lag0, nl, wv, l, [&](int lag) __attribute__((always_inline)) {
+    return [&, lag](int row, int col, double v) __attribute__((always_inline)) {
+      v = v * scale;
+      if (!blk && lag == 0 && row == col && row >= m) v = 1.0;       // padded channels: identity block keeps G SPD
+      return v;
+    };
   });
 }
 
@@ -131,7 +68,7 @@ __global__ void __launch_bounds__(256, 2) lagcov_kernel(LagcovArgs a) {
 // a broadcast) and xs[col][l + u] with col running over the lanes, which at the former stride of 32 doubles put every
 // lane of a wave on the same bank.  The elements are taken LC_E at a time so that their block-sum loads are in flight
 // together; each element's sums keep their order (Q blocks ascending, then the ascending FMA chain over u).
-constexpr int LC_CS = 2 * LC_HALO + 1;     // 65
+constexpr int LC_CS = 2 * k1::HALO + 1;     // 65
 template <int NT>
 __global__ void __launch_bounds__(256) lagcomb_kernel(LagcombArgs a) {
   constexpr int MP = 16 * NT, TILE = MP * MP, NE = TILE / 256;
@@ -191,34 +128,24 @@ __global__ void __launch_bounds__(256) lagcomb_kernel(LagcombArgs a) {
 
 int launch_lagcomb(const LagcombArgs& a, int m_pad, hipStream_t st) {
   if (a.n_win == 0) return 0;
-  if (a.p > LC_HALO) return -2;
+  if (a.p > k1::HALO) return -2;
   const dim3 grid((unsigned)a.n_win, a.p + 1), block(256);
-  switch (m_pad) {
-    case 16: hipLaunchKernelGGL(lagcomb_kernel<1>, grid, block, 0, st, a); break;
-    case 32: hipLaunchKernelGGL(lagcomb_kernel<2>, grid, block, 0, st, a); break;
-    case 48: hipLaunchKernelGGL(lagcomb_kernel<3>, grid, block, 0, st, a); break;
-    case 64: hipLaunchKernelGGL(lagcomb_kernel<4>, grid, block, 0, st, a); break;
-    default: return -1;
-  }
+  if (k1::for_nt(m_pad, [&](auto nt) { hipLaunchKernelGGL(lagcomb_kernel<decltype(nt)::value>, grid, block, 0, st, a); }))
+    return -1;
   return (int)hipGetLastError();
 }
 
 template <int LG>
 static int launch_lagcov_lg(const LagcovArgs& a, int m_pad, hipStream_t st) {
   const dim3 grid((unsigned)a.n_items, (a.p + LG) / LG), block(256);
-  switch (m_pad) {
-    case 16: hipLaunchKernelGGL((lagcov_kernel<1, LG>), grid, block, 0, st, a); break;
-    case 32: hipLaunchKernelGGL((lagcov_kernel<2, LG>), grid, block, 0, st, a); break;
-    case 48: hipLaunchKernelGGL((lagcov_kernel<3, LG>), grid, block, 0, st, a); break;
-    case 64: hipLaunchKernelGGL((lagcov_kernel<4, LG>), grid, block, 0, st, a); break;
-    default: return -1;
-  }
+  if (k1::for_nt(m_pad, [&](auto nt) { hipLaunchKernelGGL((lagcov_kernel<decltype(nt)::value, LG>), grid, block, 0, st, a); }))
+    return -1;
   return (int)hipGetLastError();
 }
 
 int launch_lagcov(const LagcovArgs& a, int m_pad, hipStream_t st) {
   if (a.n_items == 0) return 0;
-  if (a.p > LC_HALO) return -2;
+  if (a.p > k1::HALO) return -2;
   // every lag's sum runs over the same samples in the same order whatever the grouping: same bits for any LG
   const long long lg = tuning(2 /* HMV_TUNE_LAG_GROUP */);
   switch (lg) {

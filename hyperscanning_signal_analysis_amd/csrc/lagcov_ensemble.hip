@@ -4,8 +4,8 @@
 // Replaces `count_corr` on 3-D input (src/mtmvar.py:54-85 of the reference: the lag products of every trial, biased 1/n
 // scaling, no demeaning, then the mean over the trials) for every window of an epoch at once.  Two forms:
 //
-//  * direct (lagcov_ens_kernel): the mapping of lagcov_kernel (lagcov.hip) -- one workgroup = one item x LG = 3 lags, wave w
-//    owns a strip of MP/4 rows -- with the loop over the group's trials INSIDE the kernel.  The LG*NT*NT accumulators stay
+//  * direct (lagcov_ens_kernel): the direct form of lagcov_core.h -- one workgroup = one item x LG = 3 lags, wave w owns a
+//    strip of MP/4 rows -- with the loop over the group's trials INSIDE the kernel.  The LG*NT*NT accumulators stay
 //    in registers across the trials and one R stack per item is written, never one per trial.  Trials are summed in
 //    ascending order and every trial in lagcov_kernel's order (64-sample chunks, 4-sample k-steps), so a group of one
 //    trial gives the bits of hmv_lagcov_f64 on that window.  (Loading the next (trial, chunk) into registers under the
@@ -18,121 +18,60 @@
 //    the blocks (+ p lagged samples) of as many trials as fit into the 96 staged columns.
 #include "hmv_common.h"
 #include "hmv_kernels.h"
+#include "lagcov_core.h"
 
 namespace hmv {
 
-constexpr int LE_TC = 64;                      // samples per chunk (direct form: as lagcov_kernel)
-constexpr int LE_HALO = 32;                    // max lag
-constexpr int LE_W = LE_TC + LE_HALO;          // 96 staged columns per channel
-constexpr int LE_S = LE_W + 6;                 // row stride 102 = 6 (mod 32): conflict-free ds_read_b64
 constexpr int LE_MAX_TPF = 16;                 // shared form: trials per LDS fill
 constexpr int LE_MAX_K = 32;                    // shared form: hops per window (HMV_MAX_HOPS_ENSEMBLE)
 constexpr int LE_CS = 33;                      // combine step: row stride of the staged tail samples
-
-// the k-steps of one staged chunk: per 4-sample step NT A reads once and NT B reads per lag for LG*NT*NT MFMAs (the inner
-// loop of lagcov_kernel, same order of products per accumulator)
-template <int NT, int LG>
-__device__ __forceinline__ void le_ksteps(const double* xa, const double* xb, int steps, int nl, bool mask_a, int n_a,
-                                          int l, double (&acc)[LG][NT][NT]) {
-  for (int ts = 0; ts < steps; ++ts) {
-    double av[NT];
-#pragma unroll
-    for (int I = 0; I < NT; ++I) av[I] = xa[4 * I * LE_S + 4 * ts];
-    if (mask_a && 4 * ts + 3 >= n_a) {                  // uniform: only the last k-step of a hop block
-      const bool in = 4 * ts + (l >> 4) < n_a;
-#pragma unroll
-      for (int I = 0; I < NT; ++I) av[I] = in ? av[I] : 0.0;
-    }
-    static_for<LG>([&](auto gc) __attribute__((always_inline)) {
-      constexpr int g = decltype(gc)::value;
-      if (g < nl) {                                     // workgroup-uniform
-        double bv[NT];
-#pragma unroll
-        for (int J = 0; J < NT; ++J) bv[J] = xb[16 * J * LE_S + 4 * ts + g];
-#pragma unroll
-        for (int I = 0; I < NT; ++I)
-#pragma unroll
-          for (int J = 0; J < NT; ++J) acc[g][I][J] = mfma4(av[I], bv[J], acc[g][I][J]);
-      }
-    });
-  }
-}
 
 // ---- direct form: grid (items, ceil((p+1) / LG)) -----------------------------------------------------------------
 template <int NT, int LG>
 __global__ void __launch_bounds__(256, 2) lagcov_ens_kernel(LagcovEnsArgs a) {
   constexpr int MP = 16 * NT;
-  __shared__ double xs[MP * LE_S];
+  __shared__ double xs[MP * k1::S];
   const int l = lane_id();
   const int wv = uni(threadIdx.x >> 6);
   const long long item = blockIdx.x;
   const int lag0 = blockIdx.y * LG;
   const int nl = min(LG, a.p + 1 - lag0);
-  const int i = l >> 4, cc = l & 15;
   const int n = a.n, m = a.m;
   const long long g = a.item_group[item], off = a.item_offset[item];
   const long long e0 = a.group_ptr[g], e1 = a.group_ptr[g + 1];
   const long long E = e1 - e0;
 
   double acc[LG][NT][NT];
-#pragma unroll
-  for (int q = 0; q < LG; ++q)
-#pragma unroll
-    for (int I = 0; I < NT; ++I)
-#pragma unroll
-      for (int J = 0; J < NT; ++J) acc[q][I][J] = 0.0;
-
-  constexpr int NLD = (MP * LE_W + 255) / 256;
-  double stg[NLD];
-  auto load = [&](long long e, int t0) __attribute__((always_inline)) {
-    const double* x = a.x + a.trial_rec[e] * a.rec_stride + a.trial_start[e] + off;
-#pragma unroll
-    for (int r = 0; r < NLD; ++r) {
-      const int idx = threadIdx.x + 256 * r;
-      const int ch = idx / LE_W, tt = idx - ch * LE_W;
-      const int t = t0 + tt;
-      stg[r] = (idx < MP * LE_W && ch < m && t < n) ? x[(size_t)ch * a.ld + t] : 0.0;
-    }
-  };
-  const int nch = (n + LE_TC - 1) / LE_TC;
-  const long long S = E * nch;                          // (trial, chunk) steps, trial-major
+  k1::zero_acc(acc);
+  double stg[k1::NLD<NT>];
+  const int nch = (n + k1::TC - 1) / k1::TC;
+  const long long steps = E * nch;                      // (trial, chunk) steps, trial-major
   long long e = e0;
   int t0 = 0;
-  const double* xa = xs + (4 * NT * wv + (l & 3)) * LE_S + (l >> 4);
-  const double* xb = xs + cc * LE_S + lag0 + (l >> 4);
-  for (long long s = 0; s < S; ++s) {
-    load(e, t0);                                        // all loads of the chunk in flight, then the LDS stores
+  const double* xa = k1::a_operand<NT>(xs, wv, l);
+  const double* xb = k1::b_operand(xs, lag0, l);
+  for (long long s = 0; s < steps; ++s) {
+    const double* x = a.x + a.trial_rec[e] * a.rec_stride + a.trial_start[e] + off;
+    k1::load_chunk<NT>(stg, t0, [&](int ch, int t) __attribute__((always_inline)) {
+      return (ch < m && t < n) ? x[(size_t)ch * a.ld + t] : 0.0;
+    });
     __syncthreads();                                    // the k-steps of the previous chunk have read xs
-#pragma unroll
-    for (int r = 0; r < NLD; ++r) {
-      const int idx = threadIdx.x + 256 * r;
-      const int ch = idx / LE_W, tt = idx - ch * LE_W;
-      if (idx < MP * LE_W) xs[ch * LE_S + tt] = stg[r];
-    }
+    k1::store_chunk<NT>(xs, stg);
     __syncthreads();
     const int tc = t0;
-    t0 += LE_TC;
+    t0 += k1::TC;
     if (t0 >= n) { t0 = 0; ++e; }
-    le_ksteps<NT, LG>(xa, xb, min(LE_TC, n - tc + 3) >> 2, nl, false, 0, l, acc);
+    k1::ksteps<NT, LG>(xa, xb, min(k1::TC, n - tc + 3) >> 2, nl, false, 0, l, acc);
   }
   const double scale = 1.0 / (double)n;                 // `corr_scale = 1 / n`, multiplied (mtmvar.py:57-59)
   const double Ed = (double)E;
-  static_for<LG>([&](auto gc) __attribute__((always_inline)) {
-    constexpr int q = decltype(gc)::value;
-    if (q < nl) {
-      const int lag = lag0 + q;
-      double* R = a.R + ((size_t)item * (a.p + 1) + lag) * MP * MP;
-#pragma unroll
-      for (int I = 0; I < NT; ++I)
-#pragma unroll
-        for (int J = 0; J < NT; ++J) {
-          const int row = 4 * (NT * wv + I) + i, col = 16 * J + cc;
-          double v = acc[q][I][J] * scale;
-          if (E > 1) v = v / Ed;                        // the mean over the trials (mtmvar.py:78-85)
-          if (lag == 0 && row == col && row >= m) v = 1.0;   // padded channels: identity block keeps G SPD
-          R[(size_t)row * MP + col] = v;
-        }
-    }
+  k1::store_acc(acc, a.R + (size_t)item * (a.p + 1) * MP * MP, lag0, nl, wv, l, [&](int lag) __attribute__((always_inline)) {
+    return [&, lag](int row, int col, double v) __attribute__((always_inline)) {
+      v = v * scale;
+      if (E > 1) v = v / Ed;                                         // the mean over the trials (mtmvar.py:78-85)
+      if (lag == 0 && row == col && row >= m) v = 1.0;               // padded channels: identity block keeps G SPD
+      return v;
+    };
   });
 }
 
@@ -143,39 +82,17 @@ __global__ void __launch_bounds__(256, 2) lagcov_ens_kernel(LagcovEnsArgs a) {
 // gives its bits.
 // With R_base the within-participant elements -- both indices < split or both >= split, padding counting as >= split --
 // are sums over ALL trials that no permutation changes: they are copied from R_base[item_base[item]] and an accumulator
-// whose real elements (row, col < m) are all of that kind never sees an MFMA.  `need` holds one bit per accumulator
-// [I][J] of this wave; it depends on the wave, split and m only, lives in an SGPR and is formed before the trial loop.
-// An accumulator that straddles split is computed whole and its within-participant elements are then overwritten, so
-// the result does not depend on the tiling.
-template <int NT, int LG>
-__device__ __forceinline__ void le_ksteps_masked(const double* xa, const double* xb, int steps, int nl, unsigned need,
-                                                 double (&acc)[LG][NT][NT]) {
-  for (int ts = 0; ts < steps; ++ts) {
-    double av[NT];
-#pragma unroll
-    for (int I = 0; I < NT; ++I) av[I] = xa[4 * I * LE_S + 4 * ts];
-    static_for<LG>([&](auto gc) __attribute__((always_inline)) {
-      constexpr int g = decltype(gc)::value;
-      if (g < nl) {                                     // workgroup-uniform
-        static_for<NT>([&](auto jc) __attribute__((always_inline)) {
-          constexpr int J = decltype(jc)::value;
-          constexpr unsigned COL = ((1u << (NT * NT)) - 1) / ((1u << NT) - 1) << J;   // bits I * NT + J, all I
-          if (need & COL) {                             // wave-uniform
-            const double bv = xb[16 * J * LE_S + 4 * ts + g];
-#pragma unroll
-            for (int I = 0; I < NT; ++I)
-              if (need & (1u << (I * NT + J))) acc[g][I][J] = mfma4(av[I], bv, acc[g][I][J]);
-          }
-        });
-      }
-    });
-  }
-}
-
+// whose real elements (row, col < m) are all of that kind never sees an MFMA (k1::need_mask, formed before the trial
+// loop).  An accumulator that straddles split is computed whole and its within-participant elements are then overwritten,
+// so the result does not depend on the tiling.
+// This kernel takes the core's geometry, need mask, operand pointers and masked k-steps and keeps its own staging and
+// accumulator store: on k1::load_chunk / store_chunk / store_acc its K1 time was 2 to 3.6 % above the parent's at both
+// channel counts measured (profiles/k1_core_refactor.json, `split_kernel_on_shared_staging`) with nothing in the resource
+// table or the k-step loop to account for it; written as here, its ISA is the parent's but for a few scalar instructions.
 template <int NT, int LG>
 __global__ void __launch_bounds__(256, 2) lagcov_ens_split_kernel(LagcovEnsArgs a) {
   constexpr int MP = 16 * NT;
-  __shared__ double xs[MP * LE_S];
+  __shared__ double xs[MP * k1::S];
   const int l = lane_id();
   const int wv = uni(threadIdx.x >> 6);
   const long long item = blockIdx.x;
@@ -188,27 +105,11 @@ __global__ void __launch_bounds__(256, 2) lagcov_ens_split_kernel(LagcovEnsArgs 
   const long long E = e1 - e0;
   const bool based = a.R_base != nullptr;
 
-  unsigned need = 0;
-#pragma unroll
-  for (int I = 0; I < NT; ++I)
-#pragma unroll
-    for (int J = 0; J < NT; ++J) {
-      const int r0 = 4 * (NT * wv + I), c0 = 16 * J;     // rows r0 .. r0 + 3, columns c0 .. c0 + 15
-      const bool rows_a = r0 < split, rows_b = max(r0, split) <= min(r0 + 3, m - 1);
-      const bool cols_a = c0 < split, cols_b = max(c0, split) <= min(c0 + 15, m - 1);
-      if (!based || (rows_a && cols_b) || (rows_b && cols_a)) need |= 1u << (I * NT + J);
-    }
-  need = (unsigned)uni((int)need);
+  const unsigned need = k1::need_mask<NT>(wv, split, m, based);
 
   double acc[LG][NT][NT];
-#pragma unroll
-  for (int q = 0; q < LG; ++q)
-#pragma unroll
-    for (int I = 0; I < NT; ++I)
-#pragma unroll
-      for (int J = 0; J < NT; ++J) acc[q][I][J] = 0.0;
-
-  constexpr int NLD = (MP * LE_W + 255) / 256;
+  k1::zero_acc(acc);
+  constexpr int NLD = (MP * k1::W + 255) / 256;
   double stg[NLD];
   auto load = [&](long long e, int t0) __attribute__((always_inline)) {
     const double* xA = a.x + a.trial_rec[e] * a.rec_stride + a.trial_start[e] + off;
@@ -216,32 +117,32 @@ __global__ void __launch_bounds__(256, 2) lagcov_ens_split_kernel(LagcovEnsArgs 
 #pragma unroll
     for (int r = 0; r < NLD; ++r) {
       const int idx = threadIdx.x + 256 * r;
-      const int ch = idx / LE_W, tt = idx - ch * LE_W;
+      const int ch = idx / k1::W, tt = idx - ch * k1::W;
       const int t = t0 + tt;
       const double* x = ch < split ? xA : xB;
-      stg[r] = (idx < MP * LE_W && ch < m && t < n) ? x[(size_t)ch * a.ld + t] : 0.0;
+      stg[r] = (idx < MP * k1::W && ch < m && t < n) ? x[(size_t)ch * a.ld + t] : 0.0;
     }
   };
-  const int nch = (n + LE_TC - 1) / LE_TC;
+  const int nch = (n + k1::TC - 1) / k1::TC;
   const long long S = E * nch;                          // (trial, chunk) steps, trial-major
   long long e = e0;
   int t0 = 0;
-  const double* xa = xs + (4 * NT * wv + (l & 3)) * LE_S + (l >> 4);
-  const double* xb = xs + cc * LE_S + lag0 + (l >> 4);
+  const double* xa = k1::a_operand<NT>(xs, wv, l);
+  const double* xb = k1::b_operand(xs, lag0, l);
   for (long long s = 0; s < S; ++s) {
     load(e, t0);
     __syncthreads();                                    // the k-steps of the previous chunk have read xs
 #pragma unroll
     for (int r = 0; r < NLD; ++r) {
       const int idx = threadIdx.x + 256 * r;
-      const int ch = idx / LE_W, tt = idx - ch * LE_W;
-      if (idx < MP * LE_W) xs[ch * LE_S + tt] = stg[r];
+      const int ch = idx / k1::W, tt = idx - ch * k1::W;
+      if (idx < MP * k1::W) xs[ch * k1::S + tt] = stg[r];
     }
     __syncthreads();
     const int tc = t0;
-    t0 += LE_TC;
+    t0 += k1::TC;
     if (t0 >= n) { t0 = 0; ++e; }
-    le_ksteps_masked<NT, LG>(xa, xb, min(LE_TC, n - tc + 3) >> 2, nl, need, acc);
+    k1::ksteps_masked<NT, LG>(xa, xb, min(k1::TC, n - tc + 3) >> 2, nl, need, acc);
   }
   const double scale = 1.0 / (double)n;
   const double Ed = (double)E;
@@ -269,92 +170,50 @@ __global__ void __launch_bounds__(256, 2) lagcov_ens_split_kernel(LagcovEnsArgs 
 // ---- pairs of recordings (pseudo-dyad surrogates) -------------------------------------------------------------------------
 // Item `it` stages the channels < split from recording rec_a[it] and the channels >= split from recording rec_b[it], both at
 // item_start[it]: participant A of one dyad beside participant B of another, time-locked.  One window per item, so there is
-// no trial loop and no division by a trial count: the chunks, the k-steps, the order of products per accumulator and the
-// final scaling are lagcov_kernel's, and every computed element has the bits hmv_lagcov_f64 gives for the same window
-// written out as one recording.  With R_base the elements with both indices < split come from R_base[base_a[it]] and the
-// elements with both indices >= split (padding and its lag-0 identity included) from R_base[base_b[it]] -- two different
-// stacks, where lagcov_ens_split_kernel has one; the `need` mask, its place in an SGPR and the rule for accumulators that
-// straddle split are that kernel's.
+// no trial loop and no division by a trial count: every computed element has the bits hmv_lagcov_f64 gives for the same
+// window written out as one recording.  With R_base the elements with both indices < split come from R_base[base_a[it]] and
+// the elements with both indices >= split (padding and its lag-0 identity included) from R_base[base_b[it]] -- two different
+// stacks, where lagcov_ens_split_kernel has one; the `need` mask and the rule for accumulators that straddle split are that
+// kernel's.
 template <int NT, int LG>
 __global__ void __launch_bounds__(256, 2) lagcov_pairs_kernel(LagcovPairsArgs a) {
   constexpr int MP = 16 * NT;
-  __shared__ double xs[MP * LE_S];
+  __shared__ double xs[MP * k1::S];
   const int l = lane_id();
   const int wv = uni(threadIdx.x >> 6);
   const long long item = blockIdx.x;
   const int lag0 = blockIdx.y * LG;
   const int nl = min(LG, a.p + 1 - lag0);
-  const int i = l >> 4, cc = l & 15;
   const int n = a.n, m = a.m, split = a.split;
   const bool based = a.R_base != nullptr;
   const long long start = a.item_start[item];
   const double* xA = a.x + a.rec_a[item] * a.rec_stride + start;
   const double* xB = a.x + a.rec_b[item] * a.rec_stride + start;
-
-  unsigned need = 0;
-#pragma unroll
-  for (int I = 0; I < NT; ++I)
-#pragma unroll
-    for (int J = 0; J < NT; ++J) {
-      const int r0 = 4 * (NT * wv + I), c0 = 16 * J;     // rows r0 .. r0 + 3, columns c0 .. c0 + 15
-      const bool rows_a = r0 < split, rows_b = max(r0, split) <= min(r0 + 3, m - 1);
-      const bool cols_a = c0 < split, cols_b = max(c0, split) <= min(c0 + 15, m - 1);
-      if (!based || (rows_a && cols_b) || (rows_b && cols_a)) need |= 1u << (I * NT + J);
-    }
-  need = (unsigned)uni((int)need);
+  const unsigned need = k1::need_mask<NT>(wv, split, m, based);
 
   double acc[LG][NT][NT];
-#pragma unroll
-  for (int q = 0; q < LG; ++q)
-#pragma unroll
-    for (int I = 0; I < NT; ++I)
-#pragma unroll
-      for (int J = 0; J < NT; ++J) acc[q][I][J] = 0.0;
-
-  constexpr int NLD = (MP * LE_W + 255) / 256;
-  const double* xa = xs + (4 * NT * wv + (l & 3)) * LE_S + (l >> 4);
-  const double* xb = xs + cc * LE_S + lag0 + (l >> 4);
-  for (int t0 = 0; t0 < n; t0 += LE_TC) {
-    double stg[NLD];
-#pragma unroll
-    for (int r = 0; r < NLD; ++r) {                     // all loads of the chunk in flight, then the LDS stores
-      const int idx = threadIdx.x + 256 * r;
-      const int ch = idx / LE_W, tt = idx - ch * LE_W;
-      const int t = t0 + tt;
+  k1::zero_acc(acc);
+  const double* xa = k1::a_operand<NT>(xs, wv, l);
+  const double* xb = k1::b_operand(xs, lag0, l);
+  for (int t0 = 0; t0 < n; t0 += k1::TC) {
+    k1::stage_chunk<NT>(xs, t0, [&](int ch, int t) __attribute__((always_inline)) {
       const double* x = ch < split ? xA : xB;
-      stg[r] = (idx < MP * LE_W && ch < m && t < n) ? x[(size_t)ch * a.ld + t] : 0.0;
-    }
-    __syncthreads();                                    // the k-steps of the previous chunk have read xs
-#pragma unroll
-    for (int r = 0; r < NLD; ++r) {
-      const int idx = threadIdx.x + 256 * r;
-      const int ch = idx / LE_W, tt = idx - ch * LE_W;
-      if (idx < MP * LE_W) xs[ch * LE_S + tt] = stg[r];
-    }
-    __syncthreads();
-    le_ksteps_masked<NT, LG>(xa, xb, min(LE_TC, n - t0 + 3) >> 2, nl, need, acc);
+      return (ch < m && t < n) ? x[(size_t)ch * a.ld + t] : 0.0;
+    });
+    k1::ksteps_masked<NT, LG>(xa, xb, min(k1::TC, n - t0 + 3) >> 2, nl, need, acc);
   }
   const double scale = 1.0 / (double)n;                 // `corr_scale = 1 / n`, multiplied (mtmvar.py:57-59)
-  static_for<LG>([&](auto gc) __attribute__((always_inline)) {
-    constexpr int q = decltype(gc)::value;
-    if (q < nl) {
-      const int lag = lag0 + q;
-      const size_t tile = (size_t)MP * MP, stack = (size_t)(a.p + 1) * tile;
-      double* R = a.R + (size_t)item * stack + lag * tile;
-      const double* Ra = based ? a.R_base + (size_t)a.base_a[item] * stack + lag * tile : nullptr;
-      const double* Rb = based ? a.R_base + (size_t)a.base_b[item] * stack + lag * tile : nullptr;
-#pragma unroll
-      for (int I = 0; I < NT; ++I)
-#pragma unroll
-        for (int J = 0; J < NT; ++J) {
-          const int row = 4 * (NT * wv + I) + i, col = 16 * J + cc;
-          double v = acc[q][I][J] * scale;
-          if (lag == 0 && row == col && row >= m) v = 1.0;   // padded channels: identity block keeps G SPD
-          if (based && (row < split) == (col < split))        // (split < m: padding is >= split)
-            v = (row < split ? Ra : Rb)[(size_t)row * MP + col];
-          R[(size_t)row * MP + col] = v;
-        }
-    }
+  const size_t stack = (size_t)(a.p + 1) * MP * MP;
+  k1::store_acc(acc, a.R + (size_t)item * stack, lag0, nl, wv, l, [&](int lag) __attribute__((always_inline)) {
+    const double* Ra = based ? a.R_base + (size_t)a.base_a[item] * stack + (size_t)lag * MP * MP : nullptr;
+    const double* Rb = based ? a.R_base + (size_t)a.base_b[item] * stack + (size_t)lag * MP * MP : nullptr;
+    return [&, lag, Ra, Rb](int row, int col, double v) __attribute__((always_inline)) {
+      v = v * scale;
+      if (lag == 0 && row == col && row >= m) v = 1.0;               // padded channels: identity block keeps G SPD
+      if (based && (row < split) == (col < split))                   // (split < m: padding is >= split)
+        v = (row < split ? Ra : Rb)[(size_t)row * MP + col];
+      return v;
+    };
   });
 }
 
@@ -381,7 +240,7 @@ __device__ __forceinline__ LeSpan le_span(const LagcovEnsArgs& a, long long gi) 
 template <int NT, int LG>
 __global__ void __launch_bounds__(256, 2) lagens_block_kernel(LagcovEnsArgs a) {
   constexpr int MP = 16 * NT;
-  __shared__ double xs[MP * LE_S];
+  __shared__ double xs[MP * k1::S];
   __shared__ long long tb_off[2][LE_MAX_TPF];           // per fill: where the block of trial slot j starts ...
   __shared__ int tb_vl[2][LE_MAX_TPF];                  // ... and how many samples from there exist (0: no trial)
   const long long nblk = a.nwin + a.k - 1;
@@ -392,32 +251,26 @@ __global__ void __launch_bounds__(256, 2) lagens_block_kernel(LagcovEnsArgs a) {
   const int wv = uni(threadIdx.x >> 6);
   const int lag0 = blockIdx.y * LG;
   const int nl = min(LG, a.p + 1 - lag0);
-  const int i = l >> 4, cc = l & 15;
   const int m = a.m, hop = (int)a.hop;
   const int hopr = (hop + 3) & ~3;                      // whole k-steps
   const int SW = hopr + a.p;                            // staged columns per trial: the block and its p lagged samples
-  const int TPF = min(LE_MAX_TPF, LE_W / SW);           // >= 1: the launcher refuses SW > LE_W
+  const int TPF = min(LE_MAX_TPF, k1::W / SW);           // >= 1: the launcher refuses SW > k1::W
   const long long e0 = a.group_ptr[sp.g], e1 = a.group_ptr[sp.g + 1];
   const long long E = e1 - e0;
 
   double acc[LG][NT][NT];
-#pragma unroll
-  for (int q = 0; q < LG; ++q)
-#pragma unroll
-    for (int I = 0; I < NT; ++I)
-#pragma unroll
-      for (int J = 0; J < NT; ++J) acc[q][I][J] = 0.0;
+  k1::zero_acc(acc);
 
   // element r of this thread in every fill: channel (threadIdx.x + 256 r) / 96, staged column c = (threadIdx.x + 256 r)
   // mod 96 = trial slot * SW + column inside the slot.  256 * 3 is a multiple of 96: three distinct columns per thread.
-  constexpr int NLD = (MP * LE_W + 255) / 256;
+  constexpr int NLD = k1::NLD<NT>;
   int cj[3], ct[3];
 #pragma unroll
   for (int q = 0; q < 3; ++q) {
-    const int c = (threadIdx.x + 256 * q) % LE_W;
+    const int c = (threadIdx.x + 256 * q) % k1::W;
     cj[q] = c / SW;
     ct[q] = c - cj[q] * SW;
-    if (cj[q] >= TPF) { cj[q] = 0; ct[q] = LE_W; }       // columns past the last slot: staged as zeros, never read
+    if (cj[q] >= TPF) { cj[q] = 0; ct[q] = k1::W; }       // columns past the last slot: staged as zeros, never read
   }
   auto table = [&](long long f, int buf) __attribute__((always_inline)) {
     if ((int)threadIdx.x < TPF) {
@@ -439,8 +292,8 @@ __global__ void __launch_bounds__(256, 2) lagens_block_kernel(LagcovEnsArgs a) {
 #pragma unroll
     for (int r = 0; r < NLD; ++r) {
       const int idx = threadIdx.x + 256 * r;
-      const int ch = idx / LE_W, j = cj[r % 3], tt = ct[r % 3];
-      const bool in = idx < MP * LE_W && ch < m && tt < tb_vl[buf][j];
+      const int ch = idx / k1::W, j = cj[r % 3], tt = ct[r % 3];
+      const bool in = idx < MP * k1::W && ch < m && tt < tb_vl[buf][j];
       stg[r] = in ? a.x[tb_off[buf][j] + (long long)ch * a.ld + tt] : 0.0;
     }
   };
@@ -449,33 +302,21 @@ __global__ void __launch_bounds__(256, 2) lagens_block_kernel(LagcovEnsArgs a) {
     table(0, 0);
     __syncthreads();
   }
-  const double* xa = xs + (4 * NT * wv + (l & 3)) * LE_S + (l >> 4);
-  const double* xb = xs + cc * LE_S + lag0 + (l >> 4);
+  const double* xa = k1::a_operand<NT>(xs, wv, l);
+  const double* xb = k1::b_operand(xs, lag0, l);
   const bool mask_a = (hop & 3) != 0;                   // the A operand ends at the block even if real samples follow
   for (long long f = 0; f < nf; ++f) {
     load((int)(f & 1));
     __syncthreads();                                    // the k-steps of the previous fill have read xs
-#pragma unroll
-    for (int r = 0; r < NLD; ++r) {
-      const int idx = threadIdx.x + 256 * r;
-      const int ch = idx / LE_W, tt = idx - ch * LE_W;
-      if (idx < MP * LE_W) xs[ch * LE_S + tt] = stg[r];
-    }
+    k1::store_chunk<NT>(xs, stg);
     if (f + 1 < nf) table(f + 1, (int)((f + 1) & 1));   // for the next fill's loads; its buffer was last read a fill ago
     __syncthreads();
     const long long left = E - f * TPF;
     const int live = (int)(left < TPF ? left : TPF);
-    for (int j = 0; j < live; ++j) le_ksteps<NT, LG>(xa + j * SW, xb + j * SW, hopr >> 2, nl, mask_a, hop, l, acc);
+    for (int j = 0; j < live; ++j) k1::ksteps<NT, LG>(xa + j * SW, xb + j * SW, hopr >> 2, nl, mask_a, hop, l, acc);
   }
-  static_for<LG>([&](auto gc) __attribute__((always_inline)) {
-    constexpr int q = decltype(gc)::value;
-    if (q < nl) {
-      double* Q = a.Q + ((size_t)blockIdx.x * (a.p + 1) + lag0 + q) * MP * MP;
-#pragma unroll
-      for (int I = 0; I < NT; ++I)
-#pragma unroll
-        for (int J = 0; J < NT; ++J) Q[(size_t)(4 * (NT * wv + I) + i) * MP + 16 * J + cc] = acc[q][I][J];
-    }
+  k1::store_acc(acc, a.Q + (size_t)blockIdx.x * (a.p + 1) * MP * MP, lag0, nl, wv, l, [](int) __attribute__((always_inline)) {
+    return [](int, int, double v) __attribute__((always_inline)) { return v; };   // unscaled, padding zero
   });
 }
 
@@ -542,7 +383,7 @@ __global__ void __launch_bounds__(256) lagens_comb_kernel(LagcovEnsArgs a) {
 bool lagcov_ensemble_shared_ok(int n, long long hop, int p, int max_k) {
   if (hop < 1 || n % hop != 0 || hop <= p) return false;
   const long long k = n / hop;
-  return k >= 2 && k <= max_k && ((hop + 3) & ~3LL) + p <= LE_W;   // one LDS fill holds a trial's block and its lags
+  return k >= 2 && k <= max_k && ((hop + 3) & ~3LL) + p <= k1::W;   // one LDS fill holds a trial's block and its lags
 }
 
 long long lagcov_ensemble_q_tiles(long long n_items, long long nwin, int k) {
@@ -552,77 +393,53 @@ long long lagcov_ensemble_q_tiles(long long n_items, long long nwin, int k) {
 
 int launch_lagcov_ensemble(const LagcovEnsArgs& a, int m_pad, bool shared, hipStream_t st) {
   if (a.n_items == 0) return 0;
-  if (a.p > LE_HALO) return -2;
+  if (a.p > k1::HALO) return -2;
   constexpr int LG = 3;
-  const dim3 block(256);
+  const dim3 block(256), grid((unsigned)a.n_items, (a.p + LG) / LG);
   if (!shared) {
-    const dim3 grid((unsigned)a.n_items, (a.p + LG) / LG);
-    switch (m_pad) {
-      case 16: hipLaunchKernelGGL((lagcov_ens_kernel<1, LG>), grid, block, 0, st, a); break;
-      case 32: hipLaunchKernelGGL((lagcov_ens_kernel<2, LG>), grid, block, 0, st, a); break;
-      case 48: hipLaunchKernelGGL((lagcov_ens_kernel<3, LG>), grid, block, 0, st, a); break;
-      case 64: hipLaunchKernelGGL((lagcov_ens_kernel<4, LG>), grid, block, 0, st, a); break;
-      default: return -1;
-    }
+    if (k1::for_nt(m_pad, [&](auto nt) {
+          hipLaunchKernelGGL((lagcov_ens_kernel<decltype(nt)::value, LG>), grid, block, 0, st, a);
+        }))
+      return -1;
     return (int)hipGetLastError();
   }
   if (!lagcov_ensemble_shared_ok(a.n, a.hop, a.p, LE_MAX_K) || a.n / a.hop != a.k || a.nwin < 1 || !a.Q) return -3;
   const long long ngc = (a.it0 + a.n_items - 1) / a.nwin - a.it0 / a.nwin + 1;
   const dim3 gq((unsigned)(ngc * (a.nwin + a.k - 1)), (a.p + LG) / LG), gc((unsigned)a.n_items, a.p + 1);
-  switch (m_pad) {
-    case 16:
-      hipLaunchKernelGGL((lagens_block_kernel<1, LG>), gq, block, 0, st, a);
-      hipLaunchKernelGGL(lagens_comb_kernel<1>, gc, block, 0, st, a);
-      break;
-    case 32:
-      hipLaunchKernelGGL((lagens_block_kernel<2, LG>), gq, block, 0, st, a);
-      hipLaunchKernelGGL(lagens_comb_kernel<2>, gc, block, 0, st, a);
-      break;
-    case 48:
-      hipLaunchKernelGGL((lagens_block_kernel<3, LG>), gq, block, 0, st, a);
-      hipLaunchKernelGGL(lagens_comb_kernel<3>, gc, block, 0, st, a);
-      break;
-    case 64:
-      hipLaunchKernelGGL((lagens_block_kernel<4, LG>), gq, block, 0, st, a);
-      hipLaunchKernelGGL(lagens_comb_kernel<4>, gc, block, 0, st, a);
-      break;
-    default: return -1;
-  }
+  if (k1::for_nt(m_pad, [&](auto nt) {
+        hipLaunchKernelGGL((lagens_block_kernel<decltype(nt)::value, LG>), gq, block, 0, st, a);
+        hipLaunchKernelGGL(lagens_comb_kernel<decltype(nt)::value>, gc, block, 0, st, a);
+      }))
+    return -1;
   return (int)hipGetLastError();
 }
 
 int launch_lagcov_ensemble_split(const LagcovEnsArgs& a, int m_pad, hipStream_t st) {
   if (a.n_items == 0) return 0;
-  if (a.p > LE_HALO) return -2;
+  if (a.p > k1::HALO) return -2;
   if (!a.trial_rec_b || !a.trial_start_b || a.split < 1 || a.split >= a.m || (a.R_base != nullptr) != (a.item_base != nullptr))
     return -4;
   constexpr int LG = 3;
   const dim3 block(256), grid((unsigned)a.n_items, (a.p + LG) / LG);
-  switch (m_pad) {
-    case 16: hipLaunchKernelGGL((lagcov_ens_split_kernel<1, LG>), grid, block, 0, st, a); break;
-    case 32: hipLaunchKernelGGL((lagcov_ens_split_kernel<2, LG>), grid, block, 0, st, a); break;
-    case 48: hipLaunchKernelGGL((lagcov_ens_split_kernel<3, LG>), grid, block, 0, st, a); break;
-    case 64: hipLaunchKernelGGL((lagcov_ens_split_kernel<4, LG>), grid, block, 0, st, a); break;
-    default: return -1;
-  }
+  if (k1::for_nt(m_pad, [&](auto nt) {
+        hipLaunchKernelGGL((lagcov_ens_split_kernel<decltype(nt)::value, LG>), grid, block, 0, st, a);
+      }))
+    return -1;
   return (int)hipGetLastError();
 }
 
 int launch_lagcov_pairs(const LagcovPairsArgs& a, int m_pad, hipStream_t st) {
   if (a.n_items == 0) return 0;
-  if (a.p > LE_HALO) return -2;
+  if (a.p > k1::HALO) return -2;
   if (!a.rec_a || !a.rec_b || !a.item_start || a.split < 1 || a.split >= a.m ||
       (a.R_base != nullptr) != (a.base_a != nullptr) || (a.R_base != nullptr) != (a.base_b != nullptr))
     return -4;
   constexpr int LG = 3;
   const dim3 block(256), grid((unsigned)a.n_items, (a.p + LG) / LG);
-  switch (m_pad) {
-    case 16: hipLaunchKernelGGL((lagcov_pairs_kernel<1, LG>), grid, block, 0, st, a); break;
-    case 32: hipLaunchKernelGGL((lagcov_pairs_kernel<2, LG>), grid, block, 0, st, a); break;
-    case 48: hipLaunchKernelGGL((lagcov_pairs_kernel<3, LG>), grid, block, 0, st, a); break;
-    case 64: hipLaunchKernelGGL((lagcov_pairs_kernel<4, LG>), grid, block, 0, st, a); break;
-    default: return -1;
-  }
+  if (k1::for_nt(m_pad, [&](auto nt) {
+        hipLaunchKernelGGL((lagcov_pairs_kernel<decltype(nt)::value, LG>), grid, block, 0, st, a);
+      }))
+    return -1;
   return (int)hipGetLastError();
 }
 
