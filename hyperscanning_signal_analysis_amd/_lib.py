@@ -27,6 +27,7 @@ SIGNATURES = {
                                        c_void_p, c_void_p, c_void_p]),
     "hmv_yw_solve_f64": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_int64, c_void_p]),
+    "hmv_yw_routes_i32": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "hmv_twiddles_f64": (c_int, [c_void_p, c_int, c_double, c_int, c_void_p, c_void_p]),
     "hmv_tf_workspace_doubles": (c_int64, [c_int64, c_int, c_int]),
     "hmv_tf_f64": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
@@ -146,6 +147,7 @@ FLAG_UNFUSED_NORM = 1
 FLAG_YW_TILED = 2
 FLAG_YW_ONE_LAUNCH = 4
 FLAG_DIRECT_LAGCOV = 8
+FLAG_YW_PIVOTED = 16
 # measures of hmv_sliding_auto_f64 and the criterion numbering it shares with hmv_fad_f64
 MEASURE_FFDTF = 0
 MEASURE_DDTF = 1

@@ -22,7 +22,7 @@ inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 // Tuning knobs: the environment is parsed once, at load time, with range checks; hmv_set_tuning overrides.
 constexpr int N_TUNE = 7;
 struct TuneRange { long long lo, hi; };
-constexpr TuneRange kTuneRange[N_TUNE] = {{0, 0}, {0, 1 << 20}, {0, 3}, {0, 2}, {0, 4}, {0, 140000}, {-1, 1 << 20}};
+constexpr TuneRange kTuneRange[N_TUNE] = {{0, 0}, {0, 1 << 20}, {0, 3}, {0, 2}, {0, 5}, {0, 140000}, {-1, 1 << 20}};
 long long env_knob(const char* name, int key) {
   const char* e = getenv(name);
   if (!e || !*e) return 0;
@@ -305,9 +305,12 @@ int hmv_yw_solve_f64(const double* R, int64_t n_items, int m, int p, double* ws,
   if (mp < 0) return fail(-1, "hmv_yw_solve_f64: channel count must be in 1..64");
   if (p < 1 || p > HMV_MAX_ORDER) return fail(-2, "hmv_yw_solve_f64: model order must be in 1..32");
   if (!R || !ws || !ar || !V || !info || n_items < 0) return fail(-4, "hmv_yw_solve_f64: null pointer");
+  if (vq_logdet && ((flags & HMV_FLAG_YW_PIVOTED) || hmv::tuning(HMV_TUNE_YW_FORM) == 5))
+    return fail(-6, "hmv_yw_solve_f64: the pivoted LU gives no criterion curve (vq_logdet must be NULL)");
   hmv::YwArgs a{};
   a.R = R; a.n_items = n_items; a.m = m; a.p = p; a.ws = ws; a.ar = ar; a.V = V;
   a.Vq_logdet = vq_logdet; a.info = info; a.tiled = (flags & HMV_FLAG_YW_TILED) ? 1 : ((flags & HMV_FLAG_YW_ONE_LAUNCH) ? 0 : -1);
+  a.pivoted = (flags & HMV_FLAG_YW_PIVOTED) ? 1 : 0;
   return hmv::launch_yw(a, mp, S(stream));
 }
 
@@ -328,6 +331,8 @@ int hmv_yw_solve_auto_f64(const double* R, int64_t n_items, int m, int pmax, int
   if (crit < 0 || crit > 2) return fail(-5, "hmv_yw_solve_auto_f64: criterion must be 0 (AIC), 1 (HQ) or 2 (SC)");
   if (flags & (HMV_FLAG_YW_TILED | HMV_FLAG_YW_ONE_LAUNCH))
     return fail(-6, "hmv_yw_solve_auto_f64: the LDL^T forms of K2 have no automatic order");
+  if (flags & HMV_FLAG_YW_PIVOTED)
+    return fail(-6, "hmv_yw_solve_auto_f64: the pivoted LU has no automatic order (no criterion curve)");
   if (!R || !ws || !ar || !V || !order_out || !info || n_items < 0) return fail(-4, "hmv_yw_solve_auto_f64: null pointer");
   hmv::YwArgs a{};
   a.R = R; a.n_items = n_items; a.m = m; a.p = pmax; a.ws = ws; a.ar = ar; a.V = V; a.Vq_logdet = vq_logdet; a.info = info;
@@ -335,6 +340,14 @@ int hmv_yw_solve_auto_f64(const double* R, int64_t n_items, int m, int pmax, int
   hmv::YwAutoArgs sel{};
   sel.n = n; sel.crit_c = crit_factor(crit, n); sel.order_out = order_out; sel.crit_out = crit_out;
   return hmv::launch_yw_auto(a, sel, mp, S(stream));
+}
+
+int hmv_yw_routes_i32(const double* ws, int64_t n_items, int m, int p, int32_t* route, void* stream) {
+  const int mp = pad_of(m);
+  if (mp < 0) return fail(-1, "hmv_yw_routes_i32: channel count must be in 1..64");
+  if (p < 1 || p > HMV_MAX_ORDER) return fail(-2, "hmv_yw_routes_i32: model order must be in 1..32");
+  if (!ws || !route || n_items < 0) return fail(-4, "hmv_yw_routes_i32: null pointer");
+  return hmv::launch_yw_routes(ws, n_items, mp, p, reinterpret_cast<int*>(route), S(stream));
 }
 
 int hmv_twiddles_f64(const double* freqs, int F, double fs, int p, double* tw, void* stream) {
@@ -858,6 +871,8 @@ int sliding_impl(const SlidingArgs& a) {
   if (automatic && a.crit > 2) return fail(-5, "hmv_sliding_ffdtf_f64: criterion must be 0 (AIC), 1 (HQ) or 2 (SC)");
   if (automatic && (a.flags & (HMV_FLAG_YW_TILED | HMV_FLAG_YW_ONE_LAUNCH)))
     return fail(-6, "hmv_sliding_ffdtf_f64: the LDL^T forms of K2 have no automatic order");
+  if (automatic && (a.flags & HMV_FLAG_YW_PIVOTED))
+    return fail(-6, "hmv_sliding_ffdtf_f64: the pivoted LU has no automatic order (no criterion curve)");
   if (a.mix && (a.mix->n_trials < 1 || a.mix->n_win < 1 || a.mix->n_mix < 1))
     return fail(-10, "hmv_sliding_ffdtf_f64: n_trials, n_win and n_mix must be >= 1");
   if (a.n_items == 0) return 0;                                    // empty batch: nothing to do, nothing to check
@@ -988,7 +1003,7 @@ int sliding_impl(const SlidingArgs& a) {
       const int64_t s0 = k3_split ? k3_split_point(c, mp, norm_lag_items(mp, a.F)) : 0;
       hmv::YwArgs ya{};
       ya.R = R; ya.n_items = s0 ? s0 : c0; ya.m = a.m; ya.p = a.p; ya.ws = ws; ya.ar = ar_c; ya.V = V_c; ya.info = a.info_yw + i0;
-      ya.tiled = -1; ya.no_emit = 1;
+      ya.tiled = -1; ya.no_emit = 1; ya.pivoted = (a.flags & HMV_FLAG_YW_PIVOTED) ? 1 : 0;
       rc = hmv::launch_yw(ya, mp, st0);
       if (!rc && s0) {
         // fork behind K2's first part (the remainder never shares a compute unit with it); the join is waited for inside
@@ -1033,7 +1048,7 @@ int sliding_impl(const SlidingArgs& a) {
       auto red_flags = [&](int nx) {
         const bool chain = (a.flags & HMV_FLAG_YW_TILED) ||
                            (ldl && !(a.flags & HMV_FLAG_YW_ONE_LAUNCH) && pad_of(nx) == 64 && c >= 128);
-        return (int64_t)(ldl ? (chain ? HMV_FLAG_YW_TILED : HMV_FLAG_YW_ONE_LAUNCH) : 0);
+        return (int64_t)(ldl ? (chain ? HMV_FLAG_YW_TILED : HMV_FLAG_YW_ONE_LAUNCH) : 0) | (a.flags & HMV_FLAG_YW_PIVOTED);
       };
       rc = hmv::launch_bgc_gather(R, Ra, Rb, c, a.m, mp, a.p, na, st0);
       if (!rc) rc = hmv_yw_solve_f64(Ra, c, na, a.p, ws, arr, const_cast<double*>(ga.VrA), nullptr, ir, red_flags(na), st0);

@@ -123,6 +123,9 @@ struct YwArgs {
   // A generation's tiles of `ws` ([k][row][col] at tile (p & 1) * p), where the packing kernel of K3 reads it.  Windows
   // re-solved by the LDL^T kernel still get their `ar` (their scratch is overwritten), flagged by the guard word.
   int no_emit;
+  // pivoted fallback (HMV_FLAG_YW_PIVOTED): behind the solver above, the windows it left with info != 0 are solved again
+  // by the dense LU with partial pivoting (yw_lu.hip), which overwrites their ar, V and info and sets their route word to 2
+  int pivoted;
 };
 // automatic model order (yw_auto.hip only; a struct of its own so that the fixed-order kernels' arguments stay as they
 // were): YwArgs::p is the largest order tried, criterion of order q = log det Vf_q + crit_c * q * m^2 / n
@@ -136,6 +139,11 @@ struct YwAutoArgs {
 long long yw_ws_tiles(int p);
 int launch_yw(const YwArgs& a, int m_pad, hipStream_t st);
 int launch_yw_lwr(const YwArgs& a, int m_pad, hipStream_t st);
+// yw_lu.hip: the LU over every window (all != 0) or over the windows whose info is not zero; the route word (the last int
+// of a window's scratch: 0 recursion, 1 LDL^T, 2 LU) set for a whole batch, and copied out
+int launch_yw_lu(const YwArgs& a, int m_pad, int all, hipStream_t st);
+int launch_yw_route_set(double* ws, long long n_items, int m_pad, int p, int value, hipStream_t st);
+int launch_yw_routes(const double* ws, long long n_items, int m_pad, int p, int* route, hipStream_t st);
 // how many workgroups (= windows) of the default recursion one compute unit holds at once, from the runtime; 0: unknown
 int yw_lwr_occupancy(int m_pad);
 int launch_yw_lwr2(const YwArgs& a, int m_pad, hipStream_t st);

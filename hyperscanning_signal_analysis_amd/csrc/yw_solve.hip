@@ -16,6 +16,8 @@
 // ar[:, :, b] = Z[b].  G is a Gram matrix of lagged data (biased estimator), i.e. symmetric positive
 // (semi)definite, so no pivoting is needed; a non-positive pivot is reported through `info` and becomes
 // numpy.linalg.LinAlgError("Singular matrix") in the Python layer, like the reference's dgesv failure.
+// (Rounding makes a pivot non-positive from cond ~ 1e13 on, where dgesv still answers: with YwArgs::pivoted such windows
+// go on to the dense LU with partial pivoting of yw_lu.hip, launch_yw below.)
 //
 // Two forms walk the same tile products in the same order (bit-identical results):
 //   * tile form: one workgroup (4 waves) per (window, tile); the factorisation is launched tile column by tile
@@ -414,11 +416,10 @@ int launch_yw_guarded(const YwArgs& a_in, int m_pad, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
-int launch_yw(const YwArgs& a_in, int m_pad, hipStream_t st) {
+static int launch_yw_unpivoted(const YwArgs& a_in, int m_pad, hipStream_t st) {
   YwArgs a = a_in;
   a.only_guarded = 0;
   a.order = nullptr;                          // (fixed-order entry: one order for the batch)
-  if (a.n_items == 0) return 0;
   // No LDL^T form asked for: the block Levinson-Whittle recursion (half the tile products, a quarter of the state), then
   // the one-launch LDL^T over the windows whose tile inverses tripped the conditioning guard (normally none: every other
   // workgroup of that launch reads one int and exits).
@@ -461,6 +462,21 @@ int launch_yw(const YwArgs& a_in, int m_pad, hipStream_t st) {
     case 64: return launch_yw_nt<4>(a, st);
     default: return -1;
   }
+}
+
+// The solver the caller's form and HMV_TUNE_YW_FORM choose, then (YwArgs::pivoted) the pivoted LU over the windows it
+// left with info != 0: every other workgroup of that launch reads one int and exits.  HMV_TUNE_YW_FORM = 5 (measurement
+// and tests): the LU alone, for every window.  The route word of every window is defined afterwards: 0 recursion, 1 LDL^T
+// (the recursion writes 0 / 1 itself; an LDL^T form solves every window and writes no word, so it is set here), 2 LU.
+int launch_yw(const YwArgs& a, int m_pad, hipStream_t st) {
+  if (a.n_items == 0) return 0;
+  const long long form = tuning(4 /* HMV_TUNE_YW_FORM */);
+  if (form == 5) return a.Vq_logdet ? -1 : launch_yw_lu(a, m_pad, 1, st);
+  int rc = launch_yw_unpivoted(a, m_pad, st);
+  if (rc) return rc;
+  if (a.tiled >= 0 || form == 1) rc = launch_yw_route_set(a.ws, a.n_items, m_pad, a.p, 1, st);
+  if (!rc && a.pivoted) rc = launch_yw_lu(a, m_pad, 0, st);
+  return rc;
 }
 
 }  // namespace hmv

@@ -175,6 +175,31 @@ def no_block_auto_order(p, where: str):
     return int(p)
 
 
+def resolve_pivoted_yw(pivoted_yw) -> bool:
+    """`Engine(pivoted_yw=...)`: a bool, or None for the environment variable HYPERMVAR_YW_PIVOTED (unset, empty, "0",
+    "false", "no", "off": off; anything else: on).  Needs no GPU."""
+    if pivoted_yw is None:
+        import os
+        return os.environ.get("HYPERMVAR_YW_PIVOTED", "").strip().lower() not in ("", "0", "false", "no", "off")
+    if not isinstance(pivoted_yw, (bool, np.bool_)):
+        raise ValueError(f"pivoted_yw must be True, False or None, got {pivoted_yw!r}")
+    return bool(pivoted_yw)
+
+
+def no_pivoted_auto_order(pivoted: bool, where: str):
+    """The automatic model order compares the criterion curve of the recursion; the pivoted LU has none."""
+    if pivoted:
+        raise ValueError(f"{where}: the automatic model order (p=None) is not available with the pivoted Yule-Walker "
+                         "fallback (pivoted_yw / HYPERMVAR_YW_PIVOTED / FLAG_YW_PIVOTED): an LU gives no criterion curve; "
+                         "pass an integer p")
+
+
+def route_counts(route) -> dict:
+    """{"recursion", "ldlt", "lu"}: how many windows each K2 solver took, from their route words (0 / 1 / 2)."""
+    r = np.asarray(route.cpu() if isinstance(route, torch.Tensor) else route).reshape(-1)
+    return {"recursion": int((r == 0).sum()), "ldlt": int((r == 1).sum()), "lu": int((r == 2).sum())}
+
+
 _MEASURES = {"ffdtf": _lib.MEASURE_FFDTF, "ddtf": _lib.MEASURE_DDTF, "gpdc": _lib.MEASURE_GPDC}
 _NO_ENSEMBLE_ORDER = ("ensemble fits need an integer model order p: the reference's mvar_criterion does not take "
                       "(channels, samples, trials) input, so there is no automatic order to reproduce")
@@ -209,8 +234,14 @@ class _Route:
 
 
 class Engine:
-    def __init__(self, device=None, pivot_tau: float | None = None, max_workspace_bytes: int = 24 << 30):
+    def __init__(self, device=None, pivot_tau: float | None = None, max_workspace_bytes: int = 24 << 30,
+                 pivoted_yw: bool | None = None):
+        """pivoted_yw: windows that the Yule-Walker solvers refuse (info != 0: a pivot that rounding made non-positive,
+        from cond ~ 1e13 on) are solved again by the dense LU with partial pivoting, like the reference's
+        `np.linalg.solve`; the engine ORs `FLAG_YW_PIVOTED` into every fixed-order call.  None: HYPERMVAR_YW_PIVOTED."""
         import os
+        self.pivoted_yw = resolve_pivoted_yw(pivoted_yw)
+        self.yw_flag = _lib.FLAG_YW_PIVOTED if self.pivoted_yw else 0
         if pivot_tau is None:
             pivot_tau = float(os.environ.get("HYPERMVAR_PIVOT_TAU", DEFAULT_PIVOT_TAU))
         self.lib = _lib.load()                      # fails loudly when the HIP library is not built
@@ -316,7 +347,13 @@ class Engine:
         return out
 
     # ------------------------------------------------------------------ K2
-    def yw_solve(self, R: torch.Tensor, m: int, want_logdet: bool = False, flags: int = 0):
+    def yw_solve(self, R: torch.Tensor, m: int, want_logdet: bool = False, flags: int = 0, return_route: bool = False):
+        """K2 -> (ar, V, logdet, info[, route]).  route (return_route=True): int32 per item, which solver took it --
+        0 the recursion, 1 the LDL^T, 2 the pivoted LU (`FLAG_YW_PIVOTED`, or an engine with `pivoted_yw`)."""
+        flags = int(flags) | self.yw_flag
+        if want_logdet and (flags & _lib.FLAG_YW_PIVOTED):
+            raise ValueError("yw_solve: want_logdet is not available with the pivoted Yule-Walker fallback (pivoted_yw / "
+                             "FLAG_YW_PIVOTED): an LU gives no criterion curve")
         n_items, p1, mp, _ = R.shape
         p = p1 - 1
         ws = self.empty(n_items * int(self.lib.hmv_yw_workspace_doubles(m, p)))
@@ -328,12 +365,37 @@ class Engine:
             rc = self.lib.hmv_yw_solve_f64(R.data_ptr(), n_items, m, p, ws.data_ptr(), ar.data_ptr(), V.data_ptr(),
                                            _ptr(logdet), info.data_ptr(), int(flags), self.stream())
         _lib.check(rc, "hmv_yw_solve_f64")
+        if return_route:
+            return ar, V, logdet, info, self.yw_routes(ws, n_items, m, p)
         return ar, V, logdet, info
+
+    def window_routes(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, p: int,
+                      chunk: int = 128):
+        """K1 + K2 with the pivoted fallback on, `chunk` windows at a time -> (route int32 per item: 0 recursion, 1 LDL^T,
+        2 LU; info int32 per item, not zero where even the LU met an exactly zero pivot column)."""
+        n_items = int(item_rec.numel())
+        route = self.empty(n_items, dtype=torch.int32)
+        info = self.empty(n_items, dtype=torch.int32)
+        for i0 in range(0, n_items, int(chunk)):
+            sl = slice(i0, min(n_items, i0 + int(chunk)))
+            R = self.lagcov(x, item_rec[sl], item_start[sl], n, p)
+            _, _, _, info[sl], route[sl] = self.yw_solve(R, x.shape[1], flags=_lib.FLAG_YW_PIVOTED, return_route=True)
+        return route, info
+
+    def yw_routes(self, ws: torch.Tensor, n_items: int, m: int, p: int):
+        """The route words of a K2 workspace (`hmv_yw_routes_i32`): int32 per item, 0 recursion, 1 LDL^T, 2 LU."""
+        route = self.empty(n_items, dtype=torch.int32)
+        if n_items:
+            with torch.cuda.device(self.device):
+                rc = self.lib.hmv_yw_routes_i32(ws.data_ptr(), n_items, int(m), int(p), route.data_ptr(), self.stream())
+            _lib.check(rc, "hmv_yw_routes_i32")
+        return route
 
     def yw_solve_auto(self, R: torch.Tensor, m: int, n: int, crit_type: str = "AIC"):
         """K2 with the order chosen per item (`hmv_yw_solve_auto_f64`): R (items, pmax+1, MP, MP) from K1 at p = pmax, n the
         window length -> (ar (items, MP, MP, pmax) of the selected order, zero beyond it; V; orders int32, 0 for a failed
         item; crit (items, pmax), the criterion curve of `mvar_criterion` (mtmvar.py:551-601); info)."""
+        no_pivoted_auto_order(self.pivoted_yw, "yw_solve_auto")
         n_items, p1, mp, _ = R.shape
         pmax, crit = auto_order_args(p1 - 1, crit_type, n)
         ws = self.empty(max(1, n_items * int(self.lib.hmv_yw_workspace_doubles(m, pmax))))
@@ -651,6 +713,9 @@ class Engine:
         """The one driver of the fused entries; `rt` (a `_Route`) carries what differs between them.  Top to bottom: the
         inputs, the empty batch, the grid, where the C call writes, chunk and workspace, the outputs, the call, the band
         sums of the two-step form, `check`, the result `(out[, S][, bad][, ar, V, infos][, orders, crit])`."""
+        flags = int(flags) | self.yw_flag
+        if rt.automatic:
+            no_pivoted_auto_order(bool(flags & _lib.FLAG_YW_PIVOTED), rt.name)
         if rt.m is None:
             assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
             x = x if x.stride(2) == 1 else x.contiguous()
@@ -865,6 +930,7 @@ class Engine:
         appends the boolean device mask, False skips the check.  return_ar appends (ar, V, (info_yw, info_red, info_gc)).
         An integer p is required: the automatic order (p=None) is not available for this call."""
         p = no_block_auto_order(p, "sliding_block_granger")
+        flags = int(flags) | self.yw_flag
         assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
         x = x if x.stride(2) == 1 else x.contiguous()
         n_rec, m, T = x.shape

@@ -173,11 +173,28 @@ def savez_fast(path, compresslevel=0, **arrays):
                 np.lib.format.write_array(f, np.asanyarray(val), allow_pickle=False)
 
 
+def resolve_pivoted_fallback(pivoted_fallback, engine_setting: bool, auto: bool):
+    """`run(pivoted_fallback=...)` against the engine's own setting -> (on?, the `flags` keyword of the engine calls).  None
+    takes the engine's; False cannot switch off what the engine ORs into every call.  Needs no GPU."""
+    from . import _lib
+    if pivoted_fallback is not None and not isinstance(pivoted_fallback, bool):
+        raise ValueError(f"pivoted_fallback must be True, False or None, got {pivoted_fallback!r}")
+    if pivoted_fallback is False and engine_setting:
+        raise ValueError("escan_batch.run(pivoted_fallback=False): the engine was made with pivoted_yw (or "
+                         "HYPERMVAR_YW_PIVOTED is set) and adds the fallback to every call; pass an engine without it")
+    pivoted = bool(engine_setting) if pivoted_fallback is None else pivoted_fallback
+    if pivoted and auto:
+        raise ValueError("escan_batch.run(pivoted_fallback=True): the automatic model order (model_order=None) is not "
+                         "available with the pivoted Yule-Walker fallback (an LU gives no criterion curve); pass an integer "
+                         "model_order")
+    return pivoted, ({"flags": _lib.FLAG_YW_PIVOTED} if pivoted else {})
+
+
 def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, freqs=None, bands=hdist.DEFAULT_BANDS,
         low_cutoff_hz=None, high_cutoff_hz=None, channel_subset=None, with_psd=False, psd_fmin=1.0, psd_fmax=30.0,
         psd_bandwidth=2.0, save_full=False, skip_existing=True, reader=None, engine=None, world=1, rank=0,
         verbose=True, prefetch=2, timing=None, save_workers=4, compresslevel=0, measures=("ffdtf",), significance=None,
-        max_model_order=20, crit_type="AIC", validation_lags=None, block_granger=False):
+        max_model_order=20, crit_type="AIC", validation_lags=None, block_granger=False, pivoted_fallback=None):
     """Process every dyad under <root>/EEG.  Per dyad one `<out_dir>/<dyad>_ffdtf.npz` with, per segment `<task>/<event>`:
         <seg>/ffdtf_bands   (windows, n, n, n_bands)   band-integrated ffDTF of every window
         <seg>/ffdtf         (windows, n, n, F)         only with save_full=True (8.4 MB per window at 64 channels)
@@ -210,6 +227,10 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                                                        "block_granger": true.  Needs an integer model_order.
         <seg>/acf_fraction  (windows,)                 with validation_lags: share of the residual correlations beyond
                                                        1.96 / sqrt(N)
+      pivoted_fallback: windows that the Yule-Walker solvers refuse are solved by the pivoted LU, as the reference's
+      `np.linalg.solve` would (`Engine(pivoted_yw=...)`); None takes the engine's setting.  Every segment's meta entry then
+      carries "yw_routes": {"recursion", "ldlt", "lu"}, how many of its windows each solver took (one more K1 + K2 over the
+      segment).  Needs an integer model_order.
       plus `channels`, `freqs`, `meta` (JSON, its `measures` field lists what was computed, `significance` the test).  Returns {"done": [...], "skipped": [...], "failed": [(dyad, error)],
       "timing": {...}}.
     A window whose fit is singular is NaN-filled, not fatal (the reference would raise and lose the dyad); a segment that
@@ -239,6 +260,7 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
     order = None if auto else int(model_order)
     order_kw = dict(max_model_order=pmax, crit_type=crit_type) if auto else {}
     eng = engine or default_engine()
+    pivoted, yw_kw = resolve_pivoted_fallback(pivoted_fallback, eng.pivoted_yw, auto)
     reader = reader or xarray_reader
     out_dir = Path(out_dir)
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -319,14 +341,14 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                         extra = {}                                 # dDTF / GPDC of the same windows, NaN-filled alike
                         if save_full:
                             r = eng.sliding_ffdtf(xd, rec_i, st_i, W, order, f, fs, check="mask", grid=grid_w,
-                                                  return_orders=auto, **order_kw)
+                                                  return_orders=auto, **order_kw, **yw_kw)
                             ff, bad = r[0], r[1]
                             bsum = eng.band_sums(ff, lo, hi)
                             ff.masked_fill_(bad.view(-1, 1, 1, 1), float("nan"))
                         else:          # the reduced product straight from K3's row workers: the full array is never written
                             ff = None
                             r = eng.sliding_ffdtf(xd, rec_i, st_i, W, order, f, fs, check="mask", grid=grid_w, bands=(lo, hi),
-                                                  return_orders=auto, **order_kw)
+                                                  return_orders=auto, **order_kw, **yw_kw)
                             bsum, bad = r[0], r[1]
                         if auto:
                             extra["orders"] = r[2]
@@ -334,13 +356,13 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                         for meas in (m_ for m_ in measures if m_ != "ffdtf"):
                             run_m = eng.sliding_ddtf if meas == "ddtf" else eng.sliding_gpdc
                             if save_full:
-                                full_m, bad_m = run_m(xd, rec_i, st_i, W, order, f, fs, check="mask", grid=grid_w, **order_kw)
+                                full_m, bad_m = run_m(xd, rec_i, st_i, W, order, f, fs, check="mask", grid=grid_w, **order_kw, **yw_kw)
                                 red_m = eng.band_sums(full_m, lo, hi)
                                 full_m.masked_fill_(bad_m.view(-1, 1, 1, 1), float("nan"))
                                 extra[meas] = full_m
                             else:
                                 red_m, bad_m = run_m(xd, rec_i, st_i, W, order, f, fs, check="mask", grid=grid_w,
-                                                     bands=(lo, hi), **order_kw)
+                                                     bands=(lo, hi), **order_kw, **yw_kw)
                             red_m.masked_fill_(bad_m.view(-1, 1, 1, 1), float("nan"))
                             extra[f"{meas}_bands"] = red_m
                         if validation_lags is not None:          # K1 + K2 once more, then residuals and whiteness
@@ -349,7 +371,7 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                             if auto:
                                 ar_v, _, ord_v, _, info_v = eng.yw_solve_auto(R_v, block.shape[0], W, crit_type)
                             else:
-                                ar_v, _, _, info_v = eng.yw_solve(R_v, block.shape[0])
+                                ar_v, _, _, info_v = eng.yw_solve(R_v, block.shape[0], **yw_kw)
                                 ord_v = torch.full_like(info_v, fit_p)
                             val = eng.model_validation(xd, rec_i, st_i, W, ar_v, validation_lags, validate=False)
                             bad_v = (info_v != 0) | (val["info"] != 0)
@@ -361,7 +383,7 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                         if block_granger:                        # the child block comes first (segment_block)
                             gc_f, gc_t, gc_bad = eng.sliding_block_granger(
                                 xd, rec_i, st_i, W, order, f, fs, bands=(lo, hi), check="mask", grid=grid_w,
-                                split=sum(1 for nm in seg["names"] if nm.endswith("_ch")))
+                                split=sum(1 for nm in seg["names"] if nm.endswith("_ch")), **yw_kw)
                             extra["block_gc_bands"] = gc_f.masked_fill_(gc_bad.view(-1, 1, 1), float("nan"))
                             extra["block_gc_time"] = gc_t.masked_fill_(gc_bad.view(-1, 1), float("nan"))
                         if significance is not None:             # the child block comes first (segment_block)
@@ -374,6 +396,8 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                                                                min_shift=significance["min_shift"], check="nan", grid=grid_w)
                                 for k_ in ("p", "p_fwe", "null_mean", "null_std", "n_valid"):
                                     extra[f"{meas}_bands_{k_}"] = sig[k_]
+                        if pivoted:                              # which solver took each window: K1 + K2 once more
+                            extra["_yw_routes"] = eng.window_routes(xd, rec_i, st_i, W, order)[0]
                         pending.append((seg, key, pos, W, f, bsum, ff if save_full else None, bad, psd_dev, pf if with_psd else None,
                                         extra))
                     except Exception as e:                         # one bad segment does not discard the dyad
@@ -386,6 +410,7 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                     if ff is not None:
                         result[f"{key}/ffdtf"] = ff.cpu().numpy()
                     ord_v = extra.pop("_whiteness_orders", None)
+                    routes = extra.pop("_yw_routes", None)
                     for name, arr in extra.items():
                         result[f"{key}/{name}"] = arr.cpu().numpy()
                     if ord_v is not None:
@@ -401,6 +426,9 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                     meta["segments"].append({"task": seg["task"], "event": seg["event"], "start_s": seg["start_s"],
                                              "duration_s": seg["duration_s"], "fs": seg["fs"], "samples": int(T),
                                              "windows": int(len(pos)), "window": int(W), "singular_windows": n_bad})
+                    if routes is not None:
+                        from .engine import route_counts
+                        meta["segments"][-1]["yw_routes"] = route_counts(routes)
                     names_out, freqs_out = seg["names"], f
                     say(f"[OK] {dyad} {key}: {seg['block'].shape[0]} ch x {T} samples, {len(pos)} windows"
                         + (f", {n_bad} singular" if n_bad else ""))

@@ -164,6 +164,32 @@ def sliding_ffdtf(x, window_size, n_windows, p, freqs, fs, engine: Engine | None
     return _to_host(res, single)
 
 
+def yw_routes(x, window_size, n_windows, p, hop=None, engine: Engine | None = None):
+    """How many of my windows are ill-conditioned?  K1 + K2 only, with the pivoted fallback on.  x: (m, T) or (n_rec, m, T)
+    -> {"route": (n_rec, n_windows) int8, which solver took each window -- 0 the recursion, 1 the LDL^T behind its
+    conditioning guard, 2 the pivoted LU (the two unpivoted solvers refused it) --, "info": (n_rec, n_windows) int32, not
+    zero where even the LU met an exactly zero pivot column}, without the leading axis for a single recording.  Windows from
+    `window_positions`, or every `hop` samples when `hop` is given.  An integer p is required."""
+    from .engine import no_block_auto_order
+    p = no_block_auto_order(p, "yw_routes")
+    x = np.asarray(x, dtype=np.float64) if not isinstance(x, torch.Tensor) else x
+    if x.ndim not in (2, 3):
+        raise ValueError(f"yw_routes: x must be (m, T) or (n_rec, m, T), got shape {tuple(x.shape)}")
+    single = x.ndim == 2
+    positions, w = _positions(int(x.shape[-1]), window_size, n_windows, hop)
+    eng = engine or default_engine()
+    if isinstance(x, torch.Tensor):
+        xd = (x[None] if single else x).to(device=eng.device, dtype=torch.float64)
+    else:
+        xd = eng.to_device(x[None] if single else x)
+    n_rec, m, T = xd.shape
+    item_rec, item_start = window_items(n_rec, positions, eng.device)
+    route, info = eng.window_routes(xd, item_rec, item_start, w, p)
+    route = route.view(n_rec, len(positions)).cpu().numpy().astype(np.int8)
+    info = info.view(n_rec, len(positions)).cpu().numpy()
+    return {"route": route[0] if single else route, "info": info[0] if single else info}
+
+
 def _positions(T: int, window_size, n_windows: int, hop):
     if hop is not None:
         if window_size is None:

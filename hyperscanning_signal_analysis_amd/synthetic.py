@@ -1,12 +1,13 @@
 """Seeded synthetic workloads -- the build's own generator, not reference code.
 
-Used by bench.py, the parity tests and tests/golden/make_golden.py.  NumPy only (no GPU, no oracle).
+Used by bench.py, the parity tests and tests/golden/make_golden.py.  NumPy only (no GPU, no oracle), except
+`band_limited_dyad`, which filters with SciPy as `eeg_io` does.
 """
 from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["synthetic_var_dyad", "mixed_order_recording", "northstar_freqs", "NORTHSTAR"]
+__all__ = ["synthetic_var_dyad", "mixed_order_recording", "band_limited_dyad", "northstar_freqs", "NORTHSTAR"]
 
 NORTHSTAR = dict(m=64, fs=500.0, window=1000, hop=500, p=8, F=256, T=300_000)
 
@@ -79,5 +80,22 @@ def mixed_order_recording(seed: int, m: int, orders, seg: int, burn: int = 500):
             x[t] = e[t] + x[t - q:t][::-1].reshape(-1) @ W
         parts.append(x[burn:].T)
     x = np.concatenate(parts, axis=1)
+    x = (x - x.mean(axis=1, keepdims=True)) / x.std(axis=1, keepdims=True)
+    return np.ascontiguousarray(x)
+
+
+def band_limited_dyad(seed: int, m: int, T: int, fs: float = 500.0, high_cutoff_hz: float = 45.0, p: int = 8,
+                      burn: int = 2000):
+    """`synthetic_var_dyad(seed, m, p, T, fs, burn)` through a zero-phase Butterworth-4 low-pass at `high_cutoff_hz`
+    (`scipy.signal.filtfilt`, what `eeg_io.bandpass_filter` applies to a recording), z-scored per channel again: the
+    ill-conditioned regime of filtered recordings.  The lagged samples of a signal without power above the cut-off are
+    nearly dependent -- at fs = 500 the order-8 normal equations of a 64-channel window reach cond ~ 4e15 at 45 Hz and
+    ~ 2e18 at 30 Hz -- and the unpivoted Yule-Walker solvers refuse such windows (`Engine(pivoted_yw=True)`)."""
+    from scipy.signal import butter, filtfilt
+    if not 0.0 < float(high_cutoff_hz) < 0.5 * float(fs):
+        raise ValueError(f"high_cutoff_hz must be in (0, fs / 2) = (0, {0.5 * float(fs)}), got {high_cutoff_hz}")
+    x = synthetic_var_dyad(seed, m=m, p=p, T=T, fs=fs, burn=burn)
+    b, a = butter(4, float(high_cutoff_hz) / (0.5 * float(fs)), btype="low")
+    x = filtfilt(b, a, x, axis=1)
     x = (x - x.mean(axis=1, keepdims=True)) / x.std(axis=1, keepdims=True)
     return np.ascontiguousarray(x)

@@ -45,7 +45,9 @@ int hmv_pad(int m);
  *   HMV_TUNE_YW_FORM    0 = default, 1 = block LDL^T of the augmented matrix, 2 = block Levinson-Whittle recursion,
  *                       3 = the same recursion as a software pipeline (yw_lwr2.hip; equal in time, measurement form),
  *                       4 = the recursion with its lower-lag updates unpaired, two inverses at order 0 and the model
- *                       always emitted (same bits; the form the tests hold the default against)
+ *                       always emitted (same bits; the form the tests hold the default against),
+ *                       5 = the dense LU with partial pivoting (yw_lu.hip) alone, for every window: a measurement and test
+ *                       form of the fallback that HMV_FLAG_YW_PIVOTED puts behind the other solvers (not the same bits)
  *   HMV_TUNE_K3_LDS_PAD bytes of unused dynamic LDS added to every K3 workgroup (measurement only: fewer resident
  *                       workgroups per CU, to separate latency from throughput; 0 = none)
  *   HMV_TUNE_K3_SPLIT   the fused ffDTF calls with a second stream: where a chunk's K2 -> K3 hand-over is split, so that K3
@@ -90,7 +92,15 @@ int hmv_lagcov_regular_f64(const double* x, int64_t ld, int64_t T, int64_t first
  * reference's own (m, m, p) layout when m == MP); V: [item][MP][MP] residual covariance.
  * vq_logdet (optional, may be NULL): [item][p] = log det V_q for model orders q = 1..p, all from the one
  * factorisation at order p (what mvar_criterion, src/mtmvar.py:551-601, gets from p separate fits).
- * flags: 0, HMV_FLAG_YW_TILED or HMV_FLAG_YW_ONE_LAUNCH (below). */
+ * flags: 0, HMV_FLAG_YW_TILED or HMV_FLAG_YW_ONE_LAUNCH (below), each optionally with HMV_FLAG_YW_PIVOTED.
+ * The solvers are unpivoted (the normal equations are a Gram matrix): info != 0 reports a pivot that rounding made
+ * non-positive, which happens from cond ~ 1e13 on.  With HMV_FLAG_YW_PIVOTED those windows are solved again by a dense LU
+ * with partial pivoting (LAPACK's rule; what the reference's np.linalg.solve does): ar, V and info are overwritten, info
+ * becomes 0, or c + 1 for an exactly zero pivot column c (dgesv's info > 0; ar and V are NaN then).  It promises what LU
+ * promises -- a backward-stable solution -- not coefficient parity where cond(G) eps >~ 1.  Refused with -6 together with
+ * vq_logdet (an LU gives no criterion curve).  Every window's route is left in the last int of its scratch:
+ * hmv_yw_routes_i32 copies them out, route[item] = 0 recursion, 1 LDL^T, 2 LU (device pointers, same m and p). */
+int hmv_yw_routes_i32(const double* ws, int64_t n_items, int m, int p, int32_t* route, void* stream);
 int hmv_yw_solve_f64(const double* R, int64_t n_items, int m, int p, double* ws,
                      double* ar, double* V, double* vq_logdet, int32_t* info, int64_t flags, void* stream);
 
@@ -190,6 +200,11 @@ int hmv_psd_multitaper_f64(const double* x, int64_t n_ch, int64_t n_times, int64
 #define HMV_FLAG_YW_ONE_LAUNCH 4  /* K2 as one workgroup per window in one launch: same tile products in the same
                                      order, same bits.  Neither flag: one launch, except for large 64-channel
                                      batches, where both forms are HBM-bound and the launch chain is faster. */
+
+#define HMV_FLAG_YW_PIVOTED 16     /* K2: windows that the solver leaves with info != 0 are solved again by the dense LU
+                                     with partial pivoting (hmv_yw_solve_f64).  Honoured by every fixed-order fused entry
+                                     (the restricted fits of the block Granger entries included); refused with -6 by the
+                                     automatic-order entries.  Off: nothing changes, not a bit. */
 
 /* K3 + K4 in one pass.  ffdtf[item][i][j][f] = |H_ij(f)|^2 / sum_{j',f'} |H_ij'(f')|^2, i.e. the arithmetic of
  * mvar_transfer_function (src/mtmvar.py:126-162), |H|^2 (:232) and the normalisation loop of full_freq_dtf
