@@ -89,6 +89,12 @@ SIGNATURES = {
     "hmv_sliding_block_gc_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
                                          c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 7 +
                                  [c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p]),
+    "hmv_block_gc_pairs_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "hmv_sliding_block_gc_pairs_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int,
+                                               c_int, c_int, c_int, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p,
+                                               c_int] + [c_void_p] * 7 + [c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                                                          c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                                                          c_void_p]),
     "hmv_yw_solve_auto_f64": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int] + [c_void_p] * 7 + [c_int64, c_void_p]),
     "hmv_sliding_auto_workspace_bytes": (c_int64, [c_int, c_int64, c_int, c_int, c_int, c_int]),
     "hmv_sliding_auto_f64": (c_int, [c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,

@@ -19,6 +19,9 @@
 //   bgc_prep_kernel     one workgroup per window: the five Cholesky log-determinants and the time-domain values, and per
 //                       direction Sigma_sd Sigma_dd^-1, ln det Sigma_{s|d} and D_k; a pivot of Sigma, Sigma_dd or
 //                       Sigma_{s|d} that is not positive goes to info_yw where that is still 0
+//   bgc_time_kernel     one workgroup per window: what bgc_prep_kernel does for the time-domain values and nothing else --
+//                       the log-determinants of Sigma, Sigma_AA, Sigma_BB and of the two restricted residual covariances
+//                       (or those read from a table of observed windows, BgcArgs::red_base); one LDS matrix, not two
 //   bgc_freq_kernel     one group of lanes (a power of two >= n_src, at least 8) per (window, frequency), one launch per
 //                       direction sized by n_src: W_ss and At_ss are built and factorised in the group's own slab of LDS,
 //                       lane = matrix row
@@ -58,6 +61,44 @@ __device__ double chol_logdet_256(double (*A)[65], int n, int t, int* bad) {
   }
   __syncthreads();
   return *bad ? NAN : ld;
+}
+
+// The time-domain values of one window, the tail bgc_prep_kernel and bgc_time_kernel share: ln det of the two restricted
+// residual covariances -- factorised here (Ls is free by now), or read from row base_a / base_b of a table that an earlier
+// call wrote through red_out, with the infos that went with them -- then time, info_red and red_out.  Uniform per workgroup.
+__device__ void bgc_time_values(double (*Ls)[65], const BgcRed& r, long long item, int t, double ld_full, const double* ld_blk,
+                                int m, int MPa, int MPb, int split) {
+  double ld_r[2];
+  int ir[2], bad;
+  for (int X = 0; X < 2; ++X) {
+    if (r.red_base) {
+      const long long row = (X ? r.base_b : r.base_a)[item];
+      ld_r[X] = r.red_base[row * 2 + X];
+      ir[X] = r.info_red_base[row * 2 + X];
+      continue;
+    }
+    const int nx = bgc_ns(X, split, m), MPx = X ? MPb : MPa;
+    const double* Vr = (X ? r.VrB : r.VrA) + (size_t)item * MPx * MPx;
+    ir[X] = (X ? r.info_rB : r.info_rA)[item];
+    __syncthreads();
+    for (int e = t; e < nx * nx; e += 256) Ls[e / nx][e % nx] = Vr[(size_t)(e / nx) * MPx + e % nx];
+    ld_r[X] = chol_logdet_256(Ls, nx, t, &bad);
+    if (bad && ir[X] == 0) ir[X] = -bad;
+  }
+  if (t == 0) {
+    const double fab = ld_r[1] - ld_blk[1], fba = ld_r[0] - ld_blk[0], fi = ld_blk[0] + ld_blk[1] - ld_full;
+    double* ti = r.time + item * 4;
+    ti[0] = fab;
+    ti[1] = fba;
+    ti[2] = fi;
+    ti[3] = fab + fba + fi;
+    r.info_red[item * 2] = ir[0];
+    r.info_red[item * 2 + 1] = ir[1];
+    if (r.red_out) {
+      r.red_out[item * 2] = ld_r[0];
+      r.red_out[item * 2 + 1] = ld_r[1];
+    }
+  }
 }
 }  // namespace
 
@@ -116,12 +157,11 @@ __global__ void __launch_bounds__(256) bgc_gram_kernel(const double* B, double* 
   }
 }
 
-// grid: n_items; block 256.  See the head of the file.  VrA / VrB (restricted fits' residual covariances, in the MP layouts of
-// the block sizes) may be null: the stage on its own, which has no time-domain part.
-__global__ void __launch_bounds__(256) bgc_prep_kernel(const double* ar, const double* V, const double* VrA, const double* VrB,
-                                                       const int* info_rA, const int* info_rB, double* D, double* cst,
-                                                       double* time, int* info_yw, int* info_red, int m, int MP, int MPa,
-                                                       int MPb, int NSP, int p, int split) {
+// grid: n_items; block 256.  See the head of the file.  red.VrA / VrB (restricted fits' residual covariances, in the MP
+// layouts of the block sizes) and red.red_base may all be null: the stage on its own, which has no time-domain part.
+__global__ void __launch_bounds__(256) bgc_prep_kernel(const double* ar, const double* V, BgcRed red, double* D, double* cst,
+                                                       int* info_yw, int m, int MP, int MPa, int MPb, int NSP, int p,
+                                                       int split) {
   __shared__ double Ls[64][65];      // the matrix being factorised, then its factor
   __shared__ double Gs[64][65];      // Sigma_sd Sigma_dd^-1 of the direction at hand
   const long long item = blockIdx.x;
@@ -181,28 +221,34 @@ __global__ void __launch_bounds__(256) bgc_prep_kernel(const double* ar, const d
   // Sigma passed ddtf_factor_kernel's Cholesky but a diagonal block or a rounded Schur complement did not: the window's
   // spectral rows are NaN, and nothing else would say so
   if (t == 0 && first_bad && info_yw[item] == 0) info_yw[item] = -first_bad;
-  if (!VrA) return;
-  double ld_r[2];
-  int ir[2];
+  if (!red.VrA && !red.red_base) return;
+  bgc_time_values(Ls, red, item, t, ld_full, ld_blk, m, MPa, MPb, split);
+}
+
+// grid: n_items; block 256.  bgc_prep_kernel without the spectral part: the same chol_logdet_256 on the same matrices in the
+// same order (Sigma, Sigma_AA, Sigma_BB, then the restricted ones), so the time-domain values have its bits; no G, no D_k, no
+// Schur complement, and one LDS matrix.  A pivot of Sigma or of a diagonal block that is not positive goes to info_yw where
+// that is still 0.
+__global__ void __launch_bounds__(256) bgc_time_kernel(const double* V, BgcRed red, int* info_yw, int m, int MP, int MPa,
+                                                       int MPb, int split) {
+  __shared__ double Ls[64][65];
+  const long long item = blockIdx.x;
+  const int t = threadIdx.x;
+  const double* Vi = V + item * (size_t)MP * MP;
+  int bad;
+  for (int e = t; e < m * m; e += 256) Ls[e / m][e % m] = Vi[(size_t)(e / m) * MP + e % m];
+  const double ld_full = chol_logdet_256(Ls, m, t, &bad);
+  int first_bad = bad;
+  double ld_blk[2];
   for (int X = 0; X < 2; ++X) {
-    const int nx = bgc_ns(X, split, m), MPx = X ? MPb : MPa;
-    const double* Vr = (X ? VrB : VrA) + (size_t)item * MPx * MPx;
-    ir[X] = (X ? info_rB : info_rA)[item];
+    const int x0 = bgc_s0(X, split), nx = bgc_ns(X, split, m);
     __syncthreads();
-    for (int e = t; e < nx * nx; e += 256) Ls[e / nx][e % nx] = Vr[(size_t)(e / nx) * MPx + e % nx];
-    ld_r[X] = chol_logdet_256(Ls, nx, t, &bad);
-    if (bad && ir[X] == 0) ir[X] = -bad;
+    for (int e = t; e < nx * nx; e += 256) Ls[e / nx][e % nx] = Vi[(size_t)(x0 + e / nx) * MP + x0 + e % nx];
+    ld_blk[X] = chol_logdet_256(Ls, nx, t, &bad);
+    if (bad && !first_bad) first_bad = x0 + bad;
   }
-  if (t == 0) {
-    const double fab = ld_r[1] - ld_blk[1], fba = ld_r[0] - ld_blk[0], fi = ld_blk[0] + ld_blk[1] - ld_full;
-    double* ti = time + item * 4;
-    ti[0] = fab;
-    ti[1] = fba;
-    ti[2] = fi;
-    ti[3] = fab + fba + fi;
-    info_red[item * 2] = ir[0];
-    info_red[item * 2 + 1] = ir[1];
-  }
+  if (t == 0 && first_bad && info_yw[item] == 0) info_yw[item] = -first_bad;
+  bgc_time_values(Ls, red, item, t, ld_full, ld_blk, m, MPa, MPb, split);
 }
 
 // grid: ceil(n_items * F / (WPB * G)); block 64 * WPB; dynamic LDS WPB * G * 2 * ns * RS doubles (RS = ns | 1).  A group of
@@ -390,16 +436,23 @@ int launch_bgc_gather(const double* R, double* Ra, double* Rb, long long n_items
 }
 
 int launch_bgc(const BgcArgs& a, int m_pad, hipStream_t st) {
-  if (a.n_items == 0 || a.F == 0) return 0;
-  if (a.split < 1 || a.split >= a.m || a.p < 1 || a.p > HMV_MAX_ORDER) return -3;
+  const bool timed = a.red.VrA || a.red.red_base;
+  const int want = a.want ? a.want : (timed ? 3 : 1);
+  if (a.n_items == 0 || ((want & 1) && a.F == 0)) return 0;
+  if (a.split < 1 || a.split >= a.m || a.p < 1 || a.p > HMV_MAX_ORDER || ((want & 2) && !timed)) return -3;
   const BgcPads pd = bgc_pads(a.m, a.split);
   const int nsp = pd.nsp;
+  if (!(want & 1)) {
+    hipLaunchKernelGGL(bgc_time_kernel, dim3((unsigned)a.n_items), dim3(256), 0, st, a.V, a.red, a.info_yw, a.m, m_pad, pd.mpa,
+                       pd.mpb, a.split);
+    return (int)hipGetLastError();
+  }
   int rc = launch_ddtf_factor(a.ar, a.V, a.info_yw, a.B, a.n_items, a.m, m_pad, a.p, st);
   if (rc) return rc;
   hipLaunchKernelGGL(bgc_gram_kernel, dim3((unsigned)(a.n_items * (a.p + 1) * 2)), dim3(256), 0, st, a.B, a.C, a.m, m_pad, nsp,
                      a.p, a.split);
-  hipLaunchKernelGGL(bgc_prep_kernel, dim3((unsigned)a.n_items), dim3(256), 0, st, a.ar, a.V, a.VrA, a.VrB, a.info_rA,
-                     a.info_rB, a.D, a.cst, a.time, a.info_yw, a.info_red, a.m, m_pad, pd.mpa, pd.mpb, nsp, a.p, a.split);
+  hipLaunchKernelGGL(bgc_prep_kernel, dim3((unsigned)a.n_items), dim3(256), 0, st, a.ar, a.V, (want & 2) ? a.red : BgcRed{},
+                     a.D, a.cst, a.info_yw, a.m, m_pad, pd.mpa, pd.mpb, nsp, a.p, a.split);
   const long long n_mat = a.n_items * a.F;
   for (int dir = 0; dir < 2; ++dir) {
     // a group of GS lanes per matrix (lane = row), and as many waves per workgroup (at most four) as fit 64 KiB of LDS with

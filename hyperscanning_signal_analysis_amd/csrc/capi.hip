@@ -689,15 +689,16 @@ SlidingWs sliding_layout(int64_t chunk, int mp, int p, int F, bool bands = false
 struct BgcWs {
   size_t off_B, off_C, off_D, off_cst, off_Ra, off_Rb, off_arr, off_Vra, off_Vrb, off_ir, off_full, total;
 };
-BgcWs bgc_layout(size_t front, int64_t chunk, int m, int p, int F, int split, bool bands, bool time) {
+// spectral false: the time-domain values alone (want = time of hmv_sliding_block_gc_pairs_f64), none of the stage's scratch
+BgcWs bgc_layout(size_t front, int64_t chunk, int m, int p, int F, int split, bool bands, bool time, bool spectral = true) {
   BgcWs w;
   size_t o = front;
   const hmv::BgcPads pd = hmv::bgc_pads(m, split);
   const size_t mp = (size_t)pad_of(m), mpa = (size_t)pd.mpa, mpb = (size_t)pd.mpb, nsp = (size_t)pd.nsp, pp = (size_t)p + 1;
-  w.off_B = o;      o += align256(sizeof(double) * chunk * pp * mp * mp);
-  w.off_C = o;      o += align256(sizeof(double) * chunk * 2 * pp * nsp * nsp);
-  w.off_D = o;      o += align256(sizeof(double) * chunk * 2 * pp * nsp * nsp);
-  w.off_cst = o;    o += align256(sizeof(double) * chunk * 2);
+  w.off_B = o;      if (spectral) o += align256(sizeof(double) * chunk * pp * mp * mp);
+  w.off_C = o;      if (spectral) o += align256(sizeof(double) * chunk * 2 * pp * nsp * nsp);
+  w.off_D = o;      if (spectral) o += align256(sizeof(double) * chunk * 2 * pp * nsp * nsp);
+  w.off_cst = o;    if (spectral) o += align256(sizeof(double) * chunk * 2);
   w.off_Ra = o;     if (time) o += align256(sizeof(double) * chunk * pp * mpa * mpa);
   w.off_Rb = o;     if (time) o += align256(sizeof(double) * chunk * pp * mpb * mpb);
   w.off_arr = o;    if (time) o += align256(sizeof(double) * chunk * nsp * nsp * p);
@@ -783,6 +784,11 @@ struct BgcDesc {
   double* time;                                     // [n_items][4]
   int32_t* info_red;                                // [n_items][2]
   int32_t* info_gc;                                 // [n_items*F]
+  // hmv_sliding_block_gc_pairs_f64 only (with SlidingArgs::pairs, whose base_a / base_b index red_base too)
+  int want = 3;                                     // bit 0 spectral, bit 1 time
+  double* red_out = nullptr;                        // [n_items][2]
+  const double* red_base = nullptr;                 // [n_base][2]
+  const int32_t* info_red_base = nullptr;           // [n_base][2]
 };
 // Everything sliding_impl is told, by name; a field left alone means "not asked for".  The exported entries below fill in
 // what they have.  `ffdtf` receives the full (m, m, F) arrays, `band_out` (with bin_lo / bin_hi / n_bands) the band sums.
@@ -880,8 +886,9 @@ int sliding_impl(const SlidingArgs& a) {
   if (a.mix ? (!a.mix->Rt || !a.mix->W || reinterpret_cast<uintptr_t>(a.mix->Rt) % 16 != 0)
             : (!a.x || !a.item_rec || !a.item_start))
     return fail(-4, "hmv_sliding_ffdtf_f64: null pointer / empty grid");
-  if (!a.freqs || (!a.ffdtf && !bands) || !a.info_yw ||
-      (!a.info_tf && (a.measure == MEAS_FFDTF || a.measure == MEAS_DDTF)) || !a.workspace || a.F < 1 || a.chunk < 1)
+  const bool bgc_spec = !a.bgc || (a.bgc->want & 1), bgc_time = a.bgc && (a.bgc->want & 2);   // (time alone: no frequencies)
+  if ((bgc_spec && (!a.freqs || (!a.ffdtf && !bands) || a.F < 1)) || !a.info_yw ||
+      (!a.info_tf && (a.measure == MEAS_FFDTF || a.measure == MEAS_DDTF)) || !a.workspace || a.chunk < 1)
     return fail(-4, "hmv_sliding_ffdtf_f64: null pointer / empty grid");
   if (bands && (!a.bin_lo || !a.bin_hi || a.n_bands < 1)) return fail(-4, "hmv_sliding_ffdtf_f64: band bins missing");
   bool ens_shared = false;
@@ -897,7 +904,7 @@ int sliding_impl(const SlidingArgs& a) {
                                      a.ens ? (ens_shared ? ens_q_tiles(a.chunk, a.n, a.p, a.grid_hop, a.grid_nwin) : 0)
                                            : ((a.pairs || a.mix) ? 0 : -1));
   BgcWs gw{};
-  if (a.bgc) gw = bgc_layout(w.total, a.chunk, a.m, a.p, a.F, a.bgc->split, bands, true);
+  if (a.bgc) gw = bgc_layout(w.total, a.chunk, a.m, a.p, a.F, a.bgc->split, bands, bgc_time, bgc_spec);
   if ((int64_t)(a.bgc ? gw.total : w.total) > a.workspace_bytes) return fail(-7, "hmv_sliding_ffdtf_f64: workspace too small");
   // Regular grid (the caller vouches: item = rec * grid_nwin + w starts at grid_first + w * grid_hop of recording rec,
   // recordings are grid_T samples long): K1 sums every hop block once and assembles the windows from the blocks.
@@ -944,7 +951,7 @@ int sliding_impl(const SlidingArgs& a) {
   double* tw = reinterpret_cast<double*>(base + w.off_tw);
   const bool k3_bands = bands && a.measure == MEAS_FFDTF;
   const int64_t tfws_bytes = (int64_t)tf_ff_layout(a.chunk, mp, a.p, a.F, k3_bands).total;
-  rc = hmv_twiddles_f64(a.freqs, a.F, a.fs, a.p, tw, st0);
+  if (bgc_spec) rc = hmv_twiddles_f64(a.freqs, a.F, a.fs, a.p, tw, st0);
   const size_t ws_item = (size_t)hmv_yw_workspace_doubles(a.m, a.p);
   hmv::TfSplit sp{};                         // the chunk's K2 -> K3 hand-over in two parts, if any
   auto join_k3_split = [&]() {               // st0 joins st1 unless K3's launcher already made it wait
@@ -1038,31 +1045,47 @@ int sliding_impl(const SlidingArgs& a) {
       // block's own padded size), then the stage; its full array goes to the output or (band form) to scratch ahead of
       // its band sums
       const int na = a.bgc->split, nb2 = a.m - na;
-      double* Ra = reinterpret_cast<double*>(base + gw.off_Ra);
-      double* Rb = reinterpret_cast<double*>(base + gw.off_Rb);
-      double* arr = reinterpret_cast<double*>(base + gw.off_arr);
-      int32_t* ir = reinterpret_cast<int32_t*>(base + gw.off_ir);
       hmv::BgcArgs ga{};
-      ga.VrA = reinterpret_cast<double*>(base + gw.off_Vra); ga.VrB = reinterpret_cast<double*>(base + gw.off_Vrb);
-      ga.info_rA = ir; ga.info_rB = ir + c;
-      auto red_flags = [&](int nx) {
-        const bool chain = (a.flags & HMV_FLAG_YW_TILED) ||
-                           (ldl && !(a.flags & HMV_FLAG_YW_ONE_LAUNCH) && pad_of(nx) == 64 && c >= 128);
-        return (int64_t)(ldl ? (chain ? HMV_FLAG_YW_TILED : HMV_FLAG_YW_ONE_LAUNCH) : 0) | (a.flags & HMV_FLAG_YW_PIVOTED);
-      };
-      rc = hmv::launch_bgc_gather(R, Ra, Rb, c, a.m, mp, a.p, na, st0);
-      if (!rc) rc = hmv_yw_solve_f64(Ra, c, na, a.p, ws, arr, const_cast<double*>(ga.VrA), nullptr, ir, red_flags(na), st0);
-      if (!rc)
-        rc = hmv_yw_solve_f64(Rb, c, nb2, a.p, ws, arr, const_cast<double*>(ga.VrB), nullptr, ir + c, red_flags(nb2), st0);
-      double* spec_c = bands ? reinterpret_cast<double*>(base + gw.off_full) : a.ffdtf + (size_t)i0 * 2 * a.F;
+      ga.want = a.bgc->want;
+      if (bgc_time) {
+        ga.red.time = a.bgc->time + (size_t)i0 * 4; ga.red.info_red = a.bgc->info_red + (size_t)i0 * 2;
+        ga.red.red_out = a.bgc->red_out ? a.bgc->red_out + (size_t)i0 * 2 : nullptr;
+      }
+      if (bgc_time && a.bgc->red_base) {
+        // both restricted fits are those of observed windows (a pair changes the cross blocks only): their log-determinants
+        // and infos come from the table, and nothing is gathered or solved
+        ga.red.red_base = a.bgc->red_base; ga.red.info_red_base = a.bgc->info_red_base;
+        ga.red.base_a = ll(a.pairs->base_a + i0); ga.red.base_b = ll(a.pairs->base_b + i0);
+      } else if (bgc_time) {
+        double* Ra = reinterpret_cast<double*>(base + gw.off_Ra);
+        double* Rb = reinterpret_cast<double*>(base + gw.off_Rb);
+        double* arr = reinterpret_cast<double*>(base + gw.off_arr);
+        int32_t* ir = reinterpret_cast<int32_t*>(base + gw.off_ir);
+        ga.red.VrA = reinterpret_cast<double*>(base + gw.off_Vra); ga.red.VrB = reinterpret_cast<double*>(base + gw.off_Vrb);
+        ga.red.info_rA = ir; ga.red.info_rB = ir + c;
+        auto red_flags = [&](int nx) {
+          const bool chain = (a.flags & HMV_FLAG_YW_TILED) ||
+                             (ldl && !(a.flags & HMV_FLAG_YW_ONE_LAUNCH) && pad_of(nx) == 64 && c >= 128);
+          return (int64_t)(ldl ? (chain ? HMV_FLAG_YW_TILED : HMV_FLAG_YW_ONE_LAUNCH) : 0) | (a.flags & HMV_FLAG_YW_PIVOTED);
+        };
+        rc = hmv::launch_bgc_gather(R, Ra, Rb, c, a.m, mp, a.p, na, st0);
+        if (!rc)
+          rc = hmv_yw_solve_f64(Ra, c, na, a.p, ws, arr, const_cast<double*>(ga.red.VrA), nullptr, ir, red_flags(na), st0);
+        if (!rc)
+          rc = hmv_yw_solve_f64(Rb, c, nb2, a.p, ws, arr, const_cast<double*>(ga.red.VrB), nullptr, ir + c, red_flags(nb2),
+                                st0);
+      }
+      double* spec_c = !bgc_spec ? nullptr
+                       : bands   ? reinterpret_cast<double*>(base + gw.off_full) : a.ffdtf + (size_t)i0 * 2 * a.F;
       ga.ar = ar_c; ga.V = V_c; ga.info_yw = a.info_yw + i0;
-      ga.B = reinterpret_cast<double*>(base + gw.off_B); ga.C = reinterpret_cast<double*>(base + gw.off_C);
-      ga.D = reinterpret_cast<double*>(base + gw.off_D); ga.cst = reinterpret_cast<double*>(base + gw.off_cst);
-      ga.tw = tw; ga.out = spec_c; ga.info_gc = a.bgc->info_gc + (size_t)i0 * a.F;
-      ga.time = a.bgc->time + (size_t)i0 * 4; ga.info_red = a.bgc->info_red + (size_t)i0 * 2;
+      if (bgc_spec) {
+        ga.B = reinterpret_cast<double*>(base + gw.off_B); ga.C = reinterpret_cast<double*>(base + gw.off_C);
+        ga.D = reinterpret_cast<double*>(base + gw.off_D); ga.cst = reinterpret_cast<double*>(base + gw.off_cst);
+        ga.tw = tw; ga.out = spec_c; ga.info_gc = a.bgc->info_gc + (size_t)i0 * a.F;
+      }
       ga.n_items = c; ga.F = a.F; ga.m = a.m; ga.p = a.p; ga.split = na;
       if (!rc) rc = hmv::launch_bgc(ga, mp, st0);
-      if (!rc && bands)
+      if (!rc && bgc_spec && bands)
         rc = hmv::launch_band_sums(spec_c, reinterpret_cast<const int*>(a.bin_lo), reinterpret_cast<const int*>(a.bin_hi),
                                    a.band_out + (size_t)i0 * 2 * a.n_bands, c * 2, a.F, a.n_bands, st0);
     } else if (a.measure == MEAS_GPDC) {
@@ -1296,6 +1319,61 @@ int hmv_sliding_block_gc_f64(const double* x, int64_t rec_stride, int64_t ld, co
   a.ar_out = ar_out; a.V_out = V_out; a.info_yw = info_yw;
   a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.flags = flags;
   a.grid_hop = grid_hop; a.grid_first = grid_first; a.grid_nwin = grid_nwin; a.grid_T = grid_T;
+  a.stream = stream;
+  return sliding_impl(a);
+}
+
+// ---- block Granger causality of pairs of recordings: the pair K1 in front of the stage (its surrogate tests) -----------
+int64_t hmv_block_gc_pairs_workspace_bytes(int64_t chunk, int m, int n, int p, int split, int F, int n_bands, int want) {
+  const int mp = pad_of(m);
+  if (mp < 0 || chunk < 1 || p < 1 || p > HMV_MAX_ORDER || n <= p || split < 1 || split > m - 1 || want < 1 || want > 3) return -1;
+  if ((want & 1) && (F < 1 || n_bands < 0)) return -1;
+  const bool bands = (want & 1) && n_bands > 0;
+  if (!(want & 1)) F = 0;                                // time alone takes no frequency grid
+  const SlidingWs w = sliding_layout(chunk, mp, p, F, bands, false, MEAS_BGC, 0);
+  return (int64_t)bgc_layout(w.total, chunk, m, p, F, split, bands, (want & 2) != 0, (want & 1) != 0).total;
+}
+
+int hmv_sliding_block_gc_pairs_f64(const double* x, int64_t rec_stride, int64_t ld, int64_t T, const int64_t* rec_a,
+                                   const int64_t* rec_b, const int64_t* item_start, int64_t n_items, int m, int n, int p,
+                                   int split, const double* freqs, int F, double fs, double* spectral, const int32_t* bin_lo,
+                                   const int32_t* bin_hi, int n_bands, double* time, double* ar_out, double* V_out,
+                                   int32_t* info_yw, int32_t* info_red, int32_t* info_gc, void* workspace,
+                                   int64_t workspace_bytes, int64_t chunk, int64_t flags, const double* R_base,
+                                   const int64_t* base_a, const int64_t* base_b, int want, double* red_out,
+                                   const double* red_base, const int32_t* info_red_base, void* stream) {
+  const char* who = "hmv_sliding_block_gc_pairs_f64";
+  (void)T;                                               // the caller has checked the windows against it
+  if (want < 1 || want > 3)
+    return fail(-15, "hmv_sliding_block_gc_pairs_f64: want must be 1 (spectral), 2 (time) or 3 (both)");
+  const bool spec = want & 1, timed = want & 2;
+  if (int rc = bgc_check(who, m, p, split, spec ? F : 1)) return rc;
+  if (n <= p) return fail(-3, "hmv_sliding_block_gc_pairs_f64: window shorter than the model order");
+  if (n_items < 0) return fail(-4, "hmv_sliding_block_gc_pairs_f64: n_items must be >= 0");
+  if (spec && n_bands < 0) return fail(-14, "hmv_sliding_block_gc_pairs_f64: n_bands must be >= 0");
+  if (int rc = pairs_check(who, m, rec_b, split, R_base, base_a, base_b)) return rc;
+  if ((red_base != nullptr) != (info_red_base != nullptr))
+    return fail(-4, "hmv_sliding_block_gc_pairs_f64: red_base and info_red_base go together");
+  if (red_base && !R_base)
+    return fail(-4, "hmv_sliding_block_gc_pairs_f64: red_base needs R_base, base_a and base_b (its rows are theirs)");
+  if (n_items != 0 && spec && !spectral) return fail(-13, "hmv_sliding_block_gc_pairs_f64: the spectral output is a null pointer");
+  if (n_items != 0 && ((spec && !info_gc) || (timed && (!time || !info_red))))
+    return fail(-4, "hmv_sliding_block_gc_pairs_f64: null pointer / empty grid");
+  const PairDesc pairs{rec_b, split, R_base, base_a, base_b};
+  BgcDesc g{split, time, info_red, info_gc};
+  g.want = want;
+  if (timed) { g.red_out = red_out; g.red_base = red_base; g.info_red_base = info_red_base; }
+  SlidingArgs a{who};
+  a.measure = MEAS_BGC; a.bgc = &g; a.pairs = &pairs;
+  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.item_rec = rec_a; a.item_start = item_start; a.n_items = n_items;
+  a.m = m; a.n = n; a.p = p; a.fs = fs;
+  if (spec) {
+    a.freqs = freqs; a.F = F;
+    if (n_bands > 0) a.band_out = spectral; else a.ffdtf = spectral;
+    a.bin_lo = bin_lo; a.bin_hi = bin_hi; a.n_bands = n_bands;
+  }
+  a.ar_out = ar_out; a.V_out = V_out; a.info_yw = info_yw;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.flags = flags;
   a.stream = stream;
   return sliding_impl(a);
 }

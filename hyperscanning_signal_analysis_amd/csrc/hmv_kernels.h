@@ -281,6 +281,23 @@ inline BgcPads bgc_pads(int m, int split) {
   const int mpa = ((split + 15) / 16) * 16, mpb = ((m - split + 15) / 16) * 16;
   return BgcPads{mpa, mpb, mpa > mpb ? mpa : mpb};
 }
+// The time-domain part of the stage: where the restricted fits come from and where the values go.  All null: no such part.
+struct BgcRed {
+  // the restricted fits' residual covariances and K2 infos ...
+  const double* VrA;        // [n_items][MPa][MPa]
+  const double* VrB;        // [n_items][MPb][MPb]
+  const int* info_rA;       // [n_items]
+  const int* info_rB;       // [n_items]
+  // ... or (red_base != nullptr, the four above unused) their log-determinants and infos as an earlier call left them in
+  // red_out / info_red: block A's from row base_a[item], column 0, block B's from row base_b[item], column 1
+  const double* red_base;   // [n_base][2]
+  const int* info_red_base; // [n_base][2]
+  const long long* base_a;  // [n_items]
+  const long long* base_b;  // [n_items]
+  double* time;             // [n_items][4]
+  int* info_red;            // [n_items][2]
+  double* red_out;          // [n_items][2] or null: (ln det Sr_AA, ln det Sr_BB) as the time values use them
+};
 struct BgcArgs {
   const double* ar;         // [n_items][MP][MP][p]   K2
   const double* V;          // [n_items][MP][MP]      K2 (symmetric)
@@ -293,13 +310,9 @@ struct BgcArgs {
   const double* tw;         // [F][p][2]
   double* out;              // [n_items][2][F]: 0 = A -> B, 1 = B -> A
   int* info_gc;             // [n_items*F]
-  // time domain (VrA == nullptr: none of it): the restricted fits' residual covariances and K2 infos
-  const double* VrA;        // [n_items][MPa][MPa]
-  const double* VrB;        // [n_items][MPb][MPb]
-  const int* info_rA;       // [n_items]
-  const int* info_rB;       // [n_items]
-  double* time;             // [n_items][4]
-  int* info_red;            // [n_items][2]
+  BgcRed red;               // time domain (VrA and red_base null: none of it)
+  int want;                 // bit 0 spectral, bit 1 time; 0: spectral, and time where `red` has a source.  Without bit 0
+                            // only V, info_yw and `red` are used (bgc_time_kernel alone), without bit 1 `red` is ignored
   long long n_items;
   int F, m, p, split;
 };

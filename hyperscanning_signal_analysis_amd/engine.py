@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, significance
+from . import surrogates as sg
 
 __all__ = ["Engine", "default_engine", "SingularMatrixError", "validate_items", "validate_trials", "check_block_split"]
 
@@ -1325,17 +1326,22 @@ class Engine:
         _lib.check(rc, "hmv_lagcov_pairs_f64")
         return R
 
+    @staticmethod
+    def _blame_pair(err, rec_a, rec_b, item_start, split):
+        """Say which pair of recordings and which window a SingularMatrixError is about."""
+        idx = torch.as_tensor(err.items, dtype=torch.int64, device=rec_a.device)
+        err.rec_a, err.rec_b = rec_a[idx].cpu().numpy(), rec_b[idx].cpu().numpy()
+        err.starts = item_start[idx].cpu().numpy()
+        err.args = (err.args[0], err.args[1] + f" (channels < {int(split)} of recording {int(err.rec_a[0])} with channels "
+                    f">= {int(split)} of recording {int(err.rec_b[0])}, window at sample {int(err.starts[0])})")
+
     def _pairs_route(self, measure, n, p, rec_b, split, R_base, base_a, base_b):
         """Route of `sliding_pairs` (`hmv_sliding_pairs_f64`): the items are (rec_a, item_start), the second recording table
         and the bases ride along, there is no grid, and a failed fit is reported with its pair of recordings."""
         lib, n, p, code = self.lib, int(n), int(p), _MEASURES[measure]
 
-        def blame(err, items):       # say which pair of recordings and which window
-            idx = torch.as_tensor(err.items, dtype=torch.int64, device=items[0].device)
-            err.rec_a, err.rec_b = items[0][idx].cpu().numpy(), rec_b[idx].cpu().numpy()
-            err.starts = items[1][idx].cpu().numpy()
-            err.args = (err.args[0], err.args[1] + f" (channels < {int(split)} of recording {int(err.rec_a[0])} with channels "
-                        f">= {int(split)} of recording {int(err.rec_b[0])}, window at sample {int(err.starts[0])})")
+        def blame(err, items):
+            self._blame_pair(err, items[0], rec_b, items[1], split)
 
         def call(a):
             return "hmv_sliding_pairs_f64", (
@@ -1368,6 +1374,175 @@ class Engine:
         rt = self._pairs_route(measure, n, p, rec_b, split, R_base, base_a, base_b)
         return self._sliding_call(rt, x, (rec_a, item_start), freqs, fs, bands=bands, out=out, return_ar=return_ar,
                                   check=check, chunk=chunk, flags=flags, validate=validate)
+
+    @staticmethod
+    def _check_red_base(red_base, R_base):
+        """red_base = (red, info_red) of `sliding_block_granger_pairs(..., return_red=True)`, one row per row of R_base."""
+        if R_base is None:
+            raise ValueError("red_base needs R_base, base_a and base_b: its rows are the observed windows of R_base")
+        ok = isinstance(red_base, (tuple, list)) and len(red_base) == 2 and all(isinstance(t, torch.Tensor) for t in red_base)
+        ok = ok and red_base[0].dtype == torch.float64 and red_base[1].dtype == torch.int32
+        if not (ok and all(t.device == R_base.device and tuple(t.shape) == (R_base.shape[0], 2) and t.is_contiguous()
+                           for t in red_base)):
+            raise ValueError(f"red_base must be (red float64, info_red int32), contiguous ({R_base.shape[0]}, 2) tensors on "
+                             f"{R_base.device}")
+
+    def block_significance_chunk(self, null: str, m: int, n: int, p: int, split: int, F: int, nb: int, want) -> int:
+        """Items (surrogate x window) per block of `block_granger_significance`: `max_workspace_bytes` over what one item
+        needs -- the call's workspace, the item buffer (m n doubles; the phase null also its spectrum) and its values."""
+        spec, timed = sg.block_want(want)
+        ws = int(self.lib.hmv_block_gc_pairs_workspace_bytes(1, m, n, p, split, F, nb, (1 if spec else 0) | (2 if timed else 0)))
+        per_item = ws + 8 * m * n + 8 * 4 * (nb + 1) + 8 * (nb + 1) + 64
+        if null == "phase":
+            per_item += 16 * m * (n // 2 + 1)
+        return max(1, self.max_workspace_bytes // per_item)
+
+    def sliding_block_granger_pairs(self, x: torch.Tensor, rec_a: torch.Tensor, rec_b: torch.Tensor, item_start: torch.Tensor,
+                                    n: int, p: int, freqs, fs: float, *, split: int, want=("spectral", "time"), bands=None,
+                                    R_base: torch.Tensor | None = None, base_a: torch.Tensor | None = None,
+                                    base_b: torch.Tensor | None = None, red_base=None, return_red: bool = False,
+                                    return_ar: bool = False, check=True, chunk: int | None = None, flags: int = 0,
+                                    validate: bool = True):
+        """Block Granger causality of pairs of recordings: `sliding_block_granger` of the window at item_start[it] whose
+        channels < split are those of recording rec_a[it] and whose channels >= split are those of recording rec_b[it] --
+        bit for bit what that call gives for the two halves written out as one recording (with rec_b = rec_a: for the
+        recording itself), without writing it.  One C-ABI call (`hmv_sliding_block_gc_pairs_f64`).  -> (spectral, time).
+            want      which of the two: "spectral" and / or "time"; the other one is returned as None and none of its
+                      kernels runs.  ("time",) needs no frequency grid: freqs may be None, and the call is K1, K2, the two
+                      restricted fits and one small kernel.
+            bands     (bin_lo, bin_hi): the band sums (items, 2, n_bands) in place of the full (items, 2, F) array.
+            R_base, base_a, base_b    as in `lagcov_pairs`: both within-recording covariance blocks are copied from
+                      observed windows.
+            return_red   appends (red, info_red): red (items, 2) = (ln det Sr_AA, ln det Sr_BB) of the restricted fits
+                      and their infos -- what `red_base` takes.
+            red_base  (red, info_red) of a call on the observed windows that R_base holds (row = window): the restricted
+                      fit of block A is then that of window base_a[it], the one of block B that of window base_b[it]; they
+                      are looked up, not computed.  Needs R_base.  Same bits.
+        check, chunk, flags as in `sliding_block_granger`; the SingularMatrixError of check=True names the pair, "mask"
+        appends the boolean device mask (behind (red, info_red)).  return_ar appends (ar, V, (info_yw, info_red, info_gc)),
+        an info that was not asked for being None.  An integer p is required."""
+        p = no_block_auto_order(p, "sliding_block_granger_pairs")
+        spec, timed = sg.block_want(want)
+        flags = int(flags) | self.yw_flag
+        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
+        x = x if x.stride(2) == 1 else x.contiguous()
+        n_rec, m, T = x.shape
+        split = check_block_split(split, m, "sliding_block_granger_pairs")
+        mp, n = self.pad(m), int(n)
+        n_items = int(rec_a.numel())
+        if validate:
+            self._validate_pairs(x, rec_a, rec_b, item_start, n, p, split, R_base, base_a, base_b)
+        if red_base is not None:
+            self._check_red_base(red_base, R_base)
+        if (red_base is not None or return_red) and not timed:
+            raise ValueError("red_base and return_red belong to the time-domain values: want must include 'time'")
+        F = nb = knb = 0
+        two_step = False
+        f = spectral = info_gc = None
+        if spec:
+            f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
+            F = int(f.numel())
+            if bands is not None:
+                b_lo, b_hi = self.band_tables(bands[0], bands[1], F)
+                nb = int(b_lo.numel())
+            two_step = bands is not None and nb == 0      # an empty band set: the full array, then its (empty) band sums
+            knb = 0 if two_step else nb
+            spectral = self.empty(n_items, 2, knb or F)
+            info_gc = torch.zeros(n_items * F, dtype=torch.int32, device=self.device)
+        time = self.empty(n_items, 4) if timed else None
+        info_red = torch.zeros(n_items, 2, dtype=torch.int32, device=self.device) if timed else None
+        red = self.empty(n_items, 2) if return_red else None
+        ar = self.empty(n_items, mp, mp, p) if return_ar else None
+        V = self.empty(n_items, mp, mp) if return_ar else None
+        info_yw = torch.zeros(n_items, dtype=torch.int32, device=self.device)
+        code = (1 if spec else 0) | (2 if timed else 0)
+        if n_items:
+            ws_bytes = self.lib.hmv_block_gc_pairs_workspace_bytes
+            if chunk is None:
+                chunk = self._chunk(n_items, int(ws_bytes(1, m, n, p, split, F, knb, code)), self.max_workspace_bytes)
+            chunk = int(chunk)
+            nbytes = int(ws_bytes(chunk, m, n, p, split, F, knb, code))
+            if nbytes < 0:
+                raise ValueError(f"sliding_block_granger_pairs: bad sizes (m={m}, n={n}, p={p}, split={split}, F={F}, "
+                                 f"chunk={chunk})")
+            ws = self._workspace(nbytes)
+            with torch.cuda.device(self.device):
+                rc = self.lib.hmv_sliding_block_gc_pairs_f64(
+                    x.data_ptr(), x.stride(0), x.stride(1), T, rec_a.data_ptr(), rec_b.data_ptr(), item_start.data_ptr(),
+                    n_items, m, n, p, split, _ptr(f), F, float(fs), _ptr(spectral), b_lo.data_ptr() if knb else 0,
+                    b_hi.data_ptr() if knb else 0, knb, _ptr(time), _ptr(ar), _ptr(V), info_yw.data_ptr(), _ptr(info_red),
+                    _ptr(info_gc), ws.data_ptr(), nbytes, chunk, int(flags), _ptr(R_base), _ptr(base_a), _ptr(base_b), code,
+                    _ptr(red), _ptr(red_base[0]) if red_base is not None else 0,
+                    _ptr(red_base[1]) if red_base is not None else 0, self.stream())
+            _lib.check(rc, "hmv_sliding_block_gc_pairs_f64")
+        if two_step:
+            spectral = self.band_sums(spectral, bands[0], bands[1])
+        r = (spectral, time)
+        if return_red:
+            r += ((red, info_red),)
+        if check == "nan" or check == "mask":
+            bad = info_yw != 0
+            if timed:
+                bad = bad | (info_red != 0).any(dim=1)
+            if spec:
+                bad = bad | (info_gc.view(n_items, F) != 0).any(dim=1)
+            if check == "nan":
+                if bool(bad.any()):
+                    for v in (spectral, time):
+                        if v is not None:
+                            v[bad] = float("nan")
+            else:
+                r += (bad,)
+        elif check:
+            try:
+                self.raise_on_info(info_yw, "ar_coeff (Yule-Walker solve; a negative info: residual covariance not positive "
+                                            "definite)")
+                if timed:
+                    self.raise_on_info(info_red.view(-1), "block Granger causality (Yule-Walker solve of one block alone)",
+                                       per_item=2)
+                if spec:
+                    self.raise_on_info(info_gc, "block Granger causality (per-frequency factorisation)", per_item=F)
+            except SingularMatrixError as err:
+                self._blame_pair(err, rec_a, rec_b, item_start, split)
+                raise
+        if return_ar:
+            r += (ar, V, (info_yw, info_red, info_gc))
+        return r
+
+    def block_granger_significance(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, p: int,
+                                   freqs, fs: float, bands, *, split: int, null: str, n_surrogates: int, seed,
+                                   values=("time", "bands"), min_shift=None, check=True, chunk: int | None = None):
+        """Surrogate test of the block Granger causality of `sliding_block_granger` for every window: the time-domain
+        values F_{A->B}, F_{B->A} and / or the band sums of the spectral decomposition against null="shift" (block B
+        circularly shifted against block A) or null="phase" (every channel phase-randomised).  The surrogate windows are
+        those of `sliding_significance`: `surrogates.shift_offsets` / `phase_draws` from numpy.random.default_rng(seed), in
+        the same order.  values: "time" and / or "bands"; with ("time",) no frequency-domain kernel runs (bands and freqs
+        may be None) and a surrogate costs K1, K2, two restricted fits and one small kernel.
+        Statistics as in `sliding_significance` over the two directions: p = (1 + #{T_s >= T_obs}) / (1 + n_valid), p_fwe
+        with the maximum over the two directions (per value column), null_mean, null_std (ddof 1).  F_{A.B} and the total
+        are returned as observed and not tested.  check: True raises LinAlgError for a failed observed window, "nan" gives
+        NaN statistics for it; chunk: items (surrogate x window) per block, the same bits for any chunk.
+        Returns a dict of device tensors, index 0 = A -> B, 1 = B -> A: time = {observed, p, p_fwe, null_mean, null_std
+        (W, 2)}, bands = {the same, (W, 2, n_bands)}, observed_time (W, 4), n_valid (W,) int32; a leaf that was not asked
+        for is absent."""
+        return significance.block_granger_significance(self, x, item_rec, item_start, n, p, freqs, fs, bands, split=split,
+                                                       null=null, n_surrogates=n_surrogates, seed=seed, values=values,
+                                                       min_shift=min_shift, check=check, chunk=chunk)
+
+    def block_granger_pseudo_dyad_significance(self, x: torch.Tensor, item_start: torch.Tensor, n: int, p: int, freqs,
+                                               fs: float, bands, *, split: int, n_surrogates=None, seed=None,
+                                               values=("time", "bands"), check=True, chunk: int | None = None):
+        """Pseudo-dyad (shuffled-partner) test of block Granger causality: `pseudo_dyad_significance` with the two block
+        values per window in place of the (m, m) band array.  x (D, m, T), recording d = dyad d, channels < split its
+        participant A; surrogate s analyses A of dyad d with B of dyad pi[s][d] (`surrogates.partner_derangements`).  A pseudo
+        dyad changes only the cross-participant covariance blocks, so both within-participant blocks (R_base) and both
+        restricted fits (red_base) are those of the observed windows: a surrogate of the time-domain values is a cross-block
+        K1, one K2 and three small Cholesky log-determinants.  values as in `block_granger_significance`.
+        Returns its dict with a leading (D, W) in place of (W,) -- per dyad over the 2 S A-anchored and B-anchored values
+        -- plus group = {time, bands, n_valid (W,)} for the mean over the dyads, and partners (S, D) int64."""
+        return significance.block_granger_pseudo_dyad_significance(self, x, item_start, n, p, freqs, fs, bands, split=split,
+                                                                   n_surrogates=n_surrogates, seed=seed, values=values,
+                                                                   check=check, chunk=chunk)
 
     def pseudo_dyad_significance(self, x: torch.Tensor, item_start: torch.Tensor, n: int, p: int, freqs, fs: float, bands, *,
                                  measure: str, split=None, n_surrogates=None, seed=None, check=True,

@@ -1,5 +1,5 @@
 """The surrogate null tests: `Engine.sliding_significance`, `.ensemble_significance`, `.pseudo_dyad_significance` and
-`.ensemble_contrast` are the four functions at the end, each taking the engine first.  What they share is here once: the
+`.ensemble_contrast` and the two tests of block Granger causality are the functions at the end, each taking the engine first.  What they share is here once: the
 block planners (integers in, integers out), the preamble and `NullAccumulator`, which owns the running state of
 `hmv_null_accumulate_f64` and builds every returned dict.  A test's own part is how it makes a block of surrogate values.
 The draws and the argument checks are `surrogates`; everything that wraps one C call is a method of the engine.
@@ -13,7 +13,8 @@ from . import engine as _engine
 from . import surrogates as sg
 
 __all__ = ["sliding_plan", "ensemble_plan", "stack_plan", "window_ranges", "surrogate_blocks", "NullAccumulator",
-           "sliding_significance", "ensemble_significance", "pseudo_dyad_significance", "ensemble_contrast"]
+           "sliding_significance", "ensemble_significance", "pseudo_dyad_significance", "ensemble_contrast", "block_meta",
+           "block_leaves", "block_granger_significance", "block_granger_pseudo_dyad_significance"]
 
 STATS = ("p", "p_fwe", "null_mean", "null_std")
 
@@ -406,3 +407,167 @@ def pseudo_dyad_significance(eng, x, item_start, n, p, freqs, fs, bands, *, meas
         gbad[s] = both_bad[0].view(D, W).any(dim=0)
     group = acc.group(obs.view(D, W, m, m, nb).mean(dim=0), gmean, gbad, S, obs_bad)
     return dict(acc.result((D, W), obs, obs_bad), group=group, partners=partners_out)
+
+
+# ------------------------------------------------------------------ block Granger causality: two values per window
+def block_meta(time, band_vals):
+    """The block values of every item as a 2 x 2 "meta-channel" array for `hmv_null_accumulate_f64` (m = 2, channel 0 =
+    block A, 1 = block B, cell [destination][source]): time (items, >= 2) with F_{A->B}, F_{B->A} in front and / or band_vals
+    (items, 2, nb) with index 0 = A -> B -> (items, 2, 2, nv).  Cell [1][0] is A -> B, cell [0][1] is B -> A, the diagonal is
+    NaN and never tested; the value columns are the time-domain value (if given), then the bands.  Pure tensor code."""
+    cols = ([] if time is None else [time[:, :2, None]]) + ([] if band_vals is None else [band_vals])
+    v = torch.cat(cols, dim=2)
+    out = v.new_full((v.shape[0], 2, 2, v.shape[2]), float("nan"))
+    out[:, 1, 0] = v[:, 0]
+    out[:, 0, 1] = v[:, 1]
+    return out
+
+
+def block_leaves(res, values):
+    """A `NullAccumulator` dict over meta arrays (..., 2, 2, nv) -> {"time": {observed, p, ... (..., 2)}, "bands": {...
+    (..., 2, nb)}} for the leaves in `values`; index 0 = A -> B."""
+    out, col = {}, 0
+    per_dir = {k: torch.stack((res[k][..., 1, 0, :], res[k][..., 0, 1, :]), dim=-2) for k in ("observed",) + STATS}
+    if "time" in values:
+        out["time"] = {k: v[..., 0] for k, v in per_dir.items()}
+        col = 1
+    if "bands" in values:
+        out["bands"] = {k: v[..., col:] for k, v in per_dir.items()}
+    return out
+
+
+def _block_prepare(eng, freqs, bands, values, who):
+    """-> want, f, bands (lo, hi) or None, nv, tested_h, tested for the 2 x 2 meta array."""
+    tested_h = sg.tested_mask(2, "phase", 0)                         # the off-diagonal: the two directions
+    tested = torch.as_tensor(tested_h.astype(np.uint8)).to(eng.device)
+    timed = "time" in values
+    if "bands" not in values:
+        return ("time",), None, None, 1, tested_h, tested
+    f, F, lo, hi, nb, _, _ = prepare(eng, freqs, bands, who, 2, "phase", 0)
+    return (("spectral", "time") if timed else ("spectral",)), f, (lo, hi), nb + int(timed), tested_h, tested
+
+
+def _block_observed_time(time, obs_bad, lead, failed):
+    t = time.view(*lead, 4)
+    if failed:
+        t[obs_bad.view(lead)] = float("nan")
+    return t
+
+
+def block_granger_significance(eng, x, item_rec, item_start, n, p, freqs, fs, bands, *, split, null, n_surrogates, seed,
+                               values=sg.BLOCK_VALUES, min_shift=None, check=True, chunk=None):
+    p = _engine.no_block_auto_order(p, "block_granger_significance")
+    x = device_x(x)
+    n_rec, m, T = x.shape
+    n = int(n)
+    S, split, min_shift, values = sg.block_significance_args(null, n_surrogates, m, T, n, split, min_shift, values, bands, check)
+    eng.pad(m)
+    eng.check_items(x, item_rec, item_start, n, p)
+    W = int(item_rec.numel())
+    want, f, bins, nv, tested_h, tested = _block_prepare(eng, freqs, bands, values, "block_granger_significance")
+    acc = NullAccumulator(eng, W, 2, nv, tested_h, tested)
+    kw = dict(split=split, want=want, bands=bins, validate=False)
+
+    def finish(res, time, obs_bad):
+        out = dict(block_leaves(res, values), n_valid=res["n_valid"])
+        if "time" in values:
+            out["observed_time"] = _block_observed_time(time, obs_bad, (W,), acc.failed(obs_bad))
+        return out
+    if W == 0:
+        return finish(acc.empty((0,)), eng.empty(0, 4), None)
+    obs = eng.sliding_block_granger_pairs(x, item_rec, item_rec, item_start, n, p, f, fs,
+                                          check=True if check is True else "mask", **kw)
+    obs_bad = None if check is True else obs[2]
+    obs_meta = block_meta(obs[1], obs[0])
+    rng = np.random.default_rng(seed)
+    if null == "shift":
+        d_all = torch.as_tensor(sg.shift_offsets(rng, S, n_rec, T, min_shift)).to(eng.device)
+    else:
+        spec = eng.window_spectra(x, item_rec, item_start, n)
+    F, nb = (0, 0) if f is None else (int(f.numel()), len(bins[0]))
+    chunk = eng.block_significance_chunk(null, m, n, p, split, F, nb, want) if chunk is None else max(1, int(chunk))
+    Sb, Wb = sliding_plan(S, W, chunk)
+    zeros = torch.zeros(Sb * Wb, dtype=torch.int64, device=eng.device)          # the largest block's descriptors
+    ar_items = torch.arange(Sb * Wb, dtype=torch.int64, device=eng.device)
+    for s0, sb, w0, w1, last in surrogate_blocks(S, Sb, window_ranges(W, Wb)):
+        if null == "phase" and w0 == 0:                                         # drawn per surrogate block
+            phi = torch.as_tensor(sg.phase_draws(rng, sb, m, n)).to(eng.device)
+        ws = slice(w0, w1)
+        if null == "shift":
+            xs = eng.surrogate_shift(x, item_rec[ws], item_start[ws], n, d_all[s0:s0 + sb], split)
+        else:
+            xs = eng.surrogate_phase(spec[ws], phi, n)
+        items = sb * (w1 - w0)
+        sp, tm, bad = eng.sliding_block_granger_pairs(xs.view(items, m, n), ar_items[:items], ar_items[:items], zeros[:items],
+                                                      n, p, f, fs, check="mask", **kw)
+        acc.add(obs_meta[ws], block_meta(tm, sp), bad, ws, sb, last)
+    return finish(acc.result((W,), obs_meta, obs_bad), obs[1], obs_bad)
+
+
+def block_granger_pseudo_dyad_significance(eng, x, item_start, n, p, freqs, fs, bands, *, split, n_surrogates=None, seed=None,
+                                           values=sg.BLOCK_VALUES, check=True, chunk=None):
+    p = _engine.no_block_auto_order(p, "block_granger_pseudo_dyad_significance")
+    D, m, T = x.shape
+    n = int(n)
+    S, split, values = sg.block_pseudo_dyad_args(D, m, n_surrogates, seed, split, values, bands, check)
+    x = device_x(x)
+    eng.pad(m)
+    W = int(item_start.numel())
+    i64 = dict(dtype=torch.int64, device=eng.device)
+    dy = torch.arange(D, **i64).repeat_interleave(W)                  # item (d, w) = d * W + w: its dyad ...
+    starts = item_start.repeat(D) if isinstance(item_start, torch.Tensor) else item_start
+    eng.check_items(x, dy, starts, n, p)
+    want, f, bins, nv, tested_h, tested = _block_prepare(eng, freqs, bands, values, "block_granger_pseudo_dyad_significance")
+    timed = "time" in values
+    partners = sg.partner_derangements(None if S is None else np.random.default_rng(seed), S, D)
+    S = int(partners.shape[0])
+    N = D * W
+    acc = NullAccumulator(eng, N, 2, nv, tested_h, tested)
+    partners_out = torch.as_tensor(partners).to(eng.device)
+    kw = dict(split=split, want=want, bands=bins, validate=False)
+
+    def finish(res, time, obs_bad):
+        grp = res.pop("group")
+        out = dict(block_leaves(res, values), n_valid=res["n_valid"], partners=partners_out,
+                   group=dict(block_leaves(grp, values), n_valid=grp["n_valid"]))
+        if timed:
+            out["observed_time"] = _block_observed_time(time, obs_bad, (D, W), acc.failed(obs_bad))
+        return out
+    if W == 0:
+        return finish(acc.empty((D, 0), group=True), eng.empty(0, 4), None)
+    # the observed dyads through the same entry (rec_b = rec_a), which also hands out the restricted fits' log-determinants
+    obs = eng.sliding_block_granger_pairs(x, dy, dy, starts, n, p, f, fs, return_red=timed,
+                                          check=True if check is True else "mask", **kw)
+    obs_bad = None if check is True else obs[-1]
+    red = obs[2] if timed else None
+    obs_meta = block_meta(obs[1], obs[0])
+    # (K1 over the D W real windows a second time -- the fused call above does not hand its R out; a few per cent of it)
+    R_base = eng.lagcov(x, dy, starts, n, p)
+    base_a = torch.arange(N, **i64)
+    wrep = torch.arange(W, **i64).repeat(D)
+    blk = N if chunk is None else max(1, min(N, int(chunk)))
+    gmean = eng.empty(S, W, 2, 2, nv)
+    gbad = torch.empty(S, W, dtype=torch.bool, device=eng.device)
+    both = eng.empty(2, N, 2, 2, nv)                                  # the two surrogates one s gives every dyad
+    both_bad = torch.empty(2, N, dtype=torch.bool, device=eng.device)
+    for s in range(S):
+        pi = torch.as_tensor(partners[s]).to(eng.device)
+        inv = torch.empty_like(pi)
+        inv[pi] = torch.arange(D, **i64)
+        rec_b = pi[dy].contiguous()
+        base_b = (rec_b * W + wrep).contiguous()
+        for i0, i1 in window_ranges(N, blk):
+            sl = slice(i0, i1)
+            sp, tm, bad = eng.sliding_block_granger_pairs(x, dy[sl], rec_b[sl], starts[sl], n, p, f, fs, R_base=R_base,
+                                                          base_a=base_a[sl], base_b=base_b[sl], red_base=red, check="mask",
+                                                          **kw)
+            both[0, sl] = block_meta(tm, sp)
+            both_bad[0, sl] = bad
+        # whole surrogates only: the B-anchored value of dyad d is the item of dyad pi^-1(d), wherever its block was
+        both[1] = both[0].view(D, W, 2, 2, nv)[inv].view(N, 2, 2, nv)
+        both_bad[1] = both_bad[0].view(D, W)[inv].view(N)
+        acc.add(obs_meta, both.view(2 * N, 2, 2, nv), both_bad.view(2 * N), slice(0, N), 2, s == S - 1)
+        gmean[s] = both[0].view(D, W, 2, 2, nv).mean(dim=0)
+        gbad[s] = both_bad[0].view(D, W).any(dim=0)
+    group = acc.group(obs_meta.view(D, W, 2, 2, nv).mean(dim=0), gmean, gbad, S, obs_bad)
+    return finish(dict(acc.result((D, W), obs_meta, obs_bad), group=group), obs[1], obs_bad)

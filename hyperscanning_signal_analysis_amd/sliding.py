@@ -28,7 +28,8 @@ __all__ = ["window_positions", "hop_positions", "create_windows", "sliding_ffdtf
            "regular_grid", "sliding_ddtf", "sliding_ddtf_device", "sliding_gpdc", "sliding_gpdc_device", "sliding_fad",
            "sliding_significance", "ensemble_items", "sliding_ensemble", "sliding_ensemble_epochs",
            "sliding_ensemble_significance", "sliding_ensemble_epochs_significance", "sliding_pseudo_dyad_significance",
-           "sliding_model_validation", "validation_p_values", "sliding_ensemble_contrast", "sliding_ensemble_epochs_contrast"]
+           "sliding_model_validation", "validation_p_values", "sliding_ensemble_contrast", "sliding_ensemble_epochs_contrast",
+           "sliding_block_granger_significance", "sliding_block_granger_pseudo_dyad_significance"]
 
 
 def window_positions(T: int, n_windows: int = 3, window_size=None):
@@ -361,6 +362,76 @@ def sliding_pseudo_dyad_significance(x, window_size, n_windows, p, freqs, fs, ba
     out = {k: v.cpu().numpy() for k, v in res.items() if k != "group"}
     out["group"] = {k: v.cpu().numpy() for k, v in res["group"].items()}
     return out
+
+
+def _block_to_host(res, lead):
+    """The device dict of a block Granger test -> NumPy, the per-item leaves reshaped to `lead` + their own trailing axes."""
+    def host(v, lead):
+        a = v.cpu().numpy()
+        return a if lead is None else a.reshape(lead + a.shape[1:])
+    out = {}
+    for k, v in res.items():
+        if k == "group":
+            out[k] = {g: ({h: u.cpu().numpy() for h, u in w.items()} if isinstance(w, dict) else w.cpu().numpy())
+                      for g, w in v.items()}
+        elif isinstance(v, dict):
+            out[k] = {h: host(u, lead) for h, u in v.items()}
+        else:
+            out[k] = host(v, None if k == "partners" else lead)
+    return out
+
+
+def sliding_block_granger_significance(x, window_size, n_windows, p, freqs, fs, bands, *, split, null, n_surrogates, seed,
+                                       values=("time", "bands"), min_shift=None, check=True, chunk=None, hop=None,
+                                       engine: Engine | None = None):
+    """NumPy (or tensor) in / NumPy out: the surrogate test of `Engine.block_granger_significance` for the block Granger
+    causality `sliding_block_granger(x, window_size, n_windows, p, freqs, fs, split=split, hop=hop, bands=bands)` of every
+    window.  x: (m, T) or (n_rec, m, T).  Returns a dict, index 0 = A -> B, 1 = B -> A: time = {observed, p, p_fwe, null_mean,
+    null_std (n_windows, 2)}, bands = {the same, (n_windows, 2, n_bands)}, observed_time (n_windows, 4), n_valid
+    (n_windows,), each with a leading n_rec for several recordings; values=("time",) leaves `bands` out (and needs neither
+    freqs nor bands), values=("bands",) leaves `time` and `observed_time` out.  The arguments are checked before the GPU is
+    touched (`surrogates.block_significance_args`)."""
+    from . import surrogates as sg
+    from .engine import no_block_auto_order
+    no_block_auto_order(p, "sliding_block_granger_significance")
+    single = np.ndim(x) == 2
+    shape = tuple(np.shape(x))
+    n_rec, m, T = (1,) + shape if single else shape
+    positions, w = _positions(T, window_size, n_windows, hop)
+    sg.block_significance_args(null, n_surrogates, m, T, w, split, min_shift, values, bands, check)
+    eng = engine or default_engine()
+    xd = _recordings_to_device(eng, x, single)
+    item_rec, item_start = window_items(n_rec, positions, eng.device)
+    res = eng.block_granger_significance(xd, item_rec, item_start, w, p, freqs, fs, bands, split=split, null=null,
+                                         n_surrogates=n_surrogates, seed=seed, values=values, min_shift=min_shift,
+                                         check=check, chunk=chunk)
+    return _block_to_host(res, (len(positions),) if single else (n_rec, len(positions)))
+
+
+def sliding_block_granger_pseudo_dyad_significance(x, window_size, n_windows, p, freqs, fs, bands, *, split, n_surrogates=None,
+                                                   seed=None, values=("time", "bands"), hop=None, check=True, chunk=None,
+                                                   engine: Engine | None = None):
+    """NumPy (or tensor) in / NumPy out: the pseudo-dyad test of `Engine.block_granger_pseudo_dyad_significance`.  x: (D, m,
+    T), one recording per dyad, all time-locked to the same stimulus; channels < split are participant A.  Windows as for
+    `sliding_block_granger_significance`, partners as for `sliding_pseudo_dyad_significance`.  Returns that function's dict
+    with (D, n_windows) in front, plus partners (S, D) and group = {time, bands, n_valid} with (n_windows,) in front.  The
+    arguments are checked before the GPU is touched (`surrogates.block_pseudo_dyad_args`)."""
+    from . import surrogates as sg
+    from .engine import no_block_auto_order
+    no_block_auto_order(p, "sliding_block_granger_pseudo_dyad_significance")
+    shape = tuple(np.shape(x))
+    if len(shape) != 3:
+        raise ValueError("x must have shape (dyads, channels, samples)")
+    D, m, T = shape
+    sg.block_pseudo_dyad_args(D, m, n_surrogates, seed, split, values, bands, check)
+    positions, w = _positions(T, window_size, n_windows, hop)
+    eng = engine or default_engine()
+    xd = _recordings_to_device(eng, x, False)
+    item_start = torch.as_tensor(np.asarray(positions, dtype=np.int64)).to(eng.device)
+    res = eng.block_granger_pseudo_dyad_significance(xd, item_start, w, p, freqs, fs, bands, split=split,
+                                                     n_surrogates=n_surrogates, seed=seed, values=values, check=check,
+                                                     chunk=chunk)
+    return _block_to_host(res, None)
 
 
 def sliding_fad(signals, fs, window_size=None, n_windows=3, hop=None, model_order=None, max_model_order=20,

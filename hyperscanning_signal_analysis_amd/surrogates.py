@@ -23,11 +23,14 @@ import numpy as np
 
 __all__ = ["NULLS", "ENSEMBLE_NULLS", "MEASURES", "TAILS", "significance_args", "shift_offsets", "phase_draws",
            "trial_permutations", "label_draws", "contrast_args", "partner_count", "partner_derangements", "pseudo_dyad_args",
-           "tested_mask", "check_significance_dict"]
+           "tested_mask", "check_significance_dict", "BLOCK_VALUES", "BLOCK_WANT", "block_want", "block_values",
+           "block_significance_args", "block_pseudo_dyad_args"]
 
 NULLS = ("shift", "phase")          # of continuous recordings (`sliding_significance`)
 ENSEMBLE_NULLS = ("trial",)         # of event-locked ensembles (`ensemble_significance`)
 MEASURES = ("ffdtf", "ddtf", "gpdc")
+BLOCK_VALUES = ("time", "bands")    # of the block Granger tests: the time-domain value, the band sums of the spectral one
+BLOCK_WANT = ("spectral", "time")   # outputs of `Engine.sliding_block_granger_pairs`
 TAILS = ("two-sided", "greater", "less")    # of the condition contrast: T = |D|, D, -D with D = band(A) - band(B)
 
 
@@ -257,3 +260,72 @@ def check_significance_dict(sig):
     if ms is not None and _int(ms, "significance: min_shift") < 0:
         raise ValueError(f"significance: min_shift must be >= 0, got {ms}")
     return {"null": sig["null"], "n_surrogates": S, "seed": seed, "min_shift": None if ms is None else int(ms)}
+
+
+# ------------------------------------------------------------------ block Granger causality (two values per window)
+def _subset(given, allowed, name):
+    given = (given,) if isinstance(given, str) else tuple(given)
+    if not given or len(set(given)) != len(given) or any(v not in allowed for v in given):
+        raise ValueError(f"{name} must be a non-empty selection of {allowed} without repeats, got {given!r}")
+    return given
+
+
+def block_want(want):
+    """want of `Engine.sliding_block_granger_pairs` -> (spectral, time) booleans; ValueError for anything that is not a
+    non-empty selection of "spectral" and "time"."""
+    want = _subset(want, BLOCK_WANT, "want")
+    return "spectral" in want, "time" in want
+
+
+def block_values(values, bands):
+    """values of the block Granger tests, in the order of the value columns: the time-domain value first, then the band
+    sums.  ValueError for anything that is not a non-empty selection of "time" and "bands", and for "bands" without
+    bands = (bin_lo, bin_hi) of at least one band."""
+    values = _subset(values, BLOCK_VALUES, "values")
+    if "bands" in values and (bands is None or len(bands) != 2 or len(np.atleast_1d(bands[0])) < 1
+                              or len(np.atleast_1d(bands[0])) != len(np.atleast_1d(bands[1]))):
+        raise ValueError('values with "bands" needs bands = (bin_lo, bin_hi) with at least one band')
+    return tuple(v for v in BLOCK_VALUES if v in values)
+
+
+def _block_split(split, m):
+    split = _int(split, "split")
+    if not 1 <= split <= int(m) - 1:
+        raise ValueError(f"split must be in 1..{int(m) - 1}, got {split}")
+    return split
+
+
+def _check_mode(check):
+    if check is not True and check != "nan":
+        raise ValueError(f"check must be True or 'nan', got {check!r}")
+
+
+def block_significance_args(null, n_surrogates, m, T, n, split, min_shift=None, values=BLOCK_VALUES, bands=None, check=True):
+    """Check the arguments of `Engine.block_granger_significance` BEFORE anything is drawn or launched; returns
+    (S, split, min_shift, values) with min_shift = n filled in and `values` in column order.  The split is that of the
+    blocks and has no default; both nulls need it.  ValueError for a null outside NULLS, S < 1, a split outside 1..m-1, T < 2
+    min_shift under the shift null, ill-formed values / bands and a `check` other than True / "nan"."""
+    if null not in NULLS:
+        raise ValueError(f"null must be one of {NULLS}, got {null!r}")
+    S = _int(n_surrogates, "n_surrogates")
+    if S < 1:
+        raise ValueError(f"n_surrogates must be >= 1, got {S}")
+    split = _block_split(split, m)
+    min_shift = int(n) if min_shift is None else _int(min_shift, "min_shift")
+    if min_shift < 0:
+        raise ValueError(f"min_shift must be >= 0, got {min_shift}")
+    if null == "shift" and int(T) < 2 * min_shift:
+        raise ValueError(f"the shift null needs T >= 2 min_shift (T = {int(T)}, min_shift = {min_shift})")
+    _check_mode(check)
+    return S, split, min_shift, block_values(values, bands)
+
+
+def block_pseudo_dyad_args(D, m, n_surrogates, seed, split, values=BLOCK_VALUES, bands=None, check=True):
+    """Check the arguments of `Engine.block_granger_pseudo_dyad_significance` BEFORE anything is drawn or launched; returns
+    (S or None, split, values).  ValueError for fewer than 2 dyads, a split outside 1..m-1, an integer n_surrogates < 1 or
+    without a seed, ill-formed values / bands and a `check` other than True / "nan"."""
+    _n_dyads(int(D))
+    S = partner_count(n_surrogates, seed)
+    split = _block_split(split, m)
+    _check_mode(check)
+    return S, split, block_values(values, bands)

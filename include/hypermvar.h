@@ -378,6 +378,39 @@ int hmv_sliding_block_gc_f64(const double* x, int64_t rec_stride, int64_t ld,
                              void* workspace, int64_t workspace_bytes, int64_t chunk, int64_t flags,
                              int64_t grid_hop, int64_t grid_first, int64_t grid_nwin, int64_t grid_T, void* stream);
 
+/* Block Granger causality of pairs of recordings -- what the surrogate and pseudo-dyad tests of the block values run on.
+ * hmv_sliding_block_gc_pairs_f64: hmv_sliding_block_gc_f64 of the window at item_start[it] whose channels < split are those
+ *   of recording rec_a[it] and whose channels >= split are those of recording rec_b[it] (K1 of hmv_lagcov_pairs_f64, with its
+ *   optional R_base / base_a / base_b; there is no grid).  With rec_b == rec_a every output has the bits of
+ *   hmv_sliding_block_gc_f64; with rec_b != rec_a those of that call on the pair written out as one recording.
+ *   want: bit 0 the spectral output, bit 1 the time-domain values; 0 is refused (-15).
+ *     bit 0 clear: F may be 0 and spectral, freqs, bin_lo, bin_hi, info_gc null -- none of them is read or written, and
+ *       no twiddles, factor, gram, per-frequency or band-sum kernel runs: K1, K2 and one kernel that takes the Cholesky
+ *       log-determinants of Sigma, Sigma_AA, Sigma_BB and of the restricted residual covariances (bgc_time_kernel).
+ *     bit 1 clear: time, info_red may be null, no restricted fit runs, red_out / red_base are ignored.
+ *   red_out [item][2] (optional): (ln det Sr_AA, ln det Sr_BB) exactly as the time values use them (NaN where not positive
+ *     definite).
+ *   red_base [n_base][2] with info_red_base [n_base][2] (optional, both or neither; they need R_base, base_a, base_b: -4
+ *     otherwise): red_out and info_red of an earlier call on the observed windows that R_base holds.  A pair changes only
+ *     the cross-recording covariance blocks, so the restricted fit of block A is that of window base_a[it] and the one of
+ *     block B that of window base_b[it]: ln det Sr_AA and its info are read from row base_a[it], column 0, ln det Sr_BB and
+ *     its info from row base_b[it], column 1, and neither the gather nor the two restricted solves run.  Same bits.
+ *   workspace: hmv_block_gc_pairs_workspace_bytes(chunk, m, n, p, split, F, n_bands, want) bytes (-1 for bad arguments; F and
+ *     n_bands are not looked at with bit 0 of want clear).
+ * Refusals: those of hmv_sliding_block_gc_f64, want outside 1..3 (-15), a null rec_b, R_base / base_a / base_b not all or
+ * none, red_base without info_red_base or without R_base (-4). */
+int64_t hmv_block_gc_pairs_workspace_bytes(int64_t chunk, int m, int n, int p, int split, int F, int n_bands, int want);
+int hmv_sliding_block_gc_pairs_f64(const double* x, int64_t rec_stride, int64_t ld, int64_t T,
+                                   const int64_t* rec_a, const int64_t* rec_b, const int64_t* item_start, int64_t n_items,
+                                   int m, int n, int p, int split, const double* freqs, int F, double fs,
+                                   double* spectral, const int32_t* bin_lo, const int32_t* bin_hi, int n_bands,
+                                   double* time, double* ar_out, double* V_out,
+                                   int32_t* info_yw, int32_t* info_red, int32_t* info_gc,
+                                   void* workspace, int64_t workspace_bytes, int64_t chunk, int64_t flags,
+                                   const double* R_base, const int64_t* base_a, const int64_t* base_b,
+                                   int want, double* red_out, const double* red_base, const int32_t* info_red_base,
+                                   void* stream);
+
 /* Automatic model order, window by window (csrc/yw_auto.hip).  Every connectivity function of the reference takes
  * `max_model_order=20, optimal_model_order=None, crit_type='AIC'`: with no order given it calls mvar_criterion
  * (src/mtmvar.py:551-601), which fits EVERY order 1..pmax with ar_coeff (:90-123) and returns the first arg-min of
