@@ -146,6 +146,10 @@ SIGNATURES = {
     "hmv_model_validation_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
                                          c_void_p, c_int, c_double] + [c_void_p] * 7 + [c_int64, c_void_p, c_int64, c_int64,
                                                                                        c_void_p]),
+    "hmv_decimate_out_len": (c_int64, [c_int64, c_int]),
+    "hmv_decimate_tile": (c_int, [c_int, c_int]),
+    "hmv_decimate_fir_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_int, c_void_p,
+                                     c_int64, c_int64, c_void_p]),
 }
 
 # option bits of the fused entry points (include/hypermvar.h)
@@ -166,6 +170,9 @@ TUNE_K3_FORM = 3
 TUNE_YW_FORM = 4
 TUNE_K3_LDS_PAD = 5
 TUNE_K3_SPLIT = 6
+# limits of hmv_decimate_fir_f64
+MAX_DECIMATE = 32
+MAX_DECIMATE_TAPS = 641
 
 
 _lib = None

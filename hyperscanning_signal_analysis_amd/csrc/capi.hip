@@ -1802,4 +1802,32 @@ int hmv_model_validation_f64(const double* x, int64_t rec_stride, int64_t ld, co
   return 0;
 }
 
+// ---- FIR decimation of recordings (decimate.hip) ------------------------------------------------------------------
+int64_t hmv_decimate_out_len(int64_t T, int q) {
+  if (T < 1 || q < 2 || q > HMV_MAX_DECIMATE) return -1;
+  return (T + q - 1) / q;
+}
+
+int hmv_decimate_tile(int q, int n_taps) {
+  if (q < 2 || q > HMV_MAX_DECIMATE || n_taps < 3 || n_taps > HMV_MAX_DECIMATE_TAPS || n_taps % 2 == 0) return -1;
+  return hmv::decimate_tile(q, n_taps);
+}
+
+int hmv_decimate_fir_f64(const double* x, int64_t rec_stride, int64_t ld, int64_t T, int64_t n_rec, int m, int q,
+                         const double* h, int n_taps, double* y, int64_t y_rec_stride, int64_t y_ld, void* stream) {
+  if (q < 2 || q > HMV_MAX_DECIMATE) return fail(-1, "hmv_decimate_fir_f64: decimation factor must be in 2..32");
+  if (n_taps < 3 || n_taps > HMV_MAX_DECIMATE_TAPS || n_taps % 2 == 0)
+    return fail(-2, "hmv_decimate_fir_f64: the number of taps must be odd and in 3..641");
+  if (T < 1 || n_rec < 0 || m < 1) return fail(-3, "hmv_decimate_fir_f64: bad sample / recording / channel count");
+  if (T > (int64_t(1) << 40)) return fail(-7, "hmv_decimate_fir_f64: recordings longer than 2^40 samples are not supported");
+  if (n_rec == 0) return 0;
+  if (!x || !h || !y) return fail(-4, "hmv_decimate_fir_f64: null pointer");
+  if (ld < T) return fail(-5, "hmv_decimate_fir_f64: ld is smaller than T");
+  if (y_ld < hmv_decimate_out_len(T, q)) return fail(-6, "hmv_decimate_fir_f64: y_ld is smaller than ceil(T / q)");
+  hmv::DecimateArgs a{};
+  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.T = T; a.n_rec = n_rec; a.m = m; a.q = q;
+  a.h = h; a.n_taps = n_taps; a.y = y; a.y_rec_stride = y_rec_stride; a.y_ld = y_ld;
+  return hmv::launch_decimate(a, S(stream));
+}
+
 }  // extern "C"

@@ -409,4 +409,17 @@ struct WhiteArgs {
 };
 int launch_whiteness(const WhiteArgs& a, int m_pad, hipStream_t st);
 
+// ---- FIR decimation of recordings (decimate.hip) ------------------------------------------------------------------
+struct DecimateArgs {
+  const double* x;          // [n_rec][m][ld], T samples used
+  long long rec_stride, ld, T, n_rec;
+  int m, q;
+  const double* h;          // [n_taps]
+  int n_taps;
+  double* y;                // [n_rec][m][y_ld], ceil(T / q) samples written
+  long long y_rec_stride, y_ld;
+};
+int decimate_tile(int q, int n_taps);      // outputs per workgroup
+int launch_decimate(const DecimateArgs& a, hipStream_t st);
+
 }  // namespace hmv

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["filter_eeg", "preprocess_eeg", "load_eeg_signals", "load_dyad_block"]
+__all__ = ["filter_eeg", "preprocess_eeg", "load_eeg_signals", "load_dyad_block", "decimation_taps", "DECIMATION_DESIGNS"]
 
 
 def filter_eeg(data_tc, fs, low_cutoff_hz=None, high_cutoff_hz=None):
@@ -36,6 +36,34 @@ def filter_eeg(data_tc, fs, low_cutoff_hz=None, high_cutoff_hz=None):
         b, a = iirnotch(50.0, Q=15, fs=fs)
         x = filtfilt(b, a, x, axis=-1)
     return x.T
+
+
+DECIMATION_DESIGNS = ("decimate", "resample_poly")
+
+
+def decimation_taps(q, design="decimate"):
+    """The anti-aliasing FIR of an integer-factor decimation by q, as float64 taps on the host (SciPy's own calls).
+        "decimate"       scipy.signal.decimate(x, q, ftype='fir', zero_phase=True) -- what the reference's
+                         `MultimodalData._decimate_signals` calls (data_structures.py:792):
+                         firwin(20 q + 1, 1 / q, window="hamming")
+        "resample_poly"  scipy.signal.resample_poly(x, 1, q) -- `_downsample_signal` (eeg_alpha_ibi_ffdtf.py:404):
+                         firwin(20 q + 1, 1 / q, window=("kaiser", 5.0))
+    A 1-D array is taken as the taps themselves (odd length, 3 .. 641)."""
+    from . import _lib
+    q = int(q)
+    if not 2 <= q <= _lib.MAX_DECIMATE:
+        raise ValueError(f"decimation factor must be in 2..{_lib.MAX_DECIMATE}, got {q}")
+    if isinstance(design, str):
+        from scipy.signal import firwin
+        if design == "decimate":
+            return firwin(20 * q + 1, 1.0 / q, window="hamming")
+        if design == "resample_poly":
+            return firwin(20 * q + 1, 1.0 / q, window=("kaiser", 5.0))
+        raise ValueError(f"design must be one of {DECIMATION_DESIGNS} or a 1-D array of taps, got {design!r}")
+    h = np.ascontiguousarray(np.asarray(design, dtype=np.float64))
+    if h.ndim != 1 or h.size % 2 == 0 or not 3 <= h.size <= _lib.MAX_DECIMATE_TAPS:
+        raise ValueError(f"taps must be a 1-D array of odd length in 3..{_lib.MAX_DECIMATE_TAPS}, got shape {h.shape}")
+    return h
 
 
 def preprocess_eeg(data_tc, time_s, channel_names, fs, event_duration_s=None, channel_subset=None,

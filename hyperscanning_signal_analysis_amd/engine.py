@@ -253,6 +253,7 @@ class Engine:
         self.max_workspace_bytes = int(max_workspace_bytes)
         self._ws = {}
         self._aux = {}        # second HIP stream for chunk overlap in the fused path
+        self._taps = {}       # decimation filters on the device, per (q, design)
 
     # ------------------------------------------------------------------ helpers
     def stream(self):
@@ -2005,6 +2006,49 @@ class Engine:
                 ws.data_ptr(), nbytes, chunk, self.stream())
         _lib.check(rc, "hmv_model_validation_f64")
         return o
+
+    # ------------------------------------------------------------------ FIR decimation (decimate.hip)
+    def decimation_taps(self, q: int, design="decimate"):
+        """Device copy of `eeg_io.decimation_taps(q, design)`; the two named designs are uploaded once per q."""
+        from .eeg_io import decimation_taps
+        key = (int(q), design) if isinstance(design, str) else None
+        h = self._taps.get(key) if key is not None else None
+        if h is None:
+            h = self.to_device(decimation_taps(q, design))
+            if key is not None:
+                self._taps[key] = h
+        return h
+
+    def decimate(self, x: torch.Tensor, q: int, design="decimate", out: torch.Tensor | None = None):
+        """Anti-aliased decimation by the integer q (`hmv_decimate_fir_f64`): x (n_rec, m, T) or (m, T) float64 on the
+        device -> (.., ceil(T / q)), what `scipy.signal.decimate(x, q, ftype='fir', zero_phase=True)` (design="decimate") or
+        `scipy.signal.resample_poly(x, 1, q)` (design="resample_poly") return on the host; a 1-D array as `design` is taken
+        as the taps.  x may be a strided view (unit stride along time); `out` (optional) a float64 device tensor of the
+        result's shape, strided likewise.  On the engine's stream, no host synchronisation.  m is not limited to 64."""
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.device != self.device or x.dim() not in (2, 3):
+            raise ValueError(f"decimate: x must be a float64 tensor (n_rec, m, T) or (m, T) on {self.device}")
+        q = int(q)
+        h = self.decimation_taps(q, design)
+        x3 = x[None] if x.dim() == 2 else x
+        n_rec, m, T = x3.shape
+        T_out = int(self.lib.hmv_decimate_out_len(T, q))
+        if T_out < 0 or m < 1:
+            raise ValueError(f"decimate: bad shape {tuple(x.shape)} for q={q}")
+        if n_rec > 0 and (x3.stride(2) != 1 or x3.stride(1) < T or x3.stride(0) < 0):
+            x3 = x3.contiguous()
+        if out is None:
+            y3 = self.empty(n_rec, m, T_out)
+        else:
+            y3 = out[None] if out.dim() == 2 else out
+            if (out.dtype != torch.float64 or out.device != self.device or out.dim() != x.dim()
+                    or tuple(y3.shape) != (n_rec, m, T_out) or (n_rec > 0 and (y3.stride(2) != 1 or y3.stride(1) < T_out))):
+                raise ValueError(f"decimate: out must be a float64 tensor of shape {(*x.shape[:-1], T_out)} on {self.device}, "
+                                 "unit stride along time")
+        with torch.cuda.device(self.device):
+            rc = self.lib.hmv_decimate_fir_f64(x3.data_ptr(), x3.stride(0), x3.stride(1), T, n_rec, m, q, h.data_ptr(),
+                                               int(h.numel()), y3.data_ptr(), y3.stride(0), y3.stride(1), self.stream())
+        _lib.check(rc, "hmv_decimate_fir_f64")
+        return (y3[0] if x.dim() == 2 else y3) if out is None else out
 
 
 _default = None

@@ -38,7 +38,7 @@ from .engine import default_engine
 from .sliding import hop_positions, regular_grid, validation_p_values, window_items
 
 __all__ = ["discover_dyads", "decode_events", "segment_block", "prepare_dyad", "run", "run_pseudo_dyads", "savez_fast",
-           "xarray_reader"]
+           "xarray_reader", "resolve_decimate", "decimated_segment", "DecimateConfigError"]
 
 ROLES = (("ch", "child"), ("cg", "caregiver"))
 MEASURES = ("ffdtf", "ddtf", "gpdc")          # what run(measures=...) can compute per window; ffDTF always
@@ -190,11 +190,51 @@ def resolve_pivoted_fallback(pivoted_fallback, engine_setting: bool, auto: bool)
     return pivoted, ({"flags": _lib.FLAG_YW_PIVOTED} if pivoted else {})
 
 
+class DecimateConfigError(ValueError):
+    """`run(decimate=q)` cannot work at this rate, window and order: raised out of the batch, not logged per segment."""
+
+
+def resolve_decimate(decimate, design="decimate"):
+    """`run(decimate=..., decimate_design=...)` -> None, or (q, the design's name for the meta entry).  Needs no GPU."""
+    if decimate is None:
+        return None
+    from . import _lib
+    from .eeg_io import decimation_taps
+    if isinstance(decimate, bool) or not isinstance(decimate, (int, np.integer)):
+        raise DecimateConfigError(f"decimate must be None or an integer in 2..{_lib.MAX_DECIMATE}, got {decimate!r}")
+    try:
+        decimation_taps(int(decimate), design)        # the factor's range and the design, as the engine will see them
+    except ValueError as e:
+        raise DecimateConfigError(f"escan_batch.run(decimate={decimate!r}): {e}") from None
+    return int(decimate), design if isinstance(design, str) else "taps"
+
+
+def decimated_segment(q, fs, window_s, m, order, freqs=None):
+    """What `run(decimate=q)` does to a segment recorded at `fs` with m channels -> (fs / q, window length in decimated
+    samples).  Refuses, before anything is computed, a requested frequency that is not below the new Nyquist rate and a
+    window with no more samples than the m * order unknowns of one row of the model.  Needs no GPU."""
+    fs_new = float(fs) / int(q)
+    W = int(round(window_s * fs_new))
+    if freqs is not None and np.size(freqs) and float(np.max(freqs)) >= fs_new / 2.0:
+        raise DecimateConfigError(
+            f"escan_batch.run(decimate={q}): the requested frequencies reach {float(np.max(freqs)):g} Hz, which is not below "
+            f"the Nyquist rate {fs_new / 2.0:g} Hz of the decimated recording ({fs:g} Hz / (2 * {q}))")
+    if W <= int(m) * int(order):
+        raise DecimateConfigError(
+            f"escan_batch.run(decimate={q}): a {window_s:g} s window has {W} samples at {fs_new:g} Hz, no more than the "
+            f"{m} channels x order {order} = {int(m) * int(order)} unknowns of one row of the model: the normal equations "
+            f"would be rank-deficient (the rank trap of decimating without lowering the order).  Use a lower model order "
+            f"(order {max(1, int(order) // int(q))} at {fs_new:g} Hz spans the time of order {order} at {fs:g} Hz), "
+            f"a longer window or fewer channels")
+    return fs_new, W
+
+
 def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, freqs=None, bands=hdist.DEFAULT_BANDS,
         low_cutoff_hz=None, high_cutoff_hz=None, channel_subset=None, with_psd=False, psd_fmin=1.0, psd_fmax=30.0,
         psd_bandwidth=2.0, save_full=False, skip_existing=True, reader=None, engine=None, world=1, rank=0,
         verbose=True, prefetch=2, timing=None, save_workers=4, compresslevel=0, measures=("ffdtf",), significance=None,
-        max_model_order=20, crit_type="AIC", validation_lags=None, block_granger=False, pivoted_fallback=None):
+        max_model_order=20, crit_type="AIC", validation_lags=None, block_granger=False, pivoted_fallback=None,
+        decimate=None, decimate_design="decimate"):
     """Process every dyad under <root>/EEG.  Per dyad one `<out_dir>/<dyad>_ffdtf.npz` with, per segment `<task>/<event>`:
         <seg>/ffdtf_bands   (windows, n, n, n_bands)   band-integrated ffDTF of every window
         <seg>/ffdtf         (windows, n, n, F)         only with save_full=True (8.4 MB per window at 64 channels)
@@ -231,6 +271,14 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
       `np.linalg.solve` would (`Engine(pivoted_yw=...)`); None takes the engine's setting.  Every segment's meta entry then
       carries "yw_routes": {"recursion", "ldlt", "lu"}, how many of its windows each solver took (one more K1 + K2 over the
       segment).  Needs an integer model_order.
+      decimate: an integer q in 2..32 -- every segment block is decimated by q on the device right after it crosses PCIe
+      (`Engine.decimate`, anti-aliased FIR; `decimate_design`: "decimate" as scipy.signal.decimate(ftype='fir',
+      zero_phase=True), "resample_poly" as scipy.signal.resample_poly(x, 1, q), or a 1-D array of taps), before the MVAR and
+      PSD legs.  `window_s` and `overlap` then mean seconds at the new rate fs / q, `starts` are in decimated samples, meta
+      carries "decimate": q, "decimate_design" and the new "fs", and every segment entry its decimated "fs" and "samples".
+      The block is not z-scored again: a low-passed signal loses only its stop-band power.  ValueError, raised out of the
+      batch, if a requested frequency is not below fs / (2 q) or if the decimated window has no more samples than
+      channels x model_order (the rank trap: lower the order with the rate).  None (default): nothing changes.
       plus `channels`, `freqs`, `meta` (JSON, its `measures` field lists what was computed, `significance` the test).  Returns {"done": [...], "skipped": [...], "failed": [(dyad, error)],
       "timing": {...}}.
     A window whose fit is singular is NaN-filled, not fatal (the reference would raise and lose the dyad); a segment that
@@ -261,6 +309,7 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
     order_kw = dict(max_model_order=pmax, crit_type=crit_type) if auto else {}
     eng = engine or default_engine()
     pivoted, yw_kw = resolve_pivoted_fallback(pivoted_fallback, eng.pivoted_yw, auto)
+    dec = resolve_decimate(decimate, decimate_design)
     reader = reader or xarray_reader
     out_dir = Path(out_dir)
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -312,6 +361,8 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                     meta["significance"] = dict(significance)
                 if block_granger:
                     meta["block_granger"] = True
+                if dec is not None:
+                    meta["decimate"], meta["decimate_design"] = dec
                 names_out, freqs_out = None, None
                 tg = time.perf_counter()
                 pending = []                                       # device results of this dyad, fetched after the last launch
@@ -319,15 +370,21 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                     key = f"{seg['task']}/{seg['event']}"
                     try:
                         block, fs = seg["block"], seg["fs"]
-                        W = int(round(window_s * fs))
-                        hop = max(1, int(round(W * (1.0 - overlap))))
                         T = block.shape[1]
+                        if dec is None:
+                            W = int(round(window_s * fs))
+                        else:
+                            fs, W = decimated_segment(dec[0], fs, window_s, block.shape[0], pmax if auto else order, freqs)
+                            T = -(-T // dec[0])
+                        hop = max(1, int(round(W * (1.0 - overlap))))
                         if T < W:
                             say(f"[SKIP] {dyad} {key}: {T} samples < one window ({W})")
                             continue
                         pos = hop_positions(T, W, hop)            # fixed hop; the tail shorter than one hop is dropped
                         f = np.asarray(freqs if freqs is not None else np.arange(0.5, min(fs / 2.0, 128.0) + 1e-9, 0.5))
                         xd = eng.to_device(block[None])
+                        if dec is not None:
+                            xd = eng.decimate(xd, dec[0], decimate_design)
                         rec_i, st_i = window_items(1, pos, eng.device)
                         psd_dev = None
                         if with_psd:                               # second stream, same resident block
@@ -339,6 +396,8 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                         lo, hi = hdist.band_bins(f, bands)
                         grid_w = regular_grid(pos, W, pmax if auto else order)
                         extra = {}                                 # dDTF / GPDC of the same windows, NaN-filled alike
+                        if dec is not None:
+                            extra["_decimated"] = (fs, T)
                         if save_full:
                             r = eng.sliding_ffdtf(xd, rec_i, st_i, W, order, f, fs, check="mask", grid=grid_w,
                                                   return_orders=auto, **order_kw, **yw_kw)
@@ -400,6 +459,8 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                             extra["_yw_routes"] = eng.window_routes(xd, rec_i, st_i, W, order)[0]
                         pending.append((seg, key, pos, W, f, bsum, ff if save_full else None, bad, psd_dev, pf if with_psd else None,
                                         extra))
+                    except DecimateConfigError:                    # the batch's own arguments: nothing to log per segment
+                        raise
                     except Exception as e:                         # one bad segment does not discard the dyad
                         meta["failed_segments"].append({"segment": key, "error": f"{type(e).__name__}: {e}"})
                         say(f"Failed segment: {dyad} {key} -> {e}")
@@ -411,6 +472,7 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                         result[f"{key}/ffdtf"] = ff.cpu().numpy()
                     ord_v = extra.pop("_whiteness_orders", None)
                     routes = extra.pop("_yw_routes", None)
+                    decimated = extra.pop("_decimated", None)
                     for name, arr in extra.items():
                         result[f"{key}/{name}"] = arr.cpu().numpy()
                     if ord_v is not None:
@@ -429,6 +491,9 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                     if routes is not None:
                         from .engine import route_counts
                         meta["segments"][-1]["yw_routes"] = route_counts(routes)
+                    if decimated is not None:
+                        meta["fs"], T = decimated
+                        meta["segments"][-1].update(fs=meta["fs"], samples=int(T))
                     names_out, freqs_out = seg["names"], f
                     say(f"[OK] {dyad} {key}: {seg['block'].shape[0]} ch x {T} samples, {len(pos)} windows"
                         + (f", {n_bad} singular" if n_bad else ""))
@@ -454,6 +519,8 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                 tm["gpu_s"] += gpu_s; tm["save_s"] += save_s
                 tm["dyads"].append({"dyad": dyad, "host_prepare_s": prep["host_s"], "waited_for_host_s": wait_s,
                                     "gpu_s": gpu_s, "save_s": save_s, "segments": len(meta["segments"])})
+            except DecimateConfigError:
+                raise
             except Exception as e:                  # one bad dyad does not stop the batch (export_..._batch.py:93-99)
                 failed.append((dyad, f"{type(e).__name__}: {e}"))
                 say(f"Failed: {dyad} -> {e}")

@@ -10,6 +10,8 @@ With `p=None` every window gets the order `mvar_criterion(window, max_model_orde
 picks for it -- the reference's own default, `optimal_model_order=None` -- selected on the device in the same call.
 `sliding_significance` adds a surrogate test (shift or phase null) to the band values of any of the three.
 `sliding_pseudo_dyad_significance` tests them against shuffled partners: participant A of one dyad with participant B of another.
+`decimate` is the anti-aliased integer-factor decimation to run BEFORE any of them on low-passed recordings
+(`scipy.signal.decimate(..., ftype='fir', zero_phase=True)` / `resample_poly(x, 1, q)` on the device).
 `sliding_fad` is `fad_decomposition` (mtmvar.py:607-757) of every channel of every window.
 `sliding_ensemble` / `sliding_ensemble_epochs` are the event-locked form: the reference's functions take `signals` of shape
 (channels, samples, trials) and fit ONE model to the trial-averaged covariances (`count_corr`, mtmvar.py:54-85); here a
@@ -29,7 +31,23 @@ __all__ = ["window_positions", "hop_positions", "create_windows", "sliding_ffdtf
            "sliding_significance", "ensemble_items", "sliding_ensemble", "sliding_ensemble_epochs",
            "sliding_ensemble_significance", "sliding_ensemble_epochs_significance", "sliding_pseudo_dyad_significance",
            "sliding_model_validation", "validation_p_values", "sliding_ensemble_contrast", "sliding_ensemble_epochs_contrast",
-           "sliding_block_granger_significance", "sliding_block_granger_pseudo_dyad_significance"]
+           "sliding_block_granger_significance", "sliding_block_granger_pseudo_dyad_significance", "decimate"]
+
+
+def decimate(x, fs, q, design="decimate", engine: Engine | None = None):
+    """Decimate recordings by the integer q before fitting: x (m, T) or (n_rec, m, T), a NumPy array or a device tensor ->
+    (y (.., ceil(T / q)) of the same kind, fs / q).  design="decimate": `scipy.signal.decimate(x, q, ftype='fir',
+    zero_phase=True)`; "resample_poly": `scipy.signal.resample_poly(x, 1, q)`; a 1-D array: the taps themselves
+    (`eeg_io.decimation_taps`).  The output is not z-scored again: a low-passed signal loses only its stop-band power.
+    Afterwards window lengths are in decimated samples and the model order has to come down with the rate: a window
+    needs more samples than m * p unknowns per row, or its normal equations are rank-deficient."""
+    eng = engine or default_engine()
+    if isinstance(x, torch.Tensor):
+        return eng.decimate(x.to(device=eng.device, dtype=torch.float64), q, design), float(fs) / int(q)
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim not in (2, 3):
+        raise ValueError(f"decimate: x must be (m, T) or (n_rec, m, T), got shape {x.shape}")
+    return eng.decimate(eng.to_device(x), q, design).cpu().numpy(), float(fs) / int(q)
 
 
 def window_positions(T: int, n_windows: int = 3, window_size=None):

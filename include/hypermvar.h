@@ -723,6 +723,31 @@ int hmv_model_validation_f64(const double* x, int64_t rec_stride, int64_t ld,
                              double* resid_cov, double* E_out, int64_t ldE,
                              void* workspace, int64_t workspace_bytes, int64_t chunk, void* stream);
 
+/* Anti-aliased integer-factor FIR decimation of recordings (csrc/decimate.hip): the first stage of "decimate before
+ * fitting".  Replaces scipy.signal.decimate(x, q, ftype='fir', zero_phase=True) as MultimodalData._decimate_signals calls
+ * it (src/data_structures.py:792) and scipy.signal.resample_poly(signal, up=1, down=q) of _downsample_signal
+ * (src/eeg_alpha_ibi_ffdtf.py:404), which are one operation with different taps (firwin(20 q + 1, 1 / q) under a Hamming
+ * window / a Kaiser window with beta = 5):
+ *     y[r][c][k] = sum_{j=0}^{n_taps-1} h[j] * x[r][c][k*q + H - j],    H = (n_taps - 1) / 2,    k = 0 .. ceil(T / q) - 1,
+ * samples outside [0, T) counting as zero.  x: [n_rec][m][ld] (T samples used, addressed through rec_stride and ld as
+ * everywhere), h: [n_taps] device array (any taps; symmetry is neither required nor used), y: [n_rec][m][y_ld] through
+ * y_rec_stride, columns >= ceil(T / q) are not written.  Rows are independent: m has no upper limit here.
+ * float64; every output is one chain of FMAs over the taps in ascending j starting from +0.0, so its bits depend on its
+ * own taps and samples only -- not on the tile, the row, the batch or the strides -- and a NaN at sample s reaches exactly
+ * the outputs with |k q - s| <= H.  The reference's forward / backward fill of gaps (src/data_structures.py:779-797) is not
+ * part of this call.
+ * hmv_decimate_out_len: ceil(T / q); -1 for T < 1 or q outside 2..HMV_MAX_DECIMATE.
+ * hmv_decimate_tile: outputs per workgroup for these q and n_taps (1024, 512 or 256; -1 for arguments the call refuses).
+ * Refused before any launch: q outside 2..HMV_MAX_DECIMATE (-1), n_taps even or outside 3..HMV_MAX_DECIMATE_TAPS (-2),
+ *   T < 1, n_rec < 0 or m < 1 (-3), T > 2^40 (-7), a null pointer (-4), ld < T (-5), y_ld < ceil(T / q) (-6).  n_rec = 0
+ *   launches nothing and returns 0. */
+#define HMV_MAX_DECIMATE 32
+#define HMV_MAX_DECIMATE_TAPS 641      /* 20 * HMV_MAX_DECIMATE + 1 */
+int64_t hmv_decimate_out_len(int64_t T, int q);
+int hmv_decimate_tile(int q, int n_taps);
+int hmv_decimate_fir_f64(const double* x, int64_t rec_stride, int64_t ld, int64_t T, int64_t n_rec, int m, int q,
+                         const double* h, int n_taps, double* y, int64_t y_rec_stride, int64_t y_ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
