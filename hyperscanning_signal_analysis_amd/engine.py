@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import dataclasses
 import types
+import typing
 from typing import Callable
 
 import numpy as np
@@ -206,28 +207,59 @@ _NO_ENSEMBLE_ORDER = ("ensemble fits need an integer model order p: the referenc
                       "(channels, samples, trials) input, so there is no automatic order to reproduce")
 
 
+class _Info(typing.NamedTuple):
+    """One LAPACK-style info array of a fused C entry."""
+    name: str                   # `call` finds its pointer as info_<name>
+    text: str                   # the stage as `raise_on_info` words it
+    per_item: int | None = 1    # entries per item; None: one per frequency
+    rows: bool = False          # handed out as (items, per_item), not flat
+
+
+class _More(typing.NamedTuple):
+    """One output of a fused C entry behind `out`."""
+    name: str                   # `call` finds its pointer under this name
+    shape: Callable             # (items, m, F) -> the buffer the C entry writes
+    nan: bool = True            # check="nan" fills the failed items
+    give: Callable = lambda buf, info: buf      # (the buffer, the info arrays by name) -> its place in the result tuple
+
+
+_SPECTRA = _More("S", lambda items, m, F: (items, m, m, F, 2), give=lambda S, info: torch.view_as_complex(S))
+_BLOCK_TIME = _More("time", lambda items, m, F: (items, 4))
+_BLOCK_RED = _More("red", lambda items, m, F: (items, 2), nan=False, give=lambda red, info: (red, info["red"]))
+_YW_TEXT = "ar_coeff (Yule-Walker solve; a negative info: residual covariance not positive definite)"
+_BLOCK_INFO_RED = _Info("red", "block Granger causality (Yule-Walker solve of one block alone)", per_item=2, rows=True)
+_BLOCK_INFO_GC = _Info("gc", "block Granger causality (per-frequency factorisation)", per_item=None)
+# what `call` sees for an output or an info array its route does not have: a null pointer
+_ABSENT = dict(S=0, time=0, red=0, info_tf=0, info_red=0, info_gc=0)
+
+
+def _measure_infos(measure, yw_text):
+    """info_yw, and info_tf behind it unless the measure is GPDC, which never inverts A(f)."""
+    yw = _Info("yw", yw_text)
+    return (yw,) if measure == "gpdc" else (yw, _Info("tf", "mvar_transfer_function (inverse of A(f))", per_item=None))
+
+
 @dataclasses.dataclass(frozen=True)
 class _Route:
-    """What is particular to one fused C entry (`Engine._route`, `Engine._ensemble_route`); `Engine._sliding_call` is
-    everything the entries share.  A new entry is a new route, not a new driver."""
+    """What is particular to one fused C entry (`Engine._route`, `_ensemble_route`, `_mix_route`, `_pairs_route`,
+    `_block_route`, `_block_pairs_route`); `Engine._sliding_call` is everything the entries share.  A new entry is a new
+    route, not a new driver."""
     name: str                   # who the "bad sizes" refusal says it is (sliding_<measure>, with or without spectra)
-    measure: str                # "ffdtf", "ddtf" or "gpdc"
+    measure: str                # "ffdtf", "ddtf", "gpdc" or "block_gc"
     p: int                      # lags of the coefficient arrays: the order, or max_model_order of the automatic order
-    order_text: str             # the order as the "bad sizes" refusal words it
-    yw_text: str                # the Yule-Walker stage as `raise_on_info` words it
+    order_text: str             # the order (and what else sizes the workspace) as the "bad sizes" refusal words it
+    infos: tuple                # the `_Info` arrays, info_yw first, in the order check=True raises; None: not asked for
     validate: Callable          # (x, items): the descriptors against x, ValueError before anything is launched
     grid: Callable              # (x, items, n_items, grid, compare) -> the grid arguments of the C entry
     ws_bytes: Callable          # (chunk, m, F, n_bands, grid arguments) -> hmv_sliding_*_workspace_bytes
     call: Callable              # (the driver's pointers and sizes) -> (name of the C entry, its argument tuple)
-    spectra: bool = False       # S comes out as well (full ffDTF only)
+    more: tuple = ()            # the `_More` outputs behind `out`, in the result's order; None: not asked for
+    row: tuple | None = None    # an output row in front of the frequency axis, where not (m, m)
+    zero_infos: bool = False    # the info arrays start at zero, where the entry's kernels are not known to write them all
     automatic: bool = False     # the order is selected per window: `orders` and `crit` exist
     per_item: Callable | None = None    # (m, F, n_bands) -> bytes that size the chunk, where not ws_bytes(1, ...)
     blame: Callable | None = None       # (SingularMatrixError, items): what the route adds to the error
     m: int | None = None                # the channel count, where x does not carry it (the mix route: x is the stack)
-
-    @property
-    def has_tf(self) -> bool:           # GPDC never inverts A(f): the Yule-Walker info is all it reports
-        return self.measure != "gpdc"
 
     @property
     def bands_in_k3(self) -> bool:      # ffDTF: K3's row workers add the bands up (where `bands_in_kernel` allows)
@@ -586,6 +618,9 @@ class Engine:
         return self._aux[key]
 
     # The routes: what is particular to one fused C entry, written down once each.  `_sliding_call` is all they share.
+    # `_route` and `_ensemble_route` follow; `_mix_route`, `_pairs_route`, `_block_route` and `_block_pairs_route` stand in
+    # front of the entries they serve.  A route's `call` reads the driver's pointers by name (`a.out`, `a.info_yw`, ...);
+    # an output or info array the route does not list in `more` / `infos` reads as a null pointer (`_ABSENT`).
     def _window_grid(self, x, items, n_items, grid, compare):
         """grid = (hop, first, n_win) of the single-trial routes -> the three grid arguments of the C call."""
         if grid is None:
@@ -623,7 +658,7 @@ class Engine:
         arg-min per window and leaves that order's coefficients zero-padded to max_model_order lags; the later stages run
         at max_model_order on them."""
         lib, n, code = self.lib, int(n), _MEASURES[measure]
-        common = dict(measure=measure, spectra=spectra, grid=self._window_grid)
+        common = dict(measure=measure, more=(_SPECTRA,) if spectra else (), grid=self._window_grid)
 
         def windows(a, order):
             return (*a.x, *a.items, a.n_items, a.m, n, *order, a.f, a.F, a.fs)
@@ -634,8 +669,8 @@ class Engine:
             pmax, crit = auto_order_args(max_model_order, crit_type, n)
             return _Route(
                 name=f"sliding_{measure}", p=pmax, order_text=f"max_model_order={pmax}", automatic=True,
-                yw_text="ar_coeff (Yule-Walker solve at the automatic order; a negative info: residual covariance not "
-                        "positive definite)",
+                infos=_measure_infos(measure, "ar_coeff (Yule-Walker solve at the automatic order; a negative info: residual "
+                                              "covariance not positive definite)"),
                 validate=lambda x, items: self.check_items(x, items[0], items[1], n, pmax),
                 ws_bytes=lambda chunk, m, F, nb, g: lib.hmv_sliding_auto_workspace_bytes(code, chunk, m, pmax, F,
                                                                                            -1 if spectra else nb),
@@ -654,8 +689,8 @@ class Engine:
                 if measure == "gpdc":           # no inverse of A(f): neither info_tf nor the pivot threshold
                     return "hmv_sliding_gpdc_f64", (*front, a.ws, a.nbytes, a.chunk, a.flags, *tail(a))
                 return "hmv_sliding_ddtf_f64", (*front, a.info_tf, a.ws, a.nbytes, a.chunk, a.tau, a.flags, *tail(a))
-            return _Route(yw_text="ar_coeff (Yule-Walker solve; a negative info: residual covariance not positive definite)",
-                          ws_bytes=lambda chunk, m, F, nb, g: wsf(chunk, m, p, F, nb), call=call, **fixed)
+            return _Route(infos=_measure_infos(measure, _YW_TEXT), ws_bytes=lambda chunk, m, F, nb, g: wsf(chunk, m, p, F, nb),
+                          call=call, **fixed)
 
         def ws_bytes(chunk, m, F, nb, g):
             if spectra:
@@ -671,7 +706,7 @@ class Engine:
                                                        a.stream, a.aux)
             return "hmv_sliding_ffdtf_f64", (*windows(a, (p,)), a.out, a.ar, a.V, *work, *a.k3, a.stream, a.aux)
         # (the chunk of the full and the band form is sized by the full form's workspace: `sliding_chunk`'s rule)
-        return _Route(yw_text="ar_coeff (Yule-Walker solve)", ws_bytes=ws_bytes, call=call,
+        return _Route(infos=_measure_infos(measure, "ar_coeff (Yule-Walker solve)"), ws_bytes=ws_bytes, call=call,
                       per_item=None if spectra else lambda m, F, nb: lib.hmv_sliding_workspace_bytes(1, m, p, F), **fixed)
 
     def _ensemble_route(self, measure, n, p, trial_rec, trial_start, group_ptr, spectra=False, shuffle=None):
@@ -700,21 +735,23 @@ class Engine:
             return "hmv_sliding_ensemble_split_f64", (*front, rec_b.data_ptr(), start_b.data_ptr(), int(split), _ptr(R_base),
                                                       _ptr(item_base), a.stream, a.aux)
         return _Route(
-            name="sliding_ensemble", measure=measure, p=p, order_text=f"n={n}, p={p}", spectra=spectra, blame=blame,
-            yw_text="ar_coeff (Yule-Walker solve of the trial-averaged covariances; a negative info: residual covariance "
-                    "not positive definite)",
+            name="sliding_ensemble", measure=measure, p=p, order_text=f"n={n}, p={p}", more=(_SPECTRA,) if spectra else (),
+            blame=blame, infos=_measure_infos(measure, "ar_coeff (Yule-Walker solve of the trial-averaged covariances; a negative "
+                                                       "info: residual covariance not positive definite)"),
             validate=lambda x, items: validate_trials(x, trial_rec, trial_start, group_ptr, items[0], items[1], n, p),
             grid=lambda x, items, n_items, grid, compare: self._ensemble_grid(n_groups, items, n_items, grid, compare),
             ws_bytes=lambda chunk, m, F, nb, g: lib.hmv_sliding_ensemble_workspace_bytes(
                 code, chunk, m, n, p, F, -1 if spectra else nb, *g),
             call=call)
 
-    def _sliding_call(self, rt, x, items, freqs, fs, *, bands=None, out=None, out_S=None, return_ar=False,
+    def _sliding_call(self, rt, x, items, freqs, fs, *, bands=None, out=None, out_more=None, return_ar=False,
                       return_orders=False, check=True, chunk=None, overlap=False, flags=0, grid=None, validate=True,
                       k3_events=None):
         """The one driver of the fused entries; `rt` (a `_Route`) carries what differs between them.  Top to bottom: the
-        inputs, the empty batch, the grid, where the C call writes, chunk and workspace, the outputs, the call, the band
-        sums of the two-step form, `check`, the result `(out[, S][, bad][, ar, V, infos][, orders, crit])`."""
+        inputs, the empty batch, the grid, `out`, chunk and workspace, what else the C call writes (`buffers`), the call, the
+        band sums of the two-step form, `check`, the result `(out, *more[, bad][, ar, V, infos][, orders, crit])`.
+        freqs=None: there is no frequency grid (F = 0) and no `out`; out_more: {name: buffer} for outputs behind `out`
+        that the caller brings along."""
         flags = int(flags) | self.yw_flag
         if rt.automatic:
             no_pivoted_auto_order(bool(flags & _lib.FLAG_YW_PIVOTED), rt.name)
@@ -728,61 +765,74 @@ class Engine:
         if validate:
             rt.validate(x, items)
         n_items = int(items[0].numel())
-        f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
-        F = int(f.numel())
-        nb = 0
+        f, F, nb = None, 0, 0
+        if freqs is not None:
+            f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
+            F = int(f.numel())
         if bands is not None:
             b_lo, b_hi = self.band_tables(bands[0], bands[1], F)
             nb = int(b_lo.numel())
-        has_tf = rt.has_tf
+        row = (m, m) if rt.row is None else rt.row
         return_orders = return_orders and rt.automatic
+        per_item = [0 if i is None else F if i.per_item is None else i.per_item for i in rt.infos]
 
-        def result(out, S, bad, ar, V, info_yw, info_tf, orders, curve):
-            r = (out,) if S is None else (out, torch.view_as_complex(S))
+        def buffers():                        # what the C call writes besides `out`, in the order it is allocated
+            given = out_more or {}
+            more = [None if mo is None else given[mo.name] if given.get(mo.name) is not None
+                    else self.empty(*mo.shape(n_items, m, F)) for mo in rt.more]
+            ar = self.empty(n_items, mp, mp, rt.p) if return_ar else None
+            V = self.empty(n_items, mp, mp) if return_ar else None
+            orders = self.empty(n_items, dtype=torch.int32) if rt.automatic else None
+            curve = self.empty(n_items, rt.p) if return_orders else None
+            new_info = torch.zeros if rt.zero_infos else torch.empty
+            infos = [None if i is None else new_info(n_items * k, dtype=torch.int32, device=self.device)
+                     for i, k in zip(rt.infos, per_item)]
+            return more, ar, V, orders, curve, infos
+
+        def result(out, bad):
+            info = {i.name: buf.view(n_items, k) if i.rows else buf
+                    for i, k, buf in zip(rt.infos, per_item, infos) if i is not None}
+            r = (out, *(None if mo is None else mo.give(buf, info) for mo, buf in zip(rt.more, more)))
             if check == "mask":
                 r += (bad,)
             if return_ar:
-                r += (ar, V, (info_yw, info_tf) if has_tf else info_yw)
+                r += (ar, V, tuple(None if i is None else info[i.name] for i in rt.infos) if len(infos) > 1 else infos[0])
             if return_orders:
                 r += (orders, curve)
             return r if len(r) > 1 else r[0]
         if n_items == 0:                      # empty batch (torch gives empty tensors a null data pointer)
-            i32 = self.empty(0, dtype=torch.int32)
-            return result(self.empty(0, m, m, nb if bands is not None else F), self.empty(0, m, m, F, 2) if rt.spectra else None,
-                          torch.zeros(0, dtype=torch.bool, device=self.device), self.empty(0, mp, mp, rt.p),
-                          self.empty(0, mp, mp), i32, i32, i32, self.empty(0, rt.p))
+            more, ar, V, orders, curve, infos = buffers()
+            return result(None if freqs is None else self.empty(0, *row, nb if bands is not None else F),
+                          torch.zeros(0, dtype=torch.bool, device=self.device))
         g = rt.grid(x, items, n_items, grid, validate)
         # Two steps -- the full array (scratch), then its band sums -- where the kernels cannot add the bands up themselves:
         # an empty band set, and for the ffDTF a frequency grid that does not suit K3's row workers or the unfused norm
         two_step = bands is not None and (nb == 0 or (rt.bands_in_k3 and (
             not self.bands_in_kernel(m, F) or (flags & _lib.FLAG_UNFUSED_NORM))))
         knb = 0 if two_step else nb           # the bands the C call sums itself
-        res = self.empty(n_items, m, m, knb or F) if out is None or two_step else out
-        assert res.is_contiguous() and tuple(res.shape) == (n_items, m, m, knb or F)
-        S = None
-        if rt.spectra:
-            S = self.empty(n_items, m, m, F, 2) if out_S is None else out_S
+        res = None
+        if freqs is not None:
+            res = self.empty(n_items, *row, knb or F) if out is None or two_step else out
+            assert res.is_contiguous() and tuple(res.shape) == (n_items, *row, knb or F)
         if chunk is None:
-            per_item = rt.ws_bytes(1, m, F, knb, (0,) * len(g)) if rt.per_item is None else rt.per_item(m, F, knb)
-            chunk = self._chunk(n_items, int(per_item), self.max_workspace_bytes)
+            size = rt.ws_bytes(1, m, F, knb, (0,) * len(g)) if rt.per_item is None else rt.per_item(m, F, knb)
+            chunk = self._chunk(n_items, int(size), self.max_workspace_bytes)
         chunk = int(chunk)
         nbytes = int(rt.ws_bytes(chunk, m, F, knb, g))
         if nbytes < 0:
             raise ValueError(f"{rt.name}: bad sizes (m={m}, {rt.order_text}, F={F}, chunk={chunk})")
         ws = self._workspace(nbytes)
-        ar = self.empty(n_items, mp, mp, rt.p) if return_ar else None
-        V = self.empty(n_items, mp, mp) if return_ar else None
-        orders = self.empty(n_items, dtype=torch.int32) if rt.automatic else None
-        curve = self.empty(n_items, rt.p) if return_orders else None
-        info_yw = self.empty(n_items, dtype=torch.int32)
-        info_tf = self.empty(n_items * F, dtype=torch.int32) if has_tf else None
-        entry, args = rt.call(types.SimpleNamespace(
-            x=(x.data_ptr(), x.stride(0), x.stride(1)), T=T, items=(items[0].data_ptr(), items[1].data_ptr()),
-            n_items=n_items, m=m, f=f.data_ptr(), F=F, fs=float(fs), out=res.data_ptr(), nb=knb,
-            lo=b_lo.data_ptr() if knb else 0, hi=b_hi.data_ptr() if knb else 0, S=_ptr(S), ar=_ptr(ar), V=_ptr(V),
-            orders=_ptr(orders), curve=_ptr(curve), info_yw=info_yw.data_ptr(), info_tf=_ptr(info_tf), ws=ws.data_ptr(),
-            nbytes=nbytes, chunk=chunk, tau=self.pivot_tau, flags=int(flags), grid=g, k3=tuple(k3_events) if k3_events else (0, 0),
-            stream=self.stream(), aux=self.aux_stream().cuda_stream if overlap else 0))
+        more, ar, V, orders, curve, infos = buffers()
+        ptrs = dict(_ABSENT)
+        ptrs.update((mo.name, buf.data_ptr()) for mo, buf in zip(rt.more, more) if mo is not None)
+        ptrs.update(("info_" + i.name, buf.data_ptr()) for i, buf in zip(rt.infos, infos) if i is not None)
+        a = types.SimpleNamespace(
+            **ptrs, x=(x.data_ptr(), x.stride(0), x.stride(1)), T=T, items=(items[0].data_ptr(), items[1].data_ptr()),
+            n_items=n_items, m=m, f=_ptr(f), F=F, fs=float(fs), out=_ptr(res), nb=knb, lo=b_lo.data_ptr() if knb else 0,
+            hi=b_hi.data_ptr() if knb else 0, ar=_ptr(ar), V=_ptr(V), orders=_ptr(orders), curve=_ptr(curve), ws=ws.data_ptr(),
+            nbytes=nbytes, chunk=chunk, tau=self.pivot_tau, flags=int(flags), grid=g,
+            k3=tuple(k3_events) if k3_events else (0, 0), stream=self.stream(), aux=self.aux_stream().cuda_stream if overlap else 0)
+        entry, args = rt.call(a)
         with torch.cuda.device(self.device):
             rc = getattr(self.lib, entry)(*args)
         _lib.check(rc, entry)
@@ -793,24 +843,25 @@ class Engine:
                 res = out
         bad = None
         if check == "nan" or check == "mask":   # "mask": no host synchronisation, the caller decides what to NaN-fill
-            bad = info_yw != 0
-            if has_tf:
-                bad = bad | (info_tf.view(n_items, F) != 0).any(dim=1)
+            for k, buf in zip(per_item, infos):
+                if buf is not None:
+                    b = buf != 0 if k == 1 else (buf.view(n_items, k) != 0).any(dim=1)
+                    bad = b if bad is None else bad | b
         if check == "nan":          # keep the good windows, NaN-fill the ones whose fit or inverse was singular
             if bool(bad.any()):
-                res[bad] = float("nan")
-                if S is not None:
-                    S[bad] = float("nan")
+                for buf in (res, *(buf for mo, buf in zip(rt.more, more) if mo is not None and mo.nan)):
+                    if buf is not None:
+                        buf[bad] = float("nan")
         elif check and check != "mask":
             try:
-                self.raise_on_info(info_yw, rt.yw_text)
-                if has_tf:
-                    self.raise_on_info(info_tf, "mvar_transfer_function (inverse of A(f))", per_item=F)
+                for i, k, buf in zip(rt.infos, per_item, infos):
+                    if buf is not None:
+                        self.raise_on_info(buf, i.text, per_item=k)
             except SingularMatrixError as err:
                 if rt.blame is not None:
                     rt.blame(err, items)
                 raise
-        return result(res, S, bad, ar, V, info_yw, info_tf, orders, curve)
+        return result(res, bad)
 
     def sliding_ffdtf(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, p: int,
                       freqs, fs: float, out: torch.Tensor | None = None, return_ar: bool = False,
@@ -913,6 +964,22 @@ class Engine:
         self.raise_on_info(info_gc, "block_granger (per-frequency factorisation)", per_item=F)
         return out
 
+    def _block_route(self, n, p, split):
+        """Route of `sliding_block_granger` (`hmv_sliding_block_gc_f64`): an output row is the two directions, `time` comes
+        out behind it, the restricted fits and the per-frequency factorisation report infos of their own; the grid is that of
+        the single-trial routes; neither a second stream nor K3 (and its events) is involved."""
+        lib, n = self.lib, int(n)
+
+        def call(a):
+            return "hmv_sliding_block_gc_f64", (
+                *a.x, *a.items, a.n_items, a.m, n, p, split, a.f, a.F, a.fs, a.out, a.lo, a.hi, a.nb, a.time, a.ar, a.V, a.info_yw,
+                a.info_red, a.info_gc, a.ws, a.nbytes, a.chunk, a.flags, *a.grid, a.T, a.stream)
+        return _Route(
+            name="sliding_block_granger", measure="block_gc", p=p, order_text=f"p={p}, split={split}", row=(2,),
+            more=(_BLOCK_TIME,), infos=(_Info("yw", _YW_TEXT), _BLOCK_INFO_RED, _BLOCK_INFO_GC), zero_infos=True,
+            validate=lambda x, items: self.check_items(x, items[0], items[1], n, p), grid=self._window_grid,
+            ws_bytes=lambda chunk, m, F, nb, g: lib.hmv_block_gc_sliding_workspace_bytes(chunk, m, p, split, F, nb), call=call)
+
     def sliding_block_granger(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, p: int, freqs,
                               fs: float, *, split: int, bands=None, out=None, return_ar: bool = False, check=True,
                               chunk: int | None = None, flags: int = 0, grid=None, validate: bool = True):
@@ -932,72 +999,9 @@ class Engine:
         appends the boolean device mask, False skips the check.  return_ar appends (ar, V, (info_yw, info_red, info_gc)).
         An integer p is required: the automatic order (p=None) is not available for this call."""
         p = no_block_auto_order(p, "sliding_block_granger")
-        flags = int(flags) | self.yw_flag
-        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
-        x = x if x.stride(2) == 1 else x.contiguous()
-        n_rec, m, T = x.shape
-        split = check_block_split(split, m, "sliding_block_granger")
-        mp, n = self.pad(m), int(n)
-        items = (item_rec, item_start)
-        if validate:
-            self.check_items(x, item_rec, item_start, n, p)
-        n_items = int(item_rec.numel())
-        f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
-        F = int(f.numel())
-        nb = 0
-        if bands is not None:
-            b_lo, b_hi = self.band_tables(bands[0], bands[1], F)
-            nb = int(b_lo.numel())
-        two_step = bands is not None and nb == 0          # an empty band set: the full array, then its (empty) band sums
-        knb = 0 if two_step else nb
-        last = knb or F
-        spectral = self.empty(n_items, 2, last) if out is None or two_step else out
-        assert spectral.is_contiguous() and tuple(spectral.shape) == (n_items, 2, last)
-        time = self.empty(n_items, 4)
-        ar = self.empty(n_items, mp, mp, p) if return_ar else None
-        V = self.empty(n_items, mp, mp) if return_ar else None
-        info_yw = torch.zeros(n_items, dtype=torch.int32, device=self.device)
-        info_red = torch.zeros(n_items, 2, dtype=torch.int32, device=self.device)
-        info_gc = torch.zeros(n_items * F, dtype=torch.int32, device=self.device)
-        if n_items:
-            g = self._window_grid(x, items, n_items, grid, validate)
-            ws_bytes = self.lib.hmv_block_gc_sliding_workspace_bytes
-            if chunk is None:
-                chunk = self._chunk(n_items, int(ws_bytes(1, m, p, split, F, knb)), self.max_workspace_bytes)
-            chunk = int(chunk)
-            nbytes = int(ws_bytes(chunk, m, p, split, F, knb))
-            if nbytes < 0:
-                raise ValueError(f"sliding_block_granger: bad sizes (m={m}, p={p}, split={split}, F={F}, chunk={chunk})")
-            ws = self._workspace(nbytes)
-            with torch.cuda.device(self.device):
-                rc = self.lib.hmv_sliding_block_gc_f64(
-                    x.data_ptr(), x.stride(0), x.stride(1), item_rec.data_ptr(), item_start.data_ptr(), n_items, m, n, p, split,
-                    f.data_ptr(), F, float(fs), spectral.data_ptr(), b_lo.data_ptr() if knb else 0,
-                    b_hi.data_ptr() if knb else 0, knb, time.data_ptr(), _ptr(ar), _ptr(V), info_yw.data_ptr(),
-                    info_red.data_ptr(), info_gc.data_ptr(), ws.data_ptr(), nbytes, chunk, int(flags), *g, T, self.stream())
-            _lib.check(rc, "hmv_sliding_block_gc_f64")
-        if two_step:
-            spectral = self.band_sums(spectral, bands[0], bands[1])
-            if out is not None:
-                out.copy_(spectral)
-                spectral = out
-        r = (spectral, time)
-        if check == "nan" or check == "mask":
-            bad = (info_yw != 0) | (info_red != 0).any(dim=1) | (info_gc.view(n_items, F) != 0).any(dim=1)
-            if check == "nan":
-                if bool(bad.any()):
-                    spectral[bad] = float("nan")
-                    time[bad] = float("nan")
-            else:
-                r += (bad,)
-        elif check:
-            self.raise_on_info(info_yw, "ar_coeff (Yule-Walker solve; a negative info: residual covariance not positive "
-                                        "definite)")
-            self.raise_on_info(info_red.view(-1), "block Granger causality (Yule-Walker solve of one block alone)", per_item=2)
-            self.raise_on_info(info_gc, "block Granger causality (per-frequency factorisation)", per_item=F)
-        if return_ar:
-            r += (ar, V, (info_yw, info_red, info_gc))
-        return r
+        rt = self._block_route(n, p, check_block_split(split, x.shape[1], "sliding_block_granger"))
+        return self._sliding_call(rt, x, (item_rec, item_start), freqs, fs, bands=bands, out=out, return_ar=return_ar,
+                                  check=check, chunk=chunk, flags=flags, grid=grid, validate=validate)
 
     # ------------------------------------------------------------------ event-locked ensembles (lagcov_ensemble.hip)
     def lagcov_ensemble(self, x: torch.Tensor, trial_rec: torch.Tensor, trial_start: torch.Tensor, group_ptr: torch.Tensor,
@@ -1201,9 +1205,9 @@ class Engine:
                 code, a.x[0], E, n_win, W.data_ptr(), _ptr(scale), rows, a.m, n, p, a.f, a.F, a.fs, a.out, a.lo, a.hi, a.nb, a.S,
                 a.ar, a.V, a.info_yw, a.info_tf, a.ws, a.nbytes, a.chunk, a.tau, a.flags, a.stream, a.aux)
         return _Route(
-            name="sliding_mix", measure=measure, p=p, order_text=f"n={n}, p={p}", spectra=spectra, blame=blame, m=int(m),
-            yw_text="ar_coeff (Yule-Walker solve of the mixed covariances; a negative info: residual covariance not positive "
-                    "definite)",
+            name="sliding_mix", measure=measure, p=p, order_text=f"n={n}, p={p}", more=(_SPECTRA,) if spectra else (),
+            blame=blame, m=int(m), infos=_measure_infos(measure, "ar_coeff (Yule-Walker solve of the mixed covariances; a negative "
+                                                                 "info: residual covariance not positive definite)"),
             validate=lambda x, items: self._check_mix(x, W, scale, m), grid=lambda x, items, n_items, grid, compare: (),
             ws_bytes=lambda chunk, m_, F, nb, g: lib.hmv_mix_workspace_bytes(code, chunk, m_, p, F, -1 if spectra else nb),
             call=call)
@@ -1351,7 +1355,7 @@ class Engine:
                 _ptr(R_base), _ptr(base_a), _ptr(base_b), a.stream, a.aux)
         return _Route(
             name="sliding_pairs", measure=measure, p=p, order_text=f"n={n}, p={p}", blame=blame,
-            yw_text="ar_coeff (Yule-Walker solve; a negative info: residual covariance not positive definite)",
+            infos=_measure_infos(measure, _YW_TEXT),
             validate=lambda x, items: self._validate_pairs(x, items[0], rec_b, items[1], n, p, split, R_base, base_a, base_b),
             grid=lambda x, items, n_items, grid, compare: (),
             ws_bytes=lambda chunk, m, F, nb, g: lib.hmv_pairs_workspace_bytes(code, chunk, m, n, p, F, nb),
@@ -1398,6 +1402,28 @@ class Engine:
             per_item += 16 * m * (n // 2 + 1)
         return max(1, self.max_workspace_bytes // per_item)
 
+    def _block_pairs_route(self, n, p, split, rec_b, spec, timed, R_base, base_a, base_b, red_base, return_red):
+        """Route of `sliding_block_granger_pairs` (`hmv_sliding_block_gc_pairs_f64`): `_block_route` with the items, the
+        validation and the blame of `_pairs_route` and no grid.  Of `spectral` (spec) and `time` (timed) the one not asked
+        for is None, with its info array; `red` comes out behind them on request, and the looked-up fits ride along."""
+        lib, n, code = self.lib, int(n), (1 if spec else 0) | (2 if timed else 0)
+        red_in = (0, 0) if red_base is None else (red_base[0].data_ptr(), red_base[1].data_ptr())
+
+        def call(a):
+            return "hmv_sliding_block_gc_pairs_f64", (
+                *a.x, a.T, a.items[0], rec_b.data_ptr(), a.items[1], a.n_items, a.m, n, p, split, a.f, a.F, a.fs, a.out, a.lo, a.hi,
+                a.nb, a.time, a.ar, a.V, a.info_yw, a.info_red, a.info_gc, a.ws, a.nbytes, a.chunk, a.flags, _ptr(R_base),
+                _ptr(base_a), _ptr(base_b), code, a.red, *red_in, a.stream)
+        return _Route(
+            name="sliding_block_granger_pairs", measure="block_gc", p=p, order_text=f"n={n}, p={p}, split={split}", row=(2,),
+            more=(_BLOCK_TIME if timed else None,) + ((_BLOCK_RED,) if return_red else ()), zero_infos=True,
+            infos=(_Info("yw", _YW_TEXT), _BLOCK_INFO_RED if timed else None, _BLOCK_INFO_GC if spec else None),
+            blame=lambda err, items: self._blame_pair(err, items[0], rec_b, items[1], split),
+            validate=lambda x, items: self._validate_pairs(x, items[0], rec_b, items[1], n, p, split, R_base, base_a, base_b),
+            grid=lambda x, items, n_items, grid, compare: (),
+            ws_bytes=lambda chunk, m, F, nb, g: lib.hmv_block_gc_pairs_workspace_bytes(chunk, m, n, p, split, F, nb, code),
+            call=call)
+
     def sliding_block_granger_pairs(self, x: torch.Tensor, rec_a: torch.Tensor, rec_b: torch.Tensor, item_start: torch.Tensor,
                                     n: int, p: int, freqs, fs: float, *, split: int, want=("spectral", "time"), bands=None,
                                     R_base: torch.Tensor | None = None, base_a: torch.Tensor | None = None,
@@ -1424,91 +1450,14 @@ class Engine:
         an info that was not asked for being None.  An integer p is required."""
         p = no_block_auto_order(p, "sliding_block_granger_pairs")
         spec, timed = sg.block_want(want)
-        flags = int(flags) | self.yw_flag
-        assert x.dim() == 3 and x.dtype == torch.float64 and x.is_cuda
-        x = x if x.stride(2) == 1 else x.contiguous()
-        n_rec, m, T = x.shape
-        split = check_block_split(split, m, "sliding_block_granger_pairs")
-        mp, n = self.pad(m), int(n)
-        n_items = int(rec_a.numel())
-        if validate:
-            self._validate_pairs(x, rec_a, rec_b, item_start, n, p, split, R_base, base_a, base_b)
+        split = check_block_split(split, x.shape[1], "sliding_block_granger_pairs")
         if red_base is not None:
             self._check_red_base(red_base, R_base)
         if (red_base is not None or return_red) and not timed:
             raise ValueError("red_base and return_red belong to the time-domain values: want must include 'time'")
-        F = nb = knb = 0
-        two_step = False
-        f = spectral = info_gc = None
-        if spec:
-            f = freqs if isinstance(freqs, torch.Tensor) else self.to_device(np.asarray(freqs, dtype=np.float64))
-            F = int(f.numel())
-            if bands is not None:
-                b_lo, b_hi = self.band_tables(bands[0], bands[1], F)
-                nb = int(b_lo.numel())
-            two_step = bands is not None and nb == 0      # an empty band set: the full array, then its (empty) band sums
-            knb = 0 if two_step else nb
-            spectral = self.empty(n_items, 2, knb or F)
-            info_gc = torch.zeros(n_items * F, dtype=torch.int32, device=self.device)
-        time = self.empty(n_items, 4) if timed else None
-        info_red = torch.zeros(n_items, 2, dtype=torch.int32, device=self.device) if timed else None
-        red = self.empty(n_items, 2) if return_red else None
-        ar = self.empty(n_items, mp, mp, p) if return_ar else None
-        V = self.empty(n_items, mp, mp) if return_ar else None
-        info_yw = torch.zeros(n_items, dtype=torch.int32, device=self.device)
-        code = (1 if spec else 0) | (2 if timed else 0)
-        if n_items:
-            ws_bytes = self.lib.hmv_block_gc_pairs_workspace_bytes
-            if chunk is None:
-                chunk = self._chunk(n_items, int(ws_bytes(1, m, n, p, split, F, knb, code)), self.max_workspace_bytes)
-            chunk = int(chunk)
-            nbytes = int(ws_bytes(chunk, m, n, p, split, F, knb, code))
-            if nbytes < 0:
-                raise ValueError(f"sliding_block_granger_pairs: bad sizes (m={m}, n={n}, p={p}, split={split}, F={F}, "
-                                 f"chunk={chunk})")
-            ws = self._workspace(nbytes)
-            with torch.cuda.device(self.device):
-                rc = self.lib.hmv_sliding_block_gc_pairs_f64(
-                    x.data_ptr(), x.stride(0), x.stride(1), T, rec_a.data_ptr(), rec_b.data_ptr(), item_start.data_ptr(),
-                    n_items, m, n, p, split, _ptr(f), F, float(fs), _ptr(spectral), b_lo.data_ptr() if knb else 0,
-                    b_hi.data_ptr() if knb else 0, knb, _ptr(time), _ptr(ar), _ptr(V), info_yw.data_ptr(), _ptr(info_red),
-                    _ptr(info_gc), ws.data_ptr(), nbytes, chunk, int(flags), _ptr(R_base), _ptr(base_a), _ptr(base_b), code,
-                    _ptr(red), _ptr(red_base[0]) if red_base is not None else 0,
-                    _ptr(red_base[1]) if red_base is not None else 0, self.stream())
-            _lib.check(rc, "hmv_sliding_block_gc_pairs_f64")
-        if two_step:
-            spectral = self.band_sums(spectral, bands[0], bands[1])
-        r = (spectral, time)
-        if return_red:
-            r += ((red, info_red),)
-        if check == "nan" or check == "mask":
-            bad = info_yw != 0
-            if timed:
-                bad = bad | (info_red != 0).any(dim=1)
-            if spec:
-                bad = bad | (info_gc.view(n_items, F) != 0).any(dim=1)
-            if check == "nan":
-                if bool(bad.any()):
-                    for v in (spectral, time):
-                        if v is not None:
-                            v[bad] = float("nan")
-            else:
-                r += (bad,)
-        elif check:
-            try:
-                self.raise_on_info(info_yw, "ar_coeff (Yule-Walker solve; a negative info: residual covariance not positive "
-                                            "definite)")
-                if timed:
-                    self.raise_on_info(info_red.view(-1), "block Granger causality (Yule-Walker solve of one block alone)",
-                                       per_item=2)
-                if spec:
-                    self.raise_on_info(info_gc, "block Granger causality (per-frequency factorisation)", per_item=F)
-            except SingularMatrixError as err:
-                self._blame_pair(err, rec_a, rec_b, item_start, split)
-                raise
-        if return_ar:
-            r += (ar, V, (info_yw, info_red, info_gc))
-        return r
+        rt = self._block_pairs_route(n, p, split, rec_b, spec, timed, R_base, base_a, base_b, red_base, return_red)
+        return self._sliding_call(rt, x, (rec_a, item_start), freqs if spec else None, fs, bands=bands if spec else None,
+                                  return_ar=return_ar, check=check, chunk=chunk, flags=flags, validate=validate)
 
     def block_granger_significance(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, p: int,
                                    freqs, fs: float, bands, *, split: int, null: str, n_surrogates: int, seed,
@@ -1840,7 +1789,7 @@ class Engine:
         p=None / max_model_order / crit_type: the automatic order, as in `sliding_ffdtf`; `return_orders=True` appends
         `orders` and `crit`."""
         rt = self._route("ffdtf", n, p, max_model_order, crit_type, spectra=True)
-        return self._sliding_call(rt, x, (item_rec, item_start), freqs, fs, out=out_ff, out_S=out_S,
+        return self._sliding_call(rt, x, (item_rec, item_start), freqs, fs, out=out_ff, out_more={"S": out_S},
                                   return_orders=return_orders, check=check, chunk=chunk, overlap=True, flags=flags, grid=grid)
 
     # ------------------------------------------------------------------ FAD (fad.hip)

@@ -1,8 +1,15 @@
-"""The surrogate null tests: `Engine.sliding_significance`, `.ensemble_significance`, `.pseudo_dyad_significance` and
-`.ensemble_contrast` and the two tests of block Granger causality are the functions at the end, each taking the engine first.  What they share is here once: the
-block planners (integers in, integers out), the preamble and `NullAccumulator`, which owns the running state of
-`hmv_null_accumulate_f64` and builds every returned dict.  A test's own part is how it makes a block of surrogate values.
-The draws and the argument checks are `surrogates`; everything that wraps one C call is a method of the engine.
+"""The null tests behind `Engine.sliding_significance`, `.pseudo_dyad_significance`, `.block_granger_significance`,
+`.block_granger_pseudo_dyad_significance`, `.ensemble_significance` and `.ensemble_contrast`: the functions of those names
+below, each taking the engine first.
+
+What they share is here once: the block planners (integers in, integers out), the preamble, `NullAccumulator`, which owns the
+running state of `hmv_null_accumulate_f64` and builds every returned dict, and one loop per null -- `surrogate_null` (shift and
+phase surrogates of sliding windows) and `partner_null` (pseudo dyads).  A loop does not know what a value is: the test hands
+it the observed values as (rows, mv, mv, nv) and a closure that turns a block of surrogate items into (values, bad).  For
+the connectivity measures that is the (m, m, n_bands) band array of the fused call itself; for block Granger causality it is
+the 2 x 2 meta array of `block_meta`, taken apart again by `block_leaves`.  So a test is: check the arguments, make the
+observed call, run its loop, shape the result.  The two ensemble tests plan their blocks differently and keep loops of their
+own.  The draws and the argument checks are `surrogates`; everything that wraps one C call is a method of the engine.
 """
 from __future__ import annotations
 
@@ -13,8 +20,9 @@ from . import engine as _engine
 from . import surrogates as sg
 
 __all__ = ["sliding_plan", "ensemble_plan", "stack_plan", "window_ranges", "surrogate_blocks", "NullAccumulator",
-           "sliding_significance", "ensemble_significance", "pseudo_dyad_significance", "ensemble_contrast", "block_meta",
-           "block_leaves", "block_granger_significance", "block_granger_pseudo_dyad_significance"]
+           "surrogate_null", "partner_null", "sliding_significance", "ensemble_significance", "pseudo_dyad_significance",
+           "ensemble_contrast", "block_meta", "block_leaves", "block_granger_significance",
+           "block_granger_pseudo_dyad_significance"]
 
 STATS = ("p", "p_fwe", "null_mean", "null_std")
 
@@ -154,7 +162,82 @@ class NullAccumulator:
         return grp
 
 
-# ------------------------------------------------------------------ the four tests (docstrings: the Engine methods)
+# ------------------------------------------------------------------ the loops: one per null
+def surrogate_null(eng, acc, x, item_rec, item_start, n, null, S, seed, split, min_shift, chunk, obs, surrogate):
+    """The shift / phase null of the W windows (item_rec, item_start) of x: the draws (`shift_offsets` once up front,
+    `phase_draws` per surrogate block), the blocks of `sliding_plan(S, W, chunk)`, every block's surrogate windows written
+    out as recordings of their own, `surrogate(xs (items, m, n), item_rec, item_start) -> (values, bad)` on them, and the
+    values into `acc` against the observed rows `obs`, surrogate blocks ascending (Welford's order)."""
+    n_rec, m, T = x.shape
+    W = int(item_rec.numel())
+    rng = np.random.default_rng(seed)
+    if null == "shift":
+        d_all = torch.as_tensor(sg.shift_offsets(rng, S, n_rec, T, min_shift)).to(eng.device)
+    else:
+        spec = eng.window_spectra(x, item_rec, item_start, n)
+    Sb, Wb = sliding_plan(S, W, max(1, int(chunk)))
+    zeros = torch.zeros(Sb * Wb, dtype=torch.int64, device=eng.device)          # the largest block's descriptors
+    ar_items = torch.arange(Sb * Wb, dtype=torch.int64, device=eng.device)
+    for s0, sb, w0, w1, last in surrogate_blocks(S, Sb, window_ranges(W, Wb)):
+        if null == "phase" and w0 == 0:                                         # drawn per surrogate block
+            phi = torch.as_tensor(sg.phase_draws(rng, sb, m, n)).to(eng.device)
+        ws = slice(w0, w1)
+        if null == "shift":
+            xs = eng.surrogate_shift(x, item_rec[ws], item_start[ws], n, d_all[s0:s0 + sb], split)
+        else:
+            xs = eng.surrogate_phase(spec[ws], phi, n)
+        items = sb * (w1 - w0)
+        vals, bad = surrogate(xs.view(items, m, n), ar_items[:items], zeros[:items])
+        acc.add(obs[ws], vals, bad, ws, sb, last)
+
+
+def dyad_items(eng, x, item_start, n, p):
+    """x (D, m, T), the W windows common to the dyads -> (dy, starts): item (d, w) = d * W + w, checked against x."""
+    D, W = int(x.shape[0]), int(item_start.numel())
+    dy = torch.arange(D, dtype=torch.int64, device=eng.device).repeat_interleave(W)
+    starts = item_start.repeat(D) if isinstance(item_start, torch.Tensor) else item_start
+    eng.check_items(x, dy, starts, n, p)
+    return dy, starts
+
+
+def partner_null(eng, acc, x, dy, starts, n, p, partners, chunk, obs, obs_bad, surrogate):
+    """The pseudo-dyad null of the N = D W items (dy, starts): K1 over the real windows for the within-participant blocks,
+    then per derangement `surrogate(block, rec_b, base, out) -> bad` on blocks of at most `chunk` items -- `out` (block, mv,
+    mv, nv) receives the values of A of dyad dy with B of dyad rec_b, `base` is R_base / base_a / base_b of the block --,
+    the A- and the B-anchored value of every dyad into `acc` against `obs`, and the mean over the dyads aside.  -> the group
+    dict of `NullAccumulator.group`."""
+    N, mv, _, nv = obs.shape
+    S, D = partners.shape
+    W = N // D
+    i64 = dict(dtype=torch.int64, device=eng.device)
+    # (K1 over the D W real windows a second time -- the observed fused call does not hand its R out; a few per cent of it)
+    R_base = eng.lagcov(x, dy, starts, n, p)
+    base_a = torch.arange(N, **i64)
+    wrep = torch.arange(W, **i64).repeat(D)
+    blk = N if chunk is None else max(1, min(N, int(chunk)))
+    gmean = eng.empty(S, W, mv, mv, nv)
+    gbad = torch.empty(S, W, dtype=torch.bool, device=eng.device)
+    both = eng.empty(2, N, mv, mv, nv)                                 # the two surrogates one s gives every dyad
+    both_bad = torch.empty(2, N, dtype=torch.bool, device=eng.device)
+    for s in range(S):
+        pi = torch.as_tensor(partners[s]).to(eng.device)
+        inv = torch.empty_like(pi)
+        inv[pi] = torch.arange(D, **i64)
+        rec_b = pi[dy].contiguous()
+        base_b = (rec_b * W + wrep).contiguous()
+        for i0, i1 in window_ranges(N, blk):
+            sl = slice(i0, i1)
+            both_bad[0, sl] = surrogate(sl, rec_b[sl], dict(R_base=R_base, base_a=base_a[sl], base_b=base_b[sl]), both[0, sl])
+        # whole surrogates only: the B-anchored value of dyad d is the item of dyad pi^-1(d), wherever its block was
+        both[1] = both[0].view(D, W, mv, mv, nv)[inv].view(N, mv, mv, nv)
+        both_bad[1] = both_bad[0].view(D, W)[inv].view(N)
+        acc.add(obs, both.view(2 * N, mv, mv, nv), both_bad.view(2 * N), slice(0, N), 2, s == S - 1)
+        gmean[s] = both[0].view(D, W, mv, mv, nv).mean(dim=0)
+        gbad[s] = both_bad[0].view(D, W).any(dim=0)
+    return acc.group(obs.view(D, W, mv, mv, nv).mean(dim=0), gmean, gbad, S, obs_bad)
+
+
+# ------------------------------------------------------------------ the tests (docstrings: the Engine methods)
 def sliding_significance(eng, x, item_rec, item_start, n, p, freqs, fs, bands, *, measure, null, n_surrogates, seed, split=None,
                          min_shift=None, check=True, chunk=None, grid=None):
     _engine.no_auto_order(p, "sliding_significance")
@@ -176,27 +259,9 @@ def sliding_significance(eng, x, item_rec, item_start, n, p, freqs, fs, bands, *
     if W == 0:
         return acc.empty((0,))
     obs, obs_bad = observed_run(lambda c: run(x, item_rec, item_start, n, p, f, fs, bands=(lo, hi), check=c, grid=grid), check)
-    rng = np.random.default_rng(seed)
-    if null == "shift":
-        d_all = torch.as_tensor(sg.shift_offsets(rng, S, n_rec, T, min_shift)).to(eng.device)
-    else:
-        spec = eng.window_spectra(x, item_rec, item_start, n)
-    chunk = eng.significance_chunk(measure, null, W, m, n, p, F, nb) if chunk is None else max(1, int(chunk))
-    Sb, Wb = sliding_plan(S, W, chunk)
-    zeros = torch.zeros(Sb * Wb, dtype=torch.int64, device=eng.device)          # the largest block's descriptors
-    ar_items = torch.arange(Sb * Wb, dtype=torch.int64, device=eng.device)
-    for s0, sb, w0, w1, last in surrogate_blocks(S, Sb, window_ranges(W, Wb)):
-        if null == "phase" and w0 == 0:                                         # drawn per surrogate block
-            phi = torch.as_tensor(sg.phase_draws(rng, sb, m, n)).to(eng.device)
-        ws = slice(w0, w1)
-        if null == "shift":
-            xs = eng.surrogate_shift(x, item_rec[ws], item_start[ws], n, d_all[s0:s0 + sb], split)
-        else:
-            xs = eng.surrogate_phase(spec[ws], phi, n)
-        items = sb * (w1 - w0)
-        vals, bad = run(xs.view(items, m, n), ar_items[:items], zeros[:items], n, p, f, fs, bands=(lo, hi), check="mask",
-                        validate=False)
-        acc.add(obs[ws], vals, bad, ws, sb, last)
+    surrogate_null(eng, acc, x, item_rec, item_start, n, null, S, seed, split, min_shift,
+                   eng.significance_chunk(measure, null, W, m, n, p, F, nb) if chunk is None else chunk, obs,
+                   lambda xs, rec, st: run(xs, rec, st, n, p, f, fs, bands=(lo, hi), check="mask", validate=False))
     return acc.result((W,), obs, obs_bad)
 
 
@@ -364,48 +429,20 @@ def pseudo_dyad_significance(eng, x, item_start, n, p, freqs, fs, bands, *, meas
     x = device_x(x)
     eng.pad(m)
     W = int(item_start.numel())
-    i64 = dict(dtype=torch.int64, device=eng.device)
-    dy = torch.arange(D, **i64).repeat_interleave(W)                  # item (d, w) = d * W + w: its dyad ...
-    starts = item_start.repeat(D) if isinstance(item_start, torch.Tensor) else item_start
-    eng.check_items(x, dy, starts, n, p)
+    dy, starts = dyad_items(eng, x, item_start, n, p)
     f, F, lo, hi, nb, tested_h, tested = prepare(eng, freqs, bands, "pseudo_dyad_significance", m, "shift", split)
     partners = sg.partner_derangements(None if S is None else np.random.default_rng(seed), S, D)
-    S = int(partners.shape[0])
-    N = D * W
-    acc = NullAccumulator(eng, N, m, nb, tested_h, tested)
+    acc = NullAccumulator(eng, D * W, m, nb, tested_h, tested)
     partners_out = torch.as_tensor(partners).to(eng.device)
     if W == 0:
         return dict(acc.empty((D, 0), group=True), partners=partners_out)
     run = {"ffdtf": eng.sliding_ffdtf, "ddtf": eng.sliding_ddtf, "gpdc": eng.sliding_gpdc}[measure]
     obs, obs_bad = observed_run(lambda c: run(x, dy, starts, n, p, f, fs, bands=(lo, hi), check=c, validate=False), check)
-    # (K1 over the D W real windows a second time -- the fused call above does not hand its R out; a few per cent of it)
-    R_base = eng.lagcov(x, dy, starts, n, p)
-    base_a = torch.arange(N, **i64)
-    wrep = torch.arange(W, **i64).repeat(D)
-    blk = N if chunk is None else max(1, min(N, int(chunk)))
-    gmean = eng.empty(S, W, m, m, nb)
-    gbad = torch.empty(S, W, dtype=torch.bool, device=eng.device)
-    both = eng.empty(2, N, m, m, nb)                                   # the two surrogates one s gives every dyad
-    both_bad = torch.empty(2, N, dtype=torch.bool, device=eng.device)
-    for s in range(S):
-        pi = torch.as_tensor(partners[s]).to(eng.device)
-        inv = torch.empty_like(pi)
-        inv[pi] = torch.arange(D, **i64)
-        rec_b = pi[dy].contiguous()
-        base_b = (rec_b * W + wrep).contiguous()
-        for i0, i1 in window_ranges(N, blk):
-            sl = slice(i0, i1)
-            _, bad = eng.sliding_pairs(x, dy[sl], rec_b[sl], starts[sl], n, p, f, fs, measure=measure, split=split,
-                                       bands=(lo, hi), R_base=R_base, base_a=base_a[sl], base_b=base_b[sl],
-                                       out=both[0, sl], check="mask", validate=False)
-            both_bad[0, sl] = bad
-        # whole surrogates only: the B-anchored value of dyad d is the item of dyad pi^-1(d), wherever its block was
-        both[1] = both[0].view(D, W, m, m, nb)[inv].view(N, m, m, nb)
-        both_bad[1] = both_bad[0].view(D, W)[inv].view(N)
-        acc.add(obs, both.view(2 * N, m, m, nb), both_bad.view(2 * N), slice(0, N), 2, s == S - 1)
-        gmean[s] = both[0].view(D, W, m, m, nb).mean(dim=0)
-        gbad[s] = both_bad[0].view(D, W).any(dim=0)
-    group = acc.group(obs.view(D, W, m, m, nb).mean(dim=0), gmean, gbad, S, obs_bad)
+
+    def surrogate(sl, rec_b, base, out):            # the fused call writes the block's values where they belong
+        return eng.sliding_pairs(x, dy[sl], rec_b, starts[sl], n, p, f, fs, measure=measure, split=split, bands=(lo, hi), out=out,
+                                 check="mask", validate=False, **base)[1]
+    group = partner_null(eng, acc, x, dy, starts, n, p, partners, chunk, obs, obs_bad, surrogate)
     return dict(acc.result((D, W), obs, obs_bad), group=group, partners=partners_out)
 
 
@@ -436,22 +473,27 @@ def block_leaves(res, values):
     return out
 
 
-def _block_prepare(eng, freqs, bands, values, who):
-    """-> want, f, bands (lo, hi) or None, nv, tested_h, tested for the 2 x 2 meta array."""
+def _block_test(eng, freqs, bands, values, who, N):
+    """What the two block tests share around their loops -> (acc over N rows of the 2 x 2 meta array; the keywords of
+    `sliding_block_granger_pairs` for `values`; f; finish(res, time, obs_bad, lead, group=None, **extra) -> the test's dict)."""
     tested_h = sg.tested_mask(2, "phase", 0)                         # the off-diagonal: the two directions
     tested = torch.as_tensor(tested_h.astype(np.uint8)).to(eng.device)
-    timed = "time" in values
-    if "bands" not in values:
-        return ("time",), None, None, 1, tested_h, tested
-    f, F, lo, hi, nb, _, _ = prepare(eng, freqs, bands, who, 2, "phase", 0)
-    return (("spectral", "time") if timed else ("spectral",)), f, (lo, hi), nb + int(timed), tested_h, tested
+    f, bins, nv, want = None, None, 1, ("time",)
+    if "bands" in values:
+        f, _, lo, hi, nb, _, _ = prepare(eng, freqs, bands, who, 2, "phase", 0)
+        bins, nv, want = (lo, hi), nb + int("time" in values), ("spectral", "time") if "time" in values else ("spectral",)
+    acc = NullAccumulator(eng, N, 2, nv, tested_h, tested)
 
-
-def _block_observed_time(time, obs_bad, lead, failed):
-    t = time.view(*lead, 4)
-    if failed:
-        t[obs_bad.view(lead)] = float("nan")
-    return t
+    def finish(res, time, obs_bad, lead, group=None, **extra):
+        out = dict(block_leaves(res, values), n_valid=res["n_valid"], **extra)
+        if group is not None:
+            out["group"] = dict(block_leaves(group, values), n_valid=group["n_valid"])
+        if "time" in values:
+            out["observed_time"] = time.view(*lead, 4)
+            if acc.failed(obs_bad):
+                out["observed_time"][obs_bad.view(lead)] = float("nan")
+        return out
+    return acc, dict(want=want, bands=bins, validate=False), f, finish
 
 
 def block_granger_significance(eng, x, item_rec, item_start, n, p, freqs, fs, bands, *, split, null, n_surrogates, seed,
@@ -464,44 +506,24 @@ def block_granger_significance(eng, x, item_rec, item_start, n, p, freqs, fs, ba
     eng.pad(m)
     eng.check_items(x, item_rec, item_start, n, p)
     W = int(item_rec.numel())
-    want, f, bins, nv, tested_h, tested = _block_prepare(eng, freqs, bands, values, "block_granger_significance")
-    acc = NullAccumulator(eng, W, 2, nv, tested_h, tested)
-    kw = dict(split=split, want=want, bands=bins, validate=False)
-
-    def finish(res, time, obs_bad):
-        out = dict(block_leaves(res, values), n_valid=res["n_valid"])
-        if "time" in values:
-            out["observed_time"] = _block_observed_time(time, obs_bad, (W,), acc.failed(obs_bad))
-        return out
+    acc, kw, f, finish = _block_test(eng, freqs, bands, values, "block_granger_significance", W)
     if W == 0:
-        return finish(acc.empty((0,)), eng.empty(0, 4), None)
-    obs = eng.sliding_block_granger_pairs(x, item_rec, item_rec, item_start, n, p, f, fs,
-                                          check=True if check is True else "mask", **kw)
+        return finish(acc.empty((0,)), eng.empty(0, 4), None, (0,))
+
+    def pairs(x, rec, st, **more):                  # the recording with itself: rec_b = rec_a
+        return eng.sliding_block_granger_pairs(x, rec, rec, st, n, p, f, fs, split=split, **kw, **more)
+    obs = pairs(x, item_rec, item_start, check=True if check is True else "mask")
     obs_bad = None if check is True else obs[2]
     obs_meta = block_meta(obs[1], obs[0])
-    rng = np.random.default_rng(seed)
-    if null == "shift":
-        d_all = torch.as_tensor(sg.shift_offsets(rng, S, n_rec, T, min_shift)).to(eng.device)
-    else:
-        spec = eng.window_spectra(x, item_rec, item_start, n)
-    F, nb = (0, 0) if f is None else (int(f.numel()), len(bins[0]))
-    chunk = eng.block_significance_chunk(null, m, n, p, split, F, nb, want) if chunk is None else max(1, int(chunk))
-    Sb, Wb = sliding_plan(S, W, chunk)
-    zeros = torch.zeros(Sb * Wb, dtype=torch.int64, device=eng.device)          # the largest block's descriptors
-    ar_items = torch.arange(Sb * Wb, dtype=torch.int64, device=eng.device)
-    for s0, sb, w0, w1, last in surrogate_blocks(S, Sb, window_ranges(W, Wb)):
-        if null == "phase" and w0 == 0:                                         # drawn per surrogate block
-            phi = torch.as_tensor(sg.phase_draws(rng, sb, m, n)).to(eng.device)
-        ws = slice(w0, w1)
-        if null == "shift":
-            xs = eng.surrogate_shift(x, item_rec[ws], item_start[ws], n, d_all[s0:s0 + sb], split)
-        else:
-            xs = eng.surrogate_phase(spec[ws], phi, n)
-        items = sb * (w1 - w0)
-        sp, tm, bad = eng.sliding_block_granger_pairs(xs.view(items, m, n), ar_items[:items], ar_items[:items], zeros[:items],
-                                                      n, p, f, fs, check="mask", **kw)
-        acc.add(obs_meta[ws], block_meta(tm, sp), bad, ws, sb, last)
-    return finish(acc.result((W,), obs_meta, obs_bad), obs[1], obs_bad)
+
+    def surrogate(xs, rec, st):
+        sp, tm, bad = pairs(xs, rec, st, check="mask")
+        return block_meta(tm, sp), bad
+    if chunk is None:
+        F, nb = (0, 0) if f is None else (int(f.numel()), len(kw["bands"][0]))
+        chunk = eng.block_significance_chunk(null, m, n, p, split, F, nb, kw["want"])
+    surrogate_null(eng, acc, x, item_rec, item_start, n, null, S, seed, split, min_shift, chunk, obs_meta, surrogate)
+    return finish(acc.result((W,), obs_meta, obs_bad), obs[1], obs_bad, (W,))
 
 
 def block_granger_pseudo_dyad_significance(eng, x, item_start, n, p, freqs, fs, bands, *, split, n_surrogates=None, seed=None,
@@ -513,61 +535,25 @@ def block_granger_pseudo_dyad_significance(eng, x, item_start, n, p, freqs, fs, 
     x = device_x(x)
     eng.pad(m)
     W = int(item_start.numel())
-    i64 = dict(dtype=torch.int64, device=eng.device)
-    dy = torch.arange(D, **i64).repeat_interleave(W)                  # item (d, w) = d * W + w: its dyad ...
-    starts = item_start.repeat(D) if isinstance(item_start, torch.Tensor) else item_start
-    eng.check_items(x, dy, starts, n, p)
-    want, f, bins, nv, tested_h, tested = _block_prepare(eng, freqs, bands, values, "block_granger_pseudo_dyad_significance")
+    dy, starts = dyad_items(eng, x, item_start, n, p)
+    acc, kw, f, finish = _block_test(eng, freqs, bands, values, "block_granger_pseudo_dyad_significance", D * W)
     timed = "time" in values
     partners = sg.partner_derangements(None if S is None else np.random.default_rng(seed), S, D)
-    S = int(partners.shape[0])
-    N = D * W
-    acc = NullAccumulator(eng, N, 2, nv, tested_h, tested)
     partners_out = torch.as_tensor(partners).to(eng.device)
-    kw = dict(split=split, want=want, bands=bins, validate=False)
-
-    def finish(res, time, obs_bad):
-        grp = res.pop("group")
-        out = dict(block_leaves(res, values), n_valid=res["n_valid"], partners=partners_out,
-                   group=dict(block_leaves(grp, values), n_valid=grp["n_valid"]))
-        if timed:
-            out["observed_time"] = _block_observed_time(time, obs_bad, (D, W), acc.failed(obs_bad))
-        return out
     if W == 0:
-        return finish(acc.empty((D, 0), group=True), eng.empty(0, 4), None)
+        res = acc.empty((D, 0), group=True)
+        return finish(res, eng.empty(0, 4), None, (D, 0), group=res.pop("group"), partners=partners_out)
     # the observed dyads through the same entry (rec_b = rec_a), which also hands out the restricted fits' log-determinants
-    obs = eng.sliding_block_granger_pairs(x, dy, dy, starts, n, p, f, fs, return_red=timed,
+    obs = eng.sliding_block_granger_pairs(x, dy, dy, starts, n, p, f, fs, split=split, return_red=timed,
                                           check=True if check is True else "mask", **kw)
     obs_bad = None if check is True else obs[-1]
     red = obs[2] if timed else None
     obs_meta = block_meta(obs[1], obs[0])
-    # (K1 over the D W real windows a second time -- the fused call above does not hand its R out; a few per cent of it)
-    R_base = eng.lagcov(x, dy, starts, n, p)
-    base_a = torch.arange(N, **i64)
-    wrep = torch.arange(W, **i64).repeat(D)
-    blk = N if chunk is None else max(1, min(N, int(chunk)))
-    gmean = eng.empty(S, W, 2, 2, nv)
-    gbad = torch.empty(S, W, dtype=torch.bool, device=eng.device)
-    both = eng.empty(2, N, 2, 2, nv)                                  # the two surrogates one s gives every dyad
-    both_bad = torch.empty(2, N, dtype=torch.bool, device=eng.device)
-    for s in range(S):
-        pi = torch.as_tensor(partners[s]).to(eng.device)
-        inv = torch.empty_like(pi)
-        inv[pi] = torch.arange(D, **i64)
-        rec_b = pi[dy].contiguous()
-        base_b = (rec_b * W + wrep).contiguous()
-        for i0, i1 in window_ranges(N, blk):
-            sl = slice(i0, i1)
-            sp, tm, bad = eng.sliding_block_granger_pairs(x, dy[sl], rec_b[sl], starts[sl], n, p, f, fs, R_base=R_base,
-                                                          base_a=base_a[sl], base_b=base_b[sl], red_base=red, check="mask",
-                                                          **kw)
-            both[0, sl] = block_meta(tm, sp)
-            both_bad[0, sl] = bad
-        # whole surrogates only: the B-anchored value of dyad d is the item of dyad pi^-1(d), wherever its block was
-        both[1] = both[0].view(D, W, 2, 2, nv)[inv].view(N, 2, 2, nv)
-        both_bad[1] = both_bad[0].view(D, W)[inv].view(N)
-        acc.add(obs_meta, both.view(2 * N, 2, 2, nv), both_bad.view(2 * N), slice(0, N), 2, s == S - 1)
-        gmean[s] = both[0].view(D, W, 2, 2, nv).mean(dim=0)
-        gbad[s] = both_bad[0].view(D, W).any(dim=0)
-    group = acc.group(obs_meta.view(D, W, 2, 2, nv).mean(dim=0), gmean, gbad, S, obs_bad)
-    return finish(dict(acc.result((D, W), obs_meta, obs_bad), group=group), obs[1], obs_bad)
+
+    def surrogate(sl, rec_b, base, out):
+        sp, tm, bad = eng.sliding_block_granger_pairs(x, dy[sl], rec_b, starts[sl], n, p, f, fs, split=split, red_base=red,
+                                                      check="mask", **kw, **base)
+        out[:] = block_meta(tm, sp)
+        return bad
+    group = partner_null(eng, acc, x, dy, starts, n, p, partners, chunk, obs_meta, obs_bad, surrogate)
+    return finish(acc.result((D, W), obs_meta, obs_bad), obs[1], obs_bad, (D, W), group=group, partners=partners_out)
