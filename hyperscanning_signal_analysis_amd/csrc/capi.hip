@@ -15,6 +15,11 @@ int fail(int code, const char* msg) {
   snprintf(g_err, sizeof(g_err), "%s", msg);
   return code;
 }
+// a refusal in the words of the entry `who`: the one place where "<entry>: <what is wrong>" is put together
+int refuse(const char* who, int code, const char* msg) {
+  snprintf(g_err, sizeof(g_err), "%s: %s", who, msg);
+  return code;
+}
 int pad_of(int m) { return (m < 1 || m > HMV_MAX_CHANNELS) ? -1 : ((m + 15) / 16) * 16; }
 inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
@@ -210,15 +215,10 @@ namespace {
 // what the two split entries refuse about their five extra arguments; 0 when they are fine
 int ens_split_check(const char* who, int m, const int64_t* trial_rec_b, const int64_t* trial_start_b, int split,
                     const double* R_base, const int64_t* item_base) {
-  char buf[160];
-  const char* msg = nullptr;
-  int code = -4;
-  if (split < 1 || split >= m) { code = -5; msg = "split must be in 1..m-1"; }
-  else if (!trial_rec_b || !trial_start_b) msg = "null pointer (second trial table)";
-  else if ((R_base != nullptr) != (item_base != nullptr)) msg = "R_base and item_base go together";
-  if (!msg) return 0;
-  snprintf(buf, sizeof(buf), "%s: %s", who, msg);
-  return fail(code, buf);
+  if (split < 1 || split >= m) return refuse(who, -5, "split must be in 1..m-1");
+  if (!trial_rec_b || !trial_start_b) return refuse(who, -4, "null pointer (second trial table)");
+  if ((R_base != nullptr) != (item_base != nullptr)) return refuse(who, -4, "R_base and item_base go together");
+  return 0;
 }
 }  // namespace
 
@@ -249,16 +249,11 @@ namespace {
 // what the two pair entries refuse about their extra arguments; 0 when they are fine
 int pairs_check(const char* who, int m, const int64_t* rec_b, int split, const double* R_base, const int64_t* base_a,
                 const int64_t* base_b) {
-  char buf[160];
-  const char* msg = nullptr;
-  int code = -4;
-  if (split < 1 || split >= m) { code = -5; msg = "split must be in 1..m-1"; }
-  else if (!rec_b) msg = "null pointer (rec_b)";
-  else if ((R_base != nullptr) != (base_a != nullptr) || (R_base != nullptr) != (base_b != nullptr))
-    msg = "R_base, base_a and base_b go together";
-  if (!msg) return 0;
-  snprintf(buf, sizeof(buf), "%s: %s", who, msg);
-  return fail(code, buf);
+  if (split < 1 || split >= m) return refuse(who, -5, "split must be in 1..m-1");
+  if (!rec_b) return refuse(who, -4, "null pointer (rec_b)");
+  if ((R_base != nullptr) != (base_a != nullptr) || (R_base != nullptr) != (base_b != nullptr))
+    return refuse(who, -4, "R_base, base_a and base_b go together");
+  return 0;
 }
 // Pairs of recordings in place of single windows (hmv_sliding_pairs_f64): item_rec / item_start of sliding_impl carry
 // rec_a / item_start, the channels >= split are read from recording rec_b, and only K1 differs (lagcov_pairs_kernel).
@@ -299,6 +294,18 @@ int hmv_lagcov_pairs_f64(const double* x, int64_t rec_stride, int64_t ld, int64_
   return hmv::launch_lagcov_pairs(pairs_args(in, pairs, 0, n_items, R), mp, S(stream));
 }
 
+namespace {
+// K2's arguments as every caller in this file builds them: the solver form and the pivoted fallback from the caller's flags
+hmv::YwArgs yw_args(const double* R, int64_t n_items, int m, int p, double* ws, double* ar, double* V, int32_t* info,
+                    int64_t flags) {
+  hmv::YwArgs a{};
+  a.R = R; a.n_items = n_items; a.m = m; a.p = p; a.ws = ws; a.ar = ar; a.V = V; a.info = info;
+  a.tiled = (flags & HMV_FLAG_YW_TILED) ? 1 : ((flags & HMV_FLAG_YW_ONE_LAUNCH) ? 0 : -1);
+  a.pivoted = (flags & HMV_FLAG_YW_PIVOTED) ? 1 : 0;
+  return a;
+}
+}  // namespace
+
 int hmv_yw_solve_f64(const double* R, int64_t n_items, int m, int p, double* ws, double* ar, double* V,
                      double* vq_logdet, int32_t* info, int64_t flags, void* stream) {
   const int mp = pad_of(m);
@@ -307,10 +314,8 @@ int hmv_yw_solve_f64(const double* R, int64_t n_items, int m, int p, double* ws,
   if (!R || !ws || !ar || !V || !info || n_items < 0) return fail(-4, "hmv_yw_solve_f64: null pointer");
   if (vq_logdet && ((flags & HMV_FLAG_YW_PIVOTED) || hmv::tuning(HMV_TUNE_YW_FORM) == 5))
     return fail(-6, "hmv_yw_solve_f64: the pivoted LU gives no criterion curve (vq_logdet must be NULL)");
-  hmv::YwArgs a{};
-  a.R = R; a.n_items = n_items; a.m = m; a.p = p; a.ws = ws; a.ar = ar; a.V = V;
-  a.Vq_logdet = vq_logdet; a.info = info; a.tiled = (flags & HMV_FLAG_YW_TILED) ? 1 : ((flags & HMV_FLAG_YW_ONE_LAUNCH) ? 0 : -1);
-  a.pivoted = (flags & HMV_FLAG_YW_PIVOTED) ? 1 : 0;
+  hmv::YwArgs a = yw_args(R, n_items, m, p, ws, ar, V, info, flags);
+  a.Vq_logdet = vq_logdet;
   return hmv::launch_yw(a, mp, S(stream));
 }
 
@@ -318,6 +323,12 @@ namespace {
 // c of the criterion's penalty c q m^2 / n (mtmvar.py:580-587); crit as in hmv_fad_f64: 0 AIC, 1 HQ, 2 SC
 double crit_factor(int crit, int n) {
   return crit == 0 ? 2.0 : (crit == 1 ? 2.0 * log(log((double)n)) : log((double)n));
+}
+// the selection half of launch_yw_auto's arguments (the flags that would choose another solver are refused before)
+hmv::YwAutoArgs yw_auto_args(int n, int crit, int32_t* order_out, double* crit_out) {
+  hmv::YwAutoArgs sel{};
+  sel.n = n; sel.crit_c = crit_factor(crit, n); sel.order_out = order_out; sel.crit_out = crit_out;
+  return sel;
 }
 }  // namespace
 
@@ -334,12 +345,9 @@ int hmv_yw_solve_auto_f64(const double* R, int64_t n_items, int m, int pmax, int
   if (flags & HMV_FLAG_YW_PIVOTED)
     return fail(-6, "hmv_yw_solve_auto_f64: the pivoted LU has no automatic order (no criterion curve)");
   if (!R || !ws || !ar || !V || !order_out || !info || n_items < 0) return fail(-4, "hmv_yw_solve_auto_f64: null pointer");
-  hmv::YwArgs a{};
-  a.R = R; a.n_items = n_items; a.m = m; a.p = pmax; a.ws = ws; a.ar = ar; a.V = V; a.Vq_logdet = vq_logdet; a.info = info;
-  a.tiled = -1;
-  hmv::YwAutoArgs sel{};
-  sel.n = n; sel.crit_c = crit_factor(crit, n); sel.order_out = order_out; sel.crit_out = crit_out;
-  return hmv::launch_yw_auto(a, sel, mp, S(stream));
+  hmv::YwArgs a = yw_args(R, n_items, m, pmax, ws, ar, V, info, flags);
+  a.Vq_logdet = vq_logdet;
+  return hmv::launch_yw_auto(a, yw_auto_args(n, crit, order_out, crit_out), mp, S(stream));
 }
 
 int hmv_yw_routes_i32(const double* ws, int64_t n_items, int m, int p, int32_t* route, void* stream) {
@@ -562,11 +570,7 @@ int tf_ffdtf_impl(const char* who, const double* ar, int64_t n_items, int m, int
                   int32_t* info, double pivot_tau, void* workspace, int64_t workspace_bytes, int64_t flags,
                   void* ev_k3_start, void* ev_k3_stop, void* stream, const double* yw_ws = nullptr,
                   hmv::TfSplit* k3_split = nullptr) {
-  auto failw = [&](int code, const char* msg) {
-    char buf[200];
-    snprintf(buf, sizeof(buf), "%s: %s", who, msg);
-    return fail(code, buf);
-  };
+  auto failw = [&](int code, const char* msg) { return refuse(who, code, msg); };
   const int mp = pad_of(m);
   const bool bands = (band_out != nullptr);
   if (mp < 0) return failw(-1, "channel count must be in 1..64");
@@ -790,334 +794,457 @@ struct BgcDesc {
   const double* red_base = nullptr;                 // [n_base][2]
   const int32_t* info_red_base = nullptr;           // [n_base][2]
 };
-// Everything sliding_impl is told, by name; a field left alone means "not asked for".  The exported entries below fill in
-// what they have.  `ffdtf` receives the full (m, m, F) arrays, `band_out` (with bin_lo / bin_hi / n_bands) the band sums.
-struct SlidingArgs {
-  const char* who;                                  // the entry's own name, for hmv_last_error()
-  const double* x = nullptr;
-  int64_t rec_stride = 0, ld = 0;
-  const int64_t* item_rec = nullptr;                // (ensemble: item_group)
-  const int64_t* item_start = nullptr;              // (ensemble: item_offset)
-  int64_t n_items = 0;
-  int m = 0, n = 0, p = 0;
-  const double* freqs = nullptr;
-  int F = 0;
-  double fs = 0.0;
-  double* ffdtf = nullptr;
-  double* band_out = nullptr;
-  const int32_t* bin_lo = nullptr;
-  const int32_t* bin_hi = nullptr;
-  int n_bands = 0;
-  double* S_out = nullptr;
-  double* ar_out = nullptr;
-  double* V_out = nullptr;
-  int32_t* info_yw = nullptr;
-  int32_t* info_tf = nullptr;
-  void* workspace = nullptr;
-  int64_t workspace_bytes = 0, chunk = 0;
-  double pivot_tau = 1.0;
-  int64_t flags = 0, grid_hop = 0, grid_first = 0, grid_nwin = 0, grid_T = 0;
-  void* ev_k3_start = nullptr;
-  void* ev_k3_stop = nullptr;
-  void* stream = nullptr;
-  void* aux_stream = nullptr;
-  int measure = MEAS_FFDTF;
-  int crit = -1;                                    // >= 0: automatic order, with order_out (and crit_out)
+// Everything the driver is told, in the groups the ABI passes it in; an entry hands each group over whole.
+struct Items {                                      // the samples and the windows (ensemble: item_group / item_offset in
+  const double* x;                                  // place of item_rec / item_start, pairs: rec_a / item_start; mix: none)
+  int64_t rec_stride, ld;
+  const int64_t* item_rec;
+  const int64_t* item_start;
+  int64_t n_items;
+  int m, n, p;                                      // (p: the largest order tried where the order is automatic)
+};
+struct Grid { int64_t hop, first, nwin, T; };       // the declared regular grid; hop = 0: none
+struct Spectral { const double* freqs; int F; double fs; };
+struct Output {
+  double* out;                                      // the full (m, m, F) arrays, or (bands) their band sums
+  const int32_t* bin_lo;
+  const int32_t* bin_hi;
+  int n_bands;
+  bool bands;                                       // decided by `output` below, nowhere else
+  double* S_out;                                    // the spectra beside the full ffDTF, or null
+};
+// n_bands > 0 means band sums; hmv_sliding_ffdtf_bands_f64 has no other form, whatever its n_bands
+Output output(double* out, const int32_t* bin_lo = nullptr, const int32_t* bin_hi = nullptr, int n_bands = 0,
+              bool bands_only = false, double* S_out = nullptr) {
+  return {out, bin_lo, bin_hi, n_bands, bands_only || n_bands > 0, S_out};
+}
+struct FitOut {
+  double* ar_out;
+  double* V_out;
+  int32_t* info_yw;
+  int32_t* info_tf;
+  double pivot_tau;
+};
+struct Run {
+  void* workspace;
+  int64_t workspace_bytes, chunk, flags;
+  void* stream;
+  void* aux_stream;
+  void* ev_k3_start;
+  void* ev_k3_stop;
+};
+struct OrderSel {                                   // crit >= 0: automatic order, with order_out (and crit_out)
+  int crit = -1;
   int32_t* order_out = nullptr;
   double* crit_out = nullptr;
+};
+struct SlidingArgs {
+  const char* who;                                  // the entry's own name, for hmv_last_error()
+  int measure;
+  Items it;
+  Grid grid;
+  Spectral spec;
+  Output o;
+  FitOut fit;
+  Run run;
+  OrderSel sel = {};
   const EnsDesc* ens = nullptr;
   const PairDesc* pairs = nullptr;
   const MixDesc* mix = nullptr;
-  const BgcDesc* bgc = nullptr;                     // measure == MEAS_BGC: `ffdtf` / `band_out` carry the spectral output
+  const BgcDesc* bgc = nullptr;                     // measure == MEAS_BGC: `o` carries the spectral output
 };
-// K1 of the chunk i0 .. i0 + c - 1 into R, on st: whichever form the entry's descriptors and the grid call for
-int sliding_k1(const SlidingArgs& a, int mp, bool ens_shared, bool regular, int64_t i0, int64_t c, double* R, double* Qb,
-               hipStream_t st) {
-  const K1In in{a.x, a.rec_stride, a.ld, a.item_rec, a.item_start, a.m, a.n, a.p};
-  if (a.ens) {
-    const hmv::LagcovEnsArgs ea = ens_args(in, *a.ens, i0, c, R, ens_shared ? Qb : nullptr, a.grid_hop, a.grid_nwin);
-    return a.ens->split ? hmv::launch_lagcov_ensemble_split(ea, mp, st) : hmv::launch_lagcov_ensemble(ea, mp, ens_shared, st);
-  }
-  if (a.pairs) return hmv::launch_lagcov_pairs(pairs_args(in, *a.pairs, i0, c, R), mp, st);
-  if (a.mix) {
-    hmv::LagcovMixArgs ma{};
-    ma.Rt = a.mix->Rt; ma.W = a.mix->W; ma.scale = a.mix->scale; ma.n_trials = a.mix->n_trials; ma.n_win = a.mix->n_win;
-    ma.it0 = i0; ma.n_items = c; ma.m = a.m; ma.m_pad = mp; ma.p = a.p; ma.R = R;
-    return hmv::launch_lagcov_mix(ma, st);
-  }
-  if (!regular) return hmv_lagcov_f64(a.x, a.rec_stride, a.ld, a.item_rec + i0, a.item_start + i0, c, a.m, a.n, a.p, R, st);
-  // items i0 .. i0+c-1 as runs of consecutive windows of one recording each (item = rec * grid_nwin + w)
-  const size_t stack = (size_t)(a.p + 1) * mp * mp;
-  int rc = 0;
-  for (int64_t it = i0; it < i0 + c && rc == 0;) {
-    const int64_t rec = it / a.grid_nwin, w0 = it - rec * a.grid_nwin;
-    const int64_t run = ((a.grid_nwin - w0) < (i0 + c - it)) ? (a.grid_nwin - w0) : (i0 + c - it);
-    rc = hmv_lagcov_regular_f64(a.x + rec * a.rec_stride, a.ld, a.grid_T, a.grid_first + w0 * a.grid_hop, a.grid_hop, run,
-                                a.m, a.n, a.p, R + (size_t)(it - i0) * stack, Qb, st);
-    it += run;
-  }
-  return rc;
+
+// ---- what the entries refuse ahead of the driver, once each
+// The measure-coded entries (auto, ensemble, pairs, mix): measure, n_bands and S_out -- the criterion between them where
+// the order is automatic --, and what an accepted GPDC does to the fit outputs: it inverts nothing, so it has neither
+// info_tf nor a pivot threshold.
+int measure_request(const char* who, int measure, int n_bands, const double* S_out, FitOut& fit, int crit = 0) {
+  if (measure < HMV_MEASURE_FFDTF || measure > HMV_MEASURE_GPDC)
+    return refuse(who, -4, "measure must be HMV_MEASURE_FFDTF, _DDTF or _GPDC");
+  if (crit < 0 || crit > 2) return refuse(who, -5, "criterion must be 0 (AIC), 1 (HQ) or 2 (SC)");
+  if (n_bands < 0) return refuse(who, -4, "n_bands must be >= 0");
+  if (S_out && (measure != HMV_MEASURE_FFDTF || n_bands != 0))
+    return refuse(who, -4, "spectra come with the full ffDTF only");
+  if (measure == HMV_MEASURE_GPDC) { fit.info_tf = nullptr; fit.pivot_tau = 1.0; }
+  return 0;
 }
-int sliding_impl(const SlidingArgs& a) {
+// a missing output of a batch that is not empty
+int need_output(const char* who, const void* out, int64_t n_items) {
+  return (!out && n_items != 0) ? refuse(who, -4, "null pointer / empty grid") : 0;
+}
+// The same for the entries that refuse something of their own ahead of it (ensemble, pairs, mix): only where the driver's
+// size checks would pass, so that a bad size is still refused first, as at the other entries.
+int need_output_after_sizes(const char* who, const Items& it, const void* out) {
+  const bool sizes_ok = pad_of(it.m) >= 0 && it.p >= 1 && it.p <= HMV_MAX_ORDER && it.n > it.p;
+  return sizes_ok ? need_output(who, out, it.n_items) : 0;
+}
+// n_bands = -1 to a measure-coded sizer: the full ffDTF together with S_out (one chunk of H passes through the workspace
+// between K3 and K5)
+int64_t measure_bytes(int measure, int64_t chunk, int m, int p, int F, int n_bands, int64_t q_tiles) {
+  const bool spectra = (n_bands == -1 && measure == HMV_MEASURE_FFDTF);
+  return sliding_bytes(chunk, m, p, F, spectra ? 0 : n_bands, spectra, measure, q_tiles);
+}
+
+// ---- the second stream: both of its uses fork and join through this
+// fork: st1 may start once what st0 holds is done.  join: st0 takes up again behind st1, so that the caller's stream never
+// runs ahead of work this call put on the second stream; a join that cannot be expressed as an event is made on the host.
+struct TwoStreams {
+  hipStream_t st0 = nullptr, st1 = nullptr;
+  ForkJoin* ev = nullptr;
+  int fork() const {                                // nonzero: nothing may be put on st1
+    const int hrc = (int)hipEventRecord(ev->fork, st0);
+    return hrc ? hrc : (int)hipStreamWaitEvent(st1, ev->fork, 0);
+  }
+  int record_join() const {
+    const int hrc = (int)hipEventRecord(ev->join, st1);
+    if (hrc) (void)hipStreamSynchronize(st1);
+    return hrc;
+  }
+  int wait_join(hipEvent_t join) const {
+    const int hrc = (int)hipStreamWaitEvent(st0, join, 0);
+    if (hrc) (void)hipStreamSynchronize(st1);
+    return hrc;
+  }
+  int join() const {
+    const int hrc = record_join();
+    return hrc ? hrc : wait_join(ev->join);
+  }
+  // the K2 -> K3 hand-over in two parts: st0 joins st1 unless K3's launcher already made it wait between its two launches
+  void finish(hmv::TfSplit& sp) const {
+    if (sp.join && !sp.joined) (void)wait_join(sp.join);
+    sp.joined = true;
+  }
+};
+
+// ---- the plan of a call: every refusal, in order, and everything that does not change from chunk to chunk
+struct SlidingPlan {
+  bool empty = false;                               // n_items == 0: nothing to do, nothing more was checked
+  int mp = 0;
+  size_t t = 0, ws_item = 0;                        // doubles per tile; K2 scratch doubles per window
+  bool automatic = false, bands = false, k3_bands = false, bgc_spec = false, bgc_time = false;
+  bool regular = false, ens_shared = false;         // K1: hop blocks shared between the windows of a declared grid
+  bool ldl = false, from_tiles = false;             // K2: an LDL^T form; a recursion that leaves the model in its tiles
+  bool half_split = false, k3_split = false;        // what the second stream may be used for
+  TwoStreams fj;
+  SlidingWs w{};
+  BgcWs gw{};
+  char* base = nullptr;
+  double *R = nullptr, *Qb = nullptr, *ws = nullptr, *ar = nullptr, *V = nullptr, *den = nullptr, *tw = nullptr;
+  void* tfws = nullptr;
+  int64_t tfws_bytes = 0;
+  double* at(size_t off) const { return reinterpret_cast<double*>(base + off); }        // a double array of the workspace
+  // The caller's flags as K2 takes them for `cnt` windows of padded size mpx: where the plan has an LDL^T form, the launch
+  // chain if it is asked for or chosen by shape, else the one launch
+  int64_t yw_flags(int64_t flags, int mpx, int64_t cnt) const {
+    const int64_t forms = HMV_FLAG_YW_TILED | HMV_FLAG_YW_ONE_LAUNCH;
+    const bool chain =
+        (flags & HMV_FLAG_YW_TILED) || (ldl && !(flags & HMV_FLAG_YW_ONE_LAUNCH) && hmv::yw_chain_by_shape(mpx, cnt));
+    return (flags & ~forms) | (ldl ? (chain ? HMV_FLAG_YW_TILED : HMV_FLAG_YW_ONE_LAUNCH) : 0);
+  }
+};
+int sliding_plan(const SlidingArgs& a, SlidingPlan& pl) {
+  const Items& it = a.it;
+  const int64_t flags = a.run.flags;
+  auto fail = [&](int code, const char* msg) { return refuse(a.who, code, msg); };
   // crit >= 0: automatic order (hmv_sliding_auto_f64) -- p is the largest order tried, K1 sums p + 1 lags, K2 selects every
   // window's order and leaves its coefficients zero-padded to p lags, and every later stage runs at p on those (the
   // added terms of A(f) = I - sum_k ar_k tw_k are exact zeros)
-  const bool automatic = a.crit >= 0;
-  const bool bands = (a.band_out != nullptr);
-  auto fail = [&](int code, const char* msg) {
-    const char* own = strchr(msg, ':');             // messages below are written "hmv_sliding_ffdtf_f64: ..."
-    char buf[220];
-    snprintf(buf, sizeof(buf), "%s%s", a.who, own ? own : msg);
-    return ::fail(code, buf);
-  };
-  const int mp = pad_of(a.m);
-  if (mp < 0) return fail(-1, "hmv_sliding_ffdtf_f64: channel count must be in 1..64");
-  if (a.p < 1 || a.p > HMV_MAX_ORDER) return fail(-2, "hmv_sliding_ffdtf_f64: model order must be in 1..32");
-  if (a.n <= a.p) return fail(-3, "hmv_sliding_ffdtf_f64: window shorter than the model order");
-  if (automatic && a.crit > 2) return fail(-5, "hmv_sliding_ffdtf_f64: criterion must be 0 (AIC), 1 (HQ) or 2 (SC)");
-  if (automatic && (a.flags & (HMV_FLAG_YW_TILED | HMV_FLAG_YW_ONE_LAUNCH)))
-    return fail(-6, "hmv_sliding_ffdtf_f64: the LDL^T forms of K2 have no automatic order");
-  if (automatic && (a.flags & HMV_FLAG_YW_PIVOTED))
-    return fail(-6, "hmv_sliding_ffdtf_f64: the pivoted LU has no automatic order (no criterion curve)");
+  pl.automatic = a.sel.crit >= 0;
+  pl.bands = a.o.bands;
+  pl.mp = pad_of(it.m);
+  if (pl.mp < 0) return fail(-1, "channel count must be in 1..64");
+  if (it.p < 1 || it.p > HMV_MAX_ORDER) return fail(-2, "model order must be in 1..32");
+  if (it.n <= it.p) return fail(-3, "window shorter than the model order");
+  if (pl.automatic && a.sel.crit > 2) return fail(-5, "criterion must be 0 (AIC), 1 (HQ) or 2 (SC)");
+  if (pl.automatic && (flags & (HMV_FLAG_YW_TILED | HMV_FLAG_YW_ONE_LAUNCH)))
+    return fail(-6, "the LDL^T forms of K2 have no automatic order");
+  if (pl.automatic && (flags & HMV_FLAG_YW_PIVOTED))
+    return fail(-6, "the pivoted LU has no automatic order (no criterion curve)");
   if (a.mix && (a.mix->n_trials < 1 || a.mix->n_win < 1 || a.mix->n_mix < 1))
-    return fail(-10, "hmv_sliding_ffdtf_f64: n_trials, n_win and n_mix must be >= 1");
-  if (a.n_items == 0) return 0;                                    // empty batch: nothing to do, nothing to check
-  if (automatic && !a.order_out) return fail(-4, "hmv_sliding_ffdtf_f64: null pointer / empty grid");
+    return fail(-10, "n_trials, n_win and n_mix must be >= 1");
+  if (it.n_items == 0) {                                           // empty batch: nothing to do, nothing to check
+    pl.empty = true;
+    return 0;
+  }
+  if (pl.automatic && !a.sel.order_out) return fail(-4, "null pointer / empty grid");
   if (a.mix ? (!a.mix->Rt || !a.mix->W || reinterpret_cast<uintptr_t>(a.mix->Rt) % 16 != 0)
-            : (!a.x || !a.item_rec || !a.item_start))
-    return fail(-4, "hmv_sliding_ffdtf_f64: null pointer / empty grid");
-  const bool bgc_spec = !a.bgc || (a.bgc->want & 1), bgc_time = a.bgc && (a.bgc->want & 2);   // (time alone: no frequencies)
-  if ((bgc_spec && (!a.freqs || (!a.ffdtf && !bands) || a.F < 1)) || !a.info_yw ||
-      (!a.info_tf && (a.measure == MEAS_FFDTF || a.measure == MEAS_DDTF)) || !a.workspace || a.chunk < 1)
-    return fail(-4, "hmv_sliding_ffdtf_f64: null pointer / empty grid");
-  if (bands && (!a.bin_lo || !a.bin_hi || a.n_bands < 1)) return fail(-4, "hmv_sliding_ffdtf_f64: band bins missing");
-  bool ens_shared = false;
+            : (!it.x || !it.item_rec || !it.item_start))
+    return fail(-4, "null pointer / empty grid");
+  pl.bgc_spec = !a.bgc || (a.bgc->want & 1);                       // (time alone: no frequencies)
+  pl.bgc_time = a.bgc && (a.bgc->want & 2);
+  if ((pl.bgc_spec && (!a.spec.freqs || !a.o.out || a.spec.F < 1)) || !a.fit.info_yw ||
+      (!a.fit.info_tf && (a.measure == MEAS_FFDTF || a.measure == MEAS_DDTF)) || !a.run.workspace || a.run.chunk < 1)
+    return fail(-4, "null pointer / empty grid");
+  if (pl.bands && (!a.o.bin_lo || !a.o.bin_hi || a.o.n_bands < 1)) return fail(-4, "band bins missing");
   if (a.ens) {
-    if (!a.ens->trial_rec || !a.ens->trial_start || !a.ens->group_ptr)
-      return fail(-4, "hmv_sliding_ffdtf_f64: null pointer / empty grid");
-    if (a.ens->n_groups < 1) return fail(-10, "hmv_sliding_ffdtf_f64: n_groups must be >= 1");
-    if (a.grid_hop != 0 && !ens_grid_ok(a.n_items, a.ens->n_groups, a.n, a.ld, a.ens->T, a.grid_hop, a.grid_nwin))
-      return fail(-9, "hmv_sliding_ffdtf_f64: inconsistent regular window grid");
-    ens_shared = !a.ens->split && ens_shared_form(a.n, a.p, a.grid_hop, a.flags);
+    if (!a.ens->trial_rec || !a.ens->trial_start || !a.ens->group_ptr) return fail(-4, "null pointer / empty grid");
+    if (a.ens->n_groups < 1) return fail(-10, "n_groups must be >= 1");
+    if (a.grid.hop != 0 && !ens_grid_ok(it.n_items, a.ens->n_groups, it.n, it.ld, a.ens->T, a.grid.hop, a.grid.nwin))
+      return fail(-9, "inconsistent regular window grid");
+    pl.ens_shared = !a.ens->split && ens_shared_form(it.n, it.p, a.grid.hop, flags);
   }
-  const SlidingWs w = sliding_layout(a.chunk, mp, a.p, a.F, bands, a.S_out != nullptr, a.measure,
-                                     a.ens ? (ens_shared ? ens_q_tiles(a.chunk, a.n, a.p, a.grid_hop, a.grid_nwin) : 0)
-                                           : ((a.pairs || a.mix) ? 0 : -1));
-  BgcWs gw{};
-  if (a.bgc) gw = bgc_layout(w.total, a.chunk, a.m, a.p, a.F, a.bgc->split, bands, bgc_time, bgc_spec);
-  if ((int64_t)(a.bgc ? gw.total : w.total) > a.workspace_bytes) return fail(-7, "hmv_sliding_ffdtf_f64: workspace too small");
-  // Regular grid (the caller vouches: item = rec * grid_nwin + w starts at grid_first + w * grid_hop of recording rec,
-  // recordings are grid_T samples long): K1 sums every hop block once and assembles the windows from the blocks.
-  bool regular = !a.ens && !a.pairs && !a.mix && a.grid_hop > 0 && !(a.flags & HMV_FLAG_DIRECT_LAGCOV);
-  if (regular) {
-    if (a.grid_nwin < 1 || a.grid_first < 0 || a.n_items % a.grid_nwin != 0 ||
-        a.grid_first + (a.grid_nwin - 1) * a.grid_hop + a.n > a.grid_T || a.ld < a.grid_T)
-      return fail(-9, "hmv_sliding_ffdtf_f64: inconsistent regular window grid");
-    regular = (a.n % a.grid_hop == 0) && (a.n / a.grid_hop >= 2) && (a.n / a.grid_hop <= HMV_MAX_HOPS_PER_WINDOW) &&
-              a.grid_hop > a.p;
+  const int64_t chunk = a.run.chunk;
+  pl.w = sliding_layout(chunk, pl.mp, it.p, a.spec.F, pl.bands, a.o.S_out != nullptr, a.measure,
+                        a.ens ? (pl.ens_shared ? ens_q_tiles(chunk, it.n, it.p, a.grid.hop, a.grid.nwin) : 0)
+                              : ((a.pairs || a.mix) ? 0 : -1));
+  if (a.bgc) pl.gw = bgc_layout(pl.w.total, chunk, it.m, it.p, a.spec.F, a.bgc->split, pl.bands, pl.bgc_time, pl.bgc_spec);
+  if ((int64_t)(a.bgc ? pl.gw.total : pl.w.total) > a.run.workspace_bytes) return fail(-7, "workspace too small");
+  // Regular grid (the caller vouches: item = rec * grid.nwin + w starts at grid.first + w * grid.hop of recording rec,
+  // recordings are grid.T samples long): K1 sums every hop block once and assembles the windows from the blocks.
+  pl.regular = !a.ens && !a.pairs && !a.mix && a.grid.hop > 0 && !(flags & HMV_FLAG_DIRECT_LAGCOV);
+  if (pl.regular) {
+    const Grid& g = a.grid;
+    if (g.nwin < 1 || g.first < 0 || it.n_items % g.nwin != 0 || g.first + (g.nwin - 1) * g.hop + it.n > g.T || it.ld < g.T)
+      return fail(-9, "inconsistent regular window grid");
+    pl.regular = (it.n % g.hop == 0) && (it.n / g.hop >= 2) && (it.n / g.hop <= HMV_MAX_HOPS_PER_WINDOW) && g.hop > it.p;
   }
-  // Second stream (HMV_FLAG_YW_TILED only): the tile-per-workgroup form of K2 is a chain of ~25 launches of at
-  // most a few workgroups per window that cannot fill the chip; it runs as two half-batches, one per stream,
-  // whose launches interleave on the device (fork after K1, join before K3).  The default one-launch form of K2
-  // needs none of this.  Chunk pipelining (K1/K2 of chunk c+1 under K3 of chunk c) was measured and does NOT
-  // work: K3 holds every wave slot and starves the other stream.
-  // What the default form does with the second stream is a different thing (k3_split_point, profiles/k3_split_notes.md):
-  // the work put beside K3 is the few windows of the SAME chunk that K2's last, partly filled round would make the whole
-  // chip wait for, and it is placed before K3 arrives -- forked behind K2's first part, with only the light packing kernel
-  // between the fork and K3, so its workgroups land on an almost empty chip and K3 fills in around them.  It is zero-sum
-  // in chip time like the others; what it removes is the idle tail of K2 from the critical path.  Only where nobody but
-  // K3's packing kernel reads the model (from_tiles below) and no output beyond the ffDTF is asked for.
-  hipStream_t st0 = S(a.stream), st1 = S(a.aux_stream);
-  const bool two = (a.aux_stream && a.aux_stream != a.stream);
-  const bool split = two && !(a.flags & HMV_FLAG_YW_ONE_LAUNCH);
-  const bool k3_split = two && !automatic && a.measure == MEAS_FFDTF && !a.S_out && !a.ar_out && !a.V_out &&
-                        !(a.flags & (HMV_FLAG_YW_TILED | HMV_FLAG_YW_ONE_LAUNCH));
-  ForkJoin* fj = nullptr;
-  if (split || k3_split) {
-    fj = fork_join_events();
-    if (!fj) return fail(-8, "hmv_sliding_ffdtf_f64: cannot create fork/join events");
+  // K2: the Levinson-Whittle recursion unless an LDL^T form is asked for (or HMV_TUNE_YW_FORM = 1, which picks the LDL^T
+  // form by batch shape: hmv::yw_chain_by_shape).  Nobody but K3's packing kernel reads the model when the caller does not
+  // ask for it and the measure is the ffDTF: the default recursion then leaves it in its scratch tiles, which the packing
+  // kernel reads directly (windows that the conditioning guard hands to the LDL^T re-solve come through `ar` as before).
+  const int64_t yw_form = hmv::tuning(HMV_TUNE_YW_FORM);
+  pl.ldl = (flags & (HMV_FLAG_YW_TILED | HMV_FLAG_YW_ONE_LAUNCH)) || yw_form == 1;
+  pl.from_tiles = !pl.automatic && !a.fit.ar_out && !pl.ldl && (yw_form == 0 || yw_form == 2) && a.measure == MEAS_FFDTF;
+  // Second stream, first use (the LDL^T launch chain only): that form of K2 is a chain of ~25 launches of at most a few
+  // workgroups per window that cannot fill the chip; it runs as two half-batches, one per stream, whose launches
+  // interleave on the device (fork after K1, join before K3).  The one-launch forms need none of this.  Chunk pipelining
+  // (K1/K2 of chunk c+1 under K3 of chunk c) was measured and does NOT work: K3 holds every wave slot and starves the
+  // other stream.
+  // Second use, by the default form (k3_split_point, profiles/k3_split_notes.md): the work put beside K3 is the few windows
+  // of the SAME chunk that K2's last, partly filled round would make the whole chip wait for, and it is placed before K3
+  // arrives -- forked behind K2's first part, with only the light packing kernel between the fork and K3, so its
+  // workgroups land on an almost empty chip and K3 fills in around them.  It is zero-sum in chip time like the others;
+  // what it removes is the idle tail of K2 from the critical path.  Only where nobody but K3's packing kernel reads the
+  // model (from_tiles) and no output beyond the ffDTF is asked for.
+  pl.fj.st0 = S(a.run.stream);
+  pl.fj.st1 = S(a.run.aux_stream);
+  const bool two = (a.run.aux_stream && a.run.aux_stream != a.run.stream);
+  pl.half_split = two && !(flags & HMV_FLAG_YW_ONE_LAUNCH);
+  pl.k3_split = two && !pl.automatic && a.measure == MEAS_FFDTF && !a.o.S_out && !a.fit.ar_out && !a.fit.V_out &&
+                !(flags & (HMV_FLAG_YW_TILED | HMV_FLAG_YW_ONE_LAUNCH));
+  if (pl.half_split || pl.k3_split) {
+    pl.fj.ev = fork_join_events();
+    if (!pl.fj.ev) return fail(-8, "cannot create fork/join events");
   }
+  pl.t = (size_t)pl.mp * pl.mp;
+  pl.base = static_cast<char*>(a.run.workspace);
+  pl.R = pl.at(pl.w.off_R);
+  pl.Qb = pl.at(pl.w.off_Q);
+  pl.ws = pl.at(pl.w.off_ws);
+  pl.ar = pl.at(pl.w.off_ar);
+  pl.V = pl.at(pl.w.off_V);
+  pl.tfws = pl.base + pl.w.off_tf;
+  pl.den = pl.at(pl.w.off_den);
+  pl.tw = pl.at(pl.w.off_tw);
+  pl.k3_bands = pl.bands && a.measure == MEAS_FFDTF;
+  pl.tfws_bytes = (int64_t)tf_ff_layout(chunk, pl.mp, it.p, a.spec.F, pl.k3_bands).total;
+  pl.ws_item = (size_t)hmv_yw_workspace_doubles(it.m, it.p);
+  return 0;
+}
+
+// the windows i0 .. i0 + c - 1 of the call, and where their model goes: the caller's arrays or the workspace
+struct Chunk {
+  int64_t i0, c;
+  double* ar;
+  double* V;
+  bool last;
+};
+
+// ---- K1 of a chunk into pl.R, on st0: whichever form the entry's descriptors and the grid call for
+int sliding_k1(const SlidingArgs& a, const SlidingPlan& pl, const Chunk& ch) {
+  const Items& it = a.it;
+  const int64_t i0 = ch.i0, c = ch.c;
+  hipStream_t st = pl.fj.st0;
+  const K1In in{it.x, it.rec_stride, it.ld, it.item_rec, it.item_start, it.m, it.n, it.p};
+  if (a.ens) {
+    const hmv::LagcovEnsArgs ea = ens_args(in, *a.ens, i0, c, pl.R, pl.ens_shared ? pl.Qb : nullptr, a.grid.hop, a.grid.nwin);
+    return a.ens->split ? hmv::launch_lagcov_ensemble_split(ea, pl.mp, st)
+                        : hmv::launch_lagcov_ensemble(ea, pl.mp, pl.ens_shared, st);
+  }
+  if (a.pairs) return hmv::launch_lagcov_pairs(pairs_args(in, *a.pairs, i0, c, pl.R), pl.mp, st);
+  if (a.mix) {
+    hmv::LagcovMixArgs ma{};
+    ma.Rt = a.mix->Rt; ma.W = a.mix->W; ma.scale = a.mix->scale; ma.n_trials = a.mix->n_trials; ma.n_win = a.mix->n_win;
+    ma.it0 = i0; ma.n_items = c; ma.m = it.m; ma.m_pad = pl.mp; ma.p = it.p; ma.R = pl.R;
+    return hmv::launch_lagcov_mix(ma, st);
+  }
+  if (!pl.regular)
+    return hmv_lagcov_f64(it.x, it.rec_stride, it.ld, it.item_rec + i0, it.item_start + i0, c, it.m, it.n, it.p, pl.R, st);
+  // items i0 .. i0+c-1 as runs of consecutive windows of one recording each (item = rec * grid.nwin + w)
+  const Grid& g = a.grid;
+  const size_t stack = (size_t)(it.p + 1) * pl.t;
   int rc = 0;
-  const size_t t = (size_t)mp * mp;
-  const int64_t n_chunks = (a.n_items + a.chunk - 1) / a.chunk;
-  char* base = static_cast<char*>(a.workspace);
-  double* R = reinterpret_cast<double*>(base + w.off_R);
-  double* Qb = reinterpret_cast<double*>(base + w.off_Q);
-  double* ws = reinterpret_cast<double*>(base + w.off_ws);
-  double* ar = reinterpret_cast<double*>(base + w.off_ar);
-  double* V = reinterpret_cast<double*>(base + w.off_V);
-  void* tfws = base + w.off_tf;
-  double* den = reinterpret_cast<double*>(base + w.off_den);
-  double* tw = reinterpret_cast<double*>(base + w.off_tw);
-  const bool k3_bands = bands && a.measure == MEAS_FFDTF;
-  const int64_t tfws_bytes = (int64_t)tf_ff_layout(a.chunk, mp, a.p, a.F, k3_bands).total;
-  if (bgc_spec) rc = hmv_twiddles_f64(a.freqs, a.F, a.fs, a.p, tw, st0);
-  const size_t ws_item = (size_t)hmv_yw_workspace_doubles(a.m, a.p);
-  hmv::TfSplit sp{};                         // the chunk's K2 -> K3 hand-over in two parts, if any
-  auto join_k3_split = [&]() {               // st0 joins st1 unless K3's launcher already made it wait
-    if (sp.join && !sp.joined)
-      if (hipStreamWaitEvent(st0, sp.join, 0) != hipSuccess) (void)hipStreamSynchronize(st1);
-    sp.joined = true;
-  };
-  for (int64_t ci = 0; ci < n_chunks && rc == 0; ++ci) {
-    const int64_t i0 = ci * a.chunk;
-    const int64_t c = (a.n_items - i0 < a.chunk) ? (a.n_items - i0) : a.chunk;
-    double* ar_c = a.ar_out ? a.ar_out + (size_t)i0 * t * a.p : ar;
-    double* V_c = a.V_out ? a.V_out + (size_t)i0 * t : V;
-    rc = sliding_k1(a, mp, ens_shared, regular, i0, c, R, Qb, st0);
-    if (rc) break;
-    if (automatic) {
-      hmv::YwArgs ya{};
-      ya.R = R; ya.n_items = c; ya.m = a.m; ya.p = a.p; ya.ws = ws; ya.ar = ar_c; ya.V = V_c; ya.info = a.info_yw + i0;
-      ya.tiled = -1;
-      hmv::YwAutoArgs sel{};
-      sel.n = a.n; sel.crit_c = crit_factor(a.crit, a.n); sel.order_out = a.order_out + i0;
-      sel.crit_out = a.crit_out ? a.crit_out + (size_t)i0 * a.p : nullptr;
-      rc = hmv::launch_yw_auto(ya, sel, mp, st0);
-      if (rc) break;
-    }
-    // the tiled form of K2 (asked for, or chosen for a large 64-channel chunk) as two half-batches
-    // K2: the Levinson-Whittle recursion unless an LDL^T form is asked for (or HMV_TUNE_YW_FORM = 1, which picks the
-    // LDL^T form by batch shape as before: the launch chain for large 64-channel chunks)
-    const bool ldl = (a.flags & (HMV_FLAG_YW_TILED | HMV_FLAG_YW_ONE_LAUNCH)) || hmv::tuning(HMV_TUNE_YW_FORM) == 1;
-    const bool tiled = (a.flags & HMV_FLAG_YW_TILED) || (ldl && !(a.flags & HMV_FLAG_YW_ONE_LAUNCH) && mp == 64 && c >= 128);
-    const int64_t yw_flags = (a.flags & ~(int64_t)(HMV_FLAG_YW_TILED | HMV_FLAG_YW_ONE_LAUNCH)) |
-                             (ldl ? (tiled ? HMV_FLAG_YW_TILED : HMV_FLAG_YW_ONE_LAUNCH) : 0);
-    const int64_t c0 = (split && tiled && c >= 16) ? (c + 1) / 2 : c, c1 = c - c0;
-    if (c1 > 0 && !automatic) {
-      // fork: st1 may start once K1 is done.  Whatever happens on st1 afterwards, st0 joins it again before this call
-      // returns, so that the caller's stream never runs ahead of work this call put on the second stream.
-      int hrc = (int)hipEventRecord(fj->fork, st0);
-      if (!hrc) hrc = (int)hipStreamWaitEvent(st1, fj->fork, 0);
-      if (hrc) { rc = hrc; break; }                      // nothing was put on st1
-      rc = hmv_yw_solve_f64(R + (size_t)c0 * (a.p + 1) * t, c1, a.m, a.p, ws + (size_t)c0 * ws_item,
-                            ar_c + (size_t)c0 * t * a.p, V_c + (size_t)c0 * t, nullptr, a.info_yw + i0 + c0, yw_flags, st1);
-      hrc = (int)hipEventRecord(fj->join, st1);
-      if (!hrc) hrc = (int)hipStreamWaitEvent(st0, fj->join, 0);
-      if (hrc) {                                         // cannot express the join as an event: join on the host
-        (void)hipStreamSynchronize(st1);
-        if (!rc) rc = hrc;
-      }
-      if (rc) break;
-    }
-    // Nobody but K3's packing kernel reads the model when the caller does not ask for it and the measure is the ffDTF:
-    // the default recursion then leaves it in its scratch tiles, which the packing kernel reads directly (windows that
-    // the conditioning guard hands to the LDL^T re-solve come through `ar` as before).
-    const int64_t yw_form = hmv::tuning(HMV_TUNE_YW_FORM);
-    const bool from_tiles = !automatic && !a.ar_out && !ldl && (yw_form == 0 || yw_form == 2) && a.measure == MEAS_FFDTF;
-    sp = hmv::TfSplit{};
-    if (!automatic && from_tiles) {
-      const int64_t s0 = k3_split ? k3_split_point(c, mp, norm_lag_items(mp, a.F)) : 0;
-      hmv::YwArgs ya{};
-      ya.R = R; ya.n_items = s0 ? s0 : c0; ya.m = a.m; ya.p = a.p; ya.ws = ws; ya.ar = ar_c; ya.V = V_c; ya.info = a.info_yw + i0;
-      ya.tiled = -1; ya.no_emit = 1; ya.pivoted = (a.flags & HMV_FLAG_YW_PIVOTED) ? 1 : 0;
-      rc = hmv::launch_yw(ya, mp, st0);
-      if (!rc && s0) {
-        // fork behind K2's first part (the remainder never shares a compute unit with it); the join is waited for inside
-        // K3's launcher, between its two launches, or below on every path that did not get that far
-        int hrc = (int)hipEventRecord(fj->fork, st0);
-        if (!hrc) hrc = (int)hipStreamWaitEvent(st1, fj->fork, 0);
-        if (hrc) { rc = hrc; break; }                    // nothing was put on st1
-        hmv::YwArgs yb = ya;
-        yb.R = R + (size_t)s0 * (a.p + 1) * t; yb.n_items = c - s0; yb.ws = ws + (size_t)s0 * ws_item;
-        yb.ar = ar_c + (size_t)s0 * t * a.p; yb.V = V_c + (size_t)s0 * t; yb.info = a.info_yw + i0 + s0;
-        rc = hmv::launch_yw(yb, mp, st1);
-        hrc = (int)hipEventRecord(fj->join, st1);
-        if (hrc) {                                       // cannot express the join as an event: join on the host, one K3 launch
-          (void)hipStreamSynchronize(st1);
-          if (!rc) rc = hrc;
-        } else {
-          sp.c0 = s0; sp.join = fj->join;
-        }
-      }
-    } else if (!automatic) {
-      rc = hmv_yw_solve_f64(R, c0, a.m, a.p, ws, ar_c, V_c, nullptr, a.info_yw + i0, yw_flags, st0);
-    }
-    if (rc) break;
-    const bool last = (ci == n_chunks - 1);
-    double* Hc = a.S_out ? reinterpret_cast<double*>(base + w.off_H) : nullptr;
-    // dDTF / GPDC: the chunk's full array goes to the output, or (band form) to scratch ahead of its band sums
-    double* full_c = (a.measure == MEAS_FFDTF || a.measure == MEAS_BGC) ? nullptr
-                     : bands ? reinterpret_cast<double*>(base + w.off_full) : a.ffdtf + (size_t)i0 * a.m * a.m * a.F;
-    if (a.measure == MEAS_BGC) {
-      // the two restricted fits (K2 on the gathered blocks of the same lag covariances, in the scratch the full fit has
-      // left, in the form the caller's flags / HMV_TUNE_YW_FORM choose for the full fit -- the launch chain by each
-      // block's own padded size), then the stage; its full array goes to the output or (band form) to scratch ahead of
-      // its band sums
-      const int na = a.bgc->split, nb2 = a.m - na;
-      hmv::BgcArgs ga{};
-      ga.want = a.bgc->want;
-      if (bgc_time) {
-        ga.red.time = a.bgc->time + (size_t)i0 * 4; ga.red.info_red = a.bgc->info_red + (size_t)i0 * 2;
-        ga.red.red_out = a.bgc->red_out ? a.bgc->red_out + (size_t)i0 * 2 : nullptr;
-      }
-      if (bgc_time && a.bgc->red_base) {
-        // both restricted fits are those of observed windows (a pair changes the cross blocks only): their log-determinants
-        // and infos come from the table, and nothing is gathered or solved
-        ga.red.red_base = a.bgc->red_base; ga.red.info_red_base = a.bgc->info_red_base;
-        ga.red.base_a = ll(a.pairs->base_a + i0); ga.red.base_b = ll(a.pairs->base_b + i0);
-      } else if (bgc_time) {
-        double* Ra = reinterpret_cast<double*>(base + gw.off_Ra);
-        double* Rb = reinterpret_cast<double*>(base + gw.off_Rb);
-        double* arr = reinterpret_cast<double*>(base + gw.off_arr);
-        int32_t* ir = reinterpret_cast<int32_t*>(base + gw.off_ir);
-        ga.red.VrA = reinterpret_cast<double*>(base + gw.off_Vra); ga.red.VrB = reinterpret_cast<double*>(base + gw.off_Vrb);
-        ga.red.info_rA = ir; ga.red.info_rB = ir + c;
-        auto red_flags = [&](int nx) {
-          const bool chain = (a.flags & HMV_FLAG_YW_TILED) ||
-                             (ldl && !(a.flags & HMV_FLAG_YW_ONE_LAUNCH) && pad_of(nx) == 64 && c >= 128);
-          return (int64_t)(ldl ? (chain ? HMV_FLAG_YW_TILED : HMV_FLAG_YW_ONE_LAUNCH) : 0) | (a.flags & HMV_FLAG_YW_PIVOTED);
-        };
-        rc = hmv::launch_bgc_gather(R, Ra, Rb, c, a.m, mp, a.p, na, st0);
-        if (!rc)
-          rc = hmv_yw_solve_f64(Ra, c, na, a.p, ws, arr, const_cast<double*>(ga.red.VrA), nullptr, ir, red_flags(na), st0);
-        if (!rc)
-          rc = hmv_yw_solve_f64(Rb, c, nb2, a.p, ws, arr, const_cast<double*>(ga.red.VrB), nullptr, ir + c, red_flags(nb2),
-                                st0);
-      }
-      double* spec_c = !bgc_spec ? nullptr
-                       : bands   ? reinterpret_cast<double*>(base + gw.off_full) : a.ffdtf + (size_t)i0 * 2 * a.F;
-      ga.ar = ar_c; ga.V = V_c; ga.info_yw = a.info_yw + i0;
-      if (bgc_spec) {
-        ga.B = reinterpret_cast<double*>(base + gw.off_B); ga.C = reinterpret_cast<double*>(base + gw.off_C);
-        ga.D = reinterpret_cast<double*>(base + gw.off_D); ga.cst = reinterpret_cast<double*>(base + gw.off_cst);
-        ga.tw = tw; ga.out = spec_c; ga.info_gc = a.bgc->info_gc + (size_t)i0 * a.F;
-      }
-      ga.n_items = c; ga.F = a.F; ga.m = a.m; ga.p = a.p; ga.split = na;
-      if (!rc) rc = hmv::launch_bgc(ga, mp, st0);
-      if (!rc && bgc_spec && bands)
-        rc = hmv::launch_band_sums(spec_c, reinterpret_cast<const int*>(a.bin_lo), reinterpret_cast<const int*>(a.bin_hi),
-                                   a.band_out + (size_t)i0 * 2 * a.n_bands, c * 2, a.F, a.n_bands, st0);
-    } else if (a.measure == MEAS_GPDC) {
-      rc = hmv::launch_gpdc_sliding(ar_c, V_c, tw, full_c, c, a.F, a.m, mp, a.p, st0);
-    } else {
-      rc = tf_ffdtf_impl(a.who, ar_c, c, a.m, a.p, tw, a.F,
-                         k3_bands ? nullptr : (full_c ? full_c : a.ffdtf + (size_t)i0 * a.m * a.m * a.F),
-                         k3_bands ? a.band_out + (size_t)i0 * a.m * a.m * a.n_bands : nullptr, a.bin_lo, a.bin_hi,
-                         a.n_bands, den, Hc, a.info_tf + (size_t)i0 * a.F, a.pivot_tau, tfws, tfws_bytes, a.flags,
-                         last ? a.ev_k3_start : nullptr, last ? a.ev_k3_stop : nullptr, st0, from_tiles ? ws : nullptr, &sp);
-    }
-    join_k3_split();                         // (K3's launcher did not get to its second part)
-    if (!rc && a.measure == MEAS_DDTF) {     // |kappa| from W(f) = A^T V^-1 A, multiplied into K3's ffDTF in place
-      hmv::DdtfArgs da{};
-      da.ar = ar_c; da.V = V_c; da.info_yw = a.info_yw + i0;
-      da.B = reinterpret_cast<double*>(base + w.off_B); da.G = reinterpret_cast<double*>(base + w.off_G);
-      da.freqs = a.freqs; da.fs = a.fs; da.ff = full_c; da.out = full_c;
-      da.n_items = c; da.F = a.F; da.m = a.m; da.p = a.p;
-      rc = hmv::launch_ddtf_sliding(da, mp, st0);
-    }
-    if (!rc && (a.measure == MEAS_DDTF || a.measure == MEAS_GPDC) && bands)
-      rc = hmv::launch_band_sums(full_c, reinterpret_cast<const int*>(a.bin_lo), reinterpret_cast<const int*>(a.bin_hi),
-                                 a.band_out + (size_t)i0 * a.m * a.m * a.n_bands, c * (long long)a.m * a.m, a.F,
-                                 a.n_bands, st0);
-    if (!rc && a.S_out) {      // K5 from the same inverses and the same fit; V is this library's own (symmetric) estimate
-      hmv::SpecArgs sa;
-      sa.H = Hc; sa.V = V_c; sa.S = nullptr; sa.S_mmf = a.S_out + (size_t)i0 * a.m * a.m * a.F * 2;
-      sa.n_items = c; sa.F = a.F; sa.m = a.m; sa.sym = 1;
-      rc = hmv::launch_spectra(sa, mp, st0);
-    }
+  for (int64_t k = i0; k < i0 + c && rc == 0;) {
+    const int64_t rec = k / g.nwin, w0 = k - rec * g.nwin;
+    const int64_t run = ((g.nwin - w0) < (i0 + c - k)) ? (g.nwin - w0) : (i0 + c - k);
+    rc = hmv_lagcov_regular_f64(it.x + rec * it.rec_stride, it.ld, g.T, g.first + w0 * g.hop, g.hop, run, it.m, it.n, it.p,
+                                pl.R + (size_t)(k - i0) * stack, pl.Qb, st);
+    k += run;
   }
-  join_k3_split();                           // a chunk that ended on an error between the fork and K3
+  return rc;
+}
+
+// ---- K2 of a chunk, in one of three forms.  sp comes back describing a K2 -> K3 hand-over in two parts, if one was set up.
+int sliding_k2(const SlidingArgs& a, const SlidingPlan& pl, const Chunk& ch, hmv::TfSplit& sp) {
+  const Items& it = a.it;
+  const int64_t flags = a.run.flags, c = ch.c;
+  const int mp = pl.mp;
+  const TwoStreams& fj = pl.fj;
+  // K2's arguments for the windows k0 .. k0 + cnt - 1 of the chunk
+  auto part = [&](int64_t k0, int64_t cnt, int64_t yw_flags) {
+    return yw_args(pl.R + (size_t)k0 * (it.p + 1) * pl.t, cnt, it.m, it.p, pl.ws + (size_t)k0 * pl.ws_item,
+                   ch.ar + (size_t)k0 * pl.t * it.p, ch.V + (size_t)k0 * pl.t, a.fit.info_yw + ch.i0 + k0, yw_flags);
+  };
+  sp = hmv::TfSplit{};
+  if (pl.automatic)                                  // the recursion to order p with the selection (flags: none of K2's)
+    return hmv::launch_yw_auto(part(0, c, flags),
+                               yw_auto_args(it.n, a.sel.crit, a.sel.order_out + ch.i0,
+                                            a.sel.crit_out ? a.sel.crit_out + (size_t)ch.i0 * it.p : nullptr), mp, fj.st0);
+  if (!pl.from_tiles) {
+    // An LDL^T form (or the recursion, where somebody reads the model): the launch chain where it is asked for or chosen
+    // by shape, and then, given a second stream and 16 windows, as two half-batches
+    const int64_t yw_flags = pl.yw_flags(flags, mp, c);
+    const int64_t c0 = (pl.half_split && (yw_flags & HMV_FLAG_YW_TILED) && c >= 16) ? (c + 1) / 2 : c;
+    if (c0 < c) {
+      if (const int hrc = fj.fork()) return hrc;
+      int rc = hmv::launch_yw(part(c0, c - c0, yw_flags), mp, fj.st1);
+      const int hrc = fj.join();
+      if (!rc) rc = hrc;
+      if (rc) return rc;
+    }
+    return hmv::launch_yw(part(0, c0, yw_flags), mp, fj.st0);
+  }
+  // The recursion that does not emit.  With a split point, the remainder windows go to the second stream, forked behind the
+  // first part (they never share a compute unit with it); the join is waited for inside K3's launcher, between its two
+  // launches, or by TwoStreams::finish on every path that did not get that far.
+  const int64_t s0 = pl.k3_split ? k3_split_point(c, mp, norm_lag_items(mp, a.spec.F)) : 0;
+  hmv::YwArgs ya = part(0, s0 ? s0 : c, flags);
+  ya.no_emit = 1;
+  int rc = hmv::launch_yw(ya, mp, fj.st0);
+  if (rc || !s0) return rc;
+  if (const int hrc = fj.fork()) return hrc;
+  hmv::YwArgs yb = part(s0, c - s0, flags);
+  yb.no_emit = 1;
+  rc = hmv::launch_yw(yb, mp, fj.st1);
+  if (const int hrc = fj.record_join()) return rc ? rc : hrc;      // (joined on the host: one K3 launch)
+  sp.c0 = s0;
+  sp.join = fj.ev->join;
+  return rc;
+}
+
+// ---- the block Granger stage of a chunk: gather, the two restricted fits, launch_bgc, band sums
+int sliding_bgc(const SlidingArgs& a, const SlidingPlan& pl, const Chunk& ch) {
+  const Items& it = a.it;
+  const BgcDesc& g = *a.bgc;
+  const BgcWs& gw = pl.gw;
+  const int64_t i0 = ch.i0, c = ch.c, flags = a.run.flags;
+  hipStream_t st0 = pl.fj.st0;
+  const int na = g.split, nb2 = it.m - na, F = a.spec.F;
+  int rc = 0;
+  hmv::BgcArgs ga{};
+  ga.want = g.want;
+  if (pl.bgc_time) {
+    ga.red.time = g.time + (size_t)i0 * 4; ga.red.info_red = g.info_red + (size_t)i0 * 2;
+    ga.red.red_out = g.red_out ? g.red_out + (size_t)i0 * 2 : nullptr;
+  }
+  if (pl.bgc_time && g.red_base) {
+    // both restricted fits are those of observed windows (a pair changes the cross blocks only): their log-determinants
+    // and infos come from the table, and nothing is gathered or solved
+    ga.red.red_base = g.red_base; ga.red.info_red_base = g.info_red_base;
+    ga.red.base_a = ll(a.pairs->base_a + i0); ga.red.base_b = ll(a.pairs->base_b + i0);
+  } else if (pl.bgc_time) {
+    // K2 on the gathered blocks of the same lag covariances, in the scratch the full fit has left, in the form the
+    // caller's flags / HMV_TUNE_YW_FORM choose for the full fit -- the launch chain by each block's own padded size
+    double* Ra = pl.at(gw.off_Ra);
+    double* Rb = pl.at(gw.off_Rb);
+    double* arr = pl.at(gw.off_arr);
+    double* VrA = pl.at(gw.off_Vra);
+    double* VrB = pl.at(gw.off_Vrb);
+    int32_t* ir = reinterpret_cast<int32_t*>(pl.base + gw.off_ir);
+    ga.red.VrA = VrA; ga.red.VrB = VrB;
+    ga.red.info_rA = ir; ga.red.info_rB = ir + c;
+    auto fit = [&](const double* Rx, int nx, double* Vx, int32_t* info) {
+      const int mpx = pad_of(nx);
+      return hmv::launch_yw(yw_args(Rx, c, nx, it.p, pl.ws, arr, Vx, info, pl.yw_flags(flags, mpx, c)), mpx, st0);
+    };
+    rc = hmv::launch_bgc_gather(pl.R, Ra, Rb, c, it.m, pl.mp, it.p, na, st0);
+    if (!rc) rc = fit(Ra, na, VrA, ir);
+    if (!rc) rc = fit(Rb, nb2, VrB, ir + c);
+  }
+  // the stage's full array goes to the output, or (band form) to scratch ahead of its band sums
+  double* spec_c = !pl.bgc_spec ? nullptr : pl.bands ? pl.at(gw.off_full) : a.o.out + (size_t)i0 * 2 * F;
+  ga.ar = ch.ar; ga.V = ch.V; ga.info_yw = a.fit.info_yw + i0;
+  if (pl.bgc_spec) {
+    ga.B = pl.at(gw.off_B); ga.C = pl.at(gw.off_C);
+    ga.D = pl.at(gw.off_D); ga.cst = pl.at(gw.off_cst);
+    ga.tw = pl.tw; ga.out = spec_c; ga.info_gc = g.info_gc + (size_t)i0 * F;
+  }
+  ga.n_items = c; ga.F = F; ga.m = it.m; ga.p = it.p; ga.split = na;
+  if (!rc) rc = hmv::launch_bgc(ga, pl.mp, st0);
+  if (!rc && pl.bgc_spec && pl.bands)
+    rc = hmv::launch_band_sums(spec_c, reinterpret_cast<const int*>(a.o.bin_lo), reinterpret_cast<const int*>(a.o.bin_hi),
+                               a.o.out + (size_t)i0 * 2 * a.o.n_bands, c * 2, F, a.o.n_bands, st0);
+  return rc;
+}
+
+// ---- the measure stage of a chunk: GPDC or K3's ffDTF, then dDTF, band sums, spectra
+int sliding_measure(const SlidingArgs& a, const SlidingPlan& pl, const Chunk& ch, hmv::TfSplit& sp) {
+  const Items& it = a.it;
+  const Output& o = a.o;
+  const int64_t i0 = ch.i0, c = ch.c;
+  const int F = a.spec.F, m = it.m;
+  hipStream_t st0 = pl.fj.st0;
+  const int* lo = reinterpret_cast<const int*>(o.bin_lo);
+  const int* hi = reinterpret_cast<const int*>(o.bin_hi);
+  double* Hc = o.S_out ? pl.at(pl.w.off_H) : nullptr;
+  double* out_c = o.out + (size_t)i0 * m * m * (pl.bands ? o.n_bands : F);
+  // dDTF / GPDC: the chunk's full array goes to the output, or (band form) to scratch ahead of its band sums;
+  // ffDTF: K3 writes the output itself, the full array or (k3_bands) its band sums
+  double* full_c = pl.k3_bands ? nullptr : (pl.bands ? pl.at(pl.w.off_full) : out_c);
+  int rc;
+  if (a.measure == MEAS_GPDC)
+    rc = hmv::launch_gpdc_sliding(ch.ar, ch.V, pl.tw, full_c, c, F, m, pl.mp, it.p, st0);
+  else
+    rc = tf_ffdtf_impl(a.who, ch.ar, c, m, it.p, pl.tw, F, full_c, pl.k3_bands ? out_c : nullptr, o.bin_lo, o.bin_hi,
+                       o.n_bands, pl.den, Hc, a.fit.info_tf + (size_t)i0 * F, a.fit.pivot_tau, pl.tfws, pl.tfws_bytes,
+                       a.run.flags,
+                       ch.last ? a.run.ev_k3_start : nullptr, ch.last ? a.run.ev_k3_stop : nullptr, st0,
+                       pl.from_tiles ? pl.ws : nullptr, &sp);
+  if (!rc && a.measure == MEAS_DDTF) {     // |kappa| from W(f) = A^T V^-1 A, multiplied into K3's ffDTF in place
+    hmv::DdtfArgs da{};
+    da.ar = ch.ar; da.V = ch.V; da.info_yw = a.fit.info_yw + i0;
+    da.B = pl.at(pl.w.off_B); da.G = pl.at(pl.w.off_G);
+    da.freqs = a.spec.freqs; da.fs = a.spec.fs; da.ff = full_c; da.out = full_c;
+    da.n_items = c; da.F = F; da.m = m; da.p = it.p;
+    rc = hmv::launch_ddtf_sliding(da, pl.mp, st0);
+  }
+  if (!rc && pl.bands && !pl.k3_bands)
+    rc = hmv::launch_band_sums(full_c, lo, hi, out_c, c * (long long)m * m, F, o.n_bands, st0);
+  if (!rc && o.S_out) {        // K5 from the same inverses and the same fit; V is this library's own (symmetric) estimate
+    hmv::SpecArgs sa;
+    sa.H = Hc; sa.V = ch.V; sa.S = nullptr; sa.S_mmf = o.S_out + (size_t)i0 * m * m * F * 2;
+    sa.n_items = c; sa.F = F; sa.m = m; sa.sym = 1;
+    rc = hmv::launch_spectra(sa, pl.mp, st0);
+  }
+  return rc;
+}
+
+// ---- the driver of the twelve fused entries: plan, twiddles, then per chunk K1, K2, the measure or block stage, join
+int sliding_impl(const SlidingArgs& a) {
+  SlidingPlan pl;
+  int rc = sliding_plan(a, pl);
+  if (rc || pl.empty) return rc;
+  if (pl.bgc_spec) rc = hmv_twiddles_f64(a.spec.freqs, a.spec.F, a.spec.fs, a.it.p, pl.tw, a.run.stream);
+  const int64_t n = a.it.n_items, chunk = a.run.chunk;
+  hmv::TfSplit sp{};                         // the chunk's K2 -> K3 hand-over in two parts, if any
+  for (int64_t i0 = 0; i0 < n && rc == 0; i0 += chunk) {
+    const Chunk ch{i0, n - i0 < chunk ? n - i0 : chunk, a.fit.ar_out ? a.fit.ar_out + (size_t)i0 * pl.t * a.it.p : pl.ar,
+                   a.fit.V_out ? a.fit.V_out + (size_t)i0 * pl.t : pl.V, i0 + chunk >= n};
+    rc = sliding_k1(a, pl, ch);
+    if (!rc) rc = sliding_k2(a, pl, ch, sp);
+    if (!rc) rc = a.measure == MEAS_BGC ? sliding_bgc(a, pl, ch) : sliding_measure(a, pl, ch, sp);
+    pl.fj.finish(sp);                        // (K3's launcher did not get to its second part, or the chunk ended on an error)
+  }
   return rc;
 }
 }  // namespace
@@ -1131,16 +1258,10 @@ int hmv_sliding_ffdtf_f64(const double* x, int64_t rec_stride, int64_t ld, const
                           int64_t chunk, double pivot_tau, int64_t flags, int64_t grid_hop, int64_t grid_first,
                           int64_t grid_nwin, int64_t grid_T, void* ev_k3_start, void* ev_k3_stop, void* stream,
                           void* aux_stream) {
-  SlidingArgs a{"hmv_sliding_ffdtf_f64"};
-  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.item_rec = item_rec; a.item_start = item_start; a.n_items = n_items;
-  a.m = m; a.n = n; a.p = p; a.freqs = freqs; a.F = F; a.fs = fs;
-  a.ffdtf = ffdtf;
-  a.ar_out = ar_out; a.V_out = V_out; a.info_yw = info_yw; a.info_tf = info_tf;
-  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.pivot_tau = pivot_tau; a.flags = flags;
-  a.grid_hop = grid_hop; a.grid_first = grid_first; a.grid_nwin = grid_nwin; a.grid_T = grid_T;
-  a.ev_k3_start = ev_k3_start; a.ev_k3_stop = ev_k3_stop;
-  a.stream = stream; a.aux_stream = aux_stream;
-  return sliding_impl(a);
+  return sliding_impl({"hmv_sliding_ffdtf_f64", MEAS_FFDTF, {x, rec_stride, ld, item_rec, item_start, n_items, m, n, p},
+                       {grid_hop, grid_first, grid_nwin, grid_T}, {freqs, F, fs}, output(ffdtf),
+                       {ar_out, V_out, info_yw, info_tf, pivot_tau},
+                       {workspace, workspace_bytes, chunk, flags, stream, aux_stream, ev_k3_start, ev_k3_stop}});
 }
 
 int hmv_sliding_ffdtf_bands_f64(const double* x, int64_t rec_stride, int64_t ld, const int64_t* item_rec,
@@ -1151,17 +1272,12 @@ int hmv_sliding_ffdtf_bands_f64(const double* x, int64_t rec_stride, int64_t ld,
                                 int64_t chunk, double pivot_tau, int64_t flags, int64_t grid_hop, int64_t grid_first,
                                 int64_t grid_nwin, int64_t grid_T, void* ev_k3_start, void* ev_k3_stop, void* stream,
                                 void* aux_stream) {
-  if (!band_out && n_items != 0) return fail(-4, "hmv_sliding_ffdtf_bands_f64: null pointer / empty grid");
-  SlidingArgs a{"hmv_sliding_ffdtf_bands_f64"};
-  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.item_rec = item_rec; a.item_start = item_start; a.n_items = n_items;
-  a.m = m; a.n = n; a.p = p; a.freqs = freqs; a.F = F; a.fs = fs;
-  a.band_out = band_out; a.bin_lo = bin_lo; a.bin_hi = bin_hi; a.n_bands = n_bands;
-  a.ar_out = ar_out; a.V_out = V_out; a.info_yw = info_yw; a.info_tf = info_tf;
-  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.pivot_tau = pivot_tau; a.flags = flags;
-  a.grid_hop = grid_hop; a.grid_first = grid_first; a.grid_nwin = grid_nwin; a.grid_T = grid_T;
-  a.ev_k3_start = ev_k3_start; a.ev_k3_stop = ev_k3_stop;
-  a.stream = stream; a.aux_stream = aux_stream;
-  return sliding_impl(a);
+  const char* who = "hmv_sliding_ffdtf_bands_f64";
+  if (int rc = need_output(who, band_out, n_items)) return rc;
+  return sliding_impl({who, MEAS_FFDTF, {x, rec_stride, ld, item_rec, item_start, n_items, m, n, p},
+                       {grid_hop, grid_first, grid_nwin, grid_T}, {freqs, F, fs},
+                       output(band_out, bin_lo, bin_hi, n_bands, true), {ar_out, V_out, info_yw, info_tf, pivot_tau},
+                       {workspace, workspace_bytes, chunk, flags, stream, aux_stream, ev_k3_start, ev_k3_stop}});
 }
 
 int64_t hmv_sliding_spectra_workspace_bytes(int64_t chunk, int m, int p, int F) {
@@ -1175,16 +1291,12 @@ int hmv_sliding_ffdtf_spectra_f64(const double* x, int64_t rec_stride, int64_t l
                                   int64_t workspace_bytes, int64_t chunk, double pivot_tau, int64_t flags,
                                   int64_t grid_hop, int64_t grid_first, int64_t grid_nwin, int64_t grid_T, void* stream,
                                   void* aux_stream) {
-  if (!S_out && n_items != 0) return fail(-4, "hmv_sliding_ffdtf_spectra_f64: null pointer / empty grid");
-  SlidingArgs a{"hmv_sliding_ffdtf_spectra_f64"};
-  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.item_rec = item_rec; a.item_start = item_start; a.n_items = n_items;
-  a.m = m; a.n = n; a.p = p; a.freqs = freqs; a.F = F; a.fs = fs;
-  a.ffdtf = ffdtf; a.S_out = S_out;
-  a.ar_out = ar_out; a.V_out = V_out; a.info_yw = info_yw; a.info_tf = info_tf;
-  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.pivot_tau = pivot_tau; a.flags = flags;
-  a.grid_hop = grid_hop; a.grid_first = grid_first; a.grid_nwin = grid_nwin; a.grid_T = grid_T;
-  a.stream = stream; a.aux_stream = aux_stream;
-  return sliding_impl(a);
+  const char* who = "hmv_sliding_ffdtf_spectra_f64";
+  if (int rc = need_output(who, S_out, n_items)) return rc;
+  return sliding_impl({who, MEAS_FFDTF, {x, rec_stride, ld, item_rec, item_start, n_items, m, n, p},
+                       {grid_hop, grid_first, grid_nwin, grid_T}, {freqs, F, fs},
+                       output(ffdtf, nullptr, nullptr, 0, false, S_out), {ar_out, V_out, info_yw, info_tf, pivot_tau},
+                       {workspace, workspace_bytes, chunk, flags, stream, aux_stream, nullptr, nullptr}});
 }
 
 // ---- sliding-window dDTF / GPDC (sliding_conn.hip) ------------------------------------------------------
@@ -1194,25 +1306,26 @@ int64_t hmv_sliding_ddtf_workspace_bytes(int64_t chunk, int m, int p, int F, int
   return sliding_bytes(chunk, m, p, F, n_bands, false, MEAS_DDTF);
 }
 
+namespace {
+// what the two entries share: GPDC comes without info_tf and without a pivot threshold (it inverts nothing)
+int sliding_conn_entry(const char* who, int measure, const Items& it, const Grid& grid, const Spectral& spec, double* out,
+                       const int32_t* bin_lo, const int32_t* bin_hi, int n_bands, const FitOut& fit, const Run& run) {
+  if (n_bands < 0) return refuse(who, -4, "n_bands must be >= 0");
+  if (int rc = need_output(who, out, it.n_items)) return rc;
+  return sliding_impl({who, measure, it, grid, spec, output(out, bin_lo, bin_hi, n_bands), fit, run});
+}
+}  // namespace
+
 int hmv_sliding_ddtf_f64(const double* x, int64_t rec_stride, int64_t ld, const int64_t* item_rec,
                          const int64_t* item_start, int64_t n_items, int m, int n, int p, const double* freqs, int F,
                          double fs, double* out, const int32_t* bin_lo, const int32_t* bin_hi, int n_bands,
                          double* ar_out, double* V_out, int32_t* info_yw, int32_t* info_tf, void* workspace,
                          int64_t workspace_bytes, int64_t chunk, double pivot_tau, int64_t flags, int64_t grid_hop,
                          int64_t grid_first, int64_t grid_nwin, int64_t grid_T, void* stream, void* aux_stream) {
-  if (n_bands < 0) return fail(-4, "hmv_sliding_ddtf_f64: n_bands must be >= 0");
-  if (!out && n_items != 0) return fail(-4, "hmv_sliding_ddtf_f64: null pointer / empty grid");
-  SlidingArgs a{"hmv_sliding_ddtf_f64"};
-  a.measure = MEAS_DDTF;
-  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.item_rec = item_rec; a.item_start = item_start; a.n_items = n_items;
-  a.m = m; a.n = n; a.p = p; a.freqs = freqs; a.F = F; a.fs = fs;
-  if (n_bands > 0) a.band_out = out; else a.ffdtf = out;
-  a.bin_lo = bin_lo; a.bin_hi = bin_hi; a.n_bands = n_bands;
-  a.ar_out = ar_out; a.V_out = V_out; a.info_yw = info_yw; a.info_tf = info_tf;
-  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.pivot_tau = pivot_tau; a.flags = flags;
-  a.grid_hop = grid_hop; a.grid_first = grid_first; a.grid_nwin = grid_nwin; a.grid_T = grid_T;
-  a.stream = stream; a.aux_stream = aux_stream;
-  return sliding_impl(a);
+  return sliding_conn_entry("hmv_sliding_ddtf_f64", MEAS_DDTF, {x, rec_stride, ld, item_rec, item_start, n_items, m, n, p},
+                            {grid_hop, grid_first, grid_nwin, grid_T}, {freqs, F, fs}, out, bin_lo, bin_hi, n_bands,
+                            {ar_out, V_out, info_yw, info_tf, pivot_tau},
+                            {workspace, workspace_bytes, chunk, flags, stream, aux_stream, nullptr, nullptr});
 }
 
 int64_t hmv_sliding_gpdc_workspace_bytes(int64_t chunk, int m, int p, int F, int n_bands) {
@@ -1225,34 +1338,20 @@ int hmv_sliding_gpdc_f64(const double* x, int64_t rec_stride, int64_t ld, const 
                          double* ar_out, double* V_out, int32_t* info_yw, void* workspace, int64_t workspace_bytes,
                          int64_t chunk, int64_t flags, int64_t grid_hop, int64_t grid_first, int64_t grid_nwin,
                          int64_t grid_T, void* stream, void* aux_stream) {
-  if (n_bands < 0) return fail(-4, "hmv_sliding_gpdc_f64: n_bands must be >= 0");
-  if (!out && n_items != 0) return fail(-4, "hmv_sliding_gpdc_f64: null pointer / empty grid");
-  SlidingArgs a{"hmv_sliding_gpdc_f64"};
-  a.measure = MEAS_GPDC;
-  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.item_rec = item_rec; a.item_start = item_start; a.n_items = n_items;
-  a.m = m; a.n = n; a.p = p; a.freqs = freqs; a.F = F; a.fs = fs;
-  if (n_bands > 0) a.band_out = out; else a.ffdtf = out;
-  a.bin_lo = bin_lo; a.bin_hi = bin_hi; a.n_bands = n_bands;
-  a.ar_out = ar_out; a.V_out = V_out; a.info_yw = info_yw;
-  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.flags = flags;
-  a.grid_hop = grid_hop; a.grid_first = grid_first; a.grid_nwin = grid_nwin; a.grid_T = grid_T;
-  a.stream = stream; a.aux_stream = aux_stream;
-  return sliding_impl(a);
+  return sliding_conn_entry("hmv_sliding_gpdc_f64", MEAS_GPDC, {x, rec_stride, ld, item_rec, item_start, n_items, m, n, p},
+                            {grid_hop, grid_first, grid_nwin, grid_T}, {freqs, F, fs}, out, bin_lo, bin_hi, n_bands,
+                            {ar_out, V_out, info_yw, nullptr, 1.0},
+                            {workspace, workspace_bytes, chunk, flags, stream, aux_stream, nullptr, nullptr});
 }
 
 // ---- block Granger causality (block_gc.hip) ----------------------------------------------------------------------
 namespace {
 // the checks the three block Granger entries share; 0 or the refusal
 int bgc_check(const char* who, int m, int p, int split, int F) {
-  char buf[200];
-  auto refuse = [&](int code, const char* msg) {
-    snprintf(buf, sizeof(buf), "%s: %s", who, msg);
-    return fail(code, buf);
-  };
-  if (pad_of(m) < 0) return refuse(-1, "channel count must be in 1..64");
-  if (p < 1 || p > HMV_MAX_ORDER) return refuse(-2, "model order must be in 1..32");
-  if (split < 1 || split > m - 1) return refuse(-11, "split must be in 1..m-1 (both blocks need a channel)");
-  if (F < 1) return refuse(-12, "the frequency grid is empty (F must be >= 1)");
+  if (pad_of(m) < 0) return refuse(who, -1, "channel count must be in 1..64");
+  if (p < 1 || p > HMV_MAX_ORDER) return refuse(who, -2, "model order must be in 1..32");
+  if (split < 1 || split > m - 1) return refuse(who, -11, "split must be in 1..m-1 (both blocks need a channel)");
+  if (F < 1) return refuse(who, -12, "the frequency grid is empty (F must be >= 1)");
   return 0;
 }
 }  // namespace
@@ -1304,22 +1403,17 @@ int hmv_sliding_block_gc_f64(const double* x, int64_t rec_stride, int64_t ld, co
                              int64_t grid_nwin, int64_t grid_T, void* stream) {
   const char* who = "hmv_sliding_block_gc_f64";
   if (int rc = bgc_check(who, m, p, split, F)) return rc;
-  if (n <= p) return fail(-3, "hmv_sliding_block_gc_f64: window shorter than the model order");
-  if (n_items < 0) return fail(-4, "hmv_sliding_block_gc_f64: n_items must be >= 0");
-  if (n_bands < 0) return fail(-14, "hmv_sliding_block_gc_f64: n_bands must be >= 0");
-  if (n_items != 0 && !spectral) return fail(-13, "hmv_sliding_block_gc_f64: the spectral output is a null pointer");
-  if (n_items != 0 && (!time || !info_red || !info_gc)) return fail(-4, "hmv_sliding_block_gc_f64: null pointer / empty grid");
-  BgcDesc g{split, time, info_red, info_gc};
-  SlidingArgs a{who};
-  a.measure = MEAS_BGC; a.bgc = &g;
-  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.item_rec = item_rec; a.item_start = item_start; a.n_items = n_items;
-  a.m = m; a.n = n; a.p = p; a.freqs = freqs; a.F = F; a.fs = fs;
-  if (n_bands > 0) a.band_out = spectral; else a.ffdtf = spectral;
-  a.bin_lo = bin_lo; a.bin_hi = bin_hi; a.n_bands = n_bands;
-  a.ar_out = ar_out; a.V_out = V_out; a.info_yw = info_yw;
-  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.flags = flags;
-  a.grid_hop = grid_hop; a.grid_first = grid_first; a.grid_nwin = grid_nwin; a.grid_T = grid_T;
-  a.stream = stream;
+  if (n <= p) return refuse(who, -3, "window shorter than the model order");
+  if (n_items < 0) return refuse(who, -4, "n_items must be >= 0");
+  if (n_bands < 0) return refuse(who, -14, "n_bands must be >= 0");
+  if (n_items != 0 && !spectral) return refuse(who, -13, "the spectral output is a null pointer");
+  if (n_items != 0 && (!time || !info_red || !info_gc)) return refuse(who, -4, "null pointer / empty grid");
+  const BgcDesc g{split, time, info_red, info_gc};
+  SlidingArgs a{who, MEAS_BGC, {x, rec_stride, ld, item_rec, item_start, n_items, m, n, p},
+                {grid_hop, grid_first, grid_nwin, grid_T}, {freqs, F, fs}, output(spectral, bin_lo, bin_hi, n_bands),
+                {ar_out, V_out, info_yw, nullptr, 1.0},
+                {workspace, workspace_bytes, chunk, flags, stream, nullptr, nullptr, nullptr}};
+  a.bgc = &g;
   return sliding_impl(a);
 }
 
@@ -1344,45 +1438,35 @@ int hmv_sliding_block_gc_pairs_f64(const double* x, int64_t rec_stride, int64_t 
                                    const double* red_base, const int32_t* info_red_base, void* stream) {
   const char* who = "hmv_sliding_block_gc_pairs_f64";
   (void)T;                                               // the caller has checked the windows against it
-  if (want < 1 || want > 3)
-    return fail(-15, "hmv_sliding_block_gc_pairs_f64: want must be 1 (spectral), 2 (time) or 3 (both)");
+  if (want < 1 || want > 3) return refuse(who, -15, "want must be 1 (spectral), 2 (time) or 3 (both)");
   const bool spec = want & 1, timed = want & 2;
   if (int rc = bgc_check(who, m, p, split, spec ? F : 1)) return rc;
-  if (n <= p) return fail(-3, "hmv_sliding_block_gc_pairs_f64: window shorter than the model order");
-  if (n_items < 0) return fail(-4, "hmv_sliding_block_gc_pairs_f64: n_items must be >= 0");
-  if (spec && n_bands < 0) return fail(-14, "hmv_sliding_block_gc_pairs_f64: n_bands must be >= 0");
+  if (n <= p) return refuse(who, -3, "window shorter than the model order");
+  if (n_items < 0) return refuse(who, -4, "n_items must be >= 0");
+  if (spec && n_bands < 0) return refuse(who, -14, "n_bands must be >= 0");
   if (int rc = pairs_check(who, m, rec_b, split, R_base, base_a, base_b)) return rc;
-  if ((red_base != nullptr) != (info_red_base != nullptr))
-    return fail(-4, "hmv_sliding_block_gc_pairs_f64: red_base and info_red_base go together");
-  if (red_base && !R_base)
-    return fail(-4, "hmv_sliding_block_gc_pairs_f64: red_base needs R_base, base_a and base_b (its rows are theirs)");
-  if (n_items != 0 && spec && !spectral) return fail(-13, "hmv_sliding_block_gc_pairs_f64: the spectral output is a null pointer");
+  if ((red_base != nullptr) != (info_red_base != nullptr)) return refuse(who, -4, "red_base and info_red_base go together");
+  if (red_base && !R_base) return refuse(who, -4, "red_base needs R_base, base_a and base_b (its rows are theirs)");
+  if (n_items != 0 && spec && !spectral) return refuse(who, -13, "the spectral output is a null pointer");
   if (n_items != 0 && ((spec && !info_gc) || (timed && (!time || !info_red))))
-    return fail(-4, "hmv_sliding_block_gc_pairs_f64: null pointer / empty grid");
+    return refuse(who, -4, "null pointer / empty grid");
   const PairDesc pairs{rec_b, split, R_base, base_a, base_b};
   BgcDesc g{split, time, info_red, info_gc};
   g.want = want;
   if (timed) { g.red_out = red_out; g.red_base = red_base; g.info_red_base = info_red_base; }
-  SlidingArgs a{who};
-  a.measure = MEAS_BGC; a.bgc = &g; a.pairs = &pairs;
-  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.item_rec = rec_a; a.item_start = item_start; a.n_items = n_items;
-  a.m = m; a.n = n; a.p = p; a.fs = fs;
-  if (spec) {
-    a.freqs = freqs; a.F = F;
-    if (n_bands > 0) a.band_out = spectral; else a.ffdtf = spectral;
-    a.bin_lo = bin_lo; a.bin_hi = bin_hi; a.n_bands = n_bands;
-  }
-  a.ar_out = ar_out; a.V_out = V_out; a.info_yw = info_yw;
-  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.flags = flags;
-  a.stream = stream;
+  // (time alone: neither a frequency grid nor a spectral output)
+  SlidingArgs a{who, MEAS_BGC, {x, rec_stride, ld, rec_a, item_start, n_items, m, n, p}, {0, 0, 0, 0},
+                spec ? Spectral{freqs, F, fs} : Spectral{nullptr, 0, fs},
+                spec ? output(spectral, bin_lo, bin_hi, n_bands) : output(nullptr), {ar_out, V_out, info_yw, nullptr, 1.0},
+                {workspace, workspace_bytes, chunk, flags, stream, nullptr, nullptr, nullptr}};
+  a.bgc = &g;
+  a.pairs = &pairs;
   return sliding_impl(a);
 }
 
 // ---- automatic model order (yw_auto.hip): mvar_criterion (mtmvar.py:551-601) per window inside the fused call -------
 int64_t hmv_sliding_auto_workspace_bytes(int measure, int64_t chunk, int m, int pmax, int F, int n_bands) {
-  // n_bands = -1: the full ffDTF together with S_out (one chunk of H passes through the workspace between K3 and K5)
-  const bool spectra = (n_bands == -1 && measure == HMV_MEASURE_FFDTF);
-  return sliding_bytes(chunk, m, pmax, F, spectra ? 0 : n_bands, spectra, measure);
+  return measure_bytes(measure, chunk, m, pmax, F, n_bands, -1);
 }
 
 int hmv_sliding_auto_f64(int measure, const double* x, int64_t rec_stride, int64_t ld, const int64_t* item_rec,
@@ -1392,67 +1476,36 @@ int hmv_sliding_auto_f64(int measure, const double* x, int64_t rec_stride, int64
                          int32_t* info_yw, int32_t* info_tf, void* workspace, int64_t workspace_bytes, int64_t chunk,
                          double pivot_tau, int64_t flags, int64_t grid_hop, int64_t grid_first, int64_t grid_nwin,
                          int64_t grid_T, void* stream, void* aux_stream) {
-  if (measure < HMV_MEASURE_FFDTF || measure > HMV_MEASURE_GPDC)
-    return fail(-4, "hmv_sliding_auto_f64: measure must be HMV_MEASURE_FFDTF, _DDTF or _GPDC");
-  if (crit < 0 || crit > 2) return fail(-5, "hmv_sliding_auto_f64: criterion must be 0 (AIC), 1 (HQ) or 2 (SC)");
-  if (n_bands < 0) return fail(-4, "hmv_sliding_auto_f64: n_bands must be >= 0");
-  if (S_out && (measure != HMV_MEASURE_FFDTF || n_bands != 0))
-    return fail(-4, "hmv_sliding_auto_f64: spectra come with the full ffDTF only");
-  if (!out && n_items != 0) return fail(-4, "hmv_sliding_auto_f64: null pointer / empty grid");
-  SlidingArgs a{"hmv_sliding_auto_f64"};
-  a.measure = measure; a.crit = crit; a.order_out = order_out; a.crit_out = crit_out;
-  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.item_rec = item_rec; a.item_start = item_start; a.n_items = n_items;
-  a.m = m; a.n = n; a.p = pmax; a.freqs = freqs; a.F = F; a.fs = fs;
-  if (n_bands > 0) a.band_out = out; else a.ffdtf = out;
-  a.bin_lo = bin_lo; a.bin_hi = bin_hi; a.n_bands = n_bands; a.S_out = S_out;
-  a.ar_out = ar_out; a.V_out = V_out; a.info_yw = info_yw; a.info_tf = info_tf;
-  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.pivot_tau = pivot_tau; a.flags = flags;
-  if (measure == HMV_MEASURE_GPDC) { a.info_tf = nullptr; a.pivot_tau = 1.0; }
-  a.grid_hop = grid_hop; a.grid_first = grid_first; a.grid_nwin = grid_nwin; a.grid_T = grid_T;
-  a.stream = stream; a.aux_stream = aux_stream;
+  const char* who = "hmv_sliding_auto_f64";
+  FitOut fit{ar_out, V_out, info_yw, info_tf, pivot_tau};
+  if (int rc = measure_request(who, measure, n_bands, S_out, fit, crit)) return rc;
+  if (int rc = need_output(who, out, n_items)) return rc;
+  SlidingArgs a{who, measure, {x, rec_stride, ld, item_rec, item_start, n_items, m, n, pmax},
+                {grid_hop, grid_first, grid_nwin, grid_T}, {freqs, F, fs},
+                output(out, bin_lo, bin_hi, n_bands, false, S_out), fit,
+                {workspace, workspace_bytes, chunk, flags, stream, aux_stream, nullptr, nullptr}};
+  a.sel = {crit, order_out, crit_out};
   return sliding_impl(a);
 }
 
 // ---- event-locked ensembles: the fused path with the trial-averaged K1 (lagcov_ensemble.hip) ----------------------------
 int64_t hmv_sliding_ensemble_workspace_bytes(int measure, int64_t chunk, int m, int n, int p, int F, int n_bands,
                                              int64_t grid_hop, int64_t grid_nwin) {
-  // n_bands = -1: the full ffDTF together with S_out, as hmv_sliding_auto_workspace_bytes
-  const bool spectra = (n_bands == -1 && measure == HMV_MEASURE_FFDTF);
   if (n <= p || grid_hop < 0 || grid_nwin < 0) return -1;
   // (ens_q_tiles sees chunk, m and p before sliding_bytes range-checks them: it guards every division itself)
-  const int64_t q_tiles = ens_q_tiles(chunk, n, p, grid_hop, grid_nwin);
-  return sliding_bytes(chunk, m, p, F, spectra ? 0 : n_bands, spectra, measure, q_tiles);
+  return measure_bytes(measure, chunk, m, p, F, n_bands, ens_q_tiles(chunk, n, p, grid_hop, grid_nwin));
 }
 
 namespace {
-int sliding_ensemble_entry(const char* who, int measure, const double* x, int64_t rec_stride, int64_t ld, const EnsDesc& ens,
-                           const int64_t* item_group, const int64_t* item_offset, int64_t n_items, int m, int n, int p,
-                           const double* freqs, int F, double fs, double* out, const int32_t* bin_lo, const int32_t* bin_hi,
-                           int n_bands, double* S_out, double* ar_out, double* V_out, int32_t* info_yw, int32_t* info_tf,
-                           void* workspace, int64_t workspace_bytes, int64_t chunk, double pivot_tau, int64_t flags,
-                           int64_t grid_hop, int64_t grid_nwin, void* stream, void* aux_stream) {
-  auto refuse = [&](const char* msg) {
-    char buf[200];
-    snprintf(buf, sizeof(buf), "%s: %s", who, msg);
-    return fail(-4, buf);
-  };
-  if (measure < HMV_MEASURE_FFDTF || measure > HMV_MEASURE_GPDC)
-    return refuse("measure must be HMV_MEASURE_FFDTF, _DDTF or _GPDC");
-  if (n_bands < 0) return refuse("n_bands must be >= 0");
-  if (S_out && (measure != HMV_MEASURE_FFDTF || n_bands != 0)) return refuse("spectra come with the full ffDTF only");
-  const int mp = pad_of(m);                              // ahead of the pointer checks, in the order of the other entries
-  if (mp >= 0 && p >= 1 && p <= HMV_MAX_ORDER && n > p && !out && n_items != 0) return refuse("null pointer / empty grid");
-  SlidingArgs a{who};
-  a.measure = measure; a.ens = &ens;
-  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.item_rec = item_group; a.item_start = item_offset; a.n_items = n_items;
-  a.m = m; a.n = n; a.p = p; a.freqs = freqs; a.F = F; a.fs = fs;
-  if (n_bands > 0) a.band_out = out; else a.ffdtf = out;
-  a.bin_lo = bin_lo; a.bin_hi = bin_hi; a.n_bands = n_bands; a.S_out = S_out;
-  a.ar_out = ar_out; a.V_out = V_out; a.info_yw = info_yw; a.info_tf = info_tf;
-  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.pivot_tau = pivot_tau; a.flags = flags;
-  if (measure == HMV_MEASURE_GPDC) { a.info_tf = nullptr; a.pivot_tau = 1.0; }
-  a.grid_hop = grid_hop; a.grid_nwin = grid_nwin; a.grid_T = ens.T;
-  a.stream = stream; a.aux_stream = aux_stream;
+// The entries whose K1 is not the single-trial one (ensemble, ensemble split, pairs, mix): measure-coded, no declared grid
+// but the ensemble's own two numbers, no K3 events.  `a` comes with its items, spectral request and run filled in.
+int sliding_k1_entry(SlidingArgs a, int measure, double* out, const int32_t* bin_lo, const int32_t* bin_hi, int n_bands,
+                     double* S_out, FitOut fit) {
+  if (int rc = measure_request(a.who, measure, n_bands, S_out, fit)) return rc;
+  if (int rc = need_output_after_sizes(a.who, a.it, out)) return rc;
+  a.measure = measure;
+  a.o = output(out, bin_lo, bin_hi, n_bands, false, S_out);
+  a.fit = fit;
   return sliding_impl(a);
 }
 }  // namespace
@@ -1466,9 +1519,11 @@ int hmv_sliding_ensemble_f64(int measure, const double* x, int64_t rec_stride, i
                              int64_t chunk, double pivot_tau, int64_t flags, int64_t grid_hop, int64_t grid_nwin,
                              void* stream, void* aux_stream) {
   const EnsDesc ens{trial_rec, trial_start, group_ptr, n_groups, T};
-  return sliding_ensemble_entry("hmv_sliding_ensemble_f64", measure, x, rec_stride, ld, ens, item_group, item_offset, n_items, m,
-                                n, p, freqs, F, fs, out, bin_lo, bin_hi, n_bands, S_out, ar_out, V_out, info_yw, info_tf,
-                                workspace, workspace_bytes, chunk, pivot_tau, flags, grid_hop, grid_nwin, stream, aux_stream);
+  SlidingArgs a{"hmv_sliding_ensemble_f64", MEAS_FFDTF, {x, rec_stride, ld, item_group, item_offset, n_items, m, n, p},
+                {grid_hop, 0, grid_nwin, T}, {freqs, F, fs}, {}, {},
+                {workspace, workspace_bytes, chunk, flags, stream, aux_stream, nullptr, nullptr}};
+  a.ens = &ens;
+  return sliding_k1_entry(a, measure, out, bin_lo, bin_hi, n_bands, S_out, {ar_out, V_out, info_yw, info_tf, pivot_tau});
 }
 
 int hmv_sliding_ensemble_split_f64(int measure, const double* x, int64_t rec_stride, int64_t ld, int64_t T,
@@ -1480,23 +1535,22 @@ int hmv_sliding_ensemble_split_f64(int measure, const double* x, int64_t rec_str
                                    int64_t workspace_bytes, int64_t chunk, double pivot_tau, int64_t flags,
                                    const int64_t* trial_rec_b, const int64_t* trial_start_b, int split, const double* R_base,
                                    const int64_t* item_base, void* stream, void* aux_stream) {
-  if (pad_of(m) >= 0)                                    // (a bad channel count is sliding_impl's -1)
-    if (int rc = ens_split_check("hmv_sliding_ensemble_split_f64", m, trial_rec_b, trial_start_b, split, R_base, item_base))
-      return rc;
+  const char* who = "hmv_sliding_ensemble_split_f64";
+  if (pad_of(m) >= 0)                                    // (a bad channel count is the driver's -1)
+    if (int rc = ens_split_check(who, m, trial_rec_b, trial_start_b, split, R_base, item_base)) return rc;
   EnsDesc ens{trial_rec, trial_start, group_ptr, n_groups, T};
   ens.trial_rec_b = trial_rec_b; ens.trial_start_b = trial_start_b; ens.split = split; ens.R_base = R_base;
   ens.item_base = item_base;
-  return sliding_ensemble_entry("hmv_sliding_ensemble_split_f64", measure, x, rec_stride, ld, ens, item_group, item_offset,
-                                n_items, m, n, p, freqs, F, fs, out, bin_lo, bin_hi, n_bands, S_out, ar_out, V_out, info_yw,
-                                info_tf, workspace, workspace_bytes, chunk, pivot_tau, flags, 0, 0, stream, aux_stream);
+  SlidingArgs a{who, MEAS_FFDTF, {x, rec_stride, ld, item_group, item_offset, n_items, m, n, p}, {0, 0, 0, T}, {freqs, F, fs},
+                {}, {}, {workspace, workspace_bytes, chunk, flags, stream, aux_stream, nullptr, nullptr}};
+  a.ens = &ens;
+  return sliding_k1_entry(a, measure, out, bin_lo, bin_hi, n_bands, S_out, {ar_out, V_out, info_yw, info_tf, pivot_tau});
 }
 
 // ---- pairs of recordings: the fused path with the pair K1 (pseudo-dyad surrogates) -------------------------------------
 int64_t hmv_pairs_workspace_bytes(int measure, int64_t chunk, int m, int n, int p, int F, int n_bands) {
-  // n_bands = -1: the full ffDTF together with S_out, as hmv_sliding_auto_workspace_bytes
-  const bool spectra = (n_bands == -1 && measure == HMV_MEASURE_FFDTF);
   if (n <= p) return -1;
-  return sliding_bytes(chunk, m, p, F, spectra ? 0 : n_bands, spectra, measure, 0);
+  return measure_bytes(measure, chunk, m, p, F, n_bands, 0);
 }
 
 int hmv_sliding_pairs_f64(int measure, const double* x, int64_t rec_stride, int64_t ld, int64_t T, const int64_t* rec_a,
@@ -1508,27 +1562,13 @@ int hmv_sliding_pairs_f64(int measure, const double* x, int64_t rec_stride, int6
                           void* aux_stream) {
   const char* who = "hmv_sliding_pairs_f64";
   (void)T;                                               // the caller has checked the windows against it
-  if (pad_of(m) >= 0)                                    // (a bad channel count is sliding_impl's -1)
+  if (pad_of(m) >= 0)                                    // (a bad channel count is the driver's -1)
     if (int rc = pairs_check(who, m, rec_b, split, R_base, base_a, base_b)) return rc;
-  if (measure < HMV_MEASURE_FFDTF || measure > HMV_MEASURE_GPDC)
-    return fail(-4, "hmv_sliding_pairs_f64: measure must be HMV_MEASURE_FFDTF, _DDTF or _GPDC");
-  if (n_bands < 0) return fail(-4, "hmv_sliding_pairs_f64: n_bands must be >= 0");
-  if (S_out && (measure != HMV_MEASURE_FFDTF || n_bands != 0))
-    return fail(-4, "hmv_sliding_pairs_f64: spectra come with the full ffDTF only");
-  if (pad_of(m) >= 0 && p >= 1 && p <= HMV_MAX_ORDER && n > p && !out && n_items != 0)
-    return fail(-4, "hmv_sliding_pairs_f64: null pointer / empty grid");
   const PairDesc pairs{rec_b, split, R_base, base_a, base_b};
-  SlidingArgs a{who};
-  a.measure = measure; a.pairs = &pairs;
-  a.x = x; a.rec_stride = rec_stride; a.ld = ld; a.item_rec = rec_a; a.item_start = item_start; a.n_items = n_items;
-  a.m = m; a.n = n; a.p = p; a.freqs = freqs; a.F = F; a.fs = fs;
-  if (n_bands > 0) a.band_out = out; else a.ffdtf = out;
-  a.bin_lo = bin_lo; a.bin_hi = bin_hi; a.n_bands = n_bands; a.S_out = S_out;
-  a.ar_out = ar_out; a.V_out = V_out; a.info_yw = info_yw; a.info_tf = info_tf;
-  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.pivot_tau = pivot_tau; a.flags = flags;
-  if (measure == HMV_MEASURE_GPDC) { a.info_tf = nullptr; a.pivot_tau = 1.0; }
-  a.stream = stream; a.aux_stream = aux_stream;
-  return sliding_impl(a);
+  SlidingArgs a{who, MEAS_FFDTF, {x, rec_stride, ld, rec_a, item_start, n_items, m, n, p}, {0, 0, 0, 0}, {freqs, F, fs},
+                {}, {}, {workspace, workspace_bytes, chunk, flags, stream, aux_stream, nullptr, nullptr}};
+  a.pairs = &pairs;
+  return sliding_k1_entry(a, measure, out, bin_lo, bin_hi, n_bands, S_out, {ar_out, V_out, info_yw, info_tf, pivot_tau});
 }
 
 // ---- weighted trial sums: the fused path with the mix K1 (label permutations of the condition contrast) ----------------
@@ -1547,9 +1587,7 @@ int hmv_lagcov_mix_f64(const double* Rt, int64_t n_trials, int64_t n_win, const 
 }
 
 int64_t hmv_mix_workspace_bytes(int measure, int64_t chunk, int m, int p, int F, int n_bands) {
-  // n_bands = -1: the full ffDTF together with S_out, as hmv_sliding_auto_workspace_bytes
-  const bool spectra = (n_bands == -1 && measure == HMV_MEASURE_FFDTF);
-  return sliding_bytes(chunk, m, p, F, spectra ? 0 : n_bands, spectra, measure, 0);
+  return measure_bytes(measure, chunk, m, p, F, n_bands, 0);
 }
 
 int hmv_sliding_mix_f64(int measure, const double* Rt, int64_t n_trials, int64_t n_win, const double* W, const double* scale,
@@ -1557,27 +1595,14 @@ int hmv_sliding_mix_f64(int measure, const double* Rt, int64_t n_trials, int64_t
                         const int32_t* bin_lo, const int32_t* bin_hi, int n_bands, double* S_out, double* ar_out,
                         double* V_out, int32_t* info_yw, int32_t* info_tf, void* workspace, int64_t workspace_bytes,
                         int64_t chunk, double pivot_tau, int64_t flags, void* stream, void* aux_stream) {
-  const char* who = "hmv_sliding_mix_f64";
-  if (measure < HMV_MEASURE_FFDTF || measure > HMV_MEASURE_GPDC)
-    return fail(-4, "hmv_sliding_mix_f64: measure must be HMV_MEASURE_FFDTF, _DDTF or _GPDC");
-  if (n_bands < 0) return fail(-4, "hmv_sliding_mix_f64: n_bands must be >= 0");
-  if (S_out && (measure != HMV_MEASURE_FFDTF || n_bands != 0))
-    return fail(-4, "hmv_sliding_mix_f64: spectra come with the full ffDTF only");
+  // (bad sizes: an empty batch as far as the entry's own check goes; the driver refuses them in their turn)
   const bool sizes_ok = n_trials >= 1 && n_win >= 1 && n_mix >= 1;
-  if (pad_of(m) >= 0 && p >= 1 && p <= HMV_MAX_ORDER && n > p && sizes_ok && !out)
-    return fail(-4, "hmv_sliding_mix_f64: null pointer / empty grid");
   const MixDesc mix{Rt, W, scale, n_trials, n_win, n_mix};
-  SlidingArgs a{who};
-  a.measure = measure; a.mix = &mix;
-  a.n_items = sizes_ok ? n_mix * n_win : 0;
-  a.m = m; a.n = n; a.p = p; a.freqs = freqs; a.F = F; a.fs = fs;
-  if (n_bands > 0) a.band_out = out; else a.ffdtf = out;
-  a.bin_lo = bin_lo; a.bin_hi = bin_hi; a.n_bands = n_bands; a.S_out = S_out;
-  a.ar_out = ar_out; a.V_out = V_out; a.info_yw = info_yw; a.info_tf = info_tf;
-  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.chunk = chunk; a.pivot_tau = pivot_tau; a.flags = flags;
-  if (measure == HMV_MEASURE_GPDC) { a.info_tf = nullptr; a.pivot_tau = 1.0; }
-  a.stream = stream; a.aux_stream = aux_stream;
-  return sliding_impl(a);
+  SlidingArgs a{"hmv_sliding_mix_f64", MEAS_FFDTF, {nullptr, 0, 0, nullptr, nullptr, sizes_ok ? n_mix * n_win : 0, m, n, p},
+                {0, 0, 0, 0}, {freqs, F, fs}, {}, {},
+                {workspace, workspace_bytes, chunk, flags, stream, aux_stream, nullptr, nullptr}};
+  a.mix = &mix;
+  return sliding_k1_entry(a, measure, out, bin_lo, bin_hi, n_bands, S_out, {ar_out, V_out, info_yw, info_tf, pivot_tau});
 }
 
 int64_t hmv_fad_workspace_bytes(int64_t n_series, int pmax) {

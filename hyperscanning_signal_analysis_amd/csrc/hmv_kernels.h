@@ -119,9 +119,10 @@ struct YwArgs {
   // <= p from the first order[item] + 1 lag blocks of its [p+1]-strided R, in its ws_tiles(p)-strided scratch, and its
   // [MP][MP][p] coefficients are written with the lags >= order[item] as +0.0.
   const int* order;
-  // internal (fused sliding path, default recursion only): the recursion does not write `ar`; the model stays in the final
-  // A generation's tiles of `ws` ([k][row][col] at tile (p & 1) * p), where the packing kernel of K3 reads it.  Windows
-  // re-solved by the LDL^T kernel still get their `ar` (their scratch is overwritten), flagged by the guard word.
+  // internal (fused sliding path -- capi.hip, sliding_k2 where the plan says from_tiles --, default recursion only): the
+  // recursion does not write `ar`; the model stays in the final A generation's tiles of `ws` ([k][row][col] at tile
+  // (p & 1) * p), where the packing kernel of K3 reads it.  Windows re-solved by the LDL^T kernel still get their `ar`
+  // (their scratch is overwritten), flagged by the guard word.
   int no_emit;
   // pivoted fallback (HMV_FLAG_YW_PIVOTED): behind the solver above, the windows it left with info != 0 are solved again
   // by the dense LU with partial pivoting (yw_lu.hip), which overwrites their ar, V and info and sets their route word to 2
@@ -137,6 +138,13 @@ struct YwAutoArgs {
   double* crit_out;         // optional [n_items][p]
 };
 long long yw_ws_tiles(int p);
+// Which LDL^T form a batch takes where none is asked for: the launch chain (true) or one launch (false).  One launch per
+// batch is the low-latency form (small batches, small tiles).  At 64 channels and hundreds of windows both forms are
+// bound by the same HBM traffic (~14 MB of tile operands per window, far more than any cache holds for a resident
+// batch) and the launch chain, whose every launch streams with the whole chip, is the faster one: 2.0 ms against 2.26 ms
+// for 599 windows (profiles/r02_ab_notes.md).  The one rule for launch_yw, the fused sliding step's chunks and the
+// restricted fits of block Granger causality (each block by its own padded size).
+inline bool yw_chain_by_shape(int m_pad, long long n_items) { return m_pad == 64 && n_items >= 128; }
 int launch_yw(const YwArgs& a, int m_pad, hipStream_t st);
 int launch_yw_lwr(const YwArgs& a, int m_pad, hipStream_t st);
 // yw_lu.hip: the LU over every window (all != 0) or over the windows whose info is not zero; the route word (the last int

@@ -1181,7 +1181,7 @@ int launch_tf_inv(const TfArgs& a_in, int m_pad, hipStream_t st, hipEvent_t ev_s
   if (fused) {
     if (!a.P || !a.den || !a.wcount || !a.ready || !a.missed || a.lag < 1) return -3;
     if (a.bands && (!a.band_lo || !a.band_hi || a.nb < 1 || a.F % 32 != 0 || a.F > tf_band_max_F(m_pad) || a.A)) return -3;
-    // wcount, ready and missed[0] are one zeroed block (capi.hip lays them out back to back)
+    // wcount, ready and missed[0] are one zeroed block (capi.hip, tf_ffdtf_impl, lays them out back to back)
     if (const hipError_t e = hipMemsetAsync(a.wcount, 0, sizeof(int) * (2 * (size_t)a.n_items + 1), st)) return (int)e;
   } else {
     a.ff = nullptr;

@@ -85,7 +85,7 @@ int launch_yw_lwr(const YwArgs& a, int m_pad, hipStream_t st) {
 }
 
 // Windows of the default form that one compute unit holds at once, asked of the runtime (registers and LDS of the build in
-// use decide it, not a constant here); the sliding step sizes its K2 -> K3 hand-over by it (capi.hip).  0: not known.
+// use decide it, not a constant here); the sliding step sizes its K2 -> K3 hand-over by it (capi.hip, k3_split_point, for sliding_k2).  0: not known.
 int yw_lwr_occupancy(int m_pad) {
   if (tuning(4 /* HMV_TUNE_YW_FORM */) == 3 || tuning(4) == 4) return 0;
   int occ = 0;

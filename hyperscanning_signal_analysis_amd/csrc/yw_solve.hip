@@ -431,11 +431,8 @@ static int launch_yw_unpivoted(const YwArgs& a_in, int m_pad, hipStream_t st) {
     a.only_guarded = 1;
     a.tiled = 0;
   }
-  // One launch per batch is the low-latency form (small batches, small tiles).  At 64 channels and hundreds of
-  // windows both forms are bound by the same HBM traffic (~14 MB of tile operands per window, far more than any
-  // cache holds for a resident batch) and the launch chain, whose every launch streams with the whole chip, is the
-  // faster one: 2.0 ms against 2.26 ms for 599 windows (profiles/r02_ab_notes.md).
-  const bool one_launch = a.tiled == 0 || (a.tiled < 0 && !(m_pad == 64 && a.n_items >= 128));
+  // one launch per batch, or the launch chain where it is asked for or the batch's shape calls for it (hmv_kernels.h)
+  const bool one_launch = a.tiled == 0 || (a.tiled < 0 && !yw_chain_by_shape(m_pad, a.n_items));
   if (one_launch) {
     if (!a.only_guarded)
       if (const hipError_t e = hipMemsetAsync(a.info, 0, sizeof(int) * a.n_items, st)) return (int)e;
