@@ -150,6 +150,8 @@ SIGNATURES = {
     "hmv_decimate_tile": (c_int, [c_int, c_int]),
     "hmv_decimate_fir_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_int, c_void_p,
                                      c_int64, c_int64, c_void_p]),
+    "hmv_phase_sync_c128": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 # option bits of the fused entry points (include/hypermvar.h)
@@ -173,6 +175,9 @@ TUNE_K3_SPLIT = 6
 # limits of hmv_decimate_fir_f64
 MAX_DECIMATE = 32
 MAX_DECIMATE_TAPS = 641
+# modes of hmv_phase_sync_c128
+PHASE_UNIT = 0
+PHASE_RAW = 1
 
 
 _lib = None

@@ -430,4 +430,19 @@ struct DecimateArgs {
 int decimate_tile(int q, int n_taps);      // outputs per workgroup
 int launch_decimate(const DecimateArgs& a, hipStream_t st);
 
+// ---- phase synchrony of analytic signals (phase_sync.hip) ---------------------------------------------------------
+struct PhaseSyncArgs {
+  const double2* z;         // [n_rec][m][ld] complex (re, im), strides in complex elements; T samples used
+  long long rec_stride, ld, T, n_rec;
+  const long long* item_rec;    // [n_items] (device)
+  const long long* item_start;  // [n_items] (device)
+  long long n_items;
+  int m, n, mode;           // channels, window length, HMV_PHASE_UNIT / HMV_PHASE_RAW
+  double* coherency;        // optional [n_items][2][m][m]
+  double* mag;              // optional [n_items][m][m]
+  double* lagged;           // optional [n_items][m][m]
+  int* info;                // [n_items]
+};
+int launch_phase_sync(const PhaseSyncArgs& a, int m_pad, hipStream_t st);
+
 }  // namespace hmv

@@ -171,6 +171,67 @@ __device__ __forceinline__ void store_acc(const double (&acc)[LG][NT][NT], doubl
   });
 }
 
+// ---- two planes, lag 0: the Hermitian Gram matrix C = U U^H of a complex block (phase_sync.hip) ---------------------
+// The chunk is staged as two planes (re, im) of TC samples per channel and no halo; the row stride keeps the 6 (mod 32).
+// Wave wv owns the row blocks 4 * I + wv, I < NT (interleaved, not a strip), so that in every wave the accumulator [I][J]
+// lies on or above the diagonal exactly when J >= I: the triangle is a compile-time loop and the four waves carry the
+// same NT (NT + 1) / 2 tiles each.  Lane l holds element (row 4 * (4 * I + wv) + (l >> 4), col 16 * J + (l & 15)).
+constexpr int S2 = TC + 6;         // row stride 70 = 6 (mod 32)
+template <int NT>
+constexpr int NLD2 = 16 * NT * TC / 256;         // staged complex elements per thread
+
+__device__ __forceinline__ const double* a_operand2(const double* xs, int wv, int l) {
+  return xs + (4 * wv + (l & 3)) * S2 + (l >> 4);
+}
+__device__ __forceinline__ const double* b_operand2(const double* xs, int l) { return xs + (l & 15) * S2 + (l >> 4); }
+
+// the chunk that starts at sample t0: src(ch, t) is the complex sample (re in .x, im in .y), zero where there is none.
+// All loads in flight, then the LDS stores; the first barrier waits for the k-steps of the previous chunk.
+template <int NT, typename Src>
+__device__ __forceinline__ void stage_chunk2(double* xre, double* xim, int t0, Src&& src) {
+  double2 stg[NLD2<NT>];
+#pragma unroll
+  for (int r = 0; r < NLD2<NT>; ++r) {
+    const int idx = threadIdx.x + 256 * r;
+    stg[r] = src(idx / TC, t0 + idx % TC);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < NLD2<NT>; ++r) {
+    const int idx = threadIdx.x + 256 * r;
+    xre[(idx / TC) * S2 + idx % TC] = stg[r].x;
+    xim[(idx / TC) * S2 + idx % TC] = stg[r].y;
+  }
+  __syncthreads();
+}
+
+// the k-steps of one staged chunk for the tiles J >= I:  re += re_i re_j + im_i im_j,  im += im_i re_j - re_i im_j, per
+// accumulator in this order of products whatever NT.  xa / xb: a_operand2 / b_operand2 of the re plane; the im plane
+// lies `plane` doubles behind it.
+template <int NT>
+__device__ __forceinline__ void ksteps_herm(const double* xa, const double* xb, int plane, int steps, double (&re)[NT][NT],
+                                            double (&im)[NT][NT]) {
+  for (int ts = 0; ts < steps; ++ts) {
+    double ar[NT], ai[NT], br[NT], bi[NT];
+#pragma unroll
+    for (int I = 0; I < NT; ++I) {
+      ar[I] = xa[16 * I * S2 + 4 * ts];
+      ai[I] = xa[plane + 16 * I * S2 + 4 * ts];
+      br[I] = xb[16 * I * S2 + 4 * ts];
+      bi[I] = xb[plane + 16 * I * S2 + 4 * ts];
+    }
+#pragma unroll
+    for (int I = 0; I < NT; ++I)
+#pragma unroll
+      for (int J = I; J < NT; ++J) {
+        re[I][J] = mfma4(ar[I], br[J], re[I][J]);
+        re[I][J] = mfma4(ai[I], bi[J], re[I][J]);
+        im[I][J] = mfma4(ai[I], br[J], im[I][J]);
+        im[I][J] = mfma4_nega(ar[I], bi[J], im[I][J]);
+      }
+  }
+}
+
 // host: f(std::integral_constant<int, NT>) for the padded channel count m_pad = 16 * NT; -1 for any other
 template <typename F>
 int for_nt(int m_pad, F&& f) {

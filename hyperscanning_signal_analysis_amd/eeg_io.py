@@ -12,7 +12,8 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["filter_eeg", "preprocess_eeg", "load_eeg_signals", "load_dyad_block", "decimation_taps", "DECIMATION_DESIGNS"]
+__all__ = ["filter_eeg", "preprocess_eeg", "load_eeg_signals", "load_dyad_block", "decimation_taps", "DECIMATION_DESIGNS",
+           "band_response", "PHASE_MEASURES", "resolve_phase_measures", "resolve_bands_hz"]
 
 
 def filter_eeg(data_tc, fs, low_cutoff_hz=None, high_cutoff_hz=None):
@@ -64,6 +65,84 @@ def decimation_taps(q, design="decimate"):
     if h.ndim != 1 or h.size % 2 == 0 or not 3 <= h.size <= _lib.MAX_DECIMATE_TAPS:
         raise ValueError(f"taps must be a 1-D array of odd length in 3..{_lib.MAX_DECIMATE_TAPS}, got shape {h.shape}")
     return h
+
+
+PHASE_MEASURES = ("plv", "ciplv", "coh", "imcoh")
+
+
+def resolve_phase_measures(measures):
+    """`measures` of the phase-synchrony calls -> a tuple without repeats, in the caller's order.  Needs no GPU."""
+    if isinstance(measures, str):
+        measures = (measures,)
+    out = tuple(dict.fromkeys(measures))
+    unknown = [q for q in out if q not in PHASE_MEASURES]
+    if not out or unknown:
+        raise ValueError(f"phase synchrony measures must be a non-empty subset of {PHASE_MEASURES}, got {tuple(measures)!r}")
+    return out
+
+
+def resolve_bands_hz(bands_hz, fs):
+    """`bands_hz` -> a tuple of (lo, hi) in Hz with None for an edge that is not there (lo <= 0, hi >= fs / 2), as
+    `band_response` reads them.  ValueError for an empty list, an entry that is not a pair, or lo >= hi.  Needs no GPU."""
+    nyq = float(fs) / 2.0
+    if not nyq > 0.0:
+        raise ValueError(f"the sampling rate must be positive, got {fs!r}")
+    out = []
+    for band in bands_hz:
+        if np.ndim(band) != 1 or len(band) != 2:
+            raise ValueError(f"bands_hz must be a sequence of (lo, hi) pairs in Hz, got the entry {band!r}")
+        lo, hi = band
+        lo = None if lo is None or float(lo) <= 0.0 else float(lo)
+        hi = None if hi is None or float(hi) >= nyq else float(hi)
+        if hi is not None and not hi > 0.0 or (lo is not None and not lo < nyq) or (lo is not None and hi is not None and lo >= hi):
+            raise ValueError(f"band {band!r}: the lower edge must lie below the upper edge and both inside (0, {nyq:g}) Hz")
+        out.append((lo, hi))
+    if not out:
+        raise ValueError("bands_hz is empty: at least one (lo, hi) band is needed")
+    return tuple(out)
+
+
+def band_response(T, fs, lo=None, hi=None, order=4):
+    """The one-sided zero-phase response of a Butterworth band on the FFT grid f_k = np.fft.fftfreq(T, 1 / fs), as (T,)
+    float64:  resp[k] = |H(|f_k|)|^2 * w[k].  H is the response (`sosfreqz`) of `butter(order, [lo, hi] / (fs / 2),
+    btype="band", output="sos")`, squared in magnitude as forward-backward filtering applies it; w holds the weights of
+    `scipy.signal.hilbert`: 1 at k = 0 and (T even) k = T / 2, 2 for 0 < k < T / 2, 0 on the negative frequencies.
+    lo None or <= 0: a low-pass at hi; hi None or >= fs / 2: a high-pass at lo; both: w alone, the plain Hilbert transform.
+
+    The analytic band signal of a row x is z = ifft(fft(x) * resp)  (`Engine.analytic_signal`).  It is CIRCULAR: the
+    samples within the filter's transient of either end of the recording see the other end.  Nothing is padded; keep the
+    windows away from the two ends by the transient (a few periods of the lower band edge), or accept the wrap.  This is
+    a definition of its own, not `sosfiltfilt` followed by `hilbert`: the two agree away from the ends (PLV to < 1e-3 on
+    the planted dyad of tests/test_phase_sync_cpu.py) and differ in how they treat the ends."""
+    T = int(T)
+    fs = float(fs)
+    if T < 1 or not fs > 0.0 or int(order) < 1:
+        raise ValueError(f"band_response: need T >= 1, fs > 0 and order >= 1, got T={T}, fs={fs}, order={order}")
+    nyq = fs / 2.0
+    lo = None if lo is None or float(lo) <= 0.0 else float(lo)
+    hi = None if hi is None or float(hi) >= nyq else float(hi)
+    if lo is not None and hi is not None and lo >= hi:
+        raise ValueError(f"band_response: the lower edge ({lo:g} Hz) must lie below the upper edge ({hi:g} Hz)")
+    k = np.arange(T)
+    w = np.zeros(T)
+    w[0] = 1.0
+    w[(k > 0) & (2 * k < T)] = 2.0
+    if T % 2 == 0:
+        w[T // 2] = 1.0
+    if lo is None and hi is None:
+        return w
+    from scipy.signal import butter, sosfreqz
+    try:
+        if lo is None:
+            sos = butter(int(order), hi / nyq, btype="low", output="sos")
+        elif hi is None:
+            sos = butter(int(order), lo / nyq, btype="high", output="sos")
+        else:
+            sos = butter(int(order), [lo / nyq, hi / nyq], btype="band", output="sos")
+    except ValueError as e:
+        raise ValueError(f"band_response: no Butterworth filter for the band ({lo}, {hi}) Hz at fs = {fs:g} Hz: {e}") from None
+    _, h = sosfreqz(sos, worN=2.0 * np.pi * np.abs(np.fft.fftfreq(T, 1.0 / fs)) / fs)
+    return np.abs(h) ** 2 * w
 
 
 def preprocess_eeg(data_tc, time_s, channel_names, fs, event_duration_s=None, channel_subset=None,

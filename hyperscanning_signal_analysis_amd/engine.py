@@ -286,6 +286,7 @@ class Engine:
         self._ws = {}
         self._aux = {}        # second HIP stream for chunk overlap in the fused path
         self._taps = {}       # decimation filters on the device, per (q, design)
+        self._resp = {}       # band responses of the analytic signal on the device, per (T, fs, lo, hi, order)
 
     # ------------------------------------------------------------------ helpers
     def stream(self):
@@ -1998,6 +1999,153 @@ class Engine:
                                                int(h.numel()), y3.data_ptr(), y3.stride(0), y3.stride(1), self.stream())
         _lib.check(rc, "hmv_decimate_fir_f64")
         return (y3[0] if x.dim() == 2 else y3) if out is None else out
+
+    # ------------------------------------------------------------------ phase synchrony (phase_sync.hip)
+    def band_response(self, T: int, fs: float, lo=None, hi=None, order: int = 4):
+        """Device copy of `eeg_io.band_response(T, fs, lo, hi, order)`, built and uploaded once per argument tuple."""
+        from .eeg_io import band_response
+        key = (int(T), float(fs), None if lo is None else float(lo), None if hi is None else float(hi), int(order))
+        r = self._resp.get(key)
+        if r is None:
+            r = self._resp[key] = self.to_device(band_response(*key))
+        return r
+
+    def analytic_signal(self, x: torch.Tensor, resp: torch.Tensor, out: torch.Tensor | None = None):
+        """z = ifft(fft(x) * resp) along time: x (n_rec, m, T) or (m, T) float64 on the device, resp (T,) or (n_bands, T)
+        float64 (`band_response`) -> complex128 (n_rec, [n_bands,] m, T), without the recording axis for a 2-D x.  Circular
+        (see `eeg_io.band_response`).  `torch.fft` on the engine's stream, one forward transform per recording and one
+        inverse per recording and band, each over that recording's m rows alone: a recording's bits do not depend on what
+        else is in the call.  m is not limited to 64."""
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.device != self.device or x.dim() not in (2, 3):
+            raise ValueError(f"analytic_signal: x must be a float64 tensor (n_rec, m, T) or (m, T) on {self.device}")
+        x3 = x[None] if x.dim() == 2 else x
+        n_rec, m, T = x3.shape
+        if (not isinstance(resp, torch.Tensor) or resp.dtype != torch.float64 or resp.device != self.device
+                or resp.dim() not in (1, 2) or resp.shape[-1] != T or T < 1):
+            raise ValueError(f"analytic_signal: resp must be a float64 tensor (T,) or (n_bands, T) with T = {T} on {self.device}")
+        r2 = resp[None] if resp.dim() == 1 else resp
+        nb = int(r2.shape[0])
+        z = torch.empty(n_rec, nb, m, T, dtype=torch.complex128, device=self.device) if out is None else out
+        for r in range(n_rec):
+            X = torch.fft.fft(x3[r].contiguous(), dim=-1)
+            for b in range(nb):
+                torch.fft.ifft(X * r2[b], dim=-1, out=z[r, b])
+        if out is not None:
+            return out
+        z = z[:, 0] if resp.dim() == 1 else z
+        return z[0] if x.dim() == 2 else z
+
+    def _phase_sync(self, z, item_rec, item_start, n, mode, mag, lagged, coherency):
+        n_rec, m, T = z.shape
+        n_items = int(item_rec.numel())
+        info = torch.empty(n_items, dtype=torch.int32, device=self.device)
+        out = {}
+        if mag:
+            out["mag"] = self.empty(n_items, m, m)
+        if lagged:
+            out["lagged"] = self.empty(n_items, m, m)
+        if coherency:
+            out["coherency"] = self.empty(n_items, 2, m, m)
+        with torch.cuda.device(self.device):
+            rc = self.lib.hmv_phase_sync_c128(z.data_ptr(), z.stride(0), z.stride(1), T, n_rec, m, item_rec.data_ptr(),
+                                              item_start.data_ptr(), n_items, int(n), int(mode), _ptr(out.get("coherency")),
+                                              _ptr(out.get("mag")), _ptr(out.get("lagged")), info.data_ptr(), self.stream())
+        _lib.check(rc, "hmv_phase_sync_c128")
+        out["info"] = info
+        return out
+
+    def phase_sync(self, z: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, mode: int, *,
+                   want=("mag", "lagged"), coherency: bool = False):
+        """Phase synchrony of every window (`hmv_phase_sync_c128`): z (n_rec, m, T) complex128 on the device (unit stride
+        along time; a strided view is read in place), item i = the n samples of recording item_rec[i] from item_start[i].
+        mode `_lib.PHASE_UNIT`: mag = PLV, lagged = ciPLV of the unit phasors; `_lib.PHASE_RAW`: mag = coherence, lagged =
+        imaginary coherence of z itself.  -> {"mag", "lagged": (n_items, m, m) as named in `want`, "coherency": (n_items, 2,
+        m, m) (Re R, Im R) if asked, "info": int32 (n_items,)}: 1 = a non-finite sample (the item is NaN), 2 = RAW only, a
+        channel of zero power (its row and column are NaN).  On the engine's stream; nothing is read back after the check
+        of the item tables."""
+        if (not isinstance(z, torch.Tensor) or z.dtype != torch.complex128 or z.device != self.device or z.dim() != 3
+                or z.shape[1] < 1):
+            raise ValueError(f"phase_sync: z must be a complex128 tensor (n_rec, m, T) on {self.device}")
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if any(w not in ("mag", "lagged") for w in want) or not (want or coherency):
+            raise ValueError(f"phase_sync: want must name 'mag' and / or 'lagged' (or coherency=True), got {want!r}")
+        if int(mode) not in (_lib.PHASE_UNIT, _lib.PHASE_RAW):
+            raise ValueError(f"phase_sync: mode must be PHASE_UNIT (0) or PHASE_RAW (1), got {mode!r}")
+        self.pad(z.shape[1])
+        validate_items(z, item_rec, item_start, n, 0)
+        if z.shape[0] > 0 and (z.stride(2) != 1 or z.stride(1) < z.shape[2] or z.stride(0) < z.shape[1] * z.stride(1)):
+            z = z.contiguous()
+        return self._phase_sync(z, item_rec, item_start, n, mode, "mag" in want, "lagged" in want, bool(coherency))
+
+    def sliding_phase_sync(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, fs: float,
+                           bands_hz, *, measures=("plv",), order: int = 4, check=True, max_workspace_bytes: int = 8 << 30):
+        """Band-limited phase synchrony per window: x (n_rec, m, T) float64 on the device -> {measure: (n_items, n_bands, m,
+        m), "info": int32 (n_items, n_bands)} for `measures` out of ("plv", "ciplv", "coh", "imcoh") and the bands
+        `bands_hz` = ((lo, hi), ...) in Hz (Butterworth of `order`, applied in the frequency domain: `eeg_io.band_response`).
+        The analytic signal is formed slab by slab -- some recordings times some bands, as many as keep the complex arrays
+        alive at one time under `max_workspace_bytes` -- and each slab is one kernel call per mode (PLV / ciPLV: unit
+        phasors; coh / imcoh: the signal itself), both on the same z.  Bit-identical to `phase_sync(analytic_signal(..))`
+        by hand.  check=True: ValueError naming the first (recording, window, band) whose info is not 0; check="nan": the
+        arrays come back with their NaNs."""
+        from .eeg_io import resolve_bands_hz, resolve_phase_measures
+        measures = resolve_phase_measures(measures)
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.device != self.device or x.dim() != 3:
+            raise ValueError(f"sliding_phase_sync: x must be a float64 tensor (n_rec, m, T) on {self.device}")
+        if check is not True and check != "nan":
+            raise ValueError(f"sliding_phase_sync: check must be True or 'nan', got {check!r}")
+        n_rec, m, T = x.shape
+        self.pad(m)
+        bands = resolve_bands_hz(bands_hz, fs)
+        validate_items(x, item_rec, item_start, n, 0)
+        nb, n_items = len(bands), int(item_rec.numel())
+        resp = torch.stack([self.band_response(T, fs, lo, hi, order) for lo, hi in bands])
+        modes = [(mode, [q for q in measures if q in names], names) for mode, names in
+                 ((_lib.PHASE_UNIT, ("plv", "ciplv")), (_lib.PHASE_RAW, ("coh", "imcoh")))]
+        modes = [(mode, qs, names) for mode, qs, names in modes if qs]
+        out = {q: self.empty(n_items, nb, m, m) for q in measures}
+        info = torch.zeros(n_items, nb, dtype=torch.int32, device=self.device)
+        if n_items:
+            # slabs: B bands of R recordings; alive with them are one recording's spectrum and one product
+            unit = 16 * m * T
+            B = int(max(1, min(nb, int(max_workspace_bytes) // unit - 2)))
+            R = int(max(1, min(n_rec, (int(max_workspace_bytes) // unit - 2) // nb))) if B == nb else 1
+            rec_host = item_rec.cpu()
+            for r0 in range(0, n_rec, R):
+                r1 = min(n_rec, r0 + R)
+                if R >= n_rec:
+                    idx, rec_s, start_s = None, item_rec, item_start
+                else:
+                    idx = torch.nonzero((rec_host >= r0) & (rec_host < r1)).flatten().to(self.device)
+                    if idx.numel() == 0:
+                        continue
+                    rec_s, start_s = item_rec[idx] - r0, item_start[idx]
+                for b0 in range(0, nb, B):
+                    b1 = min(nb, b0 + B)
+                    z = self.analytic_signal(x[r0:r1], resp[b0:b1])                  # (r1 - r0, b1 - b0, m, T)
+                    # the slab as (r1 - r0) * (b1 - b0) recordings; items window-major, band-minor
+                    bb = torch.arange(b1 - b0, dtype=torch.int64, device=self.device)
+                    rec_z = (rec_s[:, None] * (b1 - b0) + bb[None, :]).reshape(-1)
+                    start_z = start_s[:, None].expand(-1, b1 - b0).reshape(-1)
+                    for mode, qs, names in modes:
+                        res = self._phase_sync(z.view(-1, m, T), rec_z, start_z, n, mode, names[0] in qs, names[1] in qs,
+                                               False)
+                        sel = slice(None) if idx is None else idx
+                        for q, key in zip(names, ("mag", "lagged")):
+                            if q in qs:
+                                out[q][sel, b0:b1] = res[key].view(-1, b1 - b0, m, m)
+                        info[sel, b0:b1] = torch.maximum(info[sel, b0:b1], res["info"].view(-1, b1 - b0))
+                    del z
+        if check is True and n_items:
+            bad = torch.nonzero(info.cpu())
+            if bad.numel():
+                it, b = (int(v) for v in bad[0])
+                code = int(info[it, b])
+                why = {1: "a non-finite sample in the window", 2: "a channel of zero power in the window"}.get(code, "?")
+                raise ValueError(f"sliding_phase_sync: recording {int(item_rec[it])}, window at sample "
+                                 f"{int(item_start[it])} (item {it}), band {b} {bands[b]!r} Hz: info = {code} ({why}); "
+                                 f"check='nan' returns the arrays with their NaNs")
+        out["info"] = info
+        return out
 
 
 _default = None

@@ -234,7 +234,7 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
         psd_bandwidth=2.0, save_full=False, skip_existing=True, reader=None, engine=None, world=1, rank=0,
         verbose=True, prefetch=2, timing=None, save_workers=4, compresslevel=0, measures=("ffdtf",), significance=None,
         max_model_order=20, crit_type="AIC", validation_lags=None, block_granger=False, pivoted_fallback=None,
-        decimate=None, decimate_design="decimate"):
+        decimate=None, decimate_design="decimate", phase_sync=None):
     """Process every dyad under <root>/EEG.  Per dyad one `<out_dir>/<dyad>_ffdtf.npz` with, per segment `<task>/<event>`:
         <seg>/ffdtf_bands   (windows, n, n, n_bands)   band-integrated ffDTF of every window
         <seg>/ffdtf         (windows, n, n, F)         only with save_full=True (8.4 MB per window at 64 channels)
@@ -265,6 +265,13 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                                                        (index 1) and the time-domain values (`Engine.sliding_block_granger`;
                                                        split = the child's channel count); meta then says
                                                        "block_granger": true.  Needs an integer model_order.
+        <seg>/phase_<measure>   (windows, n_bands, n, n)   only with phase_sync=(...), a tuple out of ("plv", "ciplv", "coh",
+                                                       "imcoh"): band-limited phase synchrony of the MVAR leg's windows
+                                                       in the bands `bands` (Hz), from the segment block after the same
+                                                       filtering and decimation (`Engine.sliding_phase_sync`; the analytic
+                                                       signal is circular over the segment).  NaN where a window holds a
+                                                       non-finite sample or, for coh / imcoh, a channel of zero power; meta
+                                                       then says "phase_sync": [...].  None (default): nothing changes.
         <seg>/acf_fraction  (windows,)                 with validation_lags: share of the residual correlations beyond
                                                        1.96 / sqrt(N)
       pivoted_fallback: windows that the Yule-Walker solvers refuse are solved by the pivoted LU, as the reference's
@@ -296,6 +303,10 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
     if significance is not None:
         from .surrogates import check_significance_dict
         significance = check_significance_dict(significance)
+    if phase_sync is not None:                      # the arguments, before anything touches a device
+        from .eeg_io import resolve_bands_hz, resolve_phase_measures
+        phase_sync = resolve_phase_measures(phase_sync)
+        resolve_bands_hz(bands, float("inf"))       # not empty, pairs, lo < hi; the edges against fs / 2 per segment
     auto = model_order is None
     if block_granger and auto:
         raise ValueError("escan_batch.run(block_granger=True): the automatic model order (model_order=None) is not "
@@ -363,6 +374,8 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                     meta["block_granger"] = True
                 if dec is not None:
                     meta["decimate"], meta["decimate_design"] = dec
+                if phase_sync is not None:
+                    meta["phase_sync"] = list(phase_sync)
                 names_out, freqs_out = None, None
                 tg = time.perf_counter()
                 pending = []                                       # device results of this dyad, fetched after the last launch
@@ -445,6 +458,10 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                                 split=sum(1 for nm in seg["names"] if nm.endswith("_ch")), **yw_kw)
                             extra["block_gc_bands"] = gc_f.masked_fill_(gc_bad.view(-1, 1, 1), float("nan"))
                             extra["block_gc_time"] = gc_t.masked_fill_(gc_bad.view(-1, 1), float("nan"))
+                        if phase_sync is not None:               # no model: the same windows, the bands in Hz
+                            ps = eng.sliding_phase_sync(xd, rec_i, st_i, W, fs, bands, measures=phase_sync, check="nan")
+                            for q_ in phase_sync:
+                                extra[f"phase_{q_}"] = ps[q_]
                         if significance is not None:             # the child block comes first (segment_block)
                             split = sum(1 for nm in seg["names"] if nm.endswith("_ch"))
                             for meas in measures:

@@ -12,6 +12,8 @@ picks for it -- the reference's own default, `optimal_model_order=None` -- selec
 `sliding_pseudo_dyad_significance` tests them against shuffled partners: participant A of one dyad with participant B of another.
 `decimate` is the anti-aliased integer-factor decimation to run BEFORE any of them on low-passed recordings
 (`scipy.signal.decimate(..., ftype='fir', zero_phase=True)` / `resample_poly(x, 1, q)` on the device).
+`sliding_phase_sync` is the band-limited phase synchrony of the same windows (PLV, ciPLV, coherence, imaginary coherence of
+the analytic signal): no model, no order, no window refused for its conditioning.
 `sliding_fad` is `fad_decomposition` (mtmvar.py:607-757) of every channel of every window.
 `sliding_ensemble` / `sliding_ensemble_epochs` are the event-locked form: the reference's functions take `signals` of shape
 (channels, samples, trials) and fit ONE model to the trial-averaged covariances (`count_corr`, mtmvar.py:54-85); here a
@@ -24,6 +26,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from .distributed import DEFAULT_BANDS
 from .engine import Engine, default_engine
 
 __all__ = ["window_positions", "hop_positions", "create_windows", "sliding_ffdtf", "sliding_ffdtf_device", "window_items",
@@ -31,7 +34,8 @@ __all__ = ["window_positions", "hop_positions", "create_windows", "sliding_ffdtf
            "sliding_significance", "ensemble_items", "sliding_ensemble", "sliding_ensemble_epochs",
            "sliding_ensemble_significance", "sliding_ensemble_epochs_significance", "sliding_pseudo_dyad_significance",
            "sliding_model_validation", "validation_p_values", "sliding_ensemble_contrast", "sliding_ensemble_epochs_contrast",
-           "sliding_block_granger_significance", "sliding_block_granger_pseudo_dyad_significance", "decimate"]
+           "sliding_block_granger_significance", "sliding_block_granger_pseudo_dyad_significance", "decimate",
+           "sliding_phase_sync"]
 
 
 def decimate(x, fs, q, design="decimate", engine: Engine | None = None):
@@ -308,6 +312,40 @@ def sliding_block_granger(x, window_size, n_windows, p, freqs, fs, *, split, hop
     spectral, time = eng.sliding_block_granger(xd, item_rec, item_start, w, p, freqs, fs, split=split, bands=bands,
                                                check=check, grid=regular_grid(positions, w, p))
     return _to_host((spectral.view(n_rec, len(positions), 2, -1), time.view(n_rec, len(positions), 4)), single)
+
+
+def sliding_phase_sync(x, window_size, n_windows, fs, bands_hz=DEFAULT_BANDS, *, hop=None, measures=("plv",), order=4,
+                       check=True, engine: Engine | None = None, max_workspace_bytes: int = 8 << 30):
+    """NumPy (or tensor) in / NumPy out: band-limited phase synchrony of every window (`Engine.sliding_phase_sync`).  x: (m, T)
+    or (n_rec, m, T) -> {measure: (n_rec, n_windows, n_bands, m, m)} for `measures` out of ("plv", "ciplv", "coh", "imcoh"),
+    without the leading axis for a single recording; with check="nan" also "info" (n_rec, n_windows, n_bands).  `bands_hz`:
+    (lo, hi) pairs in Hz (not bin ranges on a frequency grid, which is what `bands` means in this module); the analytic
+    band signal is `eeg_io.band_response`'s, circular at the ends of the recording.  Windows from `window_positions`, or
+    every `hop` samples when `hop` is given.  No model is fitted: there is no order and no window is refused for its
+    conditioning."""
+    from .eeg_io import resolve_bands_hz, resolve_phase_measures
+    measures = resolve_phase_measures(measures)                  # the arguments first: nothing has touched a device yet
+    bands_hz = tuple(bands_hz)
+    resolve_bands_hz(bands_hz, fs)
+    if check is not True and check != "nan":
+        raise ValueError(f"sliding_phase_sync: check must be True or 'nan', got {check!r}")
+    x = np.asarray(x, dtype=np.float64) if not isinstance(x, torch.Tensor) else x
+    if x.ndim not in (2, 3):
+        raise ValueError(f"sliding_phase_sync: x must be (m, T) or (n_rec, m, T), got shape {tuple(x.shape)}")
+    single = x.ndim == 2
+    positions, w = _positions(int(x.shape[-1]), window_size, n_windows, hop)
+    eng = engine or default_engine()
+    if isinstance(x, torch.Tensor):
+        xd = (x[None] if single else x).to(device=eng.device, dtype=torch.float64)
+    else:
+        xd = eng.to_device(x[None] if single else x)
+    n_rec, m, T = xd.shape
+    item_rec, item_start = window_items(n_rec, positions, eng.device)
+    res = eng.sliding_phase_sync(xd, item_rec, item_start, w, fs, bands_hz, measures=measures, order=order, check=check,
+                                 max_workspace_bytes=max_workspace_bytes)
+    keys = measures + (("info",) if check == "nan" else ())
+    out = {k: res[k].view(n_rec, len(positions), len(bands_hz), *res[k].shape[2:]).cpu().numpy() for k in keys}
+    return {k: v[0] for k, v in out.items()} if single else out
 
 
 def sliding_significance(x, window_size, n_windows, p, freqs, fs, bands, *, measure, null, n_surrogates, seed, split=None,

@@ -748,6 +748,38 @@ int hmv_decimate_tile(int q, int n_taps);
 int hmv_decimate_fir_f64(const double* x, int64_t rec_stride, int64_t ld, int64_t T, int64_t n_rec, int m, int q,
                          const double* h, int n_taps, double* y, int64_t y_rec_stride, int64_t y_ld, void* stream);
 
+/* Phase synchrony of analytic signals per window (csrc/phase_sync.hip): PLV, ciPLV, coherence and imaginary coherence.
+ * The reference forms the analytic signal on the host (sosfiltfilt, then hilbert: src/eeg_alpha_ibi_ffdtf.py:271-365,
+ * src/warsaw_pilot_data.py:269-283); here it is eeg_io.band_response / Engine.analytic_signal, and this entry is the
+ * per-window statistic.  z: [n_rec][m][ld] complex128 as interleaved (re, im) doubles, 16-byte aligned, T samples used;
+ * rec_stride and ld are counted in COMPLEX elements.  Item i is the window of n samples of recording item_rec[i] that
+ * starts at item_start[i] (device arrays; keeping start + n <= T is the caller's -- a sample outside the recording is
+ * read as zero, never from memory).  With channels i, j < m:
+ *     mode HMV_PHASE_UNIT:  u_i[t] = z_i[t] / |z_i[t]|   (0 where |z_i[t]| == 0)
+ *     mode HMV_PHASE_RAW:   u_i[t] = z_i[t]
+ *     C_ij = sum_t u_i[t] conj(u_j[t]):   Re C_ij = sum re_i re_j + im_i im_j,   Im C_ij = sum im_i re_j - re_i im_j
+ *     UNIT:  R_ij = C_ij / n                   mag = |R| (PLV)         lagged = ciPLV
+ *     RAW:   R_ij = C_ij / sqrt(C_ii C_jj)     mag = |R| (coherence)   lagged = |Im R| (imaginary coherence)
+ *     ciPLV = den > 0 ? min(1, |Im R| / sqrt(den)) : 0,   den = 1 - (Re R)^2
+ *     diagonal: Im R = 0; mag = 1 and lagged = 0 where the channel has a non-zero sample in the window.
+ * coherency (optional): [n_items][2][m][m], the planes Re R and Im R; mag, lagged (optional): [n_items][m][m]; unpadded.
+ * info int32 [n_items]: 0 fine; 1 a non-finite sample in the window's m channels (read off the diagonal of C): every
+ *   output of the item is NaN; 2 (RAW only) a channel of zero power: its row and column are NaN, the rest is valid.
+ * float64 on v_mfma_f64_4x4x4_4b_f64.  Every sum runs over the samples ascending in k-steps of 4 from the window start:
+ * an item's bits depend on its own samples only, not on the batch, the item order, the strides or the padded channel
+ * count.  No atomics.  Element (r, c) is formed from C[min(r,c)][max(r,c)]: mag and lagged are exactly symmetric, Im R
+ * exactly antisymmetric.  In UNIT mode scaling a channel of z by a power of two changes no bit (while |z|^2 stays in the
+ * normal range).
+ * Refused before any launch: channel count outside 1..HMV_MAX_CHANNELS (-1), n < 1 or n > T (-2), T < 1, n_rec < 0 or
+ *   n_items < 0 (-3), more than 2^31 - 1 items (-10), mode outside 0..1 (-7), all three outputs null (-9), ld < T (-5),
+ *   rec_stride < m * ld (-6), and with n_items > 0 a null z, item table or info (-4) or a z that is not 16-byte aligned
+ *   (-8).  n_items = 0 launches nothing and returns 0. */
+#define HMV_PHASE_UNIT 0
+#define HMV_PHASE_RAW  1
+int hmv_phase_sync_c128(const double* z, int64_t rec_stride, int64_t ld, int64_t T, int64_t n_rec, int m,
+                        const int64_t* item_rec, const int64_t* item_start, int64_t n_items, int n, int mode,
+                        double* coherency, double* mag, double* lagged, int32_t* info, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
