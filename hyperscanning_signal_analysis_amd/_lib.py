@@ -172,6 +172,7 @@ TUNE_K3_FORM = 3
 TUNE_YW_FORM = 4
 TUNE_K3_LDS_PAD = 5
 TUNE_K3_SPLIT = 6
+K3_SPLIT_NO_FRONT = 1 << 19         # added to a TUNE_K3_SPLIT value: K1 is never cut at the split
 # limits of hmv_decimate_fir_f64
 MAX_DECIMATE = 32
 MAX_DECIMATE_TAPS = 641

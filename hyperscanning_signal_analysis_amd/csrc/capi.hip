@@ -722,9 +722,10 @@ int64_t sliding_bytes(int64_t chunk, int m, int p, int F, int n_bands = 0, bool 
     return -1;
   return (int64_t)sliding_layout(chunk, mp, p, F, n_bands > 0, spectra, measure, q_tiles).total;
 }
-// Fork / join events of the two-stream K2 split: created once per (host thread, device), not per call.
+// Fork / join events of the two-stream K2 split, and the early fork behind K1's first block range (sliding_front): created
+// once per (host thread, device), not per call.
 struct ForkJoin {
-  hipEvent_t fork = nullptr, join = nullptr;
+  hipEvent_t fork = nullptr, join = nullptr, front = nullptr;
 };
 ForkJoin* fork_join_events() {
   constexpr int MAXDEV = 64;
@@ -735,6 +736,7 @@ ForkJoin* fork_join_events() {
   if (!e.fork) {
     if (hipEventCreateWithFlags(&e.fork, hipEventDisableTiming) != hipSuccess) return nullptr;
     if (hipEventCreateWithFlags(&e.join, hipEventDisableTiming) != hipSuccess) return nullptr;
+    if (hipEventCreateWithFlags(&e.front, hipEventDisableTiming) != hipSuccess) return nullptr;
   }
   return &e;
 }
@@ -744,29 +746,43 @@ ForkJoin* fork_join_events() {
 // wait for them.  The r windows over are then solved on the second stream while K3 starts on the first c0 = c - r.  Chunks of
 // several rounds (k >= occupancy) are not split, nor are chunks whose first part is shorter than K3's normalisation lag.
 // CUs and occupancy come from the runtime, once per (host thread, device, padded size).
-int64_t k3_split_point(int64_t c, int mp, int64_t lag) {
-  const int64_t t = hmv::tuning(HMV_TUNE_K3_SPLIT);
+// Where the chunk's K1 can be cut at the same point (`can_front`: sliding_front), a chunk of more than one and fewer than
+// `occupancy` rounds is split after its first round instead, c0 = CUs: K2's first round then runs beside the rest of K1, and
+// most of K2's second part is done before K3 arrives (profiles/front_overlap_notes.md).  A tuning value of
+// HMV_K3_SPLIT_NO_FRONT + n means n without the K1 cut.
+struct SplitPoint {
+  int64_t c0;                                       // 0: one part
+  bool front;                                       // K1 is cut at c0 too
+};
+SplitPoint k3_split_point(int64_t c, int mp, int64_t lag, bool can_front) {
+  int64_t t = hmv::tuning(HMV_TUNE_K3_SPLIT);
+  if (t < 0) return {};
+  if (t >= HMV_K3_SPLIT_NO_FRONT) {
+    t -= HMV_K3_SPLIT_NO_FRONT;
+    can_front = false;
+  }
   int64_t c0 = t;
-  if (t < 0) return 0;
   if (t == 0) {
     constexpr int MAXDEV = 64;
     struct Shape { int cus = 0, occ[4] = {0, 0, 0, 0}; };
     thread_local Shape tl[MAXDEV];
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV || mp < 16 || mp > 64) return 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV || mp < 16 || mp > 64) return {};
     Shape& d = tl[dev];
     int& occ = d.occ[mp / 16 - 1];
     if (d.cus == 0 && hipDeviceGetAttribute(&d.cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) d.cus = -1;
     if (occ == 0 && (occ = hmv::yw_lwr_occupancy(mp)) == 0) occ = -1;
     if (d.cus < 1 || occ < 1) {
       (void)hipGetLastError();                           // (a failed query must not surface as a later launch's error)
-      return 0;
+      return {};
     }
     const int64_t k = c / d.cus, r = c % d.cus;
-    if (k < 1 || k >= occ || r == 0) return 0;
+    if (can_front && c > d.cus && k < occ && d.cus >= lag) return {d.cus, true};
+    if (k < 1 || k >= occ || r == 0) return {};
     c0 = c - r;
+    can_front = false;
   }
-  return (c0 >= lag && c0 < c) ? c0 : 0;
+  return (c0 >= lag && c0 < c) ? SplitPoint{c0, can_front} : SplitPoint{};
 }
 }  // namespace
 
@@ -885,16 +901,18 @@ int64_t measure_bytes(int measure, int64_t chunk, int m, int p, int F, int n_ban
   return sliding_bytes(chunk, m, p, F, spectra ? 0 : n_bands, spectra, measure, q_tiles);
 }
 
-// ---- the second stream: both of its uses fork and join through this
+// ---- the second stream: all of its uses fork and join through this
 // fork: st1 may start once what st0 holds is done.  join: st0 takes up again behind st1, so that the caller's stream never
 // runs ahead of work this call put on the second stream; a join that cannot be expressed as an event is made on the host.
 struct TwoStreams {
   hipStream_t st0 = nullptr, st1 = nullptr;
   ForkJoin* ev = nullptr;
-  int fork() const {                                // nonzero: nothing may be put on st1
-    const int hrc = (int)hipEventRecord(ev->fork, st0);
-    return hrc ? hrc : (int)hipStreamWaitEvent(st1, ev->fork, 0);
+  int fork(hipEvent_t at) const {                   // nonzero: nothing may be put on st1
+    const int hrc = (int)hipEventRecord(at, st0);
+    return hrc ? hrc : (int)hipStreamWaitEvent(st1, at, 0);
   }
+  int fork() const { return fork(ev->fork); }
+  int fork_front() const { return fork(ev->front); }   // the early fork, behind K1's first part (sliding_front)
   int record_join() const {
     const int hrc = (int)hipEventRecord(ev->join, st1);
     if (hrc) (void)hipStreamSynchronize(st1);
@@ -1016,6 +1034,10 @@ int sliding_plan(const SlidingArgs& a, SlidingPlan& pl) {
   // workgroups land on an almost empty chip and K3 fills in around them.  It is zero-sum in chip time like the others;
   // what it removes is the idle tail of K2 from the critical path.  Only where nobody but K3's packing kernel reads the
   // model (from_tiles) and no output beyond the ffDTF is asked for.
+  // Third use, where the second applies and the chunk's K1 can be cut at the split point (front_cut_ok, sliding_front;
+  // profiles/front_overlap_notes.md): the second stream forks earlier, behind K1 of the first part's hop blocks, and runs the
+  // rest of K1, its lagcomb and K2's second part.  K1 is bound by the matrix pipe and K2 by the latency of its chain, and
+  // K3 is not there yet, so this overlap is not zero-sum; K3 starts behind K2's first part alone, as in the second use.
   pl.fj.st0 = S(a.run.stream);
   pl.fj.st1 = S(a.run.aux_stream);
   const bool two = (a.run.aux_stream && a.run.aux_stream != a.run.stream);
@@ -1084,17 +1106,89 @@ int sliding_k1(const SlidingArgs& a, const SlidingPlan& pl, const Chunk& ch) {
   return rc;
 }
 
-// ---- K2 of a chunk, in one of three forms.  sp comes back describing a K2 -> K3 hand-over in two parts, if one was set up.
-int sliding_k2(const SlidingArgs& a, const SlidingPlan& pl, const Chunk& ch, hmv::TfSplit& sp) {
+// K2's arguments for the windows k0 .. k0 + cnt - 1 of a chunk
+hmv::YwArgs k2_part(const SlidingArgs& a, const SlidingPlan& pl, const Chunk& ch, int64_t k0, int64_t cnt, int64_t yw_flags) {
+  const Items& it = a.it;
+  return yw_args(pl.R + (size_t)k0 * (it.p + 1) * pl.t, cnt, it.m, it.p, pl.ws + (size_t)k0 * pl.ws_item,
+                 ch.ar + (size_t)k0 * pl.t * it.p, ch.V + (size_t)k0 * pl.t, a.fit.info_yw + ch.i0 + k0, yw_flags);
+}
+
+// ---- where a chunk's K2 -> K3 hand-over is split, and whether its K1 is cut there too
+// K1 can be cut where it is the direct form over single windows, or one run of sliding_k1's loop over a regular grid
+// (the chunk lies inside one recording); every other K1 (ensembles, pairs, mix) is one piece.
+bool front_cut_ok(const SlidingArgs& a, const SlidingPlan& pl, const Chunk& ch) {
+  if (a.ens || a.pairs || a.mix) return false;
+  return !pl.regular || ch.i0 % a.grid.nwin + ch.c <= a.grid.nwin;
+}
+SplitPoint sliding_split(const SlidingArgs& a, const SlidingPlan& pl, const Chunk& ch) {
+  if (!pl.k3_split || !pl.from_tiles) return {};
+  return k3_split_point(ch.c, pl.mp, norm_lag_items(pl.mp, a.spec.F), front_cut_ok(a, pl, ch));
+}
+
+// ---- K1 and K2 of a chunk cut at c0, the second parts on the second stream from the start (front_cut_ok).
+//   st0: K1 of the windows [0, c0)  |event|  lagcomb [0, c0)   K2 [0, c0)                       -> K3's first launch
+//   st1:                            |wait |  K1 of the rest    lagcomb [c0, c)   K2 [c0, c)  |join| -> K3's second launch
+// On a regular grid of k hops per window K1 is the block sums: the first part sums the hop blocks [0, c0 + k - 1), the
+// second [c0 + k - 1, c + k - 1), each into its own range of Q; lagcomb of the windows from c0 on reads the last k - 1
+// blocks of the first part, hence the event.  Every block, window and byte is computed by the launch arguments that
+// sliding_k1 / sliding_k2 would give it, by one writer.  sp comes back as from sliding_k2.
+int sliding_front(const SlidingArgs& a, const SlidingPlan& pl, const Chunk& ch, int64_t c0, hmv::TfSplit& sp) {
+  const Items& it = a.it;
+  const Grid& g = a.grid;
+  const TwoStreams& fj = pl.fj;
+  const int64_t i0 = ch.i0, c = ch.c;
+  const size_t stack = (size_t)(it.p + 1) * pl.t;
+  const int k = pl.regular ? (int)(it.n / g.hop) : 1;
+  const int64_t rec = pl.regular ? i0 / g.nwin : 0;
+  const double* x = it.x + rec * it.rec_stride;                      // (regular grid: the chunk's recording)
+  const int64_t first = pl.regular ? g.first + (i0 - rec * g.nwin) * g.hop : 0;
+  // K1 of the windows [k0, k1) without the blocks that the windows before k0 have summed
+  auto sums = [&](int64_t k0, int64_t k1, hipStream_t st) {
+    if (!pl.regular)
+      return hmv_lagcov_f64(it.x, it.rec_stride, it.ld, it.item_rec + i0 + k0, it.item_start + i0 + k0, k1 - k0, it.m, it.n,
+                            it.p, pl.R + (size_t)k0 * stack, st);
+    const int64_t b0 = k0 ? k0 + k - 1 : 0;
+    hmv::LagcovArgs la{};
+    la.x = x; la.ld = it.ld; la.n_items = k1 + k - 1 - b0; la.m = it.m; la.n = (int)g.hop; la.p = it.p;
+    la.R = pl.Qb + (size_t)b0 * stack;
+    la.blocks = 1; la.blk_first = first + b0 * g.hop; la.blk_T = g.T;
+    return hmv::launch_lagcov(la, pl.mp, st);
+  };
+  auto comb = [&](int64_t k0, int64_t k1, hipStream_t st) {
+    if (!pl.regular) return 0;
+    hmv::LagcombArgs ca{};
+    ca.Q = pl.Qb + (size_t)k0 * stack; ca.x = x; ca.ld = it.ld; ca.first = first + k0 * g.hop; ca.hop = g.hop; ca.T = g.T;
+    ca.n_win = k1 - k0; ca.k = k; ca.m = it.m; ca.p = it.p; ca.R = pl.R + (size_t)k0 * stack;
+    return hmv::launch_lagcomb(ca, pl.mp, st);
+  };
+  auto solve = [&](int64_t k0, int64_t k1, hipStream_t st) {
+    hmv::YwArgs ya = k2_part(a, pl, ch, k0, k1 - k0, a.run.flags);
+    ya.no_emit = 1;
+    return hmv::launch_yw(ya, pl.mp, st);
+  };
+  sp = hmv::TfSplit{};
+  int rc = sums(0, c0, fj.st0);
+  if (rc) return rc;
+  if (const int hrc = fj.fork_front()) return hrc;
+  rc = sums(c0, c, fj.st1);
+  if (!rc) rc = comb(c0, c, fj.st1);
+  if (!rc) rc = solve(c0, c, fj.st1);
+  if (const int hrc = fj.record_join()) return rc ? rc : hrc;        // (joined on the host)
+  sp.c0 = c0;                                                        // from here on TwoStreams::finish joins on every path
+  sp.join = fj.ev->join;
+  if (!rc) rc = comb(0, c0, fj.st0);
+  if (!rc) rc = solve(0, c0, fj.st0);
+  return rc;
+}
+
+// ---- K2 of a chunk, in one of three forms.  s0: where the K2 -> K3 hand-over is split (sliding_split), 0 for one part; sp
+// comes back describing that hand-over, if one was set up.
+int sliding_k2(const SlidingArgs& a, const SlidingPlan& pl, const Chunk& ch, int64_t s0, hmv::TfSplit& sp) {
   const Items& it = a.it;
   const int64_t flags = a.run.flags, c = ch.c;
   const int mp = pl.mp;
   const TwoStreams& fj = pl.fj;
-  // K2's arguments for the windows k0 .. k0 + cnt - 1 of the chunk
-  auto part = [&](int64_t k0, int64_t cnt, int64_t yw_flags) {
-    return yw_args(pl.R + (size_t)k0 * (it.p + 1) * pl.t, cnt, it.m, it.p, pl.ws + (size_t)k0 * pl.ws_item,
-                   ch.ar + (size_t)k0 * pl.t * it.p, ch.V + (size_t)k0 * pl.t, a.fit.info_yw + ch.i0 + k0, yw_flags);
-  };
+  auto part = [&](int64_t k0, int64_t cnt, int64_t yw_flags) { return k2_part(a, pl, ch, k0, cnt, yw_flags); };
   sp = hmv::TfSplit{};
   if (pl.automatic)                                  // the recursion to order p with the selection (flags: none of K2's)
     return hmv::launch_yw_auto(part(0, c, flags),
@@ -1117,7 +1211,6 @@ int sliding_k2(const SlidingArgs& a, const SlidingPlan& pl, const Chunk& ch, hmv
   // The recursion that does not emit.  With a split point, the remainder windows go to the second stream, forked behind the
   // first part (they never share a compute unit with it); the join is waited for inside K3's launcher, between its two
   // launches, or by TwoStreams::finish on every path that did not get that far.
-  const int64_t s0 = pl.k3_split ? k3_split_point(c, mp, norm_lag_items(mp, a.spec.F)) : 0;
   hmv::YwArgs ya = part(0, s0 ? s0 : c, flags);
   ya.no_emit = 1;
   int rc = hmv::launch_yw(ya, mp, fj.st0);
@@ -1240,8 +1333,13 @@ int sliding_impl(const SlidingArgs& a) {
   for (int64_t i0 = 0; i0 < n && rc == 0; i0 += chunk) {
     const Chunk ch{i0, n - i0 < chunk ? n - i0 : chunk, a.fit.ar_out ? a.fit.ar_out + (size_t)i0 * pl.t * a.it.p : pl.ar,
                    a.fit.V_out ? a.fit.V_out + (size_t)i0 * pl.t : pl.V, i0 + chunk >= n};
-    rc = sliding_k1(a, pl, ch);
-    if (!rc) rc = sliding_k2(a, pl, ch, sp);
+    const SplitPoint s = sliding_split(a, pl, ch);
+    if (s.front) {
+      rc = sliding_front(a, pl, ch, s.c0, sp);
+    } else {
+      rc = sliding_k1(a, pl, ch);
+      if (!rc) rc = sliding_k2(a, pl, ch, s.c0, sp);
+    }
     if (!rc) rc = a.measure == MEAS_BGC ? sliding_bgc(a, pl, ch) : sliding_measure(a, pl, ch, sp);
     pl.fj.finish(sp);                        // (K3's launcher did not get to its second part, or the chunk ended on an error)
   }

@@ -52,8 +52,12 @@ int hmv_pad(int m);
  *                       workgroups per CU, to separate latency from throughput; 0 = none)
  *   HMV_TUNE_K3_SPLIT   the fused ffDTF calls with a second stream: where a chunk's K2 -> K3 hand-over is split, so that K3
  *                       starts on the chunk's first windows while K2 finishes the rest on the second stream.  0 = by rule
- *                       (the windows past the last full round of one K2 workgroup per compute unit), -1 = never,
- *                       n > 0 = after the chunk's first n windows (same bits at every setting)
+ *                       (the windows past the last full round of one K2 workgroup per compute unit; or, where the chunk's
+ *                       K1 can be cut at the same point -- single windows or a regular grid inside one recording -- and
+ *                       the chunk is more than one such round, after the first round, with the rest of K1 and K2's second
+ *                       part on the second stream from there), -1 = never, n > 0 = after the chunk's first n windows,
+ *                       K1 cut there too where it can be, HMV_K3_SPLIT_NO_FRONT + n = n (0 included) with K1 never cut:
+ *                       the sequence of builds before the cut existed (same bits at every setting)
  * Returns 0, or -1 for an unknown key / value out of range.  hmv_get_tuning returns the value in force (-1: unknown key). */
 #define HMV_TUNE_NORM_LAG 1
 #define HMV_TUNE_LAG_GROUP 2
@@ -61,6 +65,7 @@ int hmv_pad(int m);
 #define HMV_TUNE_YW_FORM 4
 #define HMV_TUNE_K3_LDS_PAD 5
 #define HMV_TUNE_K3_SPLIT 6
+#define HMV_K3_SPLIT_NO_FRONT (1 << 19)
 int hmv_set_tuning(int key, int64_t value);
 int64_t hmv_get_tuning(int key);
 /* Number of doubles of K2 scratch per item. */
@@ -254,8 +259,9 @@ int hmv_tf_ffdtf_bands_f64(const double* ar, int64_t n_items, int m, int p, cons
  * launches that cannot fill the chip -- it runs as two half-batches, one per stream (fork
  * after K1, join before K3), so their launches interleave on the device.  The default form of K2, when only the
  * ffDTF is asked for (no ar_out / V_out), uses it for the windows of its last, partly filled round: they are solved
- * on aux_stream while K3 already runs on the windows before them (HMV_TUNE_K3_SPLIT; same bits).  Either way the
- * call still behaves as one operation on `stream`. */
+ * on aux_stream while K3 already runs on the windows before them (HMV_TUNE_K3_SPLIT; same bits); where K1 can be
+ * cut as well (single windows, or a regular grid with the chunk inside one recording), the windows behind the first
+ * round go to aux_stream from K1 on.  Either way the call still behaves as one operation on `stream`. */
 int64_t hmv_sliding_workspace_bytes(int64_t chunk, int m, int p, int F);
 int hmv_sliding_ffdtf_f64(const double* x, int64_t rec_stride, int64_t ld,
                           const int64_t* item_rec, const int64_t* item_start, int64_t n_items,
