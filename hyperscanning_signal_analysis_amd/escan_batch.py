@@ -28,6 +28,7 @@ from __future__ import annotations
 import json
 import re
 import time
+import typing
 from pathlib import Path
 
 import numpy as np
@@ -38,7 +39,8 @@ from .engine import default_engine
 from .sliding import hop_positions, regular_grid, validation_p_values, window_items
 
 __all__ = ["discover_dyads", "decode_events", "segment_block", "prepare_dyad", "run", "run_pseudo_dyads", "savez_fast",
-           "xarray_reader", "resolve_decimate", "decimated_segment", "DecimateConfigError"]
+           "xarray_reader", "resolve_decimate", "decimated_segment", "DecimateConfigError", "resolve_settings",
+           "segment_geometry", "child_channels"]
 
 ROLES = (("ch", "child"), ("cg", "caregiver"))
 MEASURES = ("ffdtf", "ddtf", "gpdc")          # what run(measures=...) can compute per window; ffDTF always
@@ -86,38 +88,57 @@ def decode_events(attrs):
     return out
 
 
-def _filtered(rec, low_cutoff_hz, high_cutoff_hz):
-    """Whole-file filtering + mastoid drop with load_eeg_signals' semantics, WITHOUT its trim and z-score."""
+def _member(rec, low_cutoff_hz, high_cutoff_hz, channel_subset):
+    """One member's whole file -> (x (time, channel), channel names, time, fs): filtering + mastoid drop with
+    load_eeg_signals' semantics, WITHOUT its trim and z-score, then the requested channels in the order asked for."""
     fs = float(rec["attrs"].get("sampling_freq", rec["attrs"].get("sampling_frequency_Hz", 128.0)))
     x = filter_eeg(rec["data_tc"], fs, low_cutoff_hz, high_cutoff_hz)
     names = [str(c) for c in rec["channels"]]
     keep = [k for k, c in enumerate(names) if c not in ("M1", "M2")]
-    return x[:, keep], [names[k] for k in keep], np.asarray(rec["time"], dtype=np.float64), fs
+    x, ch = x[:, keep], [names[k] for k in keep]
+    if channel_subset is not None:
+        idx = [ch.index(c) for c in channel_subset if c in ch]
+        if not idx:
+            raise ValueError(f"None of the requested channels {channel_subset} found. Available: {ch}")
+        x, ch = x[:, idx], [ch[k] for k in idx]
+    return x, ch, np.asarray(rec["time"], dtype=np.float64), fs
 
 
-def segment_block(child, caregiver, start_s, duration_s, low_cutoff_hz=None, high_cutoff_hz=None, channel_subset=None):
-    """(block (2 n_ch, T) z-scored, names, fs) of one event: both members filtered over their whole file, cut to
-    start <= t <= start + duration (io_utils.py:148-150), z-scored per channel inside the segment, stacked child
-    first on their common length."""
-    parts, names, fss = [], [], []
-    for role, rec in (("ch", child), ("cg", caregiver)):
-        x, ch, t, fs = _filtered(rec, low_cutoff_hz, high_cutoff_hz)
-        if channel_subset is not None:
-            idx = [ch.index(c) for c in channel_subset if c in ch]
-            if not idx:
-                raise ValueError(f"None of the requested channels {channel_subset} found. Available: {ch}")
-            x, ch = x[:, idx], [ch[k] for k in idx]
+def _members(child, caregiver, low_cutoff_hz, high_cutoff_hz, channel_subset):
+    """`_member` of the child and of the caregiver, in that order; their sampling rates must agree."""
+    members = [_member(rec, low_cutoff_hz, high_cutoff_hz, channel_subset) for rec in (child, caregiver)]
+    if members[0][3] != members[1][3]:
+        raise ValueError(f"sampling rates differ: {members[0][3]} vs {members[1][3]}")
+    return members
+
+
+def _cut_event(members, start_s, duration_s):
+    """One event out of both members' filtered files (`_members`) -> (block, names): each cut to
+    start <= t <= start + duration (io_utils.py:148-150) and z-scored per channel inside the segment, the child stacked on the
+    caregiver on their common length."""
+    parts, names = [], []
+    for (role, _), (x, ch, t, fs) in zip(ROLES, members):
         mask = (t >= start_s) & (t <= start_s + duration_s)
         seg = np.ascontiguousarray(x[mask].T)
         sd = np.std(seg, axis=1, keepdims=True)
         sd[sd == 0] = 1.0
         parts.append((seg - np.mean(seg, axis=1, keepdims=True)) / sd)
         names += [f"{c}_{role}" for c in ch]
-        fss.append(fs)
-    if fss[0] != fss[1]:
-        raise ValueError(f"sampling rates differ: {fss[0]} vs {fss[1]}")
     T = min(p.shape[1] for p in parts)
-    return np.vstack([p[:, :T] for p in parts]), names, fss[0]
+    return np.vstack([p[:, :T] for p in parts]), names
+
+
+def child_channels(names):
+    """How many of a block's channels are the child's: the `split` of the block measures (the child block comes first)."""
+    return sum(1 for nm in names if nm.endswith("_ch"))
+
+
+def segment_block(child, caregiver, start_s, duration_s, low_cutoff_hz=None, high_cutoff_hz=None, channel_subset=None):
+    """(block (2 n_ch, T) z-scored, names, fs) of one event: both members filtered over their whole file, cut to the
+    event, z-scored per channel inside the segment, stacked child first on their common length."""
+    members = _members(child, caregiver, low_cutoff_hz, high_cutoff_hz, channel_subset)
+    block, names = _cut_event(members, start_s, duration_s)
+    return block, names, members[0][3]
 
 
 def prepare_dyad(dyad, files_by_task, reader, low_cutoff_hz=None, high_cutoff_hz=None, channel_subset=None, say=None):
@@ -131,31 +152,12 @@ def prepare_dyad(dyad, files_by_task, reader, low_cutoff_hz=None, high_cutoff_hz
         if "ch" not in files or "cg" not in files:
             notes.append(f"[SKIP] {dyad} {task}: missing {'child' if 'ch' not in files else 'caregiver'} file")
             continue
-        recs = {r: reader(files[r]) for r in ("ch", "cg")}
-        filt = {}
-        for r in ("ch", "cg"):
-            x, ch, t, fs = _filtered(recs[r], low_cutoff_hz, high_cutoff_hz)         # whole file, once
-            if channel_subset is not None:
-                idx = [ch.index(c) for c in channel_subset if c in ch]
-                if not idx:
-                    raise ValueError(f"None of the requested channels {channel_subset} found. Available: {ch}")
-                x, ch = x[:, idx], [ch[k] for k in idx]
-            filt[r] = (x, ch, t, fs)
-        if filt["ch"][3] != filt["cg"][3]:
-            raise ValueError(f"sampling rates differ: {filt['ch'][3]} vs {filt['cg'][3]}")
-        for name, start, dur in decode_events(recs["ch"]["attrs"]):
-            parts, names = [], []
-            for r in ("ch", "cg"):
-                x, ch, t, fs = filt[r]
-                mask = (t >= start) & (t <= start + dur)
-                seg = np.ascontiguousarray(x[mask].T)
-                sd = np.std(seg, axis=1, keepdims=True)
-                sd[sd == 0] = 1.0
-                parts.append((seg - np.mean(seg, axis=1, keepdims=True)) / sd)
-                names += [f"{c}_{r}" for c in ch]
-            T = min(q.shape[1] for q in parts)
-            segs.append({"task": task, "event": name, "start_s": start, "duration_s": dur, "fs": filt["ch"][3],
-                         "block": np.vstack([q[:, :T] for q in parts]), "names": names})
+        child, caregiver = reader(files["ch"]), reader(files["cg"])
+        members = _members(child, caregiver, low_cutoff_hz, high_cutoff_hz, channel_subset)         # whole files, once
+        for name, start, dur in decode_events(child["attrs"]):
+            block, names = _cut_event(members, start, dur)
+            segs.append({"task": task, "event": name, "start_s": start, "duration_s": dur, "fs": members[0][3],
+                         "block": block, "names": names})
     return {"segments": segs, "notes": notes, "host_s": time.perf_counter() - t0}
 
 
@@ -229,6 +231,272 @@ def decimated_segment(q, fs, window_s, m, order, freqs=None):
     return fs_new, W
 
 
+class _Settings(typing.NamedTuple):
+    """What `run`'s keyword arguments come to (`resolve_settings`); `run_pseudo_dyads` fills the fields that
+    `segment_geometry` reads."""
+    window_s: float
+    overlap: float
+    freqs: object                       # None: 0.5 Hz steps up to the Nyquist rate of every segment
+    bands: tuple
+    measures: tuple
+    order: int | None                   # None: the automatic order of every window
+    fit_order: int                      # lags of a fit: the order, or max_model_order of the automatic order
+    crit_type: str = "AIC"
+    order_kw: dict = {}                 # max_model_order and crit_type of the engine calls, with the automatic order only
+    significance: dict | None = None
+    phase_sync: tuple | None = None
+    validation_lags: int | None = None
+    block_granger: bool = False
+    pivoted: bool = False
+    yw_kw: dict = {}                    # the `flags` keyword of the engine calls, with the pivoted fallback only
+    decimate: tuple | None = None       # (q, the design's name for the meta entry)
+    decimate_design: object = "decimate"
+    psd: tuple | None = None            # (fmin, fmax, bandwidth)
+    save_full: bool = False
+
+
+def resolve_settings(engine=None, *, window_s=2.0, overlap=0.5, model_order=8, freqs=None, bands=hdist.DEFAULT_BANDS,
+                     with_psd=False, psd_fmin=1.0, psd_fmax=30.0, psd_bandwidth=2.0, save_full=False, measures=("ffdtf",),
+                     significance=None, max_model_order=20, crit_type="AIC", validation_lags=None, block_granger=False,
+                     pivoted_fallback=None, decimate=None, decimate_design="decimate", phase_sync=None):
+    """`run`'s keyword arguments (same names, same defaults) -> (`_Settings`, the engine).  What needs no engine is refused
+    first: the measures, the significance dict, the phase measures and bands, then the automatic order where it is not
+    offered.  Only then the engine is made (engine=None: `default_engine()`), the pivoted fallback is resolved against its
+    setting, and the decimation last.  Nothing is created or read."""
+    measures = tuple(measures)
+    unknown = [m_ for m_ in measures if m_ not in MEASURES]
+    if unknown or "ffdtf" not in measures or len(set(measures)) != len(measures):
+        raise ValueError(f"measures must list 'ffdtf' and any of {MEASURES[1:]} once each, got {measures}")
+    if significance is not None:
+        from .surrogates import check_significance_dict
+        significance = check_significance_dict(significance)
+    if phase_sync is not None:                      # the arguments, before anything touches a device
+        from .eeg_io import resolve_bands_hz, resolve_phase_measures
+        phase_sync = resolve_phase_measures(phase_sync)
+        resolve_bands_hz(bands, float("inf"))       # not empty, pairs, lo < hi; the edges against fs / 2 per segment
+    auto = model_order is None
+    if block_granger and auto:
+        raise ValueError("escan_batch.run(block_granger=True): the automatic model order (model_order=None) is not "
+                         "available for block Granger causality; pass an integer model_order")
+    if auto:
+        from .engine import auto_order_args, no_auto_order
+        pmax, _ = auto_order_args(max_model_order, crit_type, 1 << 62)     # (the window length is checked per segment)
+        if significance is not None:
+            no_auto_order(None, "escan_batch.run(significance=...)")
+    order = None if auto else int(model_order)
+    order_kw = dict(max_model_order=pmax, crit_type=crit_type) if auto else {}
+    eng = engine or default_engine()
+    pivoted, yw_kw = resolve_pivoted_fallback(pivoted_fallback, eng.pivoted_yw, auto)
+    dec = resolve_decimate(decimate, decimate_design)
+    return _Settings(window_s, overlap, freqs, bands, measures, order, pmax if auto else order, crit_type, order_kw,
+                     significance, phase_sync, validation_lags, bool(block_granger), pivoted, yw_kw, dec, decimate_design,
+                     (psd_fmin, psd_fmax, psd_bandwidth) if with_psd else None, bool(save_full)), eng
+
+
+class _Geometry(typing.NamedTuple):
+    """Where the windows of one segment lie (`segment_geometry`).  A segment shorter than one window has fs, T and W only."""
+    fs: float                           # after the decimation, if any; so is T
+    T: int
+    W: int
+    hop: int | None = None
+    pos: np.ndarray | None = None       # first sample of every window; None: T < W
+    freqs: np.ndarray | None = None
+    lo: np.ndarray | None = None        # `band_bins` of the bands on `freqs`
+    hi: np.ndarray | None = None
+    grid: tuple | None = None           # `regular_grid`: what K1 may share between overlapping windows
+
+
+def segment_geometry(cfg, fs, T, m):
+    """Host arithmetic of one segment of m channels and T samples recorded at fs -> `_Geometry`: the window of
+    `cfg.window_s` seconds and its hop at the (decimated) rate, the fixed-hop starts (the tail shorter than one hop is dropped),
+    the frequency grid and the bands' bins on it.  `DecimateConfigError` as `decimated_segment` raises it."""
+    if cfg.decimate is None:
+        W = int(round(cfg.window_s * fs))
+    else:
+        fs, W = decimated_segment(cfg.decimate[0], fs, cfg.window_s, m, cfg.fit_order, cfg.freqs)
+        T = -(-T // cfg.decimate[0])
+    if T < W:
+        return _Geometry(fs, T, W)
+    hop = max(1, int(round(W * (1.0 - cfg.overlap))))
+    pos = hop_positions(T, W, hop)
+    f = np.asarray(cfg.freqs if cfg.freqs is not None else np.arange(0.5, min(fs / 2.0, 128.0) + 1e-9, 0.5))
+    lo, hi = hdist.band_bins(f, cfg.bands)
+    return _Geometry(fs, T, W, hop, pos, f, lo, hi, regular_grid(pos, W, cfg.fit_order))
+
+
+class _Segment(typing.NamedTuple):
+    """One launched segment (`_launch_segment`): device tensors, nothing fetched yet."""
+    seg: dict                           # `prepare_dyad`'s entry
+    key: str                            # <task>/<event>
+    geo: _Geometry
+    arrays: dict                        # saved as <key>/<name>, in this order; nothing else is in here
+    bad: object                         # failed-window mask of the ffDTF call
+    whiteness_orders: object = None     # the order every window was validated at
+    routes: object = None               # which solver took every window
+    decimated: tuple | None = None      # (fs, T) after the decimation
+    psd: object = None
+    psd_freqs: object = None
+
+
+def _measure(eng, meas, xd, items, cfg, geo, **kw):
+    """One measure of every window -> (band sums, the full array or None, failed-window mask, what else the call returned),
+    failed windows NaN-filled.  save_full: the full array, then its band sums; else the reduced product straight from the
+    measure's kernels, and the full array is never written."""
+    call = getattr(eng, f"sliding_{meas}")
+    kw.update(check="mask", grid=geo.grid, **cfg.order_kw, **cfg.yw_kw)
+    if cfg.save_full:
+        full, bad, *more = call(xd, *items, geo.W, cfg.order, geo.freqs, geo.fs, **kw)
+        red = eng.band_sums(full, geo.lo, geo.hi)
+        full.masked_fill_(bad.view(-1, 1, 1, 1), float("nan"))
+    else:
+        full = None
+        red, bad, *more = call(xd, *items, geo.W, cfg.order, geo.freqs, geo.fs, bands=(geo.lo, geo.hi), **kw)
+    red.masked_fill_(bad.view(-1, 1, 1, 1), float("nan"))
+    return red, full, bad, more
+
+
+def _launch_segment(eng, cfg, seg, key, geo, psd_stream):
+    """Device work of one segment, nothing fetched: the block crosses PCIe once, the PSD goes to its own stream beside the
+    MVAR kernels, every option adds its engine calls.  Returns the `_Segment`."""
+    import torch
+    m, W, f, fs = seg["block"].shape[0], geo.W, geo.freqs, geo.fs
+    auto = cfg.order is None
+    xd = eng.to_device(seg["block"][None])
+    if cfg.decimate is not None:
+        xd = eng.decimate(xd, cfg.decimate[0], cfg.decimate_design)
+    items = window_items(1, geo.pos, eng.device)
+    psd = pf = None
+    if cfg.psd is not None:                             # second stream, same resident block
+        from .psd import compute_psd_multitaper_device
+        psd_stream.wait_stream(torch.cuda.current_stream(eng.device))
+        with torch.cuda.stream(psd_stream):
+            pf, psd = compute_psd_multitaper_device(xd[0], fs, *cfg.psd, engine=eng)
+        xd.record_stream(psd_stream)
+    arrays = {}
+    arrays["ffdtf_bands"], full, bad, more = _measure(eng, "ffdtf", xd, items, cfg, geo, return_orders=auto)
+    if full is not None:
+        arrays["ffdtf"] = full
+    if auto:
+        arrays["orders"] = more[0]
+    for meas in (m_ for m_ in cfg.measures if m_ != "ffdtf"):      # dDTF / GPDC of the same windows, NaN-filled alike
+        red, full, _, _ = _measure(eng, meas, xd, items, cfg, geo)
+        if full is not None:
+            arrays[meas] = full
+        arrays[f"{meas}_bands"] = red
+    ord_v = None
+    if cfg.validation_lags is not None:                 # K1 + K2 once more, then residuals and whiteness
+        R_v = eng.lagcov(xd, *items, W, cfg.fit_order)
+        if auto:
+            ar_v, _, ord_v, _, info_v = eng.yw_solve_auto(R_v, m, W, cfg.crit_type)
+        else:
+            ar_v, _, _, info_v = eng.yw_solve(R_v, m, **cfg.yw_kw)
+            ord_v = torch.full_like(info_v, cfg.fit_order)
+        val = eng.model_validation(xd, *items, W, ar_v, cfg.validation_lags, validate=False)
+        bad_v = (info_v != 0) | (val["info"] != 0)
+        arrays["whiteness_q"] = val["q"].masked_fill(bad_v.view(-1, 1), float("nan"))
+        arrays["acf_fraction"] = (val["acf_count"].to(torch.float64) / float(int(cfg.validation_lags) * m ** 2)
+                                  ).masked_fill(bad_v, float("nan"))
+    if cfg.block_granger:
+        gc_f, gc_t, gc_bad = eng.sliding_block_granger(xd, *items, W, cfg.order, f, fs, bands=(geo.lo, geo.hi), check="mask",
+                                                       grid=geo.grid, split=child_channels(seg["names"]), **cfg.yw_kw)
+        arrays["block_gc_bands"] = gc_f.masked_fill_(gc_bad.view(-1, 1, 1), float("nan"))
+        arrays["block_gc_time"] = gc_t.masked_fill_(gc_bad.view(-1, 1), float("nan"))
+    if cfg.phase_sync is not None:                      # no model: the same windows, the bands in Hz
+        ps = eng.sliding_phase_sync(xd, *items, W, fs, cfg.bands, measures=cfg.phase_sync, check="nan")
+        for q_ in cfg.phase_sync:
+            arrays[f"phase_{q_}"] = ps[q_]
+    if cfg.significance is not None:
+        sg = cfg.significance
+        for meas in cfg.measures:
+            sig = eng.sliding_significance(xd, *items, W, cfg.order, f, fs, (geo.lo, geo.hi), measure=meas, null=sg["null"],
+                                           n_surrogates=sg["n_surrogates"], seed=sg["seed"],
+                                           split=child_channels(seg["names"]), min_shift=sg["min_shift"], check="nan",
+                                           grid=geo.grid)
+            for k_ in ("p", "p_fwe", "null_mean", "null_std", "n_valid"):
+                arrays[f"{meas}_bands_{k_}"] = sig[k_]
+    routes = eng.window_routes(xd, *items, W, cfg.order)[0] if cfg.pivoted else None       # K1 + K2 once more
+    return _Segment(seg, key, geo, arrays, bad, ord_v, routes, (fs, geo.T) if cfg.decimate is not None else None, psd, pf)
+
+
+def _collect_segment(s, cfg, dyad, result, meta, say):
+    """Host side of one launched segment: its arrays fetched into `result`, the chi-square tails of the whiteness
+    statistics, its entry in meta["segments"] and its `[OK]` line."""
+    seg, key, pos = s.seg, s.key, s.geo.pos
+    m, T = seg["block"].shape
+    for name, arr in s.arrays.items():
+        result[f"{key}/{name}"] = arr.cpu().numpy()
+    if s.whiteness_orders is not None:
+        q_v = result[f"{key}/whiteness_q"]
+        _, result[f"{key}/whiteness_p"], _ = validation_p_values(
+            q_v, np.zeros((len(q_v), 1)), s.whiteness_orders.cpu().numpy(), m, int(cfg.validation_lags), np.isnan(q_v[:, 0]))
+    result[f"{key}/starts"] = np.asarray(pos)
+    if s.psd is not None:
+        result[f"{key}/psd"], result[f"{key}/psd_freqs"] = s.psd.cpu().numpy(), s.psd_freqs
+    n_bad = int(s.bad.sum().item())
+    meta["segments"].append({"task": seg["task"], "event": seg["event"], "start_s": seg["start_s"],
+                             "duration_s": seg["duration_s"], "fs": seg["fs"], "samples": int(T),
+                             "windows": int(len(pos)), "window": int(s.geo.W), "singular_windows": n_bad})
+    if s.routes is not None:
+        from .engine import route_counts
+        meta["segments"][-1]["yw_routes"] = route_counts(s.routes)
+    if s.decimated is not None:
+        meta["fs"], T = s.decimated
+        meta["segments"][-1].update(fs=meta["fs"], samples=int(T))
+    say(f"[OK] {dyad} {key}: {m} ch x {T} samples, {len(pos)} windows" + (f", {n_bad} singular" if n_bad else ""))
+
+
+def _process_dyad(eng, cfg, dyad, prep, psd_stream, say):
+    """GPU part of one prepared dyad -> (result {member: array}, meta, channel names, freqs).  Every segment is launched
+    before the first one is fetched.  A segment shorter than a window is skipped; one that cannot be processed is logged in
+    meta["failed_segments"] and does not discard the others; `DecimateConfigError` leaves the batch."""
+    import torch
+    auto = cfg.order is None
+    result, meta = {}, {"dyad": dyad, "segments": [], "failed_segments": [], "model_order": "auto" if auto else cfg.order,
+                        "window_s": cfg.window_s, "overlap": cfg.overlap, "measures": list(cfg.measures),
+                        "created": time.strftime("%Y-%m-%dT%H:%M:%S")}
+    if auto:
+        meta["max_model_order"], meta["crit_type"] = cfg.fit_order, cfg.crit_type
+    if cfg.significance is not None:
+        meta["significance"] = dict(cfg.significance)
+    if cfg.block_granger:
+        meta["block_granger"] = True
+    if cfg.decimate is not None:
+        meta["decimate"], meta["decimate_design"] = cfg.decimate
+    if cfg.phase_sync is not None:
+        meta["phase_sync"] = list(cfg.phase_sync)
+    pending = []
+    for seg in prep["segments"]:
+        key = f"{seg['task']}/{seg['event']}"
+        try:
+            geo = segment_geometry(cfg, seg["fs"], seg["block"].shape[1], seg["block"].shape[0])
+            if geo.pos is None:
+                say(f"[SKIP] {dyad} {key}: {geo.T} samples < one window ({geo.W})")
+                continue
+            pending.append(_launch_segment(eng, cfg, seg, key, geo, psd_stream))
+        except DecimateConfigError:                    # the batch's own arguments: nothing to log per segment
+            raise
+        except Exception as e:                         # one bad segment does not discard the dyad
+            meta["failed_segments"].append({"segment": key, "error": f"{type(e).__name__}: {e}"})
+            say(f"Failed segment: {dyad} {key} -> {e}")
+    if psd_stream is not None:
+        torch.cuda.current_stream(eng.device).wait_stream(psd_stream)
+    names, freqs = None, None
+    for s in pending:
+        _collect_segment(s, cfg, dyad, result, meta, say)
+        names, freqs = s.seg["names"], s.geo.freqs
+    return result, meta, names, freqs
+
+
+def _write_dyad(target, compresslevel, names, freqs, bands, meta, result):
+    """One dyad's file, complete or absent (skip-if-exists relies on it) -> seconds it took."""
+    t0 = time.perf_counter()
+    tmp = target.with_suffix(".tmp.npz")
+    savez_fast(tmp, compresslevel, channels=np.asarray(names), freqs=freqs, bands=np.asarray(bands, dtype=np.float64),
+               meta=np.asarray(json.dumps(meta)), **result)
+    tmp.replace(target)
+    return time.perf_counter() - t0
+
+
 def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, freqs=None, bands=hdist.DEFAULT_BANDS,
         low_cutoff_hz=None, high_cutoff_hz=None, channel_subset=None, with_psd=False, psd_fmin=1.0, psd_fmax=30.0,
         psd_bandwidth=2.0, save_full=False, skip_existing=True, reader=None, engine=None, world=1, rank=0,
@@ -286,41 +554,27 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
       The block is not z-scored again: a low-passed signal loses only its stop-band power.  ValueError, raised out of the
       batch, if a requested frequency is not below fs / (2 q) or if the decimated window has no more samples than
       channels x model_order (the rank trap: lower the order with the rate).  None (default): nothing changes.
-      plus `channels`, `freqs`, `meta` (JSON, its `measures` field lists what was computed, `significance` the test).  Returns {"done": [...], "skipped": [...], "failed": [(dyad, error)],
-      "timing": {...}}.
+    Beside the segments the file holds `channels` (the block's rows, child first), `freqs`, `bands` and `meta` (JSON: its
+    `measures` field lists what was computed, `significance` the test, `segments` and `failed_segments` what became of every
+    segment).
+    Returns {"done": [...], "skipped": [...], "failed": [(dyad, error)], "timing": {...}}.
     A window whose fit is singular is NaN-filled, not fatal (the reference would raise and lose the dyad); a segment that
     cannot be processed is logged in the dyad's meta and does not discard the dyad's other segments.
     Pipeline: reading + filtering + cutting of the next `prefetch` dyads runs in worker threads while the GPU works on the
     current one (every task file is filtered once, not once per event); per segment the block crosses PCIe once and the
-    PSD runs on a second HIP stream beside the MVAR kernels.  `timing` (optional dict) receives the host / GPU split."""
+    PSD runs on a second HIP stream beside the MVAR kernels.  `timing` (optional dict) receives the host / GPU split.
+    The stages: `resolve_settings` (the arguments, before anything is created), `prepare_dyad` (host, in the pool),
+    `_process_dyad` (`segment_geometry`, `_launch_segment` for every segment, then `_collect_segment` for every segment) and
+    `_write_dyad` (in the pool of the writes); this function keeps the pools, the prefetch, the books and the log."""
     import concurrent.futures as cf
 
     import torch
-    measures = tuple(measures)
-    unknown = [m_ for m_ in measures if m_ not in MEASURES]
-    if unknown or "ffdtf" not in measures or len(set(measures)) != len(measures):
-        raise ValueError(f"measures must list 'ffdtf' and any of {MEASURES[1:]} once each, got {measures}")
-    if significance is not None:
-        from .surrogates import check_significance_dict
-        significance = check_significance_dict(significance)
-    if phase_sync is not None:                      # the arguments, before anything touches a device
-        from .eeg_io import resolve_bands_hz, resolve_phase_measures
-        phase_sync = resolve_phase_measures(phase_sync)
-        resolve_bands_hz(bands, float("inf"))       # not empty, pairs, lo < hi; the edges against fs / 2 per segment
-    auto = model_order is None
-    if block_granger and auto:
-        raise ValueError("escan_batch.run(block_granger=True): the automatic model order (model_order=None) is not "
-                         "available for block Granger causality; pass an integer model_order")
-    if auto:
-        from .engine import auto_order_args, no_auto_order
-        pmax, _ = auto_order_args(max_model_order, crit_type, 1 << 62)     # (the window length is checked per segment)
-        if significance is not None:
-            no_auto_order(None, "escan_batch.run(significance=...)")
-    order = None if auto else int(model_order)
-    order_kw = dict(max_model_order=pmax, crit_type=crit_type) if auto else {}
-    eng = engine or default_engine()
-    pivoted, yw_kw = resolve_pivoted_fallback(pivoted_fallback, eng.pivoted_yw, auto)
-    dec = resolve_decimate(decimate, decimate_design)
+    cfg, eng = resolve_settings(
+        engine, window_s=window_s, overlap=overlap, model_order=model_order, freqs=freqs, bands=bands, with_psd=with_psd,
+        psd_fmin=psd_fmin, psd_fmax=psd_fmax, psd_bandwidth=psd_bandwidth, save_full=save_full, measures=measures,
+        significance=significance, max_model_order=max_model_order, crit_type=crit_type, validation_lags=validation_lags,
+        block_granger=block_granger, pivoted_fallback=pivoted_fallback, decimate=decimate, decimate_design=decimate_design,
+        phase_sync=phase_sync)
     reader = reader or xarray_reader
     out_dir = Path(out_dir)
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -342,7 +596,8 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
     psd_stream = torch.cuda.Stream(eng.device) if with_psd else None
     # two pools: the writes (3 - 4 s of zlib per full-size dyad when compressed) must not take the workers that prepare the
     # next dyads, or the GPU waits for its input behind somebody's output
-    pool = cf.ThreadPoolExecutor(max_workers=max(1, int(prefetch)))
+    ahead = max(1, int(prefetch))
+    pool = cf.ThreadPoolExecutor(max_workers=ahead)
     save_pool = cf.ThreadPoolExecutor(max_workers=max(1, int(save_workers)))
     futures, saves = {}, []
 
@@ -350,170 +605,19 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
         if k < len(todo) and k not in futures:
             futures[k] = pool.submit(prepare_dyad, todo[k], tree[todo[k]], reader, low_cutoff_hz, high_cutoff_hz, channel_subset)
 
-    for k in range(min(len(todo), max(1, int(prefetch)))):
+    for k in range(min(len(todo), ahead)):
         submit(k)
     try:
         for k, dyad in enumerate(todo):
-            target = out_dir / f"{dyad}_ffdtf.npz"
             try:
                 tw = time.perf_counter()
                 prep = futures.pop(k).result()
                 wait_s = time.perf_counter() - tw
-                submit(k + max(1, int(prefetch)))
+                submit(k + ahead)
                 for line in prep["notes"]:
                     say(line)
-                result, meta = {}, {"dyad": dyad, "segments": [], "failed_segments": [],
-                                    "model_order": "auto" if auto else order,
-                                    "window_s": window_s, "overlap": overlap, "measures": list(measures),
-                                    "created": time.strftime("%Y-%m-%dT%H:%M:%S")}
-                if auto:
-                    meta["max_model_order"], meta["crit_type"] = pmax, crit_type
-                if significance is not None:
-                    meta["significance"] = dict(significance)
-                if block_granger:
-                    meta["block_granger"] = True
-                if dec is not None:
-                    meta["decimate"], meta["decimate_design"] = dec
-                if phase_sync is not None:
-                    meta["phase_sync"] = list(phase_sync)
-                names_out, freqs_out = None, None
                 tg = time.perf_counter()
-                pending = []                                       # device results of this dyad, fetched after the last launch
-                for seg in prep["segments"]:
-                    key = f"{seg['task']}/{seg['event']}"
-                    try:
-                        block, fs = seg["block"], seg["fs"]
-                        T = block.shape[1]
-                        if dec is None:
-                            W = int(round(window_s * fs))
-                        else:
-                            fs, W = decimated_segment(dec[0], fs, window_s, block.shape[0], pmax if auto else order, freqs)
-                            T = -(-T // dec[0])
-                        hop = max(1, int(round(W * (1.0 - overlap))))
-                        if T < W:
-                            say(f"[SKIP] {dyad} {key}: {T} samples < one window ({W})")
-                            continue
-                        pos = hop_positions(T, W, hop)            # fixed hop; the tail shorter than one hop is dropped
-                        f = np.asarray(freqs if freqs is not None else np.arange(0.5, min(fs / 2.0, 128.0) + 1e-9, 0.5))
-                        xd = eng.to_device(block[None])
-                        if dec is not None:
-                            xd = eng.decimate(xd, dec[0], decimate_design)
-                        rec_i, st_i = window_items(1, pos, eng.device)
-                        psd_dev = None
-                        if with_psd:                               # second stream, same resident block
-                            from .psd import compute_psd_multitaper_device
-                            psd_stream.wait_stream(torch.cuda.current_stream(eng.device))
-                            with torch.cuda.stream(psd_stream):
-                                pf, psd_dev = compute_psd_multitaper_device(xd[0], fs, psd_fmin, psd_fmax, psd_bandwidth, engine=eng)
-                            xd.record_stream(psd_stream)
-                        lo, hi = hdist.band_bins(f, bands)
-                        grid_w = regular_grid(pos, W, pmax if auto else order)
-                        extra = {}                                 # dDTF / GPDC of the same windows, NaN-filled alike
-                        if dec is not None:
-                            extra["_decimated"] = (fs, T)
-                        if save_full:
-                            r = eng.sliding_ffdtf(xd, rec_i, st_i, W, order, f, fs, check="mask", grid=grid_w,
-                                                  return_orders=auto, **order_kw, **yw_kw)
-                            ff, bad = r[0], r[1]
-                            bsum = eng.band_sums(ff, lo, hi)
-                            ff.masked_fill_(bad.view(-1, 1, 1, 1), float("nan"))
-                        else:          # the reduced product straight from K3's row workers: the full array is never written
-                            ff = None
-                            r = eng.sliding_ffdtf(xd, rec_i, st_i, W, order, f, fs, check="mask", grid=grid_w, bands=(lo, hi),
-                                                  return_orders=auto, **order_kw, **yw_kw)
-                            bsum, bad = r[0], r[1]
-                        if auto:
-                            extra["orders"] = r[2]
-                        bsum.masked_fill_(bad.view(-1, 1, 1, 1), float("nan"))
-                        for meas in (m_ for m_ in measures if m_ != "ffdtf"):
-                            run_m = eng.sliding_ddtf if meas == "ddtf" else eng.sliding_gpdc
-                            if save_full:
-                                full_m, bad_m = run_m(xd, rec_i, st_i, W, order, f, fs, check="mask", grid=grid_w, **order_kw, **yw_kw)
-                                red_m = eng.band_sums(full_m, lo, hi)
-                                full_m.masked_fill_(bad_m.view(-1, 1, 1, 1), float("nan"))
-                                extra[meas] = full_m
-                            else:
-                                red_m, bad_m = run_m(xd, rec_i, st_i, W, order, f, fs, check="mask", grid=grid_w,
-                                                     bands=(lo, hi), **order_kw, **yw_kw)
-                            red_m.masked_fill_(bad_m.view(-1, 1, 1, 1), float("nan"))
-                            extra[f"{meas}_bands"] = red_m
-                        if validation_lags is not None:          # K1 + K2 once more, then residuals and whiteness
-                            fit_p = pmax if auto else order
-                            R_v = eng.lagcov(xd, rec_i, st_i, W, fit_p)
-                            if auto:
-                                ar_v, _, ord_v, _, info_v = eng.yw_solve_auto(R_v, block.shape[0], W, crit_type)
-                            else:
-                                ar_v, _, _, info_v = eng.yw_solve(R_v, block.shape[0], **yw_kw)
-                                ord_v = torch.full_like(info_v, fit_p)
-                            val = eng.model_validation(xd, rec_i, st_i, W, ar_v, validation_lags, validate=False)
-                            bad_v = (info_v != 0) | (val["info"] != 0)
-                            extra["whiteness_q"] = val["q"].masked_fill(bad_v.view(-1, 1), float("nan"))
-                            extra["acf_fraction"] = (val["acf_count"].to(torch.float64)
-                                                     / float(int(validation_lags) * block.shape[0] ** 2)
-                                                     ).masked_fill(bad_v, float("nan"))
-                            extra["_whiteness_orders"] = ord_v
-                        if block_granger:                        # the child block comes first (segment_block)
-                            gc_f, gc_t, gc_bad = eng.sliding_block_granger(
-                                xd, rec_i, st_i, W, order, f, fs, bands=(lo, hi), check="mask", grid=grid_w,
-                                split=sum(1 for nm in seg["names"] if nm.endswith("_ch")), **yw_kw)
-                            extra["block_gc_bands"] = gc_f.masked_fill_(gc_bad.view(-1, 1, 1), float("nan"))
-                            extra["block_gc_time"] = gc_t.masked_fill_(gc_bad.view(-1, 1), float("nan"))
-                        if phase_sync is not None:               # no model: the same windows, the bands in Hz
-                            ps = eng.sliding_phase_sync(xd, rec_i, st_i, W, fs, bands, measures=phase_sync, check="nan")
-                            for q_ in phase_sync:
-                                extra[f"phase_{q_}"] = ps[q_]
-                        if significance is not None:             # the child block comes first (segment_block)
-                            split = sum(1 for nm in seg["names"] if nm.endswith("_ch"))
-                            for meas in measures:
-                                sig = eng.sliding_significance(xd, rec_i, st_i, W, order, f, fs, (lo, hi),
-                                                               measure=meas, null=significance["null"],
-                                                               n_surrogates=significance["n_surrogates"],
-                                                               seed=significance["seed"], split=split,
-                                                               min_shift=significance["min_shift"], check="nan", grid=grid_w)
-                                for k_ in ("p", "p_fwe", "null_mean", "null_std", "n_valid"):
-                                    extra[f"{meas}_bands_{k_}"] = sig[k_]
-                        if pivoted:                              # which solver took each window: K1 + K2 once more
-                            extra["_yw_routes"] = eng.window_routes(xd, rec_i, st_i, W, order)[0]
-                        pending.append((seg, key, pos, W, f, bsum, ff if save_full else None, bad, psd_dev, pf if with_psd else None,
-                                        extra))
-                    except DecimateConfigError:                    # the batch's own arguments: nothing to log per segment
-                        raise
-                    except Exception as e:                         # one bad segment does not discard the dyad
-                        meta["failed_segments"].append({"segment": key, "error": f"{type(e).__name__}: {e}"})
-                        say(f"Failed segment: {dyad} {key} -> {e}")
-                if psd_stream is not None:
-                    torch.cuda.current_stream(eng.device).wait_stream(psd_stream)
-                for seg, key, pos, W, f, bsum, ff, bad, psd_dev, pf, extra in pending:
-                    result[f"{key}/ffdtf_bands"] = bsum.cpu().numpy()
-                    if ff is not None:
-                        result[f"{key}/ffdtf"] = ff.cpu().numpy()
-                    ord_v = extra.pop("_whiteness_orders", None)
-                    routes = extra.pop("_yw_routes", None)
-                    decimated = extra.pop("_decimated", None)
-                    for name, arr in extra.items():
-                        result[f"{key}/{name}"] = arr.cpu().numpy()
-                    if ord_v is not None:
-                        q_v = result[f"{key}/whiteness_q"]
-                        _, result[f"{key}/whiteness_p"], _ = validation_p_values(
-                            q_v, np.zeros((len(q_v), 1)), ord_v.cpu().numpy(), seg["block"].shape[0], int(validation_lags),
-                            np.isnan(q_v[:, 0]))
-                    result[f"{key}/starts"] = np.asarray(pos)
-                    if psd_dev is not None:
-                        result[f"{key}/psd"], result[f"{key}/psd_freqs"] = psd_dev.cpu().numpy(), pf
-                    n_bad = int(bad.sum().item())
-                    T = seg["block"].shape[1]
-                    meta["segments"].append({"task": seg["task"], "event": seg["event"], "start_s": seg["start_s"],
-                                             "duration_s": seg["duration_s"], "fs": seg["fs"], "samples": int(T),
-                                             "windows": int(len(pos)), "window": int(W), "singular_windows": n_bad})
-                    if routes is not None:
-                        from .engine import route_counts
-                        meta["segments"][-1]["yw_routes"] = route_counts(routes)
-                    if decimated is not None:
-                        meta["fs"], T = decimated
-                        meta["segments"][-1].update(fs=meta["fs"], samples=int(T))
-                    names_out, freqs_out = seg["names"], f
-                    say(f"[OK] {dyad} {key}: {seg['block'].shape[0]} ch x {T} samples, {len(pos)} windows"
-                        + (f", {n_bad} singular" if n_bad else ""))
+                result, meta, names, freqs_out = _process_dyad(eng, cfg, dyad, prep, psd_stream, say)
                 torch.cuda.synchronize(eng.device)
                 gpu_s = time.perf_counter() - tg
                 if not meta["segments"]:
@@ -521,27 +625,22 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                     skipped.append(dyad)
                     continue
                 # the write goes to a worker pool of its own (stored by default; deflate -- compresslevel > 0 -- costs 3 - 4 s of
-                # a core per full-size dyad, zlib outside the GIL): the GPU and the next dyad's host work do not wait for it
-                def _save(target=target, names_out=names_out, freqs_out=freqs_out, meta=meta, result=result):
-                    t0 = time.perf_counter()
-                    tmp = target.with_suffix(".tmp.npz")
-                    savez_fast(tmp, compresslevel, channels=np.asarray(names_out), freqs=freqs_out,
-                               bands=np.asarray(bands, dtype=np.float64), meta=np.asarray(json.dumps(meta)), **result)
-                    tmp.replace(target)                       # a file that exists is complete (skip-if-exists relies on it)
-                    return time.perf_counter() - t0
-                saves.append((dyad, target, save_pool.submit(_save)))
-                save_s = 0.0
+                # a core per full-size dyad, zlib outside the GIL): the GPU and the next dyad's host work do not wait for it,
+                # and its time is added to `save_s` of the batch when the file is on disk, not to the dyad's
+                target = out_dir / f"{dyad}_ffdtf.npz"
+                saves.append((dyad, target, save_pool.submit(_write_dyad, target, compresslevel, names, freqs_out, bands, meta,
+                                                             result)))
                 done.append(dyad)
                 tm["host_prepare_s"] += prep["host_s"]; tm["wait_for_host_s"] += wait_s
-                tm["gpu_s"] += gpu_s; tm["save_s"] += save_s
+                tm["gpu_s"] += gpu_s
                 tm["dyads"].append({"dyad": dyad, "host_prepare_s": prep["host_s"], "waited_for_host_s": wait_s,
-                                    "gpu_s": gpu_s, "save_s": save_s, "segments": len(meta["segments"])})
+                                    "gpu_s": gpu_s, "save_s": 0.0, "segments": len(meta["segments"])})
             except DecimateConfigError:
                 raise
             except Exception as e:                  # one bad dyad does not stop the batch (export_..._batch.py:93-99)
                 failed.append((dyad, f"{type(e).__name__}: {e}"))
                 say(f"Failed: {dyad} -> {e}")
-                submit(k + max(1, int(prefetch)))
+                submit(k + ahead)
         for dyad, target, fut in saves:                   # every file on disk before the call returns
             try:
                 tm["save_s"] += fut.result()
@@ -653,14 +752,12 @@ def run_pseudo_dyads(root, out_dir, task, event, window_s=2.0, overlap=0.5, mode
     dyads = sorted(blocks)
     T = min(blocks[d_][0].shape[1] for d_ in dyads)
     x = np.stack([blocks[d_][0][:, :T] for d_ in dyads])               # cropped to the shortest segment
-    split = sum(1 for nm in names if nm.endswith("_ch"))               # the child block comes first (segment_block)
-    W = int(round(window_s * fs))
-    hop = max(1, int(round(W * (1.0 - overlap))))
-    if T < W:
-        raise ValueError(f"{task}/{event}: the common length ({T} samples) is shorter than one window ({W})")
-    pos = hop_positions(T, W, hop)
-    f = np.asarray(freqs if freqs is not None else np.arange(0.5, min(fs / 2.0, 128.0) + 1e-9, 0.5))
-    lo, hi = hdist.band_bins(f, bands)
+    split = child_channels(names)
+    geo = segment_geometry(_Settings(window_s, overlap, freqs, bands, measures, int(model_order), int(model_order)),
+                           fs, T, x.shape[1])
+    if geo.pos is None:
+        raise ValueError(f"{task}/{event}: the common length ({T} samples) is shorter than one window ({geo.W})")
+    W, pos, f, lo, hi = geo.W, geo.pos, geo.freqs, geo.lo, geo.hi
     eng = engine or default_engine()
     import torch
     xd = eng.to_device(x)
