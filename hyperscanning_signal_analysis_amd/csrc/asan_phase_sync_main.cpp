@@ -1,7 +1,7 @@
-// Stand-alone driver of hmv_phase_sync_c128's host code (argument checks) for the host-sanitized twin of the library:
-// `make -C csrc asan-phase-sync` builds it with AddressSanitizer + UBSan against libhypermvar_asan.so and runs it.  Every
-// pointer is a fake non-zero address: each call must be refused (or be an empty batch) before any of them is read and
-// before anything is launched, so the program needs no GPU.
+// Stand-alone driver of the host code (argument checks) of hmv_phase_sync_c128 and hmv_phase_sync_pairs_c128 for the
+// host-sanitized twin of the library: `make -C csrc asan-phase-sync` builds it with AddressSanitizer + UBSan against
+// libhypermvar_asan.so and runs it.  Every pointer is a fake non-zero address: each call must be refused (or be an empty
+// batch) before any of them is read and before anything is launched, so the program needs no GPU.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -9,10 +9,11 @@
 #include "../../include/hypermvar.h"
 
 static int failures = 0;
+static const char* entry = "hmv_phase_sync_c128: ";
 static void expect(int got, int want, const char* text, const char* what) {
   const char* err = hmv_last_error();
-  if (got != want || (text && (!strstr(err, text) || strncmp(err, "hmv_phase_sync_c128: ", 21) != 0))) {
-    printf("FAIL %s: got %d (%s), want %d (%s)\n", what, got, err, want, text ? text : "");
+  if (got != want || (text && (!strstr(err, text) || strncmp(err, entry, strlen(entry)) != 0))) {
+    printf("FAIL %s%s: got %d (%s), want %d (%s)\n", entry, what, got, err, want, text ? text : "");
     ++failures;
   }
 }
@@ -35,7 +36,27 @@ struct Call {
   }
 };
 
-int main() {
+struct Pairs {
+  const double* z = reinterpret_cast<const double*>(0x1000);
+  int64_t rec_stride = 8000, ld = 1000, T = 1000, n_rec = 2;
+  int m = 8, split = 4;
+  const int64_t* rec_a = reinterpret_cast<const int64_t*>(0x1000);
+  const int64_t* rec_b = reinterpret_cast<const int64_t*>(0x1000);
+  const int64_t* item_start = reinterpret_cast<const int64_t*>(0x1000);
+  const int64_t* shift_b = reinterpret_cast<const int64_t*>(0x1000);
+  int64_t n_items = 5;
+  int n = 100, mode = HMV_PHASE_UNIT;
+  double* values = reinterpret_cast<double*>(0x1000);
+  int val_stride = 4, col_mag = 0, col_lagged = 1;
+  int32_t* info = reinterpret_cast<int32_t*>(0x1000);
+  int run() const {
+    return hmv_phase_sync_pairs_c128(z, rec_stride, ld, T, n_rec, m, split, rec_a, rec_b, item_start, shift_b, n_items, n, mode,
+                                     values, val_stride, col_mag, col_lagged, info, nullptr);
+  }
+};
+
+static void full_form() {
+  entry = "hmv_phase_sync_c128: ";
   Call c;
   c = Call(); c.m = 0; expect(c.run(), -1, "channel count", "m = 0");
   c = Call(); c.m = 65; c.rec_stride = 65000; expect(c.run(), -1, "channel count", "m = 65");
@@ -60,6 +81,51 @@ int main() {
   c = Call(); c.n_items = 0; c.z = nullptr; c.item_rec = nullptr; c.item_start = nullptr; c.info = nullptr;
   expect(c.run(), 0, nullptr, "empty batch, null pointers");
   c = Call(); c.n_items = 0; c.mode = 3; expect(c.run(), -7, "mode", "empty batch, bad mode");
+}
+
+static void pairs_form() {
+  entry = "hmv_phase_sync_pairs_c128: ";
+  Pairs c;
+  c = Pairs(); c.m = 0; expect(c.run(), -1, "channel count", "m = 0");
+  c = Pairs(); c.m = 65; c.rec_stride = 65000; expect(c.run(), -1, "channel count", "m = 65");
+  c = Pairs(); c.n = 0; expect(c.run(), -2, "window length", "n = 0");
+  c = Pairs(); c.n = 1001; expect(c.run(), -2, "window length", "n > T");
+  c = Pairs(); c.T = 0; c.ld = 0; expect(c.run(), -3, "count", "T = 0");
+  c = Pairs(); c.n_rec = -1; expect(c.run(), -3, "count", "n_rec < 0");
+  c = Pairs(); c.n_items = -1; expect(c.run(), -3, "count", "n_items < 0");
+  c = Pairs(); c.n_items = int64_t(1) << 31; expect(c.run(), -10, "items", "2^31 items");
+  c = Pairs(); c.mode = 2; expect(c.run(), -7, "mode", "mode = 2");
+  c = Pairs(); c.mode = -1; expect(c.run(), -7, "mode", "mode = -1");
+  c = Pairs(); c.ld = 999; expect(c.run(), -5, "ld is smaller", "ld < T");
+  c = Pairs(); c.rec_stride = 7999; expect(c.run(), -6, "rec_stride is smaller", "rec_stride < m * ld");
+  c = Pairs(); c.ld = int64_t(1) << 58; c.rec_stride = INT64_MAX; c.m = 64; c.split = 32;
+  expect(c.run(), -6, "rec_stride is smaller", "huge ld");
+  c = Pairs(); c.z = nullptr; expect(c.run(), -4, "null pointer", "null z");
+  c = Pairs(); c.rec_a = nullptr; expect(c.run(), -4, "null pointer", "null rec_a");
+  c = Pairs(); c.rec_b = nullptr; expect(c.run(), -4, "null pointer", "null rec_b");
+  c = Pairs(); c.item_start = nullptr; expect(c.run(), -4, "null pointer", "null item_start");
+  c = Pairs(); c.values = nullptr; expect(c.run(), -4, "null pointer", "null values");
+  c = Pairs(); c.info = nullptr; expect(c.run(), -4, "null pointer", "null info");
+  c = Pairs(); c.z = reinterpret_cast<const double*>(0x1008); expect(c.run(), -8, "16-byte aligned", "misaligned z");
+  c = Pairs(); c.split = 0; expect(c.run(), -11, "split", "split = 0");
+  c = Pairs(); c.split = 8; expect(c.run(), -11, "split", "split = m");
+  c = Pairs(); c.m = 1; c.split = 1; expect(c.run(), -11, "split", "m = 1");
+  c = Pairs(); c.val_stride = 0; expect(c.run(), -12, "val_stride", "val_stride = 0");
+  c = Pairs(); c.col_mag = 4; expect(c.run(), -12, "val_stride", "col_mag = val_stride");
+  c = Pairs(); c.col_lagged = -2; expect(c.run(), -12, "val_stride", "col_lagged = -2");
+  c = Pairs(); c.col_mag = -1; c.col_lagged = -1; expect(c.run(), -12, "val_stride", "no column");
+  c = Pairs(); c.col_mag = 2; c.col_lagged = 2; expect(c.run(), -12, "val_stride", "equal columns");
+  c = Pairs(); c.n_items = 0; expect(c.run(), 0, nullptr, "empty batch");
+  c = Pairs(); c.n_items = 0; c.z = nullptr; c.rec_a = nullptr; c.rec_b = nullptr; c.item_start = nullptr; c.shift_b = nullptr;
+  c.values = nullptr; c.info = nullptr;
+  expect(c.run(), 0, nullptr, "empty batch, null pointers");
+  c = Pairs(); c.n_items = 0; c.split = 9; expect(c.run(), -11, "split", "empty batch, bad split");
+  c = Pairs(); c.n_items = 0; c.col_mag = -1; c.val_stride = 1; c.col_lagged = 0; expect(c.run(), 0, nullptr, "one column");
+}
+
+int main() {
+  full_form();
+  pairs_form();
   printf(failures ? "asan phase_sync driver: %d failure(s)\n" : "asan phase_sync driver ok\n", failures);
   return failures ? 1 : 0;
 }

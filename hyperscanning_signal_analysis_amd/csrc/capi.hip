@@ -1978,4 +1978,35 @@ int hmv_phase_sync_c128(const double* z, int64_t rec_stride, int64_t ld, int64_t
   return hmv::launch_phase_sync(a, mp, S(stream));
 }
 
+int hmv_phase_sync_pairs_c128(const double* z, int64_t rec_stride, int64_t ld, int64_t T, int64_t n_rec, int m, int split,
+                              const int64_t* rec_a, const int64_t* rec_b, const int64_t* item_start, const int64_t* shift_b,
+                              int64_t n_items, int n, int mode, double* values, int val_stride, int col_mag, int col_lagged,
+                              int32_t* info, void* stream) {
+  const int mp = pad_of(m);
+  if (mp < 0) return fail(-1, "hmv_phase_sync_pairs_c128: channel count must be in 1..64");
+  if (T < 1 || n_rec < 0 || n_items < 0) return fail(-3, "hmv_phase_sync_pairs_c128: bad sample / recording / item count");
+  if (n_items > 0x7fffffffLL) return fail(-10, "hmv_phase_sync_pairs_c128: more than 2^31 - 1 items in one call");
+  if (n < 1 || n > T) return fail(-2, "hmv_phase_sync_pairs_c128: window length must be in 1..T");
+  if (mode != HMV_PHASE_UNIT && mode != HMV_PHASE_RAW)
+    return fail(-7, "hmv_phase_sync_pairs_c128: mode must be HMV_PHASE_UNIT (0) or HMV_PHASE_RAW (1)");
+  if (split < 1 || split > m - 1) return fail(-11, "hmv_phase_sync_pairs_c128: split must be in 1..m-1");
+  if (val_stride < 1 || col_mag < -1 || col_mag >= val_stride || col_lagged < -1 || col_lagged >= val_stride ||
+      col_mag == col_lagged)        // equal columns: both -1 (no output) or one column asked to hold two values
+    return fail(-12, "hmv_phase_sync_pairs_c128: val_stride must be >= 1 and col_mag, col_lagged two different columns in "
+                     "-1..val_stride-1, not both -1");
+  if (ld < T) return fail(-5, "hmv_phase_sync_pairs_c128: ld is smaller than T");
+  if (ld > INT64_MAX / m || rec_stride < (int64_t)m * ld)
+    return fail(-6, "hmv_phase_sync_pairs_c128: rec_stride is smaller than m * ld");
+  if (n_items == 0) return 0;
+  if (!z || !rec_a || !rec_b || !item_start || !values || !info) return fail(-4, "hmv_phase_sync_pairs_c128: null pointer");
+  if (reinterpret_cast<uintptr_t>(z) % 16) return fail(-8, "hmv_phase_sync_pairs_c128: z is not 16-byte aligned");
+  hmv::PhasePairsArgs a{};
+  a.z = reinterpret_cast<const double2*>(z); a.rec_stride = rec_stride; a.ld = ld; a.T = T; a.n_rec = n_rec;
+  a.rec_a = reinterpret_cast<const long long*>(rec_a); a.rec_b = reinterpret_cast<const long long*>(rec_b);
+  a.item_start = reinterpret_cast<const long long*>(item_start); a.shift_b = reinterpret_cast<const long long*>(shift_b);
+  a.n_items = n_items; a.m = m; a.n = n; a.mode = mode; a.split = split;
+  a.values = values; a.val_stride = val_stride; a.col_mag = col_mag; a.col_lagged = col_lagged; a.info = info;
+  return hmv::launch_phase_sync_pairs(a, mp, S(stream));
+}
+
 }  // extern "C"

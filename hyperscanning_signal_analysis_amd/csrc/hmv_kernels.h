@@ -444,5 +444,21 @@ struct PhaseSyncArgs {
   int* info;                // [n_items]
 };
 int launch_phase_sync(const PhaseSyncArgs& a, int m_pad, hipStream_t st);
+// the pairs form: channels < split of recording rec_a[it] against channels >= split of recording rec_b[it], read
+// shift_b[it] samples later modulo T; the cross cells only, written into columns of a [n_items][m][m][val_stride] buffer
+struct PhasePairsArgs {
+  const double2* z;         // as PhaseSyncArgs
+  long long rec_stride, ld, T, n_rec;
+  const long long* rec_a;       // [n_items] (device)
+  const long long* rec_b;       // [n_items] (device)
+  const long long* item_start;  // [n_items] (device)
+  const long long* shift_b;     // optional [n_items] (device), in 0..T-1; null: 0
+  long long n_items;
+  int m, n, mode, split;
+  double* values;           // [n_items][m][m][val_stride]
+  int val_stride, col_mag, col_lagged;    // a column of -1: not wanted
+  int* info;                // [n_items]
+};
+int launch_phase_sync_pairs(const PhasePairsArgs& a, int m_pad, hipStream_t st);
 
 }  // namespace hmv

@@ -207,29 +207,50 @@ __device__ __forceinline__ void stage_chunk2(double* xre, double* xim, int t0, S
 
 // the k-steps of one staged chunk for the tiles J >= I:  re += re_i re_j + im_i im_j,  im += im_i re_j - re_i im_j, per
 // accumulator in this order of products whatever NT.  xa / xb: a_operand2 / b_operand2 of the re plane; the im plane
-// lies `plane` doubles behind it.
-template <int NT>
+// lies `plane` doubles behind it.  MASKED: only the tiles whose bit I * NT + J is set in `need` (workgroup-uniform, see
+// herm_need) see an MFMA, and only the operands of those tiles an LDS read; a computed tile has the bits it has unmasked.
+template <int NT, bool MASKED = false>
 __device__ __forceinline__ void ksteps_herm(const double* xa, const double* xb, int plane, int steps, double (&re)[NT][NT],
-                                            double (&im)[NT][NT]) {
+                                            double (&im)[NT][NT], unsigned need = 0) {
+  constexpr unsigned ROW = (1u << NT) - 1, COL = ((1u << (NT * NT)) - 1) / ROW;   // bits I * NT + J: all J of I = 0, all I of J = 0
   for (int ts = 0; ts < steps; ++ts) {
     double ar[NT], ai[NT], br[NT], bi[NT];
 #pragma unroll
     for (int I = 0; I < NT; ++I) {
-      ar[I] = xa[16 * I * S2 + 4 * ts];
-      ai[I] = xa[plane + 16 * I * S2 + 4 * ts];
-      br[I] = xb[16 * I * S2 + 4 * ts];
-      bi[I] = xb[plane + 16 * I * S2 + 4 * ts];
+      if (!MASKED || (need & (ROW << (I * NT)))) {
+        ar[I] = xa[16 * I * S2 + 4 * ts];
+        ai[I] = xa[plane + 16 * I * S2 + 4 * ts];
+      }
+      if (!MASKED || (need & (COL << I))) {
+        br[I] = xb[16 * I * S2 + 4 * ts];
+        bi[I] = xb[plane + 16 * I * S2 + 4 * ts];
+      }
     }
 #pragma unroll
     for (int I = 0; I < NT; ++I)
 #pragma unroll
-      for (int J = I; J < NT; ++J) {
-        re[I][J] = mfma4(ar[I], br[J], re[I][J]);
-        re[I][J] = mfma4(ai[I], bi[J], re[I][J]);
-        im[I][J] = mfma4(ai[I], br[J], im[I][J]);
-        im[I][J] = mfma4_nega(ar[I], bi[J], im[I][J]);
-      }
+      for (int J = I; J < NT; ++J)
+        if (!MASKED || (need & (1u << (I * NT + J)))) {
+          re[I][J] = mfma4(ar[I], br[J], re[I][J]);
+          re[I][J] = mfma4(ai[I], bi[J], re[I][J]);
+          im[I][J] = mfma4(ai[I], br[J], im[I][J]);
+          im[I][J] = mfma4_nega(ar[I], bi[J], im[I][J]);
+        }
   }
+}
+
+// The tiles [I][J] of the pairs form (bit I * NT + J): those that hold a cross element (row < split <= column) -- not
+// 16 I >= split, not 16 J + 15 < split, not J < I; a tile that straddles split is computed whole -- and, with `diag`, the
+// diagonal tiles [I][I] (the RAW mode's C_ii).  The same in every wave: rows 16 I .. 16 I + 15 are spread over the four.
+template <int NT>
+__device__ __forceinline__ unsigned herm_need(int split, bool diag) {
+  unsigned need = 0;
+#pragma unroll
+  for (int I = 0; I < NT; ++I)
+#pragma unroll
+    for (int J = I; J < NT; ++J)
+      if ((16 * I < split && 16 * J + 15 >= split) || (diag && I == J)) need |= 1u << (I * NT + J);
+  return (unsigned)uni((int)need);
 }
 
 // host: f(std::integral_constant<int, NT>) for the padded channel count m_pad = 16 * NT; -1 for any other

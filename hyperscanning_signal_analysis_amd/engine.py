@@ -2077,6 +2077,143 @@ class Engine:
             z = z.contiguous()
         return self._phase_sync(z, item_rec, item_start, n, mode, "mag" in want, "lagged" in want, bool(coherency))
 
+    def _phase_sync_pairs(self, z, rec_a, rec_b, item_start, n, mode, split, shift_b, values, cols, info=None):
+        n_rec, m, T = z.shape
+        n_items = int(rec_a.numel())
+        info = torch.empty(n_items, dtype=torch.int32, device=self.device) if info is None else info
+        with torch.cuda.device(self.device):
+            rc = self.lib.hmv_phase_sync_pairs_c128(z.data_ptr(), z.stride(0), z.stride(1), T, n_rec, m, int(split),
+                                                    rec_a.data_ptr(), rec_b.data_ptr(), item_start.data_ptr(), _ptr(shift_b),
+                                                    n_items, int(n), int(mode), values.data_ptr(), int(values.shape[-1]),
+                                                    int(cols[0]), int(cols[1]), info.data_ptr(), self.stream())
+        _lib.check(rc, "hmv_phase_sync_pairs_c128")
+        return values, info
+
+    def phase_sync_pairs(self, z: torch.Tensor, rec_a: torch.Tensor, rec_b: torch.Tensor, item_start: torch.Tensor, n: int,
+                         mode: int, *, split: int, shift_b: torch.Tensor | None = None, out: torch.Tensor | None = None,
+                         cols=(0, 1)):
+        """The inter-brain cells of `phase_sync` for items put together from two places (`hmv_phase_sync_pairs_c128`): item
+        i = the channels < split of recording rec_a[i] at item_start[i] .. + n with the channels >= split of recording
+        rec_b[i] read shift_b[i] samples later, modulo T (shift_b None: 0).  z as for `phase_sync`.  rec_b = rec_a with a
+        shift is the shift surrogate of the window (the analytic signal is a circular filter, so shifting the recording
+        shifts z), another rec_b at shift 0 the pseudo dyad; neither is ever written out.
+        cols = (col_mag, col_lagged): the columns of `out` (n_items, m, m, K) float64 that receive mag and lagged, -1 for an
+        output that is not wanted; the other columns of `out` are left alone.  out None: a new (n_items, m, m, 1 + max(cols))
+        tensor, NaN in the columns not written.  In the written columns a cross cell (one index < split) has the bits
+        `phase_sync` gives on the written-out window and every other cell is NaN.  -> (out, info int32 (n_items,)), info as
+        in `phase_sync`.  Both recording tables and the shifts (0..T-1) are checked before the call."""
+        if (not isinstance(z, torch.Tensor) or z.dtype != torch.complex128 or z.device != self.device or z.dim() != 3
+                or z.shape[1] < 2):
+            raise ValueError(f"phase_sync_pairs: z must be a complex128 tensor (n_rec, m >= 2, T) on {self.device}")
+        n_rec, m, T = z.shape
+        if int(mode) not in (_lib.PHASE_UNIT, _lib.PHASE_RAW):
+            raise ValueError(f"phase_sync_pairs: mode must be PHASE_UNIT (0) or PHASE_RAW (1), got {mode!r}")
+        if isinstance(split, bool) or not isinstance(split, (int, np.integer)) or not 1 <= int(split) <= m - 1:
+            raise ValueError(f"phase_sync_pairs: split must be an integer in 1..{m - 1}, got {split!r}")
+        cols = tuple(int(c) for c in cols)
+        if len(cols) != 2 or min(cols) < -1 or max(cols) < 0 or cols[0] == cols[1]:
+            raise ValueError(f"phase_sync_pairs: cols must be two different columns (col_mag, col_lagged), -1 for an output "
+                             f"that is not wanted and not both, got {cols!r}")
+        self.pad(m)
+        for name, rec in (("rec_a", rec_a), ("rec_b", rec_b)):
+            try:
+                validate_items(z, rec, item_start, n, 0)
+            except ValueError as err:                      # the message names the table that is wrong
+                raise ValueError("phase_sync_pairs: " + str(err).replace("item_rec", name)) from None
+        n_items = int(rec_a.numel())
+        if shift_b is not None:
+            if (not isinstance(shift_b, torch.Tensor) or shift_b.dtype != torch.int64 or shift_b.device != z.device
+                    or shift_b.shape != (n_items,)):
+                raise ValueError(f"phase_sync_pairs: shift_b must be a 1-D int64 tensor on {z.device}, one entry per item")
+            if n_items:
+                lo, hi = torch.stack([shift_b.min(), shift_b.max()]).cpu().tolist()
+                if lo < 0 or hi >= T:
+                    raise ValueError(f"phase_sync_pairs: shift_b must lie in [0, {T}), got [{lo}, {hi}]")
+            shift_b = shift_b.contiguous()
+        if out is None:
+            out = torch.full((n_items, m, m, 1 + max(cols)), float("nan"), dtype=torch.float64, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.device != self.device or out.dim() != 4
+              or tuple(out.shape[:3]) != (n_items, m, m) or out.shape[3] <= max(cols) or not out.is_contiguous()):
+            raise ValueError(f"phase_sync_pairs: out must be a contiguous float64 tensor ({n_items}, {m}, {m}, K) on "
+                             f"{self.device} with K > {max(cols)}")
+        if n_rec > 0 and (z.stride(2) != 1 or z.stride(1) < T or z.stride(0) < m * z.stride(1)):
+            z = z.contiguous()
+        return self._phase_sync_pairs(z, rec_a.contiguous(), rec_b.contiguous(), item_start.contiguous(), n, mode, split,
+                                      shift_b, out, cols)
+
+    def phase_sync_significance(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, fs: float,
+                                bands_hz, *, measures=("plv",), n_surrogates: int, seed, split=None, min_shift=None,
+                                order: int = 4, check=True, chunk: int | None = None, full: bool = False,
+                                max_workspace_bytes: int = 8 << 30):
+        """Shift-surrogate test of the inter-brain cells of `sliding_phase_sync`: x (n_rec, m, T) float64 on the device,
+        channels < split participant A.  Surrogate s reads participant B of recording r d[s, r] samples later, circularly,
+        with d = `surrogates.shift_offsets(numpy.random.default_rng(seed), S, n_rec, T, min_shift)` modulo T (min_shift = 0 can
+        draw T itself, which reads B as it lies).  The analytic signal is a
+        circular filter, so that is the observed analytic signal of B read d samples later: z is formed once per slab of
+        recordings x bands (the slabs of `sliding_phase_sync`) and a surrogate is a table of shifts for `phase_sync_pairs` --
+        no surrogate signal, FFT or window exists.  Per window and band the statistics of `sliding_significance` over the
+        measures as value columns: p = (1 + #{v_s >= v_obs}) / (1 + n_valid), p_fwe with the maximum over the tested pairs per
+        window, band and measure, null_mean, null_std (ddof 1).  A surrogate item with a non-finite sample is left out of
+        n_valid.  check=True: ValueError naming the first (recording, window, band) whose observed info is not 0; "nan": its
+        row is NaN.  chunk: items (surrogate x window x band) per call; the same bits for any chunk and any slab size.
+        -> {"tested": (m, m) bool, "n_valid": int32 (n_items, n_bands), "info": int32 (n_items, n_bands), measure: {"observed",
+        "p", "p_fwe", "null_mean", "null_std": (n_items, n_bands, m, m)}}; observed holds the cross cells and NaN elsewhere;
+        full=True adds "full": the dict of `sliding_phase_sync` on the same z."""
+        return significance.phase_sync_significance(self, x, item_rec, item_start, n, fs, bands_hz, measures=measures,
+                                                    n_surrogates=n_surrogates, seed=seed, split=split, min_shift=min_shift,
+                                                    order=order, check=check, chunk=chunk, full=full,
+                                                    max_workspace_bytes=max_workspace_bytes)
+
+    def phase_sync_pseudo_dyad_significance(self, x: torch.Tensor, item_start: torch.Tensor, n: int, fs: float, bands_hz, *,
+                                            measures=("plv",), split=None, n_surrogates=None, seed=None, order: int = 4,
+                                            check=True, chunk: int | None = None, max_workspace_bytes: int = 8 << 30):
+        """Pseudo-dyad test of the inter-brain cells of `sliding_phase_sync`: x (D, m, T), recording d = dyad d, item_start
+        (W,) the windows common to all dyads.  Surrogate s analyses A of dyad d with B of dyad pi[s][d] at the same samples
+        (`surrogates.partner_derangements`, as `pseudo_dyad_significance`): one `phase_sync_pairs` call per mode on the
+        resident analytic signals, rec_b = pi[s][rec_a], no shift.  The bands run outermost, with the analytic signals of all
+        D dyads of one band resident together; ValueError (with the bytes needed) if they do not fit max_workspace_bytes.
+        -> {"tested", "partners" (S, D), "n_valid" (D, W, n_bands), "info" (D, W, n_bands), measure: {"observed", "p",
+        "p_fwe", "null_mean", "null_std": (D, W, n_bands, m, m)}, "group": {"n_valid" (W, n_bands), measure: {the same five,
+        (W, n_bands, m, m)}}} -- per dyad over the 2 S A-anchored and B-anchored values, and for the mean over the dyads."""
+        return significance.phase_sync_pseudo_dyad_significance(self, x, item_start, n, fs, bands_hz, measures=measures,
+                                                                split=split, n_surrogates=n_surrogates, seed=seed,
+                                                                order=order, check=check, chunk=chunk,
+                                                                max_workspace_bytes=max_workspace_bytes)
+
+    def phase_slabs(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, resp: torch.Tensor,
+                    max_workspace_bytes: int):
+        """The analytic signal of x (n_rec, m, T) for the responses resp (n_bands, T), slab by slab: B bands of R recordings, as
+        many as keep the complex arrays alive at one time -- the slab's z, one recording's spectrum and one product -- under
+        `max_workspace_bytes` (at least one recording and one band).  Yields (sel, b0, b1, z, rec_z, start_z): the slab holds
+        the bands b0 .. b1 - 1 of the items `sel` (a slice or an index tensor into the item tables), z ((recordings of the
+        slab) * (b1 - b0), m, T) is its analytic signal with the bands as recordings, and rec_z / start_z are its item tables,
+        window-major and band-minor.  The caller drops its z before asking for the next slab."""
+        n_rec, m, T = x.shape
+        nb = int(resp.shape[0])
+        if item_rec.numel() == 0:
+            return
+        unit = 16 * m * T
+        B = int(max(1, min(nb, int(max_workspace_bytes) // unit - 2)))
+        R = int(max(1, min(n_rec, (int(max_workspace_bytes) // unit - 2) // nb))) if B == nb else 1
+        rec_host = item_rec.cpu()
+        for r0 in range(0, n_rec, R):
+            r1 = min(n_rec, r0 + R)
+            if R >= n_rec:
+                sel, rec_s, start_s = slice(None), item_rec, item_start
+            else:
+                sel = torch.nonzero((rec_host >= r0) & (rec_host < r1)).flatten().to(self.device)
+                if sel.numel() == 0:
+                    continue
+                rec_s, start_s = item_rec[sel] - r0, item_start[sel]
+            for b0 in range(0, nb, B):
+                b1 = min(nb, b0 + B)
+                z = self.analytic_signal(x[r0:r1], resp[b0:b1]).view(-1, m, T)       # recording (r, b) = (r - r0) * (b1 - b0) + b
+                bb = torch.arange(b1 - b0, dtype=torch.int64, device=self.device)
+                rec_z = (rec_s[:, None] * (b1 - b0) + bb[None, :]).reshape(-1)
+                start_z = start_s[:, None].expand(-1, b1 - b0).reshape(-1)
+                yield sel, b0, b1, z, rec_z, start_z
+                del z
+
     def sliding_phase_sync(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, fs: float,
                            bands_hz, *, measures=("plv",), order: int = 4, check=True, max_workspace_bytes: int = 8 << 30):
         """Band-limited phase synchrony per window: x (n_rec, m, T) float64 on the device -> {measure: (n_items, n_bands, m,
@@ -2104,37 +2241,14 @@ class Engine:
         modes = [(mode, qs, names) for mode, qs, names in modes if qs]
         out = {q: self.empty(n_items, nb, m, m) for q in measures}
         info = torch.zeros(n_items, nb, dtype=torch.int32, device=self.device)
-        if n_items:
-            # slabs: B bands of R recordings; alive with them are one recording's spectrum and one product
-            unit = 16 * m * T
-            B = int(max(1, min(nb, int(max_workspace_bytes) // unit - 2)))
-            R = int(max(1, min(n_rec, (int(max_workspace_bytes) // unit - 2) // nb))) if B == nb else 1
-            rec_host = item_rec.cpu()
-            for r0 in range(0, n_rec, R):
-                r1 = min(n_rec, r0 + R)
-                if R >= n_rec:
-                    idx, rec_s, start_s = None, item_rec, item_start
-                else:
-                    idx = torch.nonzero((rec_host >= r0) & (rec_host < r1)).flatten().to(self.device)
-                    if idx.numel() == 0:
-                        continue
-                    rec_s, start_s = item_rec[idx] - r0, item_start[idx]
-                for b0 in range(0, nb, B):
-                    b1 = min(nb, b0 + B)
-                    z = self.analytic_signal(x[r0:r1], resp[b0:b1])                  # (r1 - r0, b1 - b0, m, T)
-                    # the slab as (r1 - r0) * (b1 - b0) recordings; items window-major, band-minor
-                    bb = torch.arange(b1 - b0, dtype=torch.int64, device=self.device)
-                    rec_z = (rec_s[:, None] * (b1 - b0) + bb[None, :]).reshape(-1)
-                    start_z = start_s[:, None].expand(-1, b1 - b0).reshape(-1)
-                    for mode, qs, names in modes:
-                        res = self._phase_sync(z.view(-1, m, T), rec_z, start_z, n, mode, names[0] in qs, names[1] in qs,
-                                               False)
-                        sel = slice(None) if idx is None else idx
-                        for q, key in zip(names, ("mag", "lagged")):
-                            if q in qs:
-                                out[q][sel, b0:b1] = res[key].view(-1, b1 - b0, m, m)
-                        info[sel, b0:b1] = torch.maximum(info[sel, b0:b1], res["info"].view(-1, b1 - b0))
-                    del z
+        for sel, b0, b1, z, rec_z, start_z in self.phase_slabs(x, item_rec, item_start, resp, max_workspace_bytes):
+            for mode, qs, names in modes:
+                res = self._phase_sync(z, rec_z, start_z, n, mode, names[0] in qs, names[1] in qs, False)
+                for q, key in zip(names, ("mag", "lagged")):
+                    if q in qs:
+                        out[q][sel, b0:b1] = res[key].view(-1, b1 - b0, m, m)
+                info[sel, b0:b1] = torch.maximum(info[sel, b0:b1], res["info"].view(-1, b1 - b0))
+            del z
         if check is True and n_items:
             bad = torch.nonzero(info.cpu())
             if bad.numel():

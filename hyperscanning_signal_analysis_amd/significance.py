@@ -1,6 +1,6 @@
 """The null tests behind `Engine.sliding_significance`, `.pseudo_dyad_significance`, `.block_granger_significance`,
-`.block_granger_pseudo_dyad_significance`, `.ensemble_significance` and `.ensemble_contrast`: the functions of those names
-below, each taking the engine first.
+`.block_granger_pseudo_dyad_significance`, `.ensemble_significance`, `.ensemble_contrast`, `.phase_sync_significance` and
+`.phase_sync_pseudo_dyad_significance`: the functions of those names below, each taking the engine first.
 
 What they share is here once: the block planners (integers in, integers out), the preamble, `NullAccumulator`, which owns the
 running state of `hmv_null_accumulate_f64` and builds every returned dict, and one loop per null -- `surrogate_null` (shift and
@@ -9,7 +9,10 @@ it the observed values as (rows, mv, mv, nv) and a closure that turns a block of
 the connectivity measures that is the (m, m, n_bands) band array of the fused call itself; for block Granger causality it is
 the 2 x 2 meta array of `block_meta`, taken apart again by `block_leaves`.  So a test is: check the arguments, make the
 observed call, run its loop, shape the result.  The two ensemble tests plan their blocks differently and keep loops of their
-own.  The draws and the argument checks are `surrogates`; everything that wraps one C call is a method of the engine.
+own.  Phase synchrony has no model and no surrogate window: its shift surrogate is a table of shifts for the pairs kernel
+on the observed analytic signal, so its shift test walks `sliding_plan`'s blocks itself, slab by slab of the analytic
+signal (`Engine.phase_slabs`), and its pseudo-dyad test is `partner_null` without the lag-covariance base (p = None).  The
+draws and the argument checks are `surrogates`; everything that wraps one C call is a method of the engine.
 """
 from __future__ import annotations
 
@@ -22,7 +25,8 @@ from . import surrogates as sg
 __all__ = ["sliding_plan", "ensemble_plan", "stack_plan", "window_ranges", "surrogate_blocks", "NullAccumulator",
            "surrogate_null", "partner_null", "sliding_significance", "ensemble_significance", "pseudo_dyad_significance",
            "ensemble_contrast", "block_meta", "block_leaves", "block_granger_significance",
-           "block_granger_pseudo_dyad_significance"]
+           "block_granger_pseudo_dyad_significance", "phase_calls", "phase_pairs", "phase_chunk", "phase_sync_significance",
+           "phase_sync_pseudo_dyad_significance"]
 
 STATS = ("p", "p_fwe", "null_mean", "null_std")
 
@@ -201,17 +205,19 @@ def dyad_items(eng, x, item_start, n, p):
 
 
 def partner_null(eng, acc, x, dy, starts, n, p, partners, chunk, obs, obs_bad, surrogate):
-    """The pseudo-dyad null of the N = D W items (dy, starts): K1 over the real windows for the within-participant blocks,
-    then per derangement `surrogate(block, rec_b, base, out) -> bad` on blocks of at most `chunk` items -- `out` (block, mv,
-    mv, nv) receives the values of A of dyad dy with B of dyad rec_b, `base` is R_base / base_a / base_b of the block --,
-    the A- and the B-anchored value of every dyad into `acc` against `obs`, and the mean over the dyads aside.  -> the group
-    dict of `NullAccumulator.group`."""
+    """The pseudo-dyad null of the N = D W items (dy, starts): K1 over the real windows for the within-participant blocks
+    (not with p = None: the value has no model order and `base` carries R_base = None), then per derangement
+    `surrogate(block, rec_b, base, out) -> bad` on blocks of at most `chunk` items -- `out` (block, mv, mv, nv) receives the
+    values of A of dyad dy with B of dyad rec_b, `base` is R_base / base_a / base_b of the block --, the A- and the
+    B-anchored value of every dyad into `acc` against `obs`, and the mean over the dyads aside.  -> the group dict of
+    `NullAccumulator.group`."""
     N, mv, _, nv = obs.shape
     S, D = partners.shape
     W = N // D
     i64 = dict(dtype=torch.int64, device=eng.device)
     # (K1 over the D W real windows a second time -- the observed fused call does not hand its R out; a few per cent of it)
-    R_base = eng.lagcov(x, dy, starts, n, p)
+    # p None: a value without a model (phase synchrony) has no within-participant blocks to copy, and R_base is None
+    R_base = None if p is None else eng.lagcov(x, dy, starts, n, p)
     base_a = torch.arange(N, **i64)
     wrep = torch.arange(W, **i64).repeat(D)
     blk = N if chunk is None else max(1, min(N, int(chunk)))
@@ -557,3 +563,176 @@ def block_granger_pseudo_dyad_significance(eng, x, item_start, n, p, freqs, fs, 
         return bad
     group = partner_null(eng, acc, x, dy, starts, n, p, partners, chunk, obs_meta, obs_bad, surrogate)
     return finish(acc.result((D, W), obs_meta, obs_bad), obs[1], obs_bad, (D, W), group=group, partners=partners_out)
+
+
+# ------------------------------------------------------------------ phase synchrony: no model, the measures as value columns
+PHASE_WHY = {1: "a non-finite sample in the window", 2: "a channel of zero power in the window"}
+
+
+def phase_calls(measures):
+    """The kernel calls that fill the value columns `measures`: [(mode, (col_mag, col_lagged))], a column of -1 for a measure
+    that was not asked for; one call per mode in use (PLV / ciPLV: unit phasors, coh / imcoh: the signal itself)."""
+    calls = []
+    for mode, names in ((_engine._lib.PHASE_UNIT, ("plv", "ciplv")), (_engine._lib.PHASE_RAW, ("coh", "imcoh"))):
+        cols = tuple(measures.index(q) if q in measures else -1 for q in names)
+        if max(cols) >= 0:
+            calls.append((mode, cols))
+    return calls
+
+
+def phase_pairs(eng, calls, z, rec_a, rec_b, start, n, split, shift, out):
+    """Every mode's call of `hmv_phase_sync_pairs_c128` into the columns of `out` (items, m, m, nq) -> info, the largest of
+    the modes' (1 = a non-finite sample, in either mode)."""
+    info = None
+    for mode, cols in calls:
+        i = eng._phase_sync_pairs(z, rec_a, rec_b, start, n, mode, split, shift, out, cols)[1]
+        info = i if info is None else torch.maximum(info, i)
+    return info
+
+
+def phase_chunk(m: int, nq: int, max_workspace_bytes: int) -> int:
+    """Items per pairs call: a quarter of the workspace over an item's values, tables and flags."""
+    return max(1, (int(max_workspace_bytes) // 4) // (8 * m * m * nq + 64))
+
+
+def _phase_leaves(res, measures, extra=()):
+    """A `NullAccumulator` dict over (..., m, m, nq) -> {measure: {observed, p, p_fwe, null_mean, null_std (..., m, m)}}."""
+    out = {k: res[k] for k in ("n_valid", *extra)}
+    for i, q in enumerate(measures):
+        out[q] = {k: res[k][..., i] for k in ("observed",) + STATS}
+    return out
+
+
+def _phase_x(eng, x, who):
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.device != eng.device or x.dim() != 3:
+        raise ValueError(f"{who}: x must be a float64 tensor (n_rec, m, T) on {eng.device}")
+
+
+def phase_sync_significance(eng, x, item_rec, item_start, n, fs, bands_hz, *, measures, n_surrogates, seed, split=None,
+                            min_shift=None, order=4, check=True, chunk=None, full=False, max_workspace_bytes=8 << 30):
+    from .eeg_io import resolve_bands_hz
+    who = "phase_sync_significance"
+    _phase_x(eng, x, who)
+    n_rec, m, T = x.shape
+    n = int(n)
+    measures, S, split, min_shift = sg.phase_significance_args(measures, n_surrogates, m, T, n, split, min_shift, check)
+    eng.pad(m)
+    bands = resolve_bands_hz(bands_hz, fs)
+    _engine.validate_items(x, item_rec, item_start, n, 0)
+    nb, nq, W = len(bands), len(measures), int(item_rec.numel())
+    calls = phase_calls(measures)
+    tested_h = sg.tested_mask(m, "shift", split)
+    tested = torch.as_tensor(tested_h.astype(np.uint8)).to(eng.device)
+    keys = ("observed",) + STATS
+    res = {k: eng.empty(W, nb, m, m, nq) for k in keys}
+    res["n_valid"] = torch.zeros(W, nb, dtype=torch.int32, device=eng.device)
+    info = torch.zeros(W, nb, dtype=torch.int32, device=eng.device)
+    full_out = {q: eng.empty(W, nb, m, m) for q in measures} if full else None
+    if W:
+        # a draw may be T itself (min_shift = 0: the draws are from [min_shift, T - min_shift] with both ends); reading B T
+        # samples later modulo T is reading it as it lies, and the kernel takes shifts in 0..T-1
+        d_all = torch.as_tensor(sg.shift_offsets(np.random.default_rng(seed), S, n_rec, T, min_shift) % T).to(eng.device)
+        resp = torch.stack([eng.band_response(T, fs, lo, hi, order) for lo, hi in bands])
+        chunk = phase_chunk(m, nq, max_workspace_bytes) if chunk is None else max(1, int(chunk))
+        for sel, b0, b1, z, rec_z, start_z in eng.phase_slabs(x, item_rec, item_start, resp, max_workspace_bytes):
+            bs = b1 - b0
+            start_z = start_z.contiguous()
+            rec_x = item_rec[sel][:, None].expand(-1, bs).reshape(-1)                     # the row's recording in x: its draws
+            N = int(rec_z.numel())
+            Ws = N // bs
+            obs = eng.empty(N, m, m, nq)
+            info_s = phase_pairs(eng, calls, z, rec_z, rec_z, start_z, n, split, None, obs)
+            info[sel, b0:b1] = info_s.view(Ws, bs)
+            if check is True:                                # before any surrogate of the slab
+                bad_rows = torch.nonzero(info_s.cpu()).flatten()
+                if bad_rows.numel():
+                    k = int(bad_rows[0])
+                    code, b = int(info_s[k]), b0 + k % bs
+                    it = k // bs if isinstance(sel, slice) else int(sel[k // bs])
+                    raise ValueError(f"{who}: recording {int(item_rec[it])}, window at sample {int(item_start[it])} (item {it}), "
+                                     f"band {b} {bands[b]!r} Hz: info = {code} ({PHASE_WHY.get(code, '?')}); check='nan' "
+                                     f"returns that row as NaN")
+            if full:
+                for mode, cols in calls:
+                    r = eng._phase_sync(z, rec_z, start_z, n, mode, cols[0] >= 0, cols[1] >= 0, False)
+                    for key, c in zip(("mag", "lagged"), cols):
+                        if c >= 0:
+                            full_out[measures[c]][sel, b0:b1] = r[key].view(Ws, bs, m, m)
+            acc = NullAccumulator(eng, N, m, nq, tested_h, tested)
+            Sb, Wb = sliding_plan(S, N, chunk)
+            vals = eng.empty(Sb * Wb, m, m, nq)
+            for s0, sb, w0, w1, last in surrogate_blocks(S, Sb, window_ranges(N, Wb)):
+                items = sb * (w1 - w0)
+                rec_k, start_k = rec_z[w0:w1].repeat(sb), start_z[w0:w1].repeat(sb)
+                shift = d_all[s0:s0 + sb][:, rec_x[w0:w1]].reshape(-1).contiguous()       # surrogate-major, as the items
+                v = vals[:items]
+                bad = phase_pairs(eng, calls, z, rec_k, rec_k, start_k, n, split, shift, v) == 1
+                acc.add(obs[w0:w1], v, bad, slice(w0, w1), sb, last)
+            del z
+            res["observed"][sel, b0:b1] = obs.view(Ws, bs, m, m, nq)
+            res["n_valid"][sel, b0:b1] = acc.st["n_valid"].view(Ws, bs)
+            for k in STATS:
+                res[k][sel, b0:b1] = acc.st[k].view(Ws, bs, m, m, nq)
+        if check is not True:
+            for k in keys:
+                res[k][info != 0] = float("nan")
+    out = dict(_phase_leaves(res, measures), tested=torch.as_tensor(tested_h).to(eng.device), info=info)
+    if full:
+        out["full"] = dict(full_out, info=info)
+    return out
+
+
+def phase_sync_pseudo_dyad_significance(eng, x, item_start, n, fs, bands_hz, *, measures, split=None, n_surrogates=None,
+                                        seed=None, order=4, check=True, chunk=None, max_workspace_bytes=8 << 30):
+    from .eeg_io import resolve_bands_hz
+    who = "phase_sync_pseudo_dyad_significance"
+    _phase_x(eng, x, who)
+    D, m, T = x.shape
+    n = int(n)
+    measures, S, split = sg.phase_pseudo_dyad_args(measures, D, m, n_surrogates, seed, split, check)
+    eng.pad(m)
+    bands = resolve_bands_hz(bands_hz, fs)
+    need = 16 * m * T * (D + 2)                    # one band of every dyad, one recording's spectrum and one product
+    if need > int(max_workspace_bytes):
+        raise ValueError(f"{who}: the analytic signals of all {D} dyads of one band must be resident together, which needs "
+                         f"{need} bytes; max_workspace_bytes is {int(max_workspace_bytes)}")
+    W = int(item_start.numel())
+    dy, starts = dyad_items(eng, x, item_start, n, 0)
+    nb, nq, N = len(bands), len(measures), D * W
+    calls = phase_calls(measures)
+    tested_h = sg.tested_mask(m, "shift", split)
+    tested = torch.as_tensor(tested_h.astype(np.uint8)).to(eng.device)
+    partners = sg.partner_derangements(None if S is None else np.random.default_rng(seed), S, D)
+    keys = ("observed",) + STATS
+    res = {k: eng.empty(D, W, nb, m, m, nq) for k in keys}
+    res["n_valid"] = torch.zeros(D, W, nb, dtype=torch.int32, device=eng.device)
+    grp = {k: eng.empty(W, nb, m, m, nq) for k in keys}
+    grp["n_valid"] = torch.zeros(W, nb, dtype=torch.int32, device=eng.device)
+    info = torch.zeros(D, W, nb, dtype=torch.int32, device=eng.device)
+    for b, (lo, hi) in enumerate(bands if W else ()):
+        z = eng.analytic_signal(x, eng.band_response(T, fs, lo, hi, order))              # (D, m, T): every dyad of the band
+        obs = eng.empty(N, m, m, nq)
+        info_b = phase_pairs(eng, calls, z, dy, dy, starts, n, split, None, obs)
+        info[:, :, b] = info_b.view(D, W)
+        obs_bad = None
+        if bool(info_b.any()):
+            if check is True:
+                it = int(torch.nonzero(info_b)[0])
+                code = int(info_b[it])
+                raise ValueError(f"{who}: dyad {it // W}, window at sample {int(starts[it])} (window {it % W}), band {b} "
+                                 f"{bands[b]!r} Hz: info = {code} ({PHASE_WHY.get(code, '?')}); check='nan' returns that row "
+                                 f"as NaN")
+            obs_bad = info_b != 0
+        acc = NullAccumulator(eng, N, m, nq, tested_h, tested)
+
+        def surrogate(sl, rec_b, base, out):
+            return phase_pairs(eng, calls, z, dy[sl], rec_b, starts[sl], n, split, None, out) == 1
+        g = partner_null(eng, acc, z, dy, starts, n, None, partners,
+                         phase_chunk(m, nq, max_workspace_bytes) if chunk is None else chunk, obs, obs_bad, surrogate)
+        r = acc.result((D, W), obs, obs_bad)
+        for k in keys + ("n_valid",):
+            res[k][:, :, b] = r[k]
+            grp[k][:, b] = g[k]
+        del z
+    return dict(_phase_leaves(res, measures), tested=torch.as_tensor(tested_h).to(eng.device), info=info,
+                partners=torch.as_tensor(partners).to(eng.device), group=_phase_leaves(grp, measures))

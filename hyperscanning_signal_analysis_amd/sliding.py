@@ -35,7 +35,7 @@ __all__ = ["window_positions", "hop_positions", "create_windows", "sliding_ffdtf
            "sliding_ensemble_significance", "sliding_ensemble_epochs_significance", "sliding_pseudo_dyad_significance",
            "sliding_model_validation", "validation_p_values", "sliding_ensemble_contrast", "sliding_ensemble_epochs_contrast",
            "sliding_block_granger_significance", "sliding_block_granger_pseudo_dyad_significance", "decimate",
-           "sliding_phase_sync"]
+           "sliding_phase_sync", "sliding_phase_sync_significance", "sliding_phase_sync_pseudo_dyad_significance"]
 
 
 def decimate(x, fs, q, design="decimate", engine: Engine | None = None):
@@ -346,6 +346,76 @@ def sliding_phase_sync(x, window_size, n_windows, fs, bands_hz=DEFAULT_BANDS, *,
     keys = measures + (("info",) if check == "nan" else ())
     out = {k: res[k].view(n_rec, len(positions), len(bands_hz), *res[k].shape[2:]).cpu().numpy() for k in keys}
     return {k: v[0] for k, v in out.items()} if single else out
+
+
+def _phase_host(v, lead=None):
+    """A leaf (or dict of leaves) of a phase-synchrony test -> NumPy, per-item leaves reshaped to `lead` + their own axes."""
+    if isinstance(v, dict):
+        return {k: _phase_host(u, lead) for k, u in v.items()}
+    a = v.cpu().numpy()
+    return a if lead is None else a.reshape(lead + a.shape[1:])
+
+
+def sliding_phase_sync_significance(x, window_size, n_windows, fs, bands_hz=DEFAULT_BANDS, *, measures=("plv",), n_surrogates,
+                                    seed, split=None, min_shift=None, hop=None, order=4, check=True, chunk=None,
+                                    engine: Engine | None = None, max_workspace_bytes: int = 8 << 30):
+    """NumPy (or tensor) in / NumPy out: the shift-surrogate test of `Engine.phase_sync_significance` for the inter-brain
+    cells of `sliding_phase_sync(x, window_size, n_windows, fs, bands_hz, hop=hop, measures=measures)`.  x: (m, T) or
+    (n_rec, m, T); channels < split are participant A (default split = m // 2).  Returns {measure: {observed, p, p_fwe,
+    null_mean, null_std (n_rec, n_windows, n_bands, m, m)}, n_valid, info (n_rec, n_windows, n_bands), tested (m, m)}, without
+    the leading axis for a single recording.  The arguments are checked before the GPU is touched
+    (`surrogates.phase_significance_args`)."""
+    from . import surrogates as sg
+    from .eeg_io import resolve_bands_hz
+    single = np.ndim(x) == 2
+    shape = tuple(np.shape(x))
+    if len(shape) not in (2, 3):
+        raise ValueError(f"sliding_phase_sync_significance: x must be (m, T) or (n_rec, m, T), got shape {shape}")
+    n_rec, m, T = (1,) + shape if single else shape
+    bands_hz = tuple(bands_hz)
+    resolve_bands_hz(bands_hz, fs)
+    positions, w = _positions(T, window_size, n_windows, hop)
+    sg.phase_significance_args(measures, n_surrogates, m, T, w, split, min_shift, check)
+    eng = engine or default_engine()
+    if isinstance(x, torch.Tensor):
+        xd = (x[None] if single else x).to(device=eng.device, dtype=torch.float64).contiguous()
+    else:
+        xd = eng.to_device(np.asarray(x, dtype=np.float64)[None] if single else np.asarray(x, dtype=np.float64))
+    item_rec, item_start = window_items(n_rec, positions, eng.device)
+    res = eng.phase_sync_significance(xd, item_rec, item_start, w, fs, bands_hz, measures=measures, n_surrogates=n_surrogates,
+                                      seed=seed, split=split, min_shift=min_shift, order=order, check=check, chunk=chunk,
+                                      max_workspace_bytes=max_workspace_bytes)
+    lead = (len(positions),) if single else (n_rec, len(positions))
+    return {k: _phase_host(v, None if k == "tested" else lead) for k, v in res.items()}
+
+
+def sliding_phase_sync_pseudo_dyad_significance(x, window_size, n_windows, fs, bands_hz=DEFAULT_BANDS, *, measures=("plv",),
+                                                split=None, n_surrogates=None, seed=None, hop=None, order=4, check=True,
+                                                chunk=None, engine: Engine | None = None,
+                                                max_workspace_bytes: int = 8 << 30):
+    """NumPy (or tensor) in / NumPy out: the pseudo-dyad test of `Engine.phase_sync_pseudo_dyad_significance`.  x: (D, m, T),
+    one recording per dyad, all time-locked to the same stimulus; windows as for `sliding_phase_sync`; partners as for
+    `sliding_pseudo_dyad_significance`.  Returns {measure: {observed, p, p_fwe, null_mean, null_std (D, n_windows, n_bands, m,
+    m)}, n_valid, info (D, n_windows, n_bands), tested (m, m), partners (S, D), group = {measure: {the same five (n_windows,
+    n_bands, m, m)}, n_valid (n_windows, n_bands)}}.  The arguments are checked before the GPU is touched
+    (`surrogates.phase_pseudo_dyad_args`)."""
+    from . import surrogates as sg
+    from .eeg_io import resolve_bands_hz
+    shape = tuple(np.shape(x))
+    if len(shape) != 3:
+        raise ValueError("x must have shape (dyads, channels, samples)")
+    D, m, T = shape
+    sg.phase_pseudo_dyad_args(measures, D, m, n_surrogates, seed, split, check)
+    bands_hz = tuple(bands_hz)
+    resolve_bands_hz(bands_hz, fs)
+    positions, w = _positions(T, window_size, n_windows, hop)
+    eng = engine or default_engine()
+    xd = _recordings_to_device(eng, x, False)
+    item_start = torch.as_tensor(np.asarray(positions, dtype=np.int64)).to(eng.device)
+    res = eng.phase_sync_pseudo_dyad_significance(xd, item_start, w, fs, bands_hz, measures=measures, split=split,
+                                                  n_surrogates=n_surrogates, seed=seed, order=order, check=check, chunk=chunk,
+                                                  max_workspace_bytes=max_workspace_bytes)
+    return {k: _phase_host(v) for k, v in res.items()}
 
 
 def sliding_significance(x, window_size, n_windows, p, freqs, fs, bands, *, measure, null, n_surrogates, seed, split=None,

@@ -4,7 +4,8 @@ drives the four tests (`Engine.sliding_significance`, `.ensemble_significance`, 
 `.ensemble_contrast`); where and how often each is drawn relative to the others is part of the result's bits.
 
 All randomness comes from `rng = numpy.random.default_rng(seed)`, in this order:
-    null="shift":  d = rng.integers(min_shift, T - min_shift, size=(S, n_rec), endpoint=True)        (once)
+    null="shift":  d = rng.integers(min_shift, T - min_shift, size=(S, n_rec), endpoint=True)        (once; also the draws of
+                   `Engine.phase_sync_significance`, whose pseudo-dyad test takes the partners below)
     null="phase":  phi = 2 pi rng.random((S, m, n // 2 + 1)), phi[..., 0] = 0, phi[..., n // 2] = 0 for even n
                    (drawn in consecutive surrogate blocks: one double per draw, so the stream is the same)
     null="trial":  for s = 0..S-1, then g = 0..G-1: pi[s][g] = rng.permutation(counts[g]), drawn again while it is the
@@ -24,7 +25,7 @@ import numpy as np
 __all__ = ["NULLS", "ENSEMBLE_NULLS", "MEASURES", "TAILS", "significance_args", "shift_offsets", "phase_draws",
            "trial_permutations", "label_draws", "contrast_args", "partner_count", "partner_derangements", "pseudo_dyad_args",
            "tested_mask", "check_significance_dict", "BLOCK_VALUES", "BLOCK_WANT", "block_want", "block_values",
-           "block_significance_args", "block_pseudo_dyad_args"]
+           "block_significance_args", "block_pseudo_dyad_args", "phase_significance_args", "phase_pseudo_dyad_args"]
 
 NULLS = ("shift", "phase")          # of continuous recordings (`sliding_significance`)
 ENSEMBLE_NULLS = ("trial",)         # of event-locked ensembles (`ensemble_significance`)
@@ -318,6 +319,48 @@ def block_significance_args(null, n_surrogates, m, T, n, split, min_shift=None, 
         raise ValueError(f"the shift null needs T >= 2 min_shift (T = {int(T)}, min_shift = {min_shift})")
     _check_mode(check)
     return S, split, min_shift, block_values(values, bands)
+
+
+def _default_split(split, m):
+    m = int(m)
+    if split is None:
+        if m % 2:
+            raise ValueError(f"an odd channel count ({m}) needs an explicit split")
+        return m // 2
+    return _block_split(split, m)
+
+
+def phase_significance_args(measures, n_surrogates, m, T, n, split=None, min_shift=None, check=True):
+    """Check the arguments of `Engine.phase_sync_significance` BEFORE anything is drawn or launched; returns (measures, S,
+    split, min_shift) with the measures resolved (`eeg_io.resolve_phase_measures`) and the defaults filled in: split = m // 2
+    for even m (odd m must pass it), min_shift = n (the window length).  ValueError for unknown or no measures, S < 1, a split
+    outside 1..m-1, min_shift < 0, T < 2 min_shift and a `check` other than True / "nan"."""
+    from .eeg_io import resolve_phase_measures
+    measures = resolve_phase_measures(measures)
+    S = _int(n_surrogates, "n_surrogates")
+    if S < 1:
+        raise ValueError(f"n_surrogates must be >= 1, got {S}")
+    split = _default_split(split, m)
+    min_shift = int(n) if min_shift is None else _int(min_shift, "min_shift")
+    if min_shift < 0:
+        raise ValueError(f"min_shift must be >= 0, got {min_shift}")
+    if int(T) < 2 * min_shift:
+        raise ValueError(f"the shift null needs T >= 2 min_shift (T = {int(T)}, min_shift = {min_shift})")
+    _check_mode(check)
+    return measures, S, split, min_shift
+
+
+def phase_pseudo_dyad_args(measures, D, m, n_surrogates, seed, split=None, check=True):
+    """Check the arguments of `Engine.phase_sync_pseudo_dyad_significance` BEFORE anything is drawn or launched; returns
+    (measures, S or None, split).  ValueError for unknown or no measures, fewer than 2 dyads, an odd channel count without a
+    split, a split outside 1..m-1, an integer n_surrogates < 1 or without a seed and a `check` other than True / "nan"."""
+    from .eeg_io import resolve_phase_measures
+    measures = resolve_phase_measures(measures)
+    _n_dyads(int(D))
+    S = partner_count(n_surrogates, seed)
+    split = _default_split(split, m)
+    _check_mode(check)
+    return measures, S, split
 
 
 def block_pseudo_dyad_args(D, m, n_surrogates, seed, split, values=BLOCK_VALUES, bands=None, check=True):

@@ -785,6 +785,36 @@ int hmv_decimate_fir_f64(const double* x, int64_t rec_stride, int64_t ld, int64_
 int hmv_phase_sync_c128(const double* z, int64_t rec_stride, int64_t ld, int64_t T, int64_t n_rec, int m,
                         const int64_t* item_rec, const int64_t* item_start, int64_t n_items, int n, int mode,
                         double* coherency, double* mag, double* lagged, int32_t* info, void* stream);
+/* The pairs form of hmv_phase_sync_c128, for the null tests of the inter-brain cells: item `it` is the m x n block whose
+ * channels c < split are z[rec_a[it]][c][item_start[it] + t] and whose channels c >= split are
+ * z[rec_b[it]][c][(item_start[it] + shift_b[it] + t) mod T], t = 0..n-1 (shift_b = NULL: 0).  Because the analytic signal is
+ * a circular filter of the recording, this is the window of the recording whose second participant was shifted by shift_b
+ * samples (rec_b = rec_a), or of the pseudo dyad A of rec_a with B of rec_b (shift 0), and no such recording is written.
+ * z, rec_stride, ld, T, n_rec, m, n, mode and the definitions of mag and lagged as above; rec_a, rec_b, item_start, shift_b
+ * are device arrays [n_items] whose contents the caller has checked (rec in 0..n_rec-1, 0 <= start, start + n <= T, shift
+ * in 0..T-1).  A side of an item whose entries would address outside its recording is read as zeros, never from memory.
+ * Only the cross cells (r < split <= c, and their mirror) are computed: the tiles of the full form that hold one, with its
+ * products in its order, so a cross cell has the bits hmv_phase_sync_c128 gives for the same block written out as one
+ * recording.  RAW mode also computes the diagonal tiles, for C_ii and C_jj with those same bits.
+ * values: [n_items][m][m][val_stride] doubles, the layout hmv_null_accumulate_f64 reads (val_stride its n_bands).  mag goes
+ *   to column col_mag and lagged to column col_lagged of every cell of the item; a column of -1: that output is not wanted.
+ *   (r, c) and (c, r) of a cross pair get the same bits; in the written columns every untested cell (both indices on one
+ *   side of split, the diagonal included) gets NaN; the other columns are not touched.  There is no coherency output.
+ * info int32 [n_items]: as above and, for an item whose entries are valid, the value hmv_phase_sync_c128 reports on the
+ *   written-out block.  1: a non-finite sample in any of the m channels as read (B through its shift) -- every written
+ *   value of the item is NaN; read off the diagonal of C in RAW mode and off the staged phasors in UNIT mode, which has no
+ *   diagonal tile.  2 (RAW only): a channel of zero power; its row and column are NaN, the rest is valid.
+ * No atomics; every sum runs over the samples ascending in k-steps of 4 from the window start; an item's bits depend on its
+ * own samples only.
+ * Refused before any launch: channel count outside 1..HMV_MAX_CHANNELS (-1), n < 1 or n > T (-2), T < 1, n_rec < 0 or
+ *   n_items < 0 (-3), more than 2^31 - 1 items (-10), mode outside 0..1 (-7), split outside 1..m-1 (-11), val_stride < 1, a
+ *   column outside -1..val_stride-1, both columns -1 or both columns equal (-12), ld < T (-5), rec_stride < m * ld (-6), and
+ *   with n_items > 0 a null z, rec_a, rec_b, item_start, values or info (-4) or a z that is not 16-byte aligned (-8).
+ *   n_items = 0 launches nothing and returns 0. */
+int hmv_phase_sync_pairs_c128(const double* z, int64_t rec_stride, int64_t ld, int64_t T, int64_t n_rec, int m, int split,
+                              const int64_t* rec_a, const int64_t* rec_b, const int64_t* item_start, const int64_t* shift_b,
+                              int64_t n_items, int n, int mode, double* values, int val_stride, int col_mag, int col_lagged,
+                              int32_t* info, void* stream);
 
 #ifdef __cplusplus
 }
