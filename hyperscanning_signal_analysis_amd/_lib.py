@@ -154,6 +154,8 @@ SIGNATURES = {
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hmv_phase_sync_pairs_c128": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "hmv_phase_lag_c128": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64, c_int,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 # option bits of the fused entry points (include/hypermvar.h)

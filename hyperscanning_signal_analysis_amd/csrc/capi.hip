@@ -2009,4 +2009,28 @@ int hmv_phase_sync_pairs_c128(const double* z, int64_t rec_stride, int64_t ld, i
   return hmv::launch_phase_sync_pairs(a, mp, S(stream));
 }
 
+// ---- phase-lag family of analytic signals (phase_lag.hip) ---------------------------------------------------------
+int hmv_phase_lag_c128(const double* z, int64_t rec_stride, int64_t ld, int64_t T, int64_t n_rec, int m, int split,
+                       const int64_t* item_rec, const int64_t* item_start, int64_t n_items, int n, double* pli, double* wpli,
+                       double* dwpli, int32_t* info, void* stream) {
+  const int mp = pad_of(m);
+  if (mp < 0) return fail(-1, "hmv_phase_lag_c128: channel count must be in 1..64");
+  if (T < 1 || n_rec < 0 || n_items < 0) return fail(-3, "hmv_phase_lag_c128: bad sample / recording / item count");
+  if (n_items > 0x7fffffffLL) return fail(-10, "hmv_phase_lag_c128: more than 2^31 - 1 items in one call");
+  if (n < 1 || n > T) return fail(-2, "hmv_phase_lag_c128: window length must be in 1..T");
+  if (split < 0 || split > m - 1) return fail(-11, "hmv_phase_lag_c128: split must be in 0..m-1 (0: all pairs)");
+  if (!pli && !wpli && !dwpli) return fail(-9, "hmv_phase_lag_c128: no output requested (pli, wpli, dwpli all null)");
+  if (ld < T) return fail(-5, "hmv_phase_lag_c128: ld is smaller than T");
+  if (ld > INT64_MAX / m || rec_stride < (int64_t)m * ld) return fail(-6, "hmv_phase_lag_c128: rec_stride is smaller than m * ld");
+  if (n_items == 0) return 0;
+  if (!z || !item_rec || !item_start || !info) return fail(-4, "hmv_phase_lag_c128: null pointer");
+  if (reinterpret_cast<uintptr_t>(z) % 16) return fail(-8, "hmv_phase_lag_c128: z is not 16-byte aligned");
+  hmv::PhaseLagArgs a{};
+  a.z = reinterpret_cast<const double2*>(z); a.rec_stride = rec_stride; a.ld = ld; a.T = T; a.n_rec = n_rec;
+  a.item_rec = reinterpret_cast<const long long*>(item_rec); a.item_start = reinterpret_cast<const long long*>(item_start);
+  a.n_items = n_items; a.m = m; a.n = n; a.split = split;
+  a.pli = pli; a.wpli = wpli; a.dwpli = dwpli; a.info = info;
+  return hmv::launch_phase_lag(a, mp, S(stream));
+}
+
 }  // extern "C"

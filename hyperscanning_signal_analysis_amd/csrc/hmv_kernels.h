@@ -461,4 +461,19 @@ struct PhasePairsArgs {
 };
 int launch_phase_sync_pairs(const PhasePairsArgs& a, int m_pad, hipStream_t st);
 
+// ---- phase-lag family of analytic signals: PLI, wPLI, debiased squared wPLI (phase_lag.hip) ------------------------
+struct PhaseLagArgs {
+  const double2* z;         // as PhaseSyncArgs
+  long long rec_stride, ld, T, n_rec;
+  const long long* item_rec;    // [n_items] (device)
+  const long long* item_start;  // [n_items] (device)
+  long long n_items;
+  int m, n, split;          // channels, window length, 0 = all pairs / 1..m-1 = the pairs i < split <= j only
+  double* pli;              // optional [n_items][m][m]
+  double* wpli;             // optional [n_items][m][m]
+  double* dwpli;            // optional [n_items][m][m]
+  int* info;                // [n_items]
+};
+int launch_phase_lag(const PhaseLagArgs& a, int m_pad, hipStream_t st);
+
 }  // namespace hmv

@@ -13,7 +13,8 @@ from __future__ import annotations
 import numpy as np
 
 __all__ = ["filter_eeg", "preprocess_eeg", "load_eeg_signals", "load_dyad_block", "decimation_taps", "DECIMATION_DESIGNS",
-           "band_response", "PHASE_MEASURES", "resolve_phase_measures", "resolve_bands_hz"]
+           "band_response", "PHASE_MEASURES", "resolve_phase_measures", "PHASE_LAG_MEASURES", "resolve_phase_lag_measures",
+           "check_phase_lag_split", "resolve_bands_hz"]
 
 
 def filter_eeg(data_tc, fs, low_cutoff_hz=None, high_cutoff_hz=None):
@@ -79,6 +80,29 @@ def resolve_phase_measures(measures):
     if not out or unknown:
         raise ValueError(f"phase synchrony measures must be a non-empty subset of {PHASE_MEASURES}, got {tuple(measures)!r}")
     return out
+
+
+PHASE_LAG_MEASURES = ("pli", "wpli", "dwpli")
+
+
+def resolve_phase_lag_measures(measures):
+    """`measures` of the phase-lag calls (PLI, weighted PLI, debiased squared weighted PLI) -> a tuple without repeats, in
+    the caller's order.  A family of its own: `PHASE_MEASURES` does not list these names.  Needs no GPU."""
+    if isinstance(measures, str):
+        measures = (measures,)
+    out = tuple(dict.fromkeys(measures))
+    unknown = [q for q in out if q not in PHASE_LAG_MEASURES]
+    if not out or unknown:
+        raise ValueError(f"phase-lag measures must be a non-empty subset of {PHASE_LAG_MEASURES}, got {tuple(measures)!r}")
+    return out
+
+
+def check_phase_lag_split(split, m, who):
+    """`split` of the phase-lag calls -> int: 0 (all pairs) or 1..m-1 (the pairs i < split <= j only).  Needs no GPU."""
+    if isinstance(split, bool) or not isinstance(split, (int, np.integer)) or not 0 <= int(split) <= max(0, int(m) - 1):
+        raise ValueError(f"{who}: split must be 0 (all pairs) or an integer in 1..{int(m) - 1} (the inter-brain pairs "
+                         f"i < split <= j only), got {split!r}")
+    return int(split)
 
 
 def resolve_bands_hz(bands_hz, fs):

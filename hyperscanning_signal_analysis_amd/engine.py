@@ -2224,42 +2224,117 @@ class Engine:
         phasors; coh / imcoh: the signal itself), both on the same z.  Bit-identical to `phase_sync(analytic_signal(..))`
         by hand.  check=True: ValueError naming the first (recording, window, band) whose info is not 0; check="nan": the
         arrays come back with their NaNs."""
-        from .eeg_io import resolve_bands_hz, resolve_phase_measures
+        from .eeg_io import resolve_phase_measures
         measures = resolve_phase_measures(measures)
+        return self._sliding_phase("sliding_phase_sync", x, item_rec, item_start, n, fs, bands_hz, sync=measures, order=order,
+                                   check=check, max_workspace_bytes=max_workspace_bytes)[0]
+
+    # ------------------------------------------------------------------ phase-lag family (phase_lag.hip)
+    def _phase_lag(self, z, item_rec, item_start, n, want, split):
+        n_rec, m, T = z.shape
+        n_items = int(item_rec.numel())
+        info = torch.empty(n_items, dtype=torch.int32, device=self.device)
+        out = {q: self.empty(n_items, m, m) for q in want}
+        with torch.cuda.device(self.device):
+            rc = self.lib.hmv_phase_lag_c128(z.data_ptr(), z.stride(0), z.stride(1), T, n_rec, m, int(split),
+                                             item_rec.data_ptr(), item_start.data_ptr(), n_items, int(n), _ptr(out.get("pli")),
+                                             _ptr(out.get("wpli")), _ptr(out.get("dwpli")), info.data_ptr(), self.stream())
+        _lib.check(rc, "hmv_phase_lag_c128")
+        out["info"] = info
+        return out
+
+    def phase_lag(self, z: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, *, want=("wpli",),
+                  split: int = 0):
+        """The phase-lag family of every window (`hmv_phase_lag_c128`): z (n_rec, m, T) complex128 on the device (unit
+        stride along time; a strided view is read in place), item i = the n samples of recording item_rec[i] from
+        item_start[i].  With x[t] = Im(z_i[t] conj z_j[t]) (two rounded products, one subtraction):
+        "pli" = |#{x > 0} - #{x < 0}| / n (Stam 2007), "wpli" = |sum x| / sum |x|, "dwpli" = (S^2 - Q) / (A^2 - Q) with
+        S = sum x, A = sum |x|, Q = sum x^2 (Vinck 2011; may be slightly negative, NaN where A^2 - Q <= 0).  The diagonal is
+        0.  split = 0: all pairs; 1..m-1: the pairs i < split <= j only, every other off-diagonal cell NaN.
+        -> {the measures named in `want`: (n_items, m, m), "info": int32 (n_items,)}: 1 = a non-finite sample (the item is
+        NaN), 2 = a computed pair with sum |x| == 0 (a flat or duplicated channel; those cells pli 0, wpli / dwpli NaN).
+        PLI is exactly what NumPy gives; every cell's bits depend on the n samples of its two channels only.  On the
+        engine's stream; nothing is read back after the check of the item tables."""
+        from .eeg_io import check_phase_lag_split, resolve_phase_lag_measures
+        if (not isinstance(z, torch.Tensor) or z.dtype != torch.complex128 or z.device != self.device or z.dim() != 3
+                or z.shape[1] < 1):
+            raise ValueError(f"phase_lag: z must be a complex128 tensor (n_rec, m, T) on {self.device}")
+        want = resolve_phase_lag_measures(want)
+        split = check_phase_lag_split(split, z.shape[1], "phase_lag")
+        self.pad(z.shape[1])
+        validate_items(z, item_rec, item_start, n, 0)
+        if z.shape[0] > 0 and (z.stride(2) != 1 or z.stride(1) < z.shape[2] or z.stride(0) < z.shape[1] * z.stride(1)):
+            z = z.contiguous()
+        return self._phase_lag(z, item_rec, item_start, n, want, split)
+
+    def sliding_phase_lag(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, fs: float,
+                          bands_hz, *, measures=("wpli",), split: int = 0, order: int = 4, check=True,
+                          max_workspace_bytes: int = 8 << 30):
+        """Band-limited phase-lag measures per window: x (n_rec, m, T) float64 on the device -> {measure: (n_items,
+        n_bands, m, m), "info": int32 (n_items, n_bands)} for `measures` out of ("pli", "wpli", "dwpli") (`phase_lag`), the
+        bands and the slabs of the analytic signal as in `sliding_phase_sync`, one kernel call per slab.  Bit-identical
+        to `phase_lag(analytic_signal(..))` by hand.  split as in `phase_lag`.  check=True: ValueError naming the first
+        (recording, window, band) whose info is not 0; check="nan": the arrays come back with their NaNs."""
+        from .eeg_io import resolve_phase_lag_measures
+        measures = resolve_phase_lag_measures(measures)
+        return self._sliding_phase("sliding_phase_lag", x, item_rec, item_start, n, fs, bands_hz, lag=measures, split=split,
+                                   order=order, check=check, max_workspace_bytes=max_workspace_bytes)[1]
+
+    PHASE_SYNC_WHY = {1: "a non-finite sample in the window", 2: "a channel of zero power in the window"}
+    PHASE_LAG_WHY = {1: "a non-finite sample in the window",
+                     2: "a pair of channels whose sum |Im(z_i conj z_j)| over the window is zero: a flat or duplicated channel"}
+
+    def _sliding_phase(self, who, x, item_rec, item_start, n, fs, bands_hz, *, sync=None, lag=None, split=0, order=4,
+                       check=True, max_workspace_bytes=8 << 30):
+        """The one driver of `sliding_phase_sync` (sync: its resolved measures) and `sliding_phase_lag` (lag: its resolved
+        measures, with `split`): every slab of `phase_slabs` is formed once and handed to the kernels of both families, so
+        a caller that wants both pays for one analytic signal.  -> (dict of `sliding_phase_sync` or None, dict of
+        `sliding_phase_lag` or None), each with its own "info" and the bits its own call gives.  check=True raises for the
+        first window refused, the synchrony family's first."""
+        from .eeg_io import check_phase_lag_split, resolve_bands_hz
         if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.device != self.device or x.dim() != 3:
-            raise ValueError(f"sliding_phase_sync: x must be a float64 tensor (n_rec, m, T) on {self.device}")
+            raise ValueError(f"{who}: x must be a float64 tensor (n_rec, m, T) on {self.device}")
         if check is not True and check != "nan":
-            raise ValueError(f"sliding_phase_sync: check must be True or 'nan', got {check!r}")
+            raise ValueError(f"{who}: check must be True or 'nan', got {check!r}")
         n_rec, m, T = x.shape
+        if lag:
+            split = check_phase_lag_split(split, m, who)
         self.pad(m)
         bands = resolve_bands_hz(bands_hz, fs)
         validate_items(x, item_rec, item_start, n, 0)
         nb, n_items = len(bands), int(item_rec.numel())
         resp = torch.stack([self.band_response(T, fs, lo, hi, order) for lo, hi in bands])
-        modes = [(mode, [q for q in measures if q in names], names) for mode, names in
+        modes = [(mode, [q for q in sync or () if q in names], names) for mode, names in
                  ((_lib.PHASE_UNIT, ("plv", "ciplv")), (_lib.PHASE_RAW, ("coh", "imcoh")))]
         modes = [(mode, qs, names) for mode, qs, names in modes if qs]
-        out = {q: self.empty(n_items, nb, m, m) for q in measures}
-        info = torch.zeros(n_items, nb, dtype=torch.int32, device=self.device)
+        outs = [{q: self.empty(n_items, nb, m, m) for q in qs or ()} for qs in (sync, lag)]
+        infos = [torch.zeros(n_items, nb, dtype=torch.int32, device=self.device) for _ in range(2)]
         for sel, b0, b1, z, rec_z, start_z in self.phase_slabs(x, item_rec, item_start, resp, max_workspace_bytes):
             for mode, qs, names in modes:
                 res = self._phase_sync(z, rec_z, start_z, n, mode, names[0] in qs, names[1] in qs, False)
                 for q, key in zip(names, ("mag", "lagged")):
                     if q in qs:
-                        out[q][sel, b0:b1] = res[key].view(-1, b1 - b0, m, m)
-                info[sel, b0:b1] = torch.maximum(info[sel, b0:b1], res["info"].view(-1, b1 - b0))
+                        outs[0][q][sel, b0:b1] = res[key].view(-1, b1 - b0, m, m)
+                infos[0][sel, b0:b1] = torch.maximum(infos[0][sel, b0:b1], res["info"].view(-1, b1 - b0))
+            if lag:
+                res = self._phase_lag(z, rec_z, start_z, n, lag, split)
+                for q in lag:
+                    outs[1][q][sel, b0:b1] = res[q].view(-1, b1 - b0, m, m)
+                infos[1][sel, b0:b1] = res["info"].view(-1, b1 - b0)
             del z
-        if check is True and n_items:
-            bad = torch.nonzero(info.cpu())
-            if bad.numel():
-                it, b = (int(v) for v in bad[0])
-                code = int(info[it, b])
-                why = {1: "a non-finite sample in the window", 2: "a channel of zero power in the window"}.get(code, "?")
-                raise ValueError(f"sliding_phase_sync: recording {int(item_rec[it])}, window at sample "
-                                 f"{int(item_start[it])} (item {it}), band {b} {bands[b]!r} Hz: info = {code} ({why}); "
-                                 f"check='nan' returns the arrays with their NaNs")
-        out["info"] = info
-        return out
+        for qs, info, why, name in ((sync, infos[0], self.PHASE_SYNC_WHY, "sliding_phase_sync"),
+                                    (lag, infos[1], self.PHASE_LAG_WHY, "sliding_phase_lag")):
+            if qs and check is True and n_items:
+                bad = torch.nonzero(info.cpu())
+                if bad.numel():
+                    it, b = (int(v) for v in bad[0])
+                    code = int(info[it, b])
+                    raise ValueError(f"{name}: recording {int(item_rec[it])}, window at sample "
+                                     f"{int(item_start[it])} (item {it}), band {b} {bands[b]!r} Hz: info = {code} "
+                                     f"({why.get(code, '?')}); check='nan' returns the arrays with their NaNs")
+        for out, info in zip(outs, infos):
+            out["info"] = info
+        return (outs[0] if sync else None), (outs[1] if lag else None)
 
 
 _default = None

@@ -253,12 +253,14 @@ class _Settings(typing.NamedTuple):
     decimate_design: object = "decimate"
     psd: tuple | None = None            # (fmin, fmax, bandwidth)
     save_full: bool = False
+    phase_lag: tuple | None = None
 
 
 def resolve_settings(engine=None, *, window_s=2.0, overlap=0.5, model_order=8, freqs=None, bands=hdist.DEFAULT_BANDS,
                      with_psd=False, psd_fmin=1.0, psd_fmax=30.0, psd_bandwidth=2.0, save_full=False, measures=("ffdtf",),
                      significance=None, max_model_order=20, crit_type="AIC", validation_lags=None, block_granger=False,
-                     pivoted_fallback=None, decimate=None, decimate_design="decimate", phase_sync=None):
+                     pivoted_fallback=None, decimate=None, decimate_design="decimate", phase_sync=None,
+                     phase_lag=None):
     """`run`'s keyword arguments (same names, same defaults) -> (`_Settings`, the engine).  What needs no engine is refused
     first: the measures, the significance dict, the phase measures and bands, then the automatic order where it is not
     offered.  Only then the engine is made (engine=None: `default_engine()`), the pivoted fallback is resolved against its
@@ -274,6 +276,10 @@ def resolve_settings(engine=None, *, window_s=2.0, overlap=0.5, model_order=8, f
         from .eeg_io import resolve_bands_hz, resolve_phase_measures
         phase_sync = resolve_phase_measures(phase_sync)
         resolve_bands_hz(bands, float("inf"))       # not empty, pairs, lo < hi; the edges against fs / 2 per segment
+    if phase_lag is not None:                       # a family of its own names ("pli", "wpli", "dwpli")
+        from .eeg_io import resolve_bands_hz, resolve_phase_lag_measures
+        phase_lag = resolve_phase_lag_measures(phase_lag)
+        resolve_bands_hz(bands, float("inf"))
     auto = model_order is None
     if block_granger and auto:
         raise ValueError("escan_batch.run(block_granger=True): the automatic model order (model_order=None) is not "
@@ -290,7 +296,7 @@ def resolve_settings(engine=None, *, window_s=2.0, overlap=0.5, model_order=8, f
     dec = resolve_decimate(decimate, decimate_design)
     return _Settings(window_s, overlap, freqs, bands, measures, order, pmax if auto else order, crit_type, order_kw,
                      significance, phase_sync, validation_lags, bool(block_granger), pivoted, yw_kw, dec, decimate_design,
-                     (psd_fmin, psd_fmax, psd_bandwidth) if with_psd else None, bool(save_full)), eng
+                     (psd_fmin, psd_fmax, psd_bandwidth) if with_psd else None, bool(save_full), phase_lag), eng
 
 
 class _Geometry(typing.NamedTuple):
@@ -401,10 +407,17 @@ def _launch_segment(eng, cfg, seg, key, geo, psd_stream):
                                                        grid=geo.grid, split=child_channels(seg["names"]), **cfg.yw_kw)
         arrays["block_gc_bands"] = gc_f.masked_fill_(gc_bad.view(-1, 1, 1), float("nan"))
         arrays["block_gc_time"] = gc_t.masked_fill_(gc_bad.view(-1, 1), float("nan"))
-    if cfg.phase_sync is not None:                      # no model: the same windows, the bands in Hz
-        ps = eng.sliding_phase_sync(xd, *items, W, fs, cfg.bands, measures=cfg.phase_sync, check="nan")
-        for q_ in cfg.phase_sync:
-            arrays[f"phase_{q_}"] = ps[q_]
+    if cfg.phase_sync is not None and cfg.phase_lag is not None:      # both families off one analytic signal
+        ps, pl = eng._sliding_phase("escan_batch.run", xd, *items, W, fs, cfg.bands, sync=cfg.phase_sync, lag=cfg.phase_lag,
+                                    check="nan")
+    else:                                               # no model: the same windows, the bands in Hz
+        ps = (eng.sliding_phase_sync(xd, *items, W, fs, cfg.bands, measures=cfg.phase_sync, check="nan")
+              if cfg.phase_sync is not None else None)
+        pl = (eng.sliding_phase_lag(xd, *items, W, fs, cfg.bands, measures=cfg.phase_lag, check="nan")
+              if cfg.phase_lag is not None else None)
+    for qs_, res_ in ((cfg.phase_sync, ps), (cfg.phase_lag, pl)):
+        for q_ in qs_ or ():
+            arrays[f"phase_{q_}"] = res_[q_]
     if cfg.significance is not None:
         sg = cfg.significance
         for meas in cfg.measures:
@@ -464,6 +477,8 @@ def _process_dyad(eng, cfg, dyad, prep, psd_stream, say):
         meta["decimate"], meta["decimate_design"] = cfg.decimate
     if cfg.phase_sync is not None:
         meta["phase_sync"] = list(cfg.phase_sync)
+    if cfg.phase_lag is not None:
+        meta["phase_lag"] = list(cfg.phase_lag)
     pending = []
     for seg in prep["segments"]:
         key = f"{seg['task']}/{seg['event']}"
@@ -502,7 +517,7 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
         psd_bandwidth=2.0, save_full=False, skip_existing=True, reader=None, engine=None, world=1, rank=0,
         verbose=True, prefetch=2, timing=None, save_workers=4, compresslevel=0, measures=("ffdtf",), significance=None,
         max_model_order=20, crit_type="AIC", validation_lags=None, block_granger=False, pivoted_fallback=None,
-        decimate=None, decimate_design="decimate", phase_sync=None):
+        decimate=None, decimate_design="decimate", phase_sync=None, phase_lag=None):
     """Process every dyad under <root>/EEG.  Per dyad one `<out_dir>/<dyad>_ffdtf.npz` with, per segment `<task>/<event>`:
         <seg>/ffdtf_bands   (windows, n, n, n_bands)   band-integrated ffDTF of every window
         <seg>/ffdtf         (windows, n, n, F)         only with save_full=True (8.4 MB per window at 64 channels)
@@ -540,6 +555,13 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
                                                        signal is circular over the segment).  NaN where a window holds a
                                                        non-finite sample or, for coh / imcoh, a channel of zero power; meta
                                                        then says "phase_sync": [...].  None (default): nothing changes.
+                                                       Also with phase_lag=(...), a tuple out of ("pli", "wpli", "dwpli"):
+                                                       the phase-lag index, weighted PLI and debiased squared weighted
+                                                       PLI of the same windows and bands, all pairs
+                                                       (`Engine.sliding_phase_lag`; zero-lag mixing cannot raise them).  NaN
+                                                       where a window holds a non-finite sample or, for wpli / dwpli, a
+                                                       pair of flat or duplicated channels; meta then says "phase_lag":
+                                                       [...].  With both options the analytic signal is formed once.
         <seg>/acf_fraction  (windows,)                 with validation_lags: share of the residual correlations beyond
                                                        1.96 / sqrt(N)
       pivoted_fallback: windows that the Yule-Walker solvers refuse are solved by the pivoted LU, as the reference's
@@ -574,7 +596,7 @@ def run(root, out_dir, tasks=None, window_s=2.0, overlap=0.5, model_order=8, fre
         psd_fmin=psd_fmin, psd_fmax=psd_fmax, psd_bandwidth=psd_bandwidth, save_full=save_full, measures=measures,
         significance=significance, max_model_order=max_model_order, crit_type=crit_type, validation_lags=validation_lags,
         block_granger=block_granger, pivoted_fallback=pivoted_fallback, decimate=decimate, decimate_design=decimate_design,
-        phase_sync=phase_sync)
+        phase_sync=phase_sync, phase_lag=phase_lag)
     reader = reader or xarray_reader
     out_dir = Path(out_dir)
     out_dir.mkdir(parents=True, exist_ok=True)

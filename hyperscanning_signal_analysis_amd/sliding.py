@@ -14,6 +14,8 @@ picks for it -- the reference's own default, `optimal_model_order=None` -- selec
 (`scipy.signal.decimate(..., ftype='fir', zero_phase=True)` / `resample_poly(x, 1, q)` on the device).
 `sliding_phase_sync` is the band-limited phase synchrony of the same windows (PLV, ciPLV, coherence, imaginary coherence of
 the analytic signal): no model, no order, no window refused for its conditioning.
+`sliding_phase_lag` is the phase-lag family of the same windows (PLI, weighted PLI, debiased squared weighted PLI), the
+measures zero-lag mixing cannot raise.
 `sliding_fad` is `fad_decomposition` (mtmvar.py:607-757) of every channel of every window.
 `sliding_ensemble` / `sliding_ensemble_epochs` are the event-locked form: the reference's functions take `signals` of shape
 (channels, samples, trials) and fit ONE model to the trial-averaged covariances (`count_corr`, mtmvar.py:54-85); here a
@@ -35,7 +37,8 @@ __all__ = ["window_positions", "hop_positions", "create_windows", "sliding_ffdtf
            "sliding_ensemble_significance", "sliding_ensemble_epochs_significance", "sliding_pseudo_dyad_significance",
            "sliding_model_validation", "validation_p_values", "sliding_ensemble_contrast", "sliding_ensemble_epochs_contrast",
            "sliding_block_granger_significance", "sliding_block_granger_pseudo_dyad_significance", "decimate",
-           "sliding_phase_sync", "sliding_phase_sync_significance", "sliding_phase_sync_pseudo_dyad_significance"]
+           "sliding_phase_sync", "sliding_phase_sync_significance", "sliding_phase_sync_pseudo_dyad_significance",
+           "sliding_phase_lag"]
 
 
 def decimate(x, fs, q, design="decimate", engine: Engine | None = None):
@@ -343,6 +346,40 @@ def sliding_phase_sync(x, window_size, n_windows, fs, bands_hz=DEFAULT_BANDS, *,
     item_rec, item_start = window_items(n_rec, positions, eng.device)
     res = eng.sliding_phase_sync(xd, item_rec, item_start, w, fs, bands_hz, measures=measures, order=order, check=check,
                                  max_workspace_bytes=max_workspace_bytes)
+    keys = measures + (("info",) if check == "nan" else ())
+    out = {k: res[k].view(n_rec, len(positions), len(bands_hz), *res[k].shape[2:]).cpu().numpy() for k in keys}
+    return {k: v[0] for k, v in out.items()} if single else out
+
+
+def sliding_phase_lag(x, window_size, n_windows, fs, bands_hz=DEFAULT_BANDS, *, hop=None, measures=("wpli",), split=0,
+                      order=4, check=True, engine: Engine | None = None, max_workspace_bytes: int = 8 << 30):
+    """NumPy (or tensor) in / NumPy out: the band-limited phase-lag measures of every window (`Engine.sliding_phase_lag`):
+    PLI, weighted PLI and debiased squared weighted PLI, which zero-lag mixing (common reference, volume conduction) cannot
+    raise.  x: (m, T) or (n_rec, m, T) -> {measure: (n_rec, n_windows, n_bands, m, m)} for `measures` out of ("pli",
+    "wpli", "dwpli"), without the leading axis for a single recording; with check="nan" also "info" (n_rec, n_windows,
+    n_bands).  split = 0: all pairs; 1..m-1: only the inter-brain pairs (i < split <= j), every other off-diagonal cell NaN.
+    Bands, windows and `hop` as in `sliding_phase_sync`.  No model is fitted."""
+    from .eeg_io import check_phase_lag_split, resolve_bands_hz, resolve_phase_lag_measures
+    measures = resolve_phase_lag_measures(measures)              # the arguments first: nothing has touched a device yet
+    bands_hz = tuple(bands_hz)
+    resolve_bands_hz(bands_hz, fs)
+    if check is not True and check != "nan":
+        raise ValueError(f"sliding_phase_lag: check must be True or 'nan', got {check!r}")
+    x = np.asarray(x, dtype=np.float64) if not isinstance(x, torch.Tensor) else x
+    if x.ndim not in (2, 3):
+        raise ValueError(f"sliding_phase_lag: x must be (m, T) or (n_rec, m, T), got shape {tuple(x.shape)}")
+    split = check_phase_lag_split(split, int(x.shape[-2]), "sliding_phase_lag")
+    single = x.ndim == 2
+    positions, w = _positions(int(x.shape[-1]), window_size, n_windows, hop)
+    eng = engine or default_engine()
+    if isinstance(x, torch.Tensor):
+        xd = (x[None] if single else x).to(device=eng.device, dtype=torch.float64)
+    else:
+        xd = eng.to_device(x[None] if single else x)
+    n_rec, m, T = xd.shape
+    item_rec, item_start = window_items(n_rec, positions, eng.device)
+    res = eng.sliding_phase_lag(xd, item_rec, item_start, w, fs, bands_hz, measures=measures, split=split, order=order,
+                                check=check, max_workspace_bytes=max_workspace_bytes)
     keys = measures + (("info",) if check == "nan" else ())
     out = {k: res[k].view(n_rec, len(positions), len(bands_hz), *res[k].shape[2:]).cpu().numpy() for k in keys}
     return {k: v[0] for k, v in out.items()} if single else out

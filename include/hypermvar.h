@@ -816,6 +816,44 @@ int hmv_phase_sync_pairs_c128(const double* z, int64_t rec_stride, int64_t ld, i
                               int64_t n_items, int n, int mode, double* values, int val_stride, int col_mag, int col_lagged,
                               int32_t* info, void* stream);
 
+/* The phase-lag family of analytic signals per window (csrc/phase_lag.hip): the phase-lag index (PLI; Stam, Nolte &
+ * Daffertshofer 2007, Hum Brain Mapp 28:1178), the weighted PLI and the debiased squared weighted PLI (Vinck, Oostenveld,
+ * van Wingerden, Battaglia & Pennartz 2011, NeuroImage 55:1548).  THIS IS NOT A FUNCTION OF THE REFERENCE, which has no
+ * phase-lag measure; it is here because zero-lag mixing (common reference, volume conduction, a shared artefact) cannot
+ * raise these measures, while it raises PLV and coherence.
+ * z, rec_stride, ld, T, n_rec, m, item_rec, item_start, n_items, n as for hmv_phase_sync_c128: item `it` is the window
+ * z[item_rec[it]][c][item_start[it] + t], t = 0..n-1, a sample past T read as zero, never from memory.  No normalisation:
+ * the measures use z itself.  For channels i != j:
+ *     x[t]  = rn( rn(im_i[t] re_j[t]) - rn(re_i[t] im_j[t]) )   = Im(z_i conj z_j): two rounded products and one
+ *                                                                 subtraction, never contracted into an FMA
+ *     P = #{t : x[t] > 0}   N = #{t : x[t] < 0}   S = sum x[t]   A = sum |x[t]|   Q = sum x[t]^2
+ *     pli   = |P - N| / n
+ *     wpli  = |S| / A                      NaN where A == 0
+ *     dwpli = (S^2 - Q) / (A^2 - Q)        NaN where A^2 - Q <= 0 (n = 1, or one non-zero sample); may be slightly
+ *                                          negative, not clamped
+ *     diagonal: 0 for all three.
+ * The unfused x is deliberate: NumPy computes the same x bit for bit, so P and N and with them PLI are exactly
+ * reproducible, and two identical or power-of-two-proportional channels give x = 0 exactly (PLI 0, wPLI NaN) where a fused
+ * form would leave rounding residue of random sign.  S, A and Q are summed over t ascending from the window start, one
+ * term after the other (Q by one FMA per term): the bits of cell (i, j) depend on the n samples of channels i and j only --
+ * not on the batch, the item index, the other channels, m or split.  Each pair is computed once and mirrored: the three
+ * outputs are symmetric bit for bit.  S and A run in the same order, so |S| <= A holds in floating point and wpli lies in
+ * [0, 1] exactly.  A power-of-two scaling of a channel changes no bit (no over- or underflow assumed).
+ * split = 0: all pairs.  1 <= split <= m-1: only the inter-brain pairs (i < split <= j) are computed, with the bits the
+ *   split = 0 call gives them; every other off-diagonal cell is NaN.
+ * pli, wpli, dwpli: [n_items][m][m], unpadded; any may be NULL, not all three.  Nothing else is written.
+ * info int32 [n_items]: 1 a non-finite sample in any of the m channels of the window (flagged while staging): everything
+ *   of the item is NaN; 2 some computed off-diagonal pair has A == 0 (a flat channel, duplicated channels): those cells
+ *   have pli = 0 and wpli = dwpli = NaN, the rest is valid; 0 otherwise.
+ * float64 VALU, no atomics.
+ * Refused before any launch: channel count outside 1..HMV_MAX_CHANNELS (-1), n < 1 or n > T (-2), T < 1, n_rec < 0 or
+ *   n_items < 0 (-3), more than 2^31 - 1 items (-10), split outside 0..m-1 (-11), all three outputs null (-9), ld < T (-5),
+ *   rec_stride < m * ld (-6), and with n_items > 0 a null z, item table or info (-4) or a z that is not 16-byte aligned
+ *   (-8).  n_items = 0 launches nothing and returns 0. */
+int hmv_phase_lag_c128(const double* z, int64_t rec_stride, int64_t ld, int64_t T, int64_t n_rec, int m, int split,
+                       const int64_t* item_rec, const int64_t* item_start, int64_t n_items, int n,
+                       double* pli, double* wpli, double* dwpli, int32_t* info, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
