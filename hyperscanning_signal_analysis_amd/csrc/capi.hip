@@ -1953,84 +1953,94 @@ int hmv_decimate_fir_f64(const double* x, int64_t rec_stride, int64_t ld, int64_
   return hmv::launch_decimate(a, S(stream));
 }
 
-// ---- phase synchrony of analytic signals (phase_sync.hip) ---------------------------------------------------------
+// ---- phase synchrony and phase-lag family of analytic signals (phase_sync.hip, phase_lag.hip) ----------------------------
+namespace {
+// What the three phase entries refuse, in the order they refuse it: phase_head, the entry's own arguments, phase_layout,
+// the empty batch (0, with whatever pointers), phase_tail.  Each returns 0 when its arguments are fine.
+int phase_head(const char* who, int64_t T, int64_t n_rec, int m, int64_t n_items, int n) {
+  if (pad_of(m) < 0) return refuse(who, -1, "channel count must be in 1..64");
+  if (T < 1 || n_rec < 0 || n_items < 0) return refuse(who, -3, "bad sample / recording / item count");
+  if (n_items > 0x7fffffffLL) return refuse(who, -10, "more than 2^31 - 1 items in one call");
+  if (n < 1 || n > T) return refuse(who, -2, "window length must be in 1..T");
+  return 0;
+}
+int phase_mode(const char* who, int mode) {
+  if (mode == HMV_PHASE_UNIT || mode == HMV_PHASE_RAW) return 0;
+  return refuse(who, -7, "mode must be HMV_PHASE_UNIT (0) or HMV_PHASE_RAW (1)");
+}
+int phase_layout(const char* who, int64_t rec_stride, int64_t ld, int64_t T, int m) {
+  if (ld < T) return refuse(who, -5, "ld is smaller than T");
+  if (ld > INT64_MAX / m || rec_stride < (int64_t)m * ld) return refuse(who, -6, "rec_stride is smaller than m * ld");
+  return 0;
+}
+int phase_tail(const char* who, const double* z, bool pointers) {
+  if (!z || !pointers) return refuse(who, -4, "null pointer");
+  if (reinterpret_cast<uintptr_t>(z) % 16) return refuse(who, -8, "z is not 16-byte aligned");
+  return 0;
+}
+// the head that PhaseSyncArgs, PhasePairsArgs and PhaseLagArgs have in common (a template: not of C linkage)
+extern "C++" template <class Args>
+Args phase_args(const double* z, int64_t rec_stride, int64_t ld, int64_t T, int64_t n_rec, int64_t n_items, int m, int n,
+                int32_t* info) {
+  Args a{};
+  a.z = reinterpret_cast<const double2*>(z); a.rec_stride = rec_stride; a.ld = ld; a.T = T; a.n_rec = n_rec;
+  a.n_items = n_items; a.m = m; a.n = n; a.info = info;
+  return a;
+}
+}  // namespace
+
 int hmv_phase_sync_c128(const double* z, int64_t rec_stride, int64_t ld, int64_t T, int64_t n_rec, int m,
                         const int64_t* item_rec, const int64_t* item_start, int64_t n_items, int n, int mode,
                         double* coherency, double* mag, double* lagged, int32_t* info, void* stream) {
-  const int mp = pad_of(m);
-  if (mp < 0) return fail(-1, "hmv_phase_sync_c128: channel count must be in 1..64");
-  if (T < 1 || n_rec < 0 || n_items < 0) return fail(-3, "hmv_phase_sync_c128: bad sample / recording / item count");
-  if (n_items > 0x7fffffffLL) return fail(-10, "hmv_phase_sync_c128: more than 2^31 - 1 items in one call");
-  if (n < 1 || n > T) return fail(-2, "hmv_phase_sync_c128: window length must be in 1..T");
-  if (mode != HMV_PHASE_UNIT && mode != HMV_PHASE_RAW)
-    return fail(-7, "hmv_phase_sync_c128: mode must be HMV_PHASE_UNIT (0) or HMV_PHASE_RAW (1)");
-  if (!coherency && !mag && !lagged) return fail(-9, "hmv_phase_sync_c128: no output requested (coherency, mag, lagged all null)");
-  if (ld < T) return fail(-5, "hmv_phase_sync_c128: ld is smaller than T");
-  if (ld > INT64_MAX / m || rec_stride < (int64_t)m * ld) return fail(-6, "hmv_phase_sync_c128: rec_stride is smaller than m * ld");
+  const char* who = "hmv_phase_sync_c128";
+  if (int rc = phase_head(who, T, n_rec, m, n_items, n)) return rc;
+  if (int rc = phase_mode(who, mode)) return rc;
+  if (!coherency && !mag && !lagged) return refuse(who, -9, "no output requested (coherency, mag, lagged all null)");
+  if (int rc = phase_layout(who, rec_stride, ld, T, m)) return rc;
   if (n_items == 0) return 0;
-  if (!z || !item_rec || !item_start || !info) return fail(-4, "hmv_phase_sync_c128: null pointer");
-  if (reinterpret_cast<uintptr_t>(z) % 16) return fail(-8, "hmv_phase_sync_c128: z is not 16-byte aligned");
-  hmv::PhaseSyncArgs a{};
-  a.z = reinterpret_cast<const double2*>(z); a.rec_stride = rec_stride; a.ld = ld; a.T = T; a.n_rec = n_rec;
-  a.item_rec = reinterpret_cast<const long long*>(item_rec); a.item_start = reinterpret_cast<const long long*>(item_start);
-  a.n_items = n_items; a.m = m; a.n = n; a.mode = mode;
-  a.coherency = coherency; a.mag = mag; a.lagged = lagged; a.info = info;
-  return hmv::launch_phase_sync(a, mp, S(stream));
+  if (int rc = phase_tail(who, z, item_rec && item_start && info)) return rc;
+  auto a = phase_args<hmv::PhaseSyncArgs>(z, rec_stride, ld, T, n_rec, n_items, m, n, info);
+  a.item_rec = ll(item_rec); a.item_start = ll(item_start); a.mode = mode;
+  a.coherency = coherency; a.mag = mag; a.lagged = lagged;
+  return hmv::launch_phase_sync(a, pad_of(m), S(stream));
 }
 
 int hmv_phase_sync_pairs_c128(const double* z, int64_t rec_stride, int64_t ld, int64_t T, int64_t n_rec, int m, int split,
                               const int64_t* rec_a, const int64_t* rec_b, const int64_t* item_start, const int64_t* shift_b,
                               int64_t n_items, int n, int mode, double* values, int val_stride, int col_mag, int col_lagged,
                               int32_t* info, void* stream) {
-  const int mp = pad_of(m);
-  if (mp < 0) return fail(-1, "hmv_phase_sync_pairs_c128: channel count must be in 1..64");
-  if (T < 1 || n_rec < 0 || n_items < 0) return fail(-3, "hmv_phase_sync_pairs_c128: bad sample / recording / item count");
-  if (n_items > 0x7fffffffLL) return fail(-10, "hmv_phase_sync_pairs_c128: more than 2^31 - 1 items in one call");
-  if (n < 1 || n > T) return fail(-2, "hmv_phase_sync_pairs_c128: window length must be in 1..T");
-  if (mode != HMV_PHASE_UNIT && mode != HMV_PHASE_RAW)
-    return fail(-7, "hmv_phase_sync_pairs_c128: mode must be HMV_PHASE_UNIT (0) or HMV_PHASE_RAW (1)");
-  if (split < 1 || split > m - 1) return fail(-11, "hmv_phase_sync_pairs_c128: split must be in 1..m-1");
+  const char* who = "hmv_phase_sync_pairs_c128";
+  if (int rc = phase_head(who, T, n_rec, m, n_items, n)) return rc;
+  if (int rc = phase_mode(who, mode)) return rc;
+  if (split < 1 || split > m - 1) return refuse(who, -11, "split must be in 1..m-1");
   if (val_stride < 1 || col_mag < -1 || col_mag >= val_stride || col_lagged < -1 || col_lagged >= val_stride ||
       col_mag == col_lagged)        // equal columns: both -1 (no output) or one column asked to hold two values
-    return fail(-12, "hmv_phase_sync_pairs_c128: val_stride must be >= 1 and col_mag, col_lagged two different columns in "
-                     "-1..val_stride-1, not both -1");
-  if (ld < T) return fail(-5, "hmv_phase_sync_pairs_c128: ld is smaller than T");
-  if (ld > INT64_MAX / m || rec_stride < (int64_t)m * ld)
-    return fail(-6, "hmv_phase_sync_pairs_c128: rec_stride is smaller than m * ld");
+    return refuse(who, -12, "val_stride must be >= 1 and col_mag, col_lagged two different columns in -1..val_stride-1, not "
+                            "both -1");
+  if (int rc = phase_layout(who, rec_stride, ld, T, m)) return rc;
   if (n_items == 0) return 0;
-  if (!z || !rec_a || !rec_b || !item_start || !values || !info) return fail(-4, "hmv_phase_sync_pairs_c128: null pointer");
-  if (reinterpret_cast<uintptr_t>(z) % 16) return fail(-8, "hmv_phase_sync_pairs_c128: z is not 16-byte aligned");
-  hmv::PhasePairsArgs a{};
-  a.z = reinterpret_cast<const double2*>(z); a.rec_stride = rec_stride; a.ld = ld; a.T = T; a.n_rec = n_rec;
-  a.rec_a = reinterpret_cast<const long long*>(rec_a); a.rec_b = reinterpret_cast<const long long*>(rec_b);
-  a.item_start = reinterpret_cast<const long long*>(item_start); a.shift_b = reinterpret_cast<const long long*>(shift_b);
-  a.n_items = n_items; a.m = m; a.n = n; a.mode = mode; a.split = split;
-  a.values = values; a.val_stride = val_stride; a.col_mag = col_mag; a.col_lagged = col_lagged; a.info = info;
-  return hmv::launch_phase_sync_pairs(a, mp, S(stream));
+  if (int rc = phase_tail(who, z, rec_a && rec_b && item_start && values && info)) return rc;
+  auto a = phase_args<hmv::PhasePairsArgs>(z, rec_stride, ld, T, n_rec, n_items, m, n, info);
+  a.rec_a = ll(rec_a); a.rec_b = ll(rec_b); a.item_start = ll(item_start); a.shift_b = ll(shift_b);
+  a.mode = mode; a.split = split;
+  a.values = values; a.val_stride = val_stride; a.col_mag = col_mag; a.col_lagged = col_lagged;
+  return hmv::launch_phase_sync_pairs(a, pad_of(m), S(stream));
 }
 
-// ---- phase-lag family of analytic signals (phase_lag.hip) ---------------------------------------------------------
 int hmv_phase_lag_c128(const double* z, int64_t rec_stride, int64_t ld, int64_t T, int64_t n_rec, int m, int split,
                        const int64_t* item_rec, const int64_t* item_start, int64_t n_items, int n, double* pli, double* wpli,
                        double* dwpli, int32_t* info, void* stream) {
-  const int mp = pad_of(m);
-  if (mp < 0) return fail(-1, "hmv_phase_lag_c128: channel count must be in 1..64");
-  if (T < 1 || n_rec < 0 || n_items < 0) return fail(-3, "hmv_phase_lag_c128: bad sample / recording / item count");
-  if (n_items > 0x7fffffffLL) return fail(-10, "hmv_phase_lag_c128: more than 2^31 - 1 items in one call");
-  if (n < 1 || n > T) return fail(-2, "hmv_phase_lag_c128: window length must be in 1..T");
-  if (split < 0 || split > m - 1) return fail(-11, "hmv_phase_lag_c128: split must be in 0..m-1 (0: all pairs)");
-  if (!pli && !wpli && !dwpli) return fail(-9, "hmv_phase_lag_c128: no output requested (pli, wpli, dwpli all null)");
-  if (ld < T) return fail(-5, "hmv_phase_lag_c128: ld is smaller than T");
-  if (ld > INT64_MAX / m || rec_stride < (int64_t)m * ld) return fail(-6, "hmv_phase_lag_c128: rec_stride is smaller than m * ld");
+  const char* who = "hmv_phase_lag_c128";
+  if (int rc = phase_head(who, T, n_rec, m, n_items, n)) return rc;
+  if (split < 0 || split > m - 1) return refuse(who, -11, "split must be in 0..m-1 (0: all pairs)");
+  if (!pli && !wpli && !dwpli) return refuse(who, -9, "no output requested (pli, wpli, dwpli all null)");
+  if (int rc = phase_layout(who, rec_stride, ld, T, m)) return rc;
   if (n_items == 0) return 0;
-  if (!z || !item_rec || !item_start || !info) return fail(-4, "hmv_phase_lag_c128: null pointer");
-  if (reinterpret_cast<uintptr_t>(z) % 16) return fail(-8, "hmv_phase_lag_c128: z is not 16-byte aligned");
-  hmv::PhaseLagArgs a{};
-  a.z = reinterpret_cast<const double2*>(z); a.rec_stride = rec_stride; a.ld = ld; a.T = T; a.n_rec = n_rec;
-  a.item_rec = reinterpret_cast<const long long*>(item_rec); a.item_start = reinterpret_cast<const long long*>(item_start);
-  a.n_items = n_items; a.m = m; a.n = n; a.split = split;
-  a.pli = pli; a.wpli = wpli; a.dwpli = dwpli; a.info = info;
-  return hmv::launch_phase_lag(a, mp, S(stream));
+  if (int rc = phase_tail(who, z, item_rec && item_start && info)) return rc;
+  auto a = phase_args<hmv::PhaseLagArgs>(z, rec_stride, ld, T, n_rec, n_items, m, n, info);
+  a.item_rec = ll(item_rec); a.item_start = ll(item_start); a.split = split;
+  a.pli = pli; a.wpli = wpli; a.dwpli = dwpli;
+  return hmv::launch_phase_lag(a, pad_of(m), S(stream));
 }
 
 }  // extern "C"

@@ -21,7 +21,7 @@ from typing import Callable
 import numpy as np
 import torch
 
-from . import _lib, significance
+from . import _lib, phase, significance
 from . import surrogates as sg
 
 __all__ = ["Engine", "default_engine", "SingularMatrixError", "validate_items", "validate_trials", "check_block_split"]
@@ -2063,19 +2063,7 @@ class Engine:
         m, m) (Re R, Im R) if asked, "info": int32 (n_items,)}: 1 = a non-finite sample (the item is NaN), 2 = RAW only, a
         channel of zero power (its row and column are NaN).  On the engine's stream; nothing is read back after the check
         of the item tables."""
-        if (not isinstance(z, torch.Tensor) or z.dtype != torch.complex128 or z.device != self.device or z.dim() != 3
-                or z.shape[1] < 1):
-            raise ValueError(f"phase_sync: z must be a complex128 tensor (n_rec, m, T) on {self.device}")
-        want = (want,) if isinstance(want, str) else tuple(want)
-        if any(w not in ("mag", "lagged") for w in want) or not (want or coherency):
-            raise ValueError(f"phase_sync: want must name 'mag' and / or 'lagged' (or coherency=True), got {want!r}")
-        if int(mode) not in (_lib.PHASE_UNIT, _lib.PHASE_RAW):
-            raise ValueError(f"phase_sync: mode must be PHASE_UNIT (0) or PHASE_RAW (1), got {mode!r}")
-        self.pad(z.shape[1])
-        validate_items(z, item_rec, item_start, n, 0)
-        if z.shape[0] > 0 and (z.stride(2) != 1 or z.stride(1) < z.shape[2] or z.stride(0) < z.shape[1] * z.stride(1)):
-            z = z.contiguous()
-        return self._phase_sync(z, item_rec, item_start, n, mode, "mag" in want, "lagged" in want, bool(coherency))
+        return phase.phase_sync(self, z, item_rec, item_start, n, mode, want=want, coherency=coherency)
 
     def _phase_sync_pairs(self, z, rec_a, rec_b, item_start, n, mode, split, shift_b, values, cols, info=None):
         n_rec, m, T = z.shape
@@ -2102,44 +2090,8 @@ class Engine:
         tensor, NaN in the columns not written.  In the written columns a cross cell (one index < split) has the bits
         `phase_sync` gives on the written-out window and every other cell is NaN.  -> (out, info int32 (n_items,)), info as
         in `phase_sync`.  Both recording tables and the shifts (0..T-1) are checked before the call."""
-        if (not isinstance(z, torch.Tensor) or z.dtype != torch.complex128 or z.device != self.device or z.dim() != 3
-                or z.shape[1] < 2):
-            raise ValueError(f"phase_sync_pairs: z must be a complex128 tensor (n_rec, m >= 2, T) on {self.device}")
-        n_rec, m, T = z.shape
-        if int(mode) not in (_lib.PHASE_UNIT, _lib.PHASE_RAW):
-            raise ValueError(f"phase_sync_pairs: mode must be PHASE_UNIT (0) or PHASE_RAW (1), got {mode!r}")
-        if isinstance(split, bool) or not isinstance(split, (int, np.integer)) or not 1 <= int(split) <= m - 1:
-            raise ValueError(f"phase_sync_pairs: split must be an integer in 1..{m - 1}, got {split!r}")
-        cols = tuple(int(c) for c in cols)
-        if len(cols) != 2 or min(cols) < -1 or max(cols) < 0 or cols[0] == cols[1]:
-            raise ValueError(f"phase_sync_pairs: cols must be two different columns (col_mag, col_lagged), -1 for an output "
-                             f"that is not wanted and not both, got {cols!r}")
-        self.pad(m)
-        for name, rec in (("rec_a", rec_a), ("rec_b", rec_b)):
-            try:
-                validate_items(z, rec, item_start, n, 0)
-            except ValueError as err:                      # the message names the table that is wrong
-                raise ValueError("phase_sync_pairs: " + str(err).replace("item_rec", name)) from None
-        n_items = int(rec_a.numel())
-        if shift_b is not None:
-            if (not isinstance(shift_b, torch.Tensor) or shift_b.dtype != torch.int64 or shift_b.device != z.device
-                    or shift_b.shape != (n_items,)):
-                raise ValueError(f"phase_sync_pairs: shift_b must be a 1-D int64 tensor on {z.device}, one entry per item")
-            if n_items:
-                lo, hi = torch.stack([shift_b.min(), shift_b.max()]).cpu().tolist()
-                if lo < 0 or hi >= T:
-                    raise ValueError(f"phase_sync_pairs: shift_b must lie in [0, {T}), got [{lo}, {hi}]")
-            shift_b = shift_b.contiguous()
-        if out is None:
-            out = torch.full((n_items, m, m, 1 + max(cols)), float("nan"), dtype=torch.float64, device=self.device)
-        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.device != self.device or out.dim() != 4
-              or tuple(out.shape[:3]) != (n_items, m, m) or out.shape[3] <= max(cols) or not out.is_contiguous()):
-            raise ValueError(f"phase_sync_pairs: out must be a contiguous float64 tensor ({n_items}, {m}, {m}, K) on "
-                             f"{self.device} with K > {max(cols)}")
-        if n_rec > 0 and (z.stride(2) != 1 or z.stride(1) < T or z.stride(0) < m * z.stride(1)):
-            z = z.contiguous()
-        return self._phase_sync_pairs(z, rec_a.contiguous(), rec_b.contiguous(), item_start.contiguous(), n, mode, split,
-                                      shift_b, out, cols)
+        return phase.phase_sync_pairs(self, z, rec_a, rec_b, item_start, n, mode, split=split, shift_b=shift_b, out=out,
+                                      cols=cols)
 
     def phase_sync_significance(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, fs: float,
                                 bands_hz, *, measures=("plv",), n_surrogates: int, seed, split=None, min_shift=None,
@@ -2188,31 +2140,7 @@ class Engine:
         the bands b0 .. b1 - 1 of the items `sel` (a slice or an index tensor into the item tables), z ((recordings of the
         slab) * (b1 - b0), m, T) is its analytic signal with the bands as recordings, and rec_z / start_z are its item tables,
         window-major and band-minor.  The caller drops its z before asking for the next slab."""
-        n_rec, m, T = x.shape
-        nb = int(resp.shape[0])
-        if item_rec.numel() == 0:
-            return
-        unit = 16 * m * T
-        B = int(max(1, min(nb, int(max_workspace_bytes) // unit - 2)))
-        R = int(max(1, min(n_rec, (int(max_workspace_bytes) // unit - 2) // nb))) if B == nb else 1
-        rec_host = item_rec.cpu()
-        for r0 in range(0, n_rec, R):
-            r1 = min(n_rec, r0 + R)
-            if R >= n_rec:
-                sel, rec_s, start_s = slice(None), item_rec, item_start
-            else:
-                sel = torch.nonzero((rec_host >= r0) & (rec_host < r1)).flatten().to(self.device)
-                if sel.numel() == 0:
-                    continue
-                rec_s, start_s = item_rec[sel] - r0, item_start[sel]
-            for b0 in range(0, nb, B):
-                b1 = min(nb, b0 + B)
-                z = self.analytic_signal(x[r0:r1], resp[b0:b1]).view(-1, m, T)       # recording (r, b) = (r - r0) * (b1 - b0) + b
-                bb = torch.arange(b1 - b0, dtype=torch.int64, device=self.device)
-                rec_z = (rec_s[:, None] * (b1 - b0) + bb[None, :]).reshape(-1)
-                start_z = start_s[:, None].expand(-1, b1 - b0).reshape(-1)
-                yield sel, b0, b1, z, rec_z, start_z
-                del z
+        return phase.phase_slabs(self, x, item_rec, item_start, resp, max_workspace_bytes)
 
     def sliding_phase_sync(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, fs: float,
                            bands_hz, *, measures=("plv",), order: int = 4, check=True, max_workspace_bytes: int = 8 << 30):
@@ -2226,8 +2154,8 @@ class Engine:
         arrays come back with their NaNs."""
         from .eeg_io import resolve_phase_measures
         measures = resolve_phase_measures(measures)
-        return self._sliding_phase("sliding_phase_sync", x, item_rec, item_start, n, fs, bands_hz, sync=measures, order=order,
-                                   check=check, max_workspace_bytes=max_workspace_bytes)[0]
+        return self.sliding_phase("sliding_phase_sync", x, item_rec, item_start, n, fs, bands_hz, sync=measures, order=order,
+                                  check=check, max_workspace_bytes=max_workspace_bytes)[0]
 
     # ------------------------------------------------------------------ phase-lag family (phase_lag.hip)
     def _phase_lag(self, z, item_rec, item_start, n, want, split):
@@ -2255,17 +2183,7 @@ class Engine:
         NaN), 2 = a computed pair with sum |x| == 0 (a flat or duplicated channel; those cells pli 0, wpli / dwpli NaN).
         PLI is exactly what NumPy gives; every cell's bits depend on the n samples of its two channels only.  On the
         engine's stream; nothing is read back after the check of the item tables."""
-        from .eeg_io import check_phase_lag_split, resolve_phase_lag_measures
-        if (not isinstance(z, torch.Tensor) or z.dtype != torch.complex128 or z.device != self.device or z.dim() != 3
-                or z.shape[1] < 1):
-            raise ValueError(f"phase_lag: z must be a complex128 tensor (n_rec, m, T) on {self.device}")
-        want = resolve_phase_lag_measures(want)
-        split = check_phase_lag_split(split, z.shape[1], "phase_lag")
-        self.pad(z.shape[1])
-        validate_items(z, item_rec, item_start, n, 0)
-        if z.shape[0] > 0 and (z.stride(2) != 1 or z.stride(1) < z.shape[2] or z.stride(0) < z.shape[1] * z.stride(1)):
-            z = z.contiguous()
-        return self._phase_lag(z, item_rec, item_start, n, want, split)
+        return phase.phase_lag(self, z, item_rec, item_start, n, want=want, split=split)
 
     def sliding_phase_lag(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, fs: float,
                           bands_hz, *, measures=("wpli",), split: int = 0, order: int = 4, check=True,
@@ -2277,64 +2195,20 @@ class Engine:
         (recording, window, band) whose info is not 0; check="nan": the arrays come back with their NaNs."""
         from .eeg_io import resolve_phase_lag_measures
         measures = resolve_phase_lag_measures(measures)
-        return self._sliding_phase("sliding_phase_lag", x, item_rec, item_start, n, fs, bands_hz, lag=measures, split=split,
-                                   order=order, check=check, max_workspace_bytes=max_workspace_bytes)[1]
+        return self.sliding_phase("sliding_phase_lag", x, item_rec, item_start, n, fs, bands_hz, lag=measures, split=split,
+                                  order=order, check=check, max_workspace_bytes=max_workspace_bytes)[1]
 
-    PHASE_SYNC_WHY = {1: "a non-finite sample in the window", 2: "a channel of zero power in the window"}
-    PHASE_LAG_WHY = {1: "a non-finite sample in the window",
-                     2: "a pair of channels whose sum |Im(z_i conj z_j)| over the window is zero: a flat or duplicated channel"}
+    PHASE_SYNC_WHY, PHASE_LAG_WHY = phase.SYNC_WHY, phase.LAG_WHY
 
-    def _sliding_phase(self, who, x, item_rec, item_start, n, fs, bands_hz, *, sync=None, lag=None, split=0, order=4,
-                       check=True, max_workspace_bytes=8 << 30):
+    def sliding_phase(self, who, x, item_rec, item_start, n, fs, bands_hz, *, sync=None, lag=None, split=0, order=4,
+                      check=True, max_workspace_bytes=8 << 30):
         """The one driver of `sliding_phase_sync` (sync: its resolved measures) and `sliding_phase_lag` (lag: its resolved
-        measures, with `split`): every slab of `phase_slabs` is formed once and handed to the kernels of both families, so
-        a caller that wants both pays for one analytic signal.  -> (dict of `sliding_phase_sync` or None, dict of
-        `sliding_phase_lag` or None), each with its own "info" and the bits its own call gives.  check=True raises for the
-        first window refused, the synchrony family's first."""
-        from .eeg_io import check_phase_lag_split, resolve_bands_hz
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.device != self.device or x.dim() != 3:
-            raise ValueError(f"{who}: x must be a float64 tensor (n_rec, m, T) on {self.device}")
-        if check is not True and check != "nan":
-            raise ValueError(f"{who}: check must be True or 'nan', got {check!r}")
-        n_rec, m, T = x.shape
-        if lag:
-            split = check_phase_lag_split(split, m, who)
-        self.pad(m)
-        bands = resolve_bands_hz(bands_hz, fs)
-        validate_items(x, item_rec, item_start, n, 0)
-        nb, n_items = len(bands), int(item_rec.numel())
-        resp = torch.stack([self.band_response(T, fs, lo, hi, order) for lo, hi in bands])
-        modes = [(mode, [q for q in sync or () if q in names], names) for mode, names in
-                 ((_lib.PHASE_UNIT, ("plv", "ciplv")), (_lib.PHASE_RAW, ("coh", "imcoh")))]
-        modes = [(mode, qs, names) for mode, qs, names in modes if qs]
-        outs = [{q: self.empty(n_items, nb, m, m) for q in qs or ()} for qs in (sync, lag)]
-        infos = [torch.zeros(n_items, nb, dtype=torch.int32, device=self.device) for _ in range(2)]
-        for sel, b0, b1, z, rec_z, start_z in self.phase_slabs(x, item_rec, item_start, resp, max_workspace_bytes):
-            for mode, qs, names in modes:
-                res = self._phase_sync(z, rec_z, start_z, n, mode, names[0] in qs, names[1] in qs, False)
-                for q, key in zip(names, ("mag", "lagged")):
-                    if q in qs:
-                        outs[0][q][sel, b0:b1] = res[key].view(-1, b1 - b0, m, m)
-                infos[0][sel, b0:b1] = torch.maximum(infos[0][sel, b0:b1], res["info"].view(-1, b1 - b0))
-            if lag:
-                res = self._phase_lag(z, rec_z, start_z, n, lag, split)
-                for q in lag:
-                    outs[1][q][sel, b0:b1] = res[q].view(-1, b1 - b0, m, m)
-                infos[1][sel, b0:b1] = res["info"].view(-1, b1 - b0)
-            del z
-        for qs, info, why, name in ((sync, infos[0], self.PHASE_SYNC_WHY, "sliding_phase_sync"),
-                                    (lag, infos[1], self.PHASE_LAG_WHY, "sliding_phase_lag")):
-            if qs and check is True and n_items:
-                bad = torch.nonzero(info.cpu())
-                if bad.numel():
-                    it, b = (int(v) for v in bad[0])
-                    code = int(info[it, b])
-                    raise ValueError(f"{name}: recording {int(item_rec[it])}, window at sample "
-                                     f"{int(item_start[it])} (item {it}), band {b} {bands[b]!r} Hz: info = {code} "
-                                     f"({why.get(code, '?')}); check='nan' returns the arrays with their NaNs")
-        for out, info in zip(outs, infos):
-            out["info"] = info
-        return (outs[0] if sync else None), (outs[1] if lag else None)
+        measures, with `split`), for a caller `who` that wants both: every slab of `phase_slabs` is formed once and handed
+        to the kernels of both families, so the two cost one analytic signal.  -> (dict of `sliding_phase_sync` or None,
+        dict of `sliding_phase_lag` or None), each with its own "info" and the bits its own call gives.  check=True raises
+        for the first window refused, the synchrony family's first."""
+        return phase.sliding_phase(self, who, x, item_rec, item_start, n, fs, bands_hz, sync=sync, lag=lag, split=split,
+                                   order=order, check=check, max_workspace_bytes=max_workspace_bytes)
 
 
 _default = None

@@ -408,8 +408,8 @@ def _launch_segment(eng, cfg, seg, key, geo, psd_stream):
         arrays["block_gc_bands"] = gc_f.masked_fill_(gc_bad.view(-1, 1, 1), float("nan"))
         arrays["block_gc_time"] = gc_t.masked_fill_(gc_bad.view(-1, 1), float("nan"))
     if cfg.phase_sync is not None and cfg.phase_lag is not None:      # both families off one analytic signal
-        ps, pl = eng._sliding_phase("escan_batch.run", xd, *items, W, fs, cfg.bands, sync=cfg.phase_sync, lag=cfg.phase_lag,
-                                    check="nan")
+        ps, pl = eng.sliding_phase("escan_batch.run", xd, *items, W, fs, cfg.bands, sync=cfg.phase_sync, lag=cfg.phase_lag,
+                                   check="nan")
     else:                                               # no model: the same windows, the bands in Hz
         ps = (eng.sliding_phase_sync(xd, *items, W, fs, cfg.bands, measures=cfg.phase_sync, check="nan")
               if cfg.phase_sync is not None else None)

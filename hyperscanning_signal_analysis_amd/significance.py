@@ -11,8 +11,9 @@ the 2 x 2 meta array of `block_meta`, taken apart again by `block_leaves`.  So a
 observed call, run its loop, shape the result.  The two ensemble tests plan their blocks differently and keep loops of their
 own.  Phase synchrony has no model and no surrogate window: its shift surrogate is a table of shifts for the pairs kernel
 on the observed analytic signal, so its shift test walks `sliding_plan`'s blocks itself, slab by slab of the analytic
-signal (`Engine.phase_slabs`), and its pseudo-dyad test is `partner_null` without the lag-covariance base (p = None).  The
-draws and the argument checks are `surrogates`; everything that wraps one C call is a method of the engine.
+signal (`phase.phase_slabs`; the mode table, the check of x and the sentence that names a refused window are `phase`'s
+too), and its pseudo-dyad test is `partner_null` without the lag-covariance base (p = None).  The draws and the argument
+checks are `surrogates`; everything that wraps one C call is a method of the engine.
 """
 from __future__ import annotations
 
@@ -20,6 +21,7 @@ import numpy as np
 import torch
 
 from . import engine as _engine
+from . import phase
 from . import surrogates as sg
 
 __all__ = ["sliding_plan", "ensemble_plan", "stack_plan", "window_ranges", "surrogate_blocks", "NullAccumulator",
@@ -566,14 +568,11 @@ def block_granger_pseudo_dyad_significance(eng, x, item_start, n, p, freqs, fs, 
 
 
 # ------------------------------------------------------------------ phase synchrony: no model, the measures as value columns
-PHASE_WHY = {1: "a non-finite sample in the window", 2: "a channel of zero power in the window"}
-
-
 def phase_calls(measures):
     """The kernel calls that fill the value columns `measures`: [(mode, (col_mag, col_lagged))], a column of -1 for a measure
     that was not asked for; one call per mode in use (PLV / ciPLV: unit phasors, coh / imcoh: the signal itself)."""
     calls = []
-    for mode, names in ((_engine._lib.PHASE_UNIT, ("plv", "ciplv")), (_engine._lib.PHASE_RAW, ("coh", "imcoh"))):
+    for mode, names in phase.MODES:
         cols = tuple(measures.index(q) if q in measures else -1 for q in names)
         if max(cols) >= 0:
             calls.append((mode, cols))
@@ -603,16 +602,11 @@ def _phase_leaves(res, measures, extra=()):
     return out
 
 
-def _phase_x(eng, x, who):
-    if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.device != eng.device or x.dim() != 3:
-        raise ValueError(f"{who}: x must be a float64 tensor (n_rec, m, T) on {eng.device}")
-
-
 def phase_sync_significance(eng, x, item_rec, item_start, n, fs, bands_hz, *, measures, n_surrogates, seed, split=None,
                             min_shift=None, order=4, check=True, chunk=None, full=False, max_workspace_bytes=8 << 30):
     from .eeg_io import resolve_bands_hz
     who = "phase_sync_significance"
-    _phase_x(eng, x, who)
+    phase.check_x(who, eng, x)
     n_rec, m, T = x.shape
     n = int(n)
     measures, S, split, min_shift = sg.phase_significance_args(measures, n_surrogates, m, T, n, split, min_shift, check)
@@ -644,14 +638,8 @@ def phase_sync_significance(eng, x, item_rec, item_start, n, fs, bands_hz, *, me
             info_s = phase_pairs(eng, calls, z, rec_z, rec_z, start_z, n, split, None, obs)
             info[sel, b0:b1] = info_s.view(Ws, bs)
             if check is True:                                # before any surrogate of the slab
-                bad_rows = torch.nonzero(info_s.cpu()).flatten()
-                if bad_rows.numel():
-                    k = int(bad_rows[0])
-                    code, b = int(info_s[k]), b0 + k % bs
-                    it = k // bs if isinstance(sel, slice) else int(sel[k // bs])
-                    raise ValueError(f"{who}: recording {int(item_rec[it])}, window at sample {int(item_start[it])} (item {it}), "
-                                     f"band {b} {bands[b]!r} Hz: info = {code} ({PHASE_WHY.get(code, '?')}); check='nan' "
-                                     f"returns that row as NaN")
+                phase.raise_first_refused(who, info_s.view(Ws, bs), item_rec, item_start, bands, phase.SYNC_WHY,
+                                          "returns that row as NaN", sel, b0)
             if full:
                 for mode, cols in calls:
                     r = eng._phase_sync(z, rec_z, start_z, n, mode, cols[0] >= 0, cols[1] >= 0, False)
@@ -686,7 +674,7 @@ def phase_sync_pseudo_dyad_significance(eng, x, item_start, n, fs, bands_hz, *, 
                                         seed=None, order=4, check=True, chunk=None, max_workspace_bytes=8 << 30):
     from .eeg_io import resolve_bands_hz
     who = "phase_sync_pseudo_dyad_significance"
-    _phase_x(eng, x, who)
+    phase.check_x(who, eng, x)
     D, m, T = x.shape
     n = int(n)
     measures, S, split = sg.phase_pseudo_dyad_args(measures, D, m, n_surrogates, seed, split, check)
@@ -720,8 +708,8 @@ def phase_sync_pseudo_dyad_significance(eng, x, item_start, n, fs, bands_hz, *, 
                 it = int(torch.nonzero(info_b)[0])
                 code = int(info_b[it])
                 raise ValueError(f"{who}: dyad {it // W}, window at sample {int(starts[it])} (window {it % W}), band {b} "
-                                 f"{bands[b]!r} Hz: info = {code} ({PHASE_WHY.get(code, '?')}); check='nan' returns that row "
-                                 f"as NaN")
+                                 f"{bands[b]!r} Hz: info = {code} ({phase.SYNC_WHY.get(code, '?')}); check='nan' returns that "
+                                 f"row as NaN")
             obs_bad = info_b != 0
         acc = NullAccumulator(eng, N, m, nq, tested_h, tested)
 

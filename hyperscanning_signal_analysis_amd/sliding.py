@@ -317,6 +317,42 @@ def sliding_block_granger(x, window_size, n_windows, p, freqs, fs, *, split, hop
     return _to_host((spectral.view(n_rec, len(positions), 2, -1), time.view(n_rec, len(positions), 4)), single)
 
 
+def _phase_x(eng, x):
+    """x (m, T) or (n_rec, m, T), array or tensor -> (x as (n_rec, m, T) float64 on the engine's device, whether it was a
+    single recording): what the four phase wrappers hand to the engine."""
+    single = np.ndim(x) == 2
+    return _recordings_to_device(eng, x, single), single
+
+
+def _sliding_phase_host(who, lag, x, window_size, n_windows, fs, bands_hz, hop, measures, split, order, check, engine,
+                        max_workspace_bytes):
+    """The host wrapper behind `sliding_phase_sync` (lag False: the synchrony measures) and `sliding_phase_lag` (lag True:
+    the phase-lag measures, with their split): the arguments first, then x to the device, `Engine.sliding_phase` and the result
+    as {measure: (n_rec, n_windows, n_bands, m, m)} on the host."""
+    from .eeg_io import check_phase_lag_split, resolve_bands_hz, resolve_phase_lag_measures, resolve_phase_measures
+    measures = (resolve_phase_lag_measures if lag else resolve_phase_measures)(measures)    # nothing has touched a device yet
+    bands_hz = tuple(bands_hz)
+    resolve_bands_hz(bands_hz, fs)
+    if check is not True and check != "nan":
+        raise ValueError(f"{who}: check must be True or 'nan', got {check!r}")
+    x = np.asarray(x, dtype=np.float64) if not isinstance(x, torch.Tensor) else x
+    if x.ndim not in (2, 3):
+        raise ValueError(f"{who}: x must be (m, T) or (n_rec, m, T), got shape {tuple(x.shape)}")
+    if lag:
+        split = check_phase_lag_split(split, int(x.shape[-2]), who)
+    positions, w = _positions(int(x.shape[-1]), window_size, n_windows, hop)
+    eng = engine or default_engine()
+    xd, single = _phase_x(eng, x)
+    n_rec = int(xd.shape[0])
+    item_rec, item_start = window_items(n_rec, positions, eng.device)
+    res = eng.sliding_phase(who, xd, item_rec, item_start, w, fs, bands_hz, sync=None if lag else measures,
+                            lag=measures if lag else None, split=split, order=order, check=check,
+                            max_workspace_bytes=max_workspace_bytes)[int(lag)]
+    keys = measures + (("info",) if check == "nan" else ())
+    out = {k: res[k].view(n_rec, len(positions), len(bands_hz), *res[k].shape[2:]).cpu().numpy() for k in keys}
+    return {k: v[0] for k, v in out.items()} if single else out
+
+
 def sliding_phase_sync(x, window_size, n_windows, fs, bands_hz=DEFAULT_BANDS, *, hop=None, measures=("plv",), order=4,
                        check=True, engine: Engine | None = None, max_workspace_bytes: int = 8 << 30):
     """NumPy (or tensor) in / NumPy out: band-limited phase synchrony of every window (`Engine.sliding_phase_sync`).  x: (m, T)
@@ -326,29 +362,8 @@ def sliding_phase_sync(x, window_size, n_windows, fs, bands_hz=DEFAULT_BANDS, *,
     band signal is `eeg_io.band_response`'s, circular at the ends of the recording.  Windows from `window_positions`, or
     every `hop` samples when `hop` is given.  No model is fitted: there is no order and no window is refused for its
     conditioning."""
-    from .eeg_io import resolve_bands_hz, resolve_phase_measures
-    measures = resolve_phase_measures(measures)                  # the arguments first: nothing has touched a device yet
-    bands_hz = tuple(bands_hz)
-    resolve_bands_hz(bands_hz, fs)
-    if check is not True and check != "nan":
-        raise ValueError(f"sliding_phase_sync: check must be True or 'nan', got {check!r}")
-    x = np.asarray(x, dtype=np.float64) if not isinstance(x, torch.Tensor) else x
-    if x.ndim not in (2, 3):
-        raise ValueError(f"sliding_phase_sync: x must be (m, T) or (n_rec, m, T), got shape {tuple(x.shape)}")
-    single = x.ndim == 2
-    positions, w = _positions(int(x.shape[-1]), window_size, n_windows, hop)
-    eng = engine or default_engine()
-    if isinstance(x, torch.Tensor):
-        xd = (x[None] if single else x).to(device=eng.device, dtype=torch.float64)
-    else:
-        xd = eng.to_device(x[None] if single else x)
-    n_rec, m, T = xd.shape
-    item_rec, item_start = window_items(n_rec, positions, eng.device)
-    res = eng.sliding_phase_sync(xd, item_rec, item_start, w, fs, bands_hz, measures=measures, order=order, check=check,
-                                 max_workspace_bytes=max_workspace_bytes)
-    keys = measures + (("info",) if check == "nan" else ())
-    out = {k: res[k].view(n_rec, len(positions), len(bands_hz), *res[k].shape[2:]).cpu().numpy() for k in keys}
-    return {k: v[0] for k, v in out.items()} if single else out
+    return _sliding_phase_host("sliding_phase_sync", False, x, window_size, n_windows, fs, bands_hz, hop, measures, 0, order,
+                               check, engine, max_workspace_bytes)
 
 
 def sliding_phase_lag(x, window_size, n_windows, fs, bands_hz=DEFAULT_BANDS, *, hop=None, measures=("wpli",), split=0,
@@ -359,30 +374,8 @@ def sliding_phase_lag(x, window_size, n_windows, fs, bands_hz=DEFAULT_BANDS, *, 
     "wpli", "dwpli"), without the leading axis for a single recording; with check="nan" also "info" (n_rec, n_windows,
     n_bands).  split = 0: all pairs; 1..m-1: only the inter-brain pairs (i < split <= j), every other off-diagonal cell NaN.
     Bands, windows and `hop` as in `sliding_phase_sync`.  No model is fitted."""
-    from .eeg_io import check_phase_lag_split, resolve_bands_hz, resolve_phase_lag_measures
-    measures = resolve_phase_lag_measures(measures)              # the arguments first: nothing has touched a device yet
-    bands_hz = tuple(bands_hz)
-    resolve_bands_hz(bands_hz, fs)
-    if check is not True and check != "nan":
-        raise ValueError(f"sliding_phase_lag: check must be True or 'nan', got {check!r}")
-    x = np.asarray(x, dtype=np.float64) if not isinstance(x, torch.Tensor) else x
-    if x.ndim not in (2, 3):
-        raise ValueError(f"sliding_phase_lag: x must be (m, T) or (n_rec, m, T), got shape {tuple(x.shape)}")
-    split = check_phase_lag_split(split, int(x.shape[-2]), "sliding_phase_lag")
-    single = x.ndim == 2
-    positions, w = _positions(int(x.shape[-1]), window_size, n_windows, hop)
-    eng = engine or default_engine()
-    if isinstance(x, torch.Tensor):
-        xd = (x[None] if single else x).to(device=eng.device, dtype=torch.float64)
-    else:
-        xd = eng.to_device(x[None] if single else x)
-    n_rec, m, T = xd.shape
-    item_rec, item_start = window_items(n_rec, positions, eng.device)
-    res = eng.sliding_phase_lag(xd, item_rec, item_start, w, fs, bands_hz, measures=measures, split=split, order=order,
-                                check=check, max_workspace_bytes=max_workspace_bytes)
-    keys = measures + (("info",) if check == "nan" else ())
-    out = {k: res[k].view(n_rec, len(positions), len(bands_hz), *res[k].shape[2:]).cpu().numpy() for k in keys}
-    return {k: v[0] for k, v in out.items()} if single else out
+    return _sliding_phase_host("sliding_phase_lag", True, x, window_size, n_windows, fs, bands_hz, hop, measures, split, order,
+                               check, engine, max_workspace_bytes)
 
 
 def _phase_host(v, lead=None):
@@ -414,10 +407,7 @@ def sliding_phase_sync_significance(x, window_size, n_windows, fs, bands_hz=DEFA
     positions, w = _positions(T, window_size, n_windows, hop)
     sg.phase_significance_args(measures, n_surrogates, m, T, w, split, min_shift, check)
     eng = engine or default_engine()
-    if isinstance(x, torch.Tensor):
-        xd = (x[None] if single else x).to(device=eng.device, dtype=torch.float64).contiguous()
-    else:
-        xd = eng.to_device(np.asarray(x, dtype=np.float64)[None] if single else np.asarray(x, dtype=np.float64))
+    xd, single = _phase_x(eng, x)
     item_rec, item_start = window_items(n_rec, positions, eng.device)
     res = eng.phase_sync_significance(xd, item_rec, item_start, w, fs, bands_hz, measures=measures, n_surrogates=n_surrogates,
                                       seed=seed, split=split, min_shift=min_shift, order=order, check=check, chunk=chunk,
@@ -447,7 +437,7 @@ def sliding_phase_sync_pseudo_dyad_significance(x, window_size, n_windows, fs, b
     resolve_bands_hz(bands_hz, fs)
     positions, w = _positions(T, window_size, n_windows, hop)
     eng = engine or default_engine()
-    xd = _recordings_to_device(eng, x, False)
+    xd, _ = _phase_x(eng, x)
     item_start = torch.as_tensor(np.asarray(positions, dtype=np.int64)).to(eng.device)
     res = eng.phase_sync_pseudo_dyad_significance(xd, item_start, w, fs, bands_hz, measures=measures, split=split,
                                                   n_surrogates=n_surrogates, seed=seed, order=order, check=check, chunk=chunk,

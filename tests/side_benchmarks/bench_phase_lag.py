@@ -128,8 +128,8 @@ def run(args):
     lag3 = wall_s(lambda: eng.sliding_phase_lag(xd, rec, st, w, FS, bands, measures=("pli", "wpli", "dwpli"), check="nan"))
     lag32 = wall_s(lambda: eng.sliding_phase_lag(xd, rec, st, w, FS, bands, measures=("wpli",), split=32, check="nan"))
     sync = wall_s(lambda: eng.sliding_phase_sync(xd, rec, st, w, FS, bands, measures=("plv", "ciplv"), check="nan"))
-    both = wall_s(lambda: eng._sliding_phase("bench", xd, rec, st, w, FS, bands, sync=("plv", "ciplv"), lag=("wpli",),
-                                             check="nan"))
+    both = wall_s(lambda: eng.sliding_phase("bench", xd, rec, st, w, FS, bands, sync=("plv", "ciplv"), lag=("wpli",),
+                                            check="nan"))
     res["whole_call"] = {"sliding_phase_lag_wpli_ms": lag * 1e3, "sliding_phase_lag_all_three_ms": lag3 * 1e3,
                          "sliding_phase_lag_wpli_split32_ms": lag32 * 1e3, "band_windows_per_s_wpli": N_WIN * nb / lag,
                          "sliding_phase_sync_plv_ciplv_ms": sync * 1e3,

@@ -272,7 +272,7 @@ def test_public_call_is_the_composition(dyads, hop):
     # the combined driver: one analytic signal for both families, each with the bits of its own call
     sync_q, lag_q = ("plv", "imcoh"), ("pli", "wpli", "dwpli")
     for ws in (8 << 30, 3 * 16 * m * T):
-        both = eng._sliding_phase("both", xd, rec, start, W, PR.FS, bands, sync=sync_q, lag=lag_q, split=4, max_workspace_bytes=ws)
+        both = eng.sliding_phase("both", xd, rec, start, W, PR.FS, bands, sync=sync_q, lag=lag_q, split=4, max_workspace_bytes=ws)
         s_alone = eng.sliding_phase_sync(xd, rec, start, W, PR.FS, bands, measures=sync_q)
         l_alone = eng.sliding_phase_lag(xd, rec, start, W, PR.FS, bands, measures=lag_q, split=4)
         for got, alone, qs in ((both[0], s_alone, sync_q), (both[1], l_alone, lag_q)):
