@@ -7,156 +7,59 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_int, c_int32, c_int64, c_void_p
+import re
+from ctypes import c_char_p, c_double, c_int, c_int32, c_int64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhypermvar.so")
+HEADER = os.path.join(_HERE, os.pardir, "include", "hypermvar.h")
 
-# name -> (restype, argtypes); mirrors include/hypermvar.h one to one
-SIGNATURES = {
-    "hmv_version": (c_int, []),
-    "hmv_last_error": (c_char_p, []),
-    "hmv_pad": (c_int, [c_int]),
-    "hmv_set_tuning": (c_int, [c_int, c_int64]),
-    "hmv_get_tuning": (c_int64, [c_int]),
-    "hmv_yw_workspace_doubles": (c_int64, [c_int, c_int]),
-    "hmv_lagcov_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
-                               c_void_p, c_void_p]),
-    "hmv_lagcov_regular_workspace_doubles": (c_int64, [c_int64, c_int, c_int, c_int64, c_int]),
-    "hmv_lagcov_regular_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int,
-                                       c_void_p, c_void_p, c_void_p]),
-    "hmv_yw_solve_f64": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                 c_void_p, c_int64, c_void_p]),
-    "hmv_yw_routes_i32": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
-    "hmv_twiddles_f64": (c_int, [c_void_p, c_int, c_double, c_int, c_void_p, c_void_p]),
-    "hmv_tf_workspace_doubles": (c_int64, [c_int64, c_int, c_int]),
-    "hmv_tf_f64": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                           c_void_p, c_void_p, c_double, c_void_p, c_void_p]),
-    "hmv_ffdtf_norm_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
-                                   c_void_p]),
-    "hmv_transpose_c128": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
-    "hmv_spectra_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
-    "hmv_spectra_mmf_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
-    "hmv_pack_c128": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
-    "hmv_cinv_c128": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p]),
-    "hmv_partial_coherence_c128": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
-    "hmv_gpdc_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
-    "hmv_trial_mean_f64": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
-    "hmv_ddtf_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
-    "hmv_band_sums_f64": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    "hmv_dpss_workspace_bytes": (c_int64, [c_int64, c_int, c_int]),
-    "hmv_dpss_f64": (c_int, [c_int64, c_double, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    "hmv_psd_workspace_bytes": (c_int64, [c_int64, c_int64, c_int]),
-    "hmv_psd_multitaper_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int, c_int64, c_int64,
-                                       c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
-    "hmv_sliding_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int]),
-    "hmv_tf_ffdtf_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int]),
-    "hmv_tf_ffdtf_f64": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                 c_double, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
-    "hmv_tf_ffdtf_bands_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int]),
-    "hmv_tf_ffdtf_bands_f64": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                                       c_void_p, c_void_p, c_double, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
-                                       c_void_p]),
-    "hmv_sliding_bands_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int]),
-    "hmv_sliding_ffdtf_bands_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int,
-                                            c_int, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int,
-                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_double,
-                                            c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
-                                            c_void_p]),
-    "hmv_sliding_spectra_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int]),
-    "hmv_sliding_ffdtf_spectra_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int,
-                                              c_int, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
-                                              c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_double, c_int64, c_int64,
-                                              c_int64, c_int64, c_int64, c_void_p, c_void_p]),
-    "hmv_sliding_ffdtf_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int,
-                                      c_int, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
-                                      c_void_p, c_void_p, c_int64, c_int64, c_double, c_int64, c_int64, c_int64, c_int64,
-                                      c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "hmv_sliding_ddtf_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int, c_int]),
-    "hmv_sliding_ddtf_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p,
-                                     c_int, c_double, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                     c_void_p, c_void_p, c_int64, c_int64, c_double, c_int64, c_int64, c_int64, c_int64,
-                                     c_int64, c_void_p, c_void_p]),
-    "hmv_sliding_gpdc_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int, c_int]),
-    "hmv_sliding_gpdc_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p,
-                                     c_int, c_double, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                     c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p,
-                                     c_void_p]),
-    "hmv_block_gc_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int, c_int]),
-    "hmv_block_gc_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_double, c_void_p,
-                                 c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    "hmv_block_gc_sliding_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int, c_int, c_int]),
-    "hmv_sliding_block_gc_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
-                                         c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 7 +
-                                 [c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p]),
-    "hmv_block_gc_pairs_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
-    "hmv_sliding_block_gc_pairs_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int,
-                                               c_int, c_int, c_int, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p,
-                                               c_int] + [c_void_p] * 7 + [c_int64, c_int64, c_int64, c_void_p, c_void_p,
-                                                                          c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                                                          c_void_p]),
-    "hmv_yw_solve_auto_f64": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int] + [c_void_p] * 7 + [c_int64, c_void_p]),
-    "hmv_sliding_auto_workspace_bytes": (c_int64, [c_int, c_int64, c_int, c_int, c_int, c_int]),
-    "hmv_sliding_auto_f64": (c_int, [c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
-                                     c_int, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int] +
-                             [c_void_p] * 8 + [c_int64, c_int64, c_double, c_int64, c_int64, c_int64, c_int64, c_int64,
-                                               c_void_p, c_void_p]),
-    "hmv_lagcov_ensemble_workspace_doubles": (c_int64, [c_int64, c_int, c_int, c_int, c_int64, c_int64]),
-    "hmv_lagcov_ensemble_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
-                                        c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int64,
-                                        c_int64, c_int64, c_int64, c_void_p]),
-    "hmv_sliding_ensemble_workspace_bytes": (c_int64, [c_int, c_int64, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64]),
-    "hmv_sliding_ensemble_f64": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
-                                         c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_double,
-                                         c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 6 +
-                                 [c_int64, c_int64, c_double, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
-    "hmv_lagcov_ensemble_split_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
-                                              c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                              c_int, c_void_p, c_void_p, c_int64, c_void_p]),
-    "hmv_sliding_ensemble_split_f64": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
-                                               c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int,
-                                               c_double, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 6 +
-                                       [c_int64, c_int64, c_double, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                                        c_void_p, c_void_p]),
-    "hmv_lagcov_pairs_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
-                                     c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    "hmv_pairs_workspace_bytes": (c_int64, [c_int, c_int64, c_int, c_int, c_int, c_int, c_int]),
-    "hmv_sliding_pairs_f64": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int,
-                                      c_int, c_int, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int] +
-                              [c_void_p] * 6 + [c_int64, c_int64, c_double, c_int64, c_int, c_void_p, c_void_p, c_void_p,
-                                                c_void_p, c_void_p]),
-    "hmv_lagcov_mix_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
-    "hmv_mix_workspace_bytes": (c_int64, [c_int, c_int64, c_int, c_int, c_int, c_int]),
-    "hmv_sliding_mix_f64": (c_int, [c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
-                                    c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 6 +
-                            [c_int64, c_int64, c_double, c_int64, c_void_p, c_void_p]),
-    "hmv_fad_workspace_bytes": (c_int64, [c_int64, c_int]),
-    "hmv_fad_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int,
-                            c_double, c_double, c_int] + [c_void_p] * 17),
-    "hmv_fad_decompose_f64": (c_int, [c_void_p, c_int64, c_int, c_double, c_double, c_int] + [c_void_p] * 13),
-    "hmv_surrogate_shift_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
-                                        c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "hmv_surrogate_phase_c128": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "hmv_null_accumulate_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int] + [c_void_p] * 12),
-    "hmv_residuals_workspace_bytes": (c_int64, [c_int64, c_int, c_int]),
-    "hmv_residuals_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p,
-                                  c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
-    "hmv_whiteness_f64": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_double] + [c_void_p] * 6),
-    "hmv_model_validation_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int, c_int]),
-    "hmv_model_validation_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
-                                         c_void_p, c_int, c_double] + [c_void_p] * 7 + [c_int64, c_void_p, c_int64, c_int64,
-                                                                                       c_void_p]),
-    "hmv_decimate_out_len": (c_int64, [c_int64, c_int]),
-    "hmv_decimate_tile": (c_int, [c_int, c_int]),
-    "hmv_decimate_fir_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_int, c_void_p,
-                                     c_int64, c_int64, c_void_p]),
-    "hmv_phase_sync_c128": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_int,
-                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "hmv_phase_sync_pairs_c128": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                          c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "hmv_phase_lag_c128": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64, c_int,
-                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-}
+
+class HypermvarLibraryError(ImportError):
+    pass
+
+
+_SCALARS = {"int": c_int, "int32_t": c_int32, "int64_t": c_int64, "double": c_double}
+
+
+def _ctype(decl, named, where):
+    """ctypes type of a return type (named=False) or of a `type name` parameter (named=True) of the prototype `where`."""
+    if "*" in decl:
+        return c_char_p if not named and decl.replace("*", " * ").split() == ["const", "char", "*"] else c_void_p
+    words = [w for w in decl.split() if w != "const"]
+    if len(words) != 1 + named or words[0] not in _SCALARS:
+        raise HypermvarLibraryError(f"cannot bind `{' '.join(decl.split())}` of `{where}`: the binding knows int, int32_t, "
+                                    "int64_t, double and pointers, and every parameter must be named")
+    return _SCALARS[words[0]]
+
+
+def signatures_from_header(text):
+    """{name: (restype, [argtypes])} of every hmv_* prototype in the text of a header.  A pointer is c_void_p (a returned
+    `const char*` c_char_p), the four scalar types are themselves, and anything else raises: a guess here would hand a
+    kernel launch a truncated or shifted argument."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = "\n".join(line for line in text.split("\n") if not line.lstrip().startswith("#"))
+    sigs = {}
+    for ret, name, args in re.findall(r"([\w\s*]*?)\b(hmv_\w+)\s*\(([^()]*)\)\s*;", text):
+        where = " ".join(f"{ret}{name}({args})".split())
+        args = [] if args.strip() in ("", "void") else args.split(",")
+        sigs[name] = (_ctype(ret, False, where), [_ctype(a, True, where) for a in args])
+    n_seen = len(re.findall(r"\bhmv_\w+\s*\(", text))
+    if n_seen != len(sigs):      # a function pointer, a macro-wrapped or a repeated declaration: never skipped silently
+        raise HypermvarLibraryError(f"`hmv_name(` occurs {n_seen} times but {len(sigs)} prototypes could be read")
+    return sigs
+
+
+def _header_text():
+    try:
+        with open(HEADER) as f:
+            return f.read()
+    except OSError as e:
+        raise HypermvarLibraryError(f"{HEADER} not found: the ctypes table is read from it") from e
+
+
+# name -> (restype, argtypes): include/hypermvar.h is the one statement of the C ABI
+SIGNATURES = signatures_from_header(_header_text())
 
 # option bits of the fused entry points (include/hypermvar.h)
 FLAG_UNFUSED_NORM = 1
@@ -188,10 +91,6 @@ PHASE_RAW = 1
 _lib = None
 
 
-class HypermvarLibraryError(ImportError):
-    pass
-
-
 def load():
     """Load libhypermvar.so and bind every symbol of include/hypermvar.h.  Raises if anything is missing."""
     global _lib
@@ -215,6 +114,13 @@ def load():
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def call(lib, entry: str, *args):
+    """lib.<entry>(*args) for an entry that returns a status, which `check` turns into an exception: a torch tensor is
+    passed as its data pointer, None as a null pointer, everything else as it is."""
+    fn = getattr(lib, entry)
+    check(fn(*(0 if a is None else a.data_ptr() if hasattr(a, "data_ptr") else a for a in args)), entry)
 
 
 def check(rc: int, what: str):

@@ -14,6 +14,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include <utility>
 
 #define HMV_WAVE 64
@@ -39,6 +40,24 @@ __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int
 template <int N, typename F>
 __device__ __forceinline__ void static_for(F&& f) {
   static_for_impl(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
+}
+
+// host: f(std::integral_constant<int, NT>) for the padded channel count m_pad = 16 * NT; -1 for any other.  The one place
+// that maps a channel count to the kernels templated on the tile count.
+template <typename F>
+int for_nt(int m_pad, F&& f) {
+  switch (m_pad) {
+    case 16: f(std::integral_constant<int, 1>{}); return 0;
+    case 32: f(std::integral_constant<int, 2>{}); return 0;
+    case 48: f(std::integral_constant<int, 3>{}); return 0;
+    case 64: f(std::integral_constant<int, 4>{}); return 0;
+    default: return -1;
+  }
+}
+// the same where a bool selects the instantiation too: f(std::integral_constant<int, NT>, std::bool_constant<b>)
+template <typename F>
+int for_nt(int m_pad, bool b, F&& f) {
+  return b ? for_nt(m_pad, [&](auto nt) { f(nt, std::true_type{}); }) : for_nt(m_pad, [&](auto nt) { f(nt, std::false_type{}); });
 }
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }

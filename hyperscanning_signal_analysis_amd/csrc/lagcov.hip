@@ -130,7 +130,7 @@ int launch_lagcomb(const LagcombArgs& a, int m_pad, hipStream_t st) {
   if (a.n_win == 0) return 0;
   if (a.p > k1::HALO) return -2;
   const dim3 grid((unsigned)a.n_win, a.p + 1), block(256);
-  if (k1::for_nt(m_pad, [&](auto nt) { hipLaunchKernelGGL(lagcomb_kernel<decltype(nt)::value>, grid, block, 0, st, a); }))
+  if (for_nt(m_pad, [&](auto nt) { hipLaunchKernelGGL(lagcomb_kernel<decltype(nt)::value>, grid, block, 0, st, a); }))
     return -1;
   return (int)hipGetLastError();
 }
@@ -138,7 +138,7 @@ int launch_lagcomb(const LagcombArgs& a, int m_pad, hipStream_t st) {
 template <int LG>
 static int launch_lagcov_lg(const LagcovArgs& a, int m_pad, hipStream_t st) {
   const dim3 grid((unsigned)a.n_items, (a.p + LG) / LG), block(256);
-  if (k1::for_nt(m_pad, [&](auto nt) { hipLaunchKernelGGL((lagcov_kernel<decltype(nt)::value, LG>), grid, block, 0, st, a); }))
+  if (for_nt(m_pad, [&](auto nt) { hipLaunchKernelGGL((lagcov_kernel<decltype(nt)::value, LG>), grid, block, 0, st, a); }))
     return -1;
   return (int)hipGetLastError();
 }

@@ -253,17 +253,5 @@ __device__ __forceinline__ unsigned herm_need(int split, bool diag) {
   return (unsigned)uni((int)need);
 }
 
-// host: f(std::integral_constant<int, NT>) for the padded channel count m_pad = 16 * NT; -1 for any other
-template <typename F>
-int for_nt(int m_pad, F&& f) {
-  switch (m_pad) {
-    case 16: f(std::integral_constant<int, 1>{}); return 0;
-    case 32: f(std::integral_constant<int, 2>{}); return 0;
-    case 48: f(std::integral_constant<int, 3>{}); return 0;
-    case 64: f(std::integral_constant<int, 4>{}); return 0;
-    default: return -1;
-  }
-}
-
 }  // namespace k1
 }  // namespace hmv

@@ -397,7 +397,7 @@ int launch_lagcov_ensemble(const LagcovEnsArgs& a, int m_pad, bool shared, hipSt
   constexpr int LG = 3;
   const dim3 block(256), grid((unsigned)a.n_items, (a.p + LG) / LG);
   if (!shared) {
-    if (k1::for_nt(m_pad, [&](auto nt) {
+    if (for_nt(m_pad, [&](auto nt) {
           hipLaunchKernelGGL((lagcov_ens_kernel<decltype(nt)::value, LG>), grid, block, 0, st, a);
         }))
       return -1;
@@ -406,7 +406,7 @@ int launch_lagcov_ensemble(const LagcovEnsArgs& a, int m_pad, bool shared, hipSt
   if (!lagcov_ensemble_shared_ok(a.n, a.hop, a.p, LE_MAX_K) || a.n / a.hop != a.k || a.nwin < 1 || !a.Q) return -3;
   const long long ngc = (a.it0 + a.n_items - 1) / a.nwin - a.it0 / a.nwin + 1;
   const dim3 gq((unsigned)(ngc * (a.nwin + a.k - 1)), (a.p + LG) / LG), gc((unsigned)a.n_items, a.p + 1);
-  if (k1::for_nt(m_pad, [&](auto nt) {
+  if (for_nt(m_pad, [&](auto nt) {
         hipLaunchKernelGGL((lagens_block_kernel<decltype(nt)::value, LG>), gq, block, 0, st, a);
         hipLaunchKernelGGL(lagens_comb_kernel<decltype(nt)::value>, gc, block, 0, st, a);
       }))
@@ -421,7 +421,7 @@ int launch_lagcov_ensemble_split(const LagcovEnsArgs& a, int m_pad, hipStream_t 
     return -4;
   constexpr int LG = 3;
   const dim3 block(256), grid((unsigned)a.n_items, (a.p + LG) / LG);
-  if (k1::for_nt(m_pad, [&](auto nt) {
+  if (for_nt(m_pad, [&](auto nt) {
         hipLaunchKernelGGL((lagcov_ens_split_kernel<decltype(nt)::value, LG>), grid, block, 0, st, a);
       }))
     return -1;
@@ -436,7 +436,7 @@ int launch_lagcov_pairs(const LagcovPairsArgs& a, int m_pad, hipStream_t st) {
     return -4;
   constexpr int LG = 3;
   const dim3 block(256), grid((unsigned)a.n_items, (a.p + LG) / LG);
-  if (k1::for_nt(m_pad, [&](auto nt) {
+  if (for_nt(m_pad, [&](auto nt) {
         hipLaunchKernelGGL((lagcov_pairs_kernel<decltype(nt)::value, LG>), grid, block, 0, st, a);
       }))
     return -1;

@@ -202,7 +202,7 @@ __global__ void __launch_bounds__(256, 2) phase_lag_kernel(PhaseLagArgs a) {
 int launch_phase_lag(const PhaseLagArgs& a, int m_pad, hipStream_t st) {
   if (a.n_items == 0) return 0;
   const dim3 grid((unsigned)a.n_items), block(256);
-  if (k1::for_nt(m_pad, [&](auto nt) { hipLaunchKernelGGL(phase_lag_kernel<decltype(nt)::value>, grid, block, 0, st, a); }))
+  if (for_nt(m_pad, [&](auto nt) { hipLaunchKernelGGL(phase_lag_kernel<decltype(nt)::value>, grid, block, 0, st, a); }))
     return -1;
   return (int)hipGetLastError();
 }

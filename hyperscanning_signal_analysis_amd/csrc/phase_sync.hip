@@ -183,7 +183,7 @@ __global__ void __launch_bounds__(256, 2) phase_gram_kernel(std::conditional_t<P
 int launch_phase_sync(const PhaseSyncArgs& a, int m_pad, hipStream_t st) {
   if (a.n_items == 0) return 0;
   const dim3 grid((unsigned)a.n_items), block(256);
-  if (k1::for_nt(m_pad, [&](auto nt) { hipLaunchKernelGGL(phase_gram_kernel<decltype(nt)::value>, grid, block, 0, st, a); }))
+  if (for_nt(m_pad, [&](auto nt) { hipLaunchKernelGGL(phase_gram_kernel<decltype(nt)::value>, grid, block, 0, st, a); }))
     return -1;
   return (int)hipGetLastError();
 }
@@ -191,7 +191,7 @@ int launch_phase_sync(const PhaseSyncArgs& a, int m_pad, hipStream_t st) {
 int launch_phase_sync_pairs(const PhasePairsArgs& a, int m_pad, hipStream_t st) {
   if (a.n_items == 0) return 0;
   const dim3 grid((unsigned)a.n_items), block(256);
-  if (k1::for_nt(m_pad, [&](auto nt) {
+  if (for_nt(m_pad, [&](auto nt) {
         hipLaunchKernelGGL((phase_gram_kernel<decltype(nt)::value, true>), grid, block, 0, st, a);
       }))
     return -1;

@@ -300,13 +300,7 @@ int launch_ddtf_sliding(const DdtfArgs& a, int m_pad, hipStream_t st) {
   hipLaunchKernelGGL(ddtf_factor_kernel, dim3((unsigned)a.n_items), dim3(256), 0, st, a.ar, a.V, a.info_yw, a.B, a.m, m_pad,
                      a.p);
   const dim3 gg((unsigned)(a.n_items * D));
-  switch (m_pad) {
-    case 16: hipLaunchKernelGGL(ddtf_gram_kernel<1>, gg, dim3(256), 0, st, a.B, a.G, a.p); break;
-    case 32: hipLaunchKernelGGL(ddtf_gram_kernel<2>, gg, dim3(256), 0, st, a.B, a.G, a.p); break;
-    case 48: hipLaunchKernelGGL(ddtf_gram_kernel<3>, gg, dim3(256), 0, st, a.B, a.G, a.p); break;
-    case 64: hipLaunchKernelGGL(ddtf_gram_kernel<4>, gg, dim3(256), 0, st, a.B, a.G, a.p); break;
-    default: return -3;
-  }
+  if (for_nt(m_pad, [&](auto nt) { hipLaunchKernelGGL(ddtf_gram_kernel<nt>, gg, dim3(256), 0, st, a.B, a.G, a.p); })) return -3;
   const int nft = (a.F + 63) / 64;
   hipLaunchKernelGGL(ddtf_apply_kernel, dim3((unsigned)(a.n_items * nft)), dim3(256), 0, st, a.G, a.freqs, a.fs, a.ff, a.out,
                      a.F, a.m, m_pad, a.p);

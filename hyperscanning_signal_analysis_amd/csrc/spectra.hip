@@ -255,23 +255,10 @@ int launch_spectra(const SpecArgs& a, int m_pad, hipStream_t st) {
   const long long n = a.n_items * (long long)a.F;
   if (n == 0) return 0;
   const dim3 grid((unsigned)n), block(256);
-  if (a.sym && a.S_mmf) {
-    switch (m_pad) {
-      case 16: hipLaunchKernelGGL((spectra_kernel<1, true>), grid, block, 0, st, a); break;
-      case 32: hipLaunchKernelGGL((spectra_kernel<2, true>), grid, block, 0, st, a); break;
-      case 48: hipLaunchKernelGGL((spectra_kernel<3, true>), grid, block, 0, st, a); break;
-      case 64: hipLaunchKernelGGL((spectra_kernel<4, true>), grid, block, 0, st, a); break;
-      default: return -1;
-    }
-    return (int)hipGetLastError();
-  }
-  switch (m_pad) {
-    case 16: hipLaunchKernelGGL((spectra_kernel<1, false>), grid, block, 0, st, a); break;
-    case 32: hipLaunchKernelGGL((spectra_kernel<2, false>), grid, block, 0, st, a); break;
-    case 48: hipLaunchKernelGGL((spectra_kernel<3, false>), grid, block, 0, st, a); break;
-    case 64: hipLaunchKernelGGL((spectra_kernel<4, false>), grid, block, 0, st, a); break;
-    default: return -1;
-  }
+  if (for_nt(m_pad, a.sym && a.S_mmf, [&](auto nt, auto mmf) {
+        hipLaunchKernelGGL((spectra_kernel<nt, mmf>), grid, block, 0, st, a);
+      }))
+    return -1;
   return (int)hipGetLastError();
 }
 

@@ -1159,13 +1159,9 @@ int launch_twiddles(const double* freqs, int F, double fs, int p, double* tw, hi
 
 // largest frequency grid the in-kernel band sums take: one band's 0 / 1 weights must fit the row worker's LDS block
 int tf_band_max_F(int m_pad) {
-  switch (m_pad) {
-    case 16: return (2 * TfLds<1>::TOTAL) & ~31;
-    case 32: return (2 * TfLds<2>::TOTAL) & ~31;
-    case 48: return (2 * TfLds<3>::TOTAL) & ~31;
-    case 64: return (2 * TfLds<4>::TOTAL) & ~31;
-  }
-  return 0;
+  int max_F = 0;               // (stays 0 for a size that is none of the four)
+  for_nt(m_pad, [&](auto nt) { max_F = (2 * TfLds<nt>::TOTAL) & ~31; });
+  return max_F;
 }
 
 long long tf_workspace_doubles(long long n_items, int m_pad, int p) {
@@ -1200,16 +1196,9 @@ int launch_tf_inv(const TfArgs& a_in, int m_pad, hipStream_t st, hipEvent_t ev_s
     const double* ar = a.ar + (size_t)i0 * m_pad * m_pad * a.p;
     const double* wsp = yw_ws ? yw_ws + (size_t)i0 * ws_item : nullptr;
     double* arx = const_cast<double*>(a.arx) + (size_t)i0 * per_item * 2;
-#define HMV_AR_PACK(NT)                                                                                             \
-  if (yw_ws) hipLaunchKernelGGL((ar_pack_kernel<NT, true>), pgrid, dim3(256), 0, st, ar, wsp, ws_item, arx, ni, a.p); \
-  else hipLaunchKernelGGL((ar_pack_kernel<NT, false>), pgrid, dim3(256), 0, st, ar, wsp, ws_item, arx, ni, a.p)
-    switch (m_pad) {
-      case 16: HMV_AR_PACK(1); break;
-      case 32: HMV_AR_PACK(2); break;
-      case 48: HMV_AR_PACK(3); break;
-      case 64: HMV_AR_PACK(4); break;
-    }
-#undef HMV_AR_PACK
+    for_nt(m_pad, yw_ws != nullptr, [&](auto nt, auto tiles) {
+      hipLaunchKernelGGL((ar_pack_kernel<nt, tiles>), pgrid, dim3(256), 0, st, ar, wsp, ws_item, arx, ni, a.p);
+    });
     // the caller's events bracket the K3 kernel alone (both launches of a split batch, and what lies between them): not the
     // packing kernel in front of it, not norm_missed_kernel behind it (what rocprofv3 reports as the kernel's duration must
     // be what bench.py prices against the roofline)
@@ -1243,12 +1232,7 @@ int launch_tf_inv(const TfArgs& a_in, int m_pad, hipStream_t st, hipEvent_t ev_s
   if (fused) {          // rows whose window was not complete in time (normally none) and the rows of the last `lag` windows
     const long long tail_rows = (a.fuse_items > a.lag ? a.lag : a.fuse_items) * a.m;
     const dim3 mgrid((unsigned)(tail_rows > 2048 ? 2048 : (tail_rows < 256 ? 256 : tail_rows)));
-    switch (m_pad) {
-      case 16: hipLaunchKernelGGL(norm_missed_kernel<1>, mgrid, dim3(64), 0, st, a); break;
-      case 32: hipLaunchKernelGGL(norm_missed_kernel<2>, mgrid, dim3(128), 0, st, a); break;
-      case 48: hipLaunchKernelGGL(norm_missed_kernel<3>, mgrid, dim3(192), 0, st, a); break;
-      case 64: hipLaunchKernelGGL(norm_missed_kernel<4>, mgrid, dim3(256), 0, st, a); break;
-    }
+    for_nt(m_pad, [&](auto nt) { hipLaunchKernelGGL(norm_missed_kernel<nt>, mgrid, dim3(64 * nt), 0, st, a); });
   }
   return (int)hipGetLastError();
 }
@@ -1262,13 +1246,7 @@ int launch_cinv(const TfArgs& a_in, int m_pad, hipStream_t st) {
   const long long n = a.n_items * (long long)a.F;
   if (n == 0) return 0;
   const dim3 grid((unsigned)n);
-  switch (m_pad) {
-    case 16: hipLaunchKernelGGL((tf_inv_kernel<1, true>), grid, dim3(64), 0, st, a); break;
-    case 32: hipLaunchKernelGGL((tf_inv_kernel<2, true>), grid, dim3(128), 0, st, a); break;
-    case 48: hipLaunchKernelGGL((tf_inv_kernel<3, true>), grid, dim3(192), 0, st, a); break;
-    case 64: hipLaunchKernelGGL((tf_inv_kernel<4, true>), grid, dim3(256), 0, st, a); break;
-    default: return -1;
-  }
+  if (for_nt(m_pad, [&](auto nt) { hipLaunchKernelGGL((tf_inv_kernel<nt, true>), grid, dim3(64 * nt), 0, st, a); })) return -1;
   return (int)hipGetLastError();
 }
 

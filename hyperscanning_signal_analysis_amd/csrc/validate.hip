@@ -294,13 +294,7 @@ int launch_residuals(const ResidArgs& a, int m_pad, hipStream_t st) {
   int rc = (int)hipGetLastError();
   if (rc) return rc;
   const dim3 grid((unsigned)a.n_items, (unsigned)((a.n - a.p + RS_TC - 1) / RS_TC)), block(256);
-  switch (m_pad) {
-    case 16: hipLaunchKernelGGL(resid_kernel<1>, grid, block, 0, st, a); break;
-    case 32: hipLaunchKernelGGL(resid_kernel<2>, grid, block, 0, st, a); break;
-    case 48: hipLaunchKernelGGL(resid_kernel<3>, grid, block, 0, st, a); break;
-    case 64: hipLaunchKernelGGL(resid_kernel<4>, grid, block, 0, st, a); break;
-    default: return -1;
-  }
+  if (for_nt(m_pad, [&](auto nt) { hipLaunchKernelGGL(resid_kernel<nt>, grid, block, 0, st, a); })) return -1;
   return (int)hipGetLastError();
 }
 
@@ -313,13 +307,7 @@ int launch_iota_items(long long* item_rec, long long* item_start, long long n, h
 int launch_whiteness(const WhiteArgs& a, int m_pad, hipStream_t st) {
   if (a.n_items == 0) return 0;
   const dim3 grid((unsigned)a.n_items), block(256);
-  switch (m_pad) {
-    case 16: hipLaunchKernelGGL(whiteness_kernel<1>, grid, block, 0, st, a); break;
-    case 32: hipLaunchKernelGGL(whiteness_kernel<2>, grid, block, 0, st, a); break;
-    case 48: hipLaunchKernelGGL(whiteness_kernel<3>, grid, block, 0, st, a); break;
-    case 64: hipLaunchKernelGGL(whiteness_kernel<4>, grid, block, 0, st, a); break;
-    default: return -1;
-  }
+  if (for_nt(m_pad, [&](auto nt) { hipLaunchKernelGGL(whiteness_kernel<nt>, grid, block, 0, st, a); })) return -1;
   return (int)hipGetLastError();
 }
 

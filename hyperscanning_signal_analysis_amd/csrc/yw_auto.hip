@@ -45,17 +45,10 @@ int launch_yw_auto(const YwArgs& a_in, const YwAutoArgs& sel, int m_pad, hipStre
   a.no_emit = 0;                              // (the selecting form always writes its snapshots)
   const dim3 grid((unsigned)a.n_items), block(256);
   const bool legacy = tuning(4 /* HMV_TUNE_YW_FORM */) == 4;      // the walk kept for the tests (LEGACY in yw_lwr_core.h)
-  switch (m_pad) {
-    case 16: if (legacy) hipLaunchKernelGGL((yw_auto_kernel<1, true>), grid, block, 0, st, a, sel);
-             else hipLaunchKernelGGL((yw_auto_kernel<1>), grid, block, 0, st, a, sel); break;
-    case 32: if (legacy) hipLaunchKernelGGL((yw_auto_kernel<2, true>), grid, block, 0, st, a, sel);
-             else hipLaunchKernelGGL((yw_auto_kernel<2>), grid, block, 0, st, a, sel); break;
-    case 48: if (legacy) hipLaunchKernelGGL((yw_auto_kernel<3, true>), grid, block, 0, st, a, sel);
-             else hipLaunchKernelGGL((yw_auto_kernel<3>), grid, block, 0, st, a, sel); break;
-    case 64: if (legacy) hipLaunchKernelGGL((yw_auto_kernel<4, true>), grid, block, 0, st, a, sel);
-             else hipLaunchKernelGGL((yw_auto_kernel<4>), grid, block, 0, st, a, sel); break;
-    default: return -1;
-  }
+  if (for_nt(m_pad, legacy, [&](auto nt, auto leg) {
+        hipLaunchKernelGGL((yw_auto_kernel<nt, leg>), grid, block, 0, st, a, sel);
+      }))
+    return -1;
   if (const int rc = (int)hipGetLastError()) return rc;
   // the flagged windows again, by the LDL^T of the first order_out[item] + 1 lag blocks (normally none: every other
   // workgroup of this launch reads one int and exits)

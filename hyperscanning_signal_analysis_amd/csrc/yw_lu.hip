@@ -278,13 +278,7 @@ __global__ void __launch_bounds__(256) yw_lu_kernel(YwArgs a, int all) {
 int launch_yw_lu(const YwArgs& a, int m_pad, int all, hipStream_t st) {
   if (a.n_items == 0) return 0;
   const dim3 grid((unsigned)a.n_items), block(256);
-  switch (m_pad) {
-    case 16: hipLaunchKernelGGL((yw_lu_kernel<1>), grid, block, 0, st, a, all); break;
-    case 32: hipLaunchKernelGGL((yw_lu_kernel<2>), grid, block, 0, st, a, all); break;
-    case 48: hipLaunchKernelGGL((yw_lu_kernel<3>), grid, block, 0, st, a, all); break;
-    case 64: hipLaunchKernelGGL((yw_lu_kernel<4>), grid, block, 0, st, a, all); break;
-    default: return -1;
-  }
+  if (for_nt(m_pad, [&](auto nt) { hipLaunchKernelGGL((yw_lu_kernel<nt>), grid, block, 0, st, a, all); })) return -1;
   return (int)hipGetLastError();
 }
 

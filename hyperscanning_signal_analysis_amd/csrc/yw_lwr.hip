@@ -47,18 +47,10 @@ __global__ void __launch_bounds__(256, 3) yw_lwr_kernel(YwArgs a) {
 // tests hold the default walk against it
 static int launch_yw_lwr_legacy(const YwArgs& a, int m_pad, hipStream_t st) {
   const dim3 grid((unsigned)a.n_items), block(256);
-  const bool vq = (a.Vq_logdet != nullptr);
-  switch (m_pad) {
-    case 16: if (vq) hipLaunchKernelGGL((yw_lwr_kernel<1, true, true>), grid, block, 0, st, a);
-             else hipLaunchKernelGGL((yw_lwr_kernel<1, false, true>), grid, block, 0, st, a); break;
-    case 32: if (vq) hipLaunchKernelGGL((yw_lwr_kernel<2, true, true>), grid, block, 0, st, a);
-             else hipLaunchKernelGGL((yw_lwr_kernel<2, false, true>), grid, block, 0, st, a); break;
-    case 48: if (vq) hipLaunchKernelGGL((yw_lwr_kernel<3, true, true>), grid, block, 0, st, a);
-             else hipLaunchKernelGGL((yw_lwr_kernel<3, false, true>), grid, block, 0, st, a); break;
-    case 64: if (vq) hipLaunchKernelGGL((yw_lwr_kernel<4, true, true>), grid, block, 0, st, a);
-             else hipLaunchKernelGGL((yw_lwr_kernel<4, false, true>), grid, block, 0, st, a); break;
-    default: return -1;
-  }
+  if (for_nt(m_pad, a.Vq_logdet != nullptr, [&](auto nt, auto vq) {
+        hipLaunchKernelGGL((yw_lwr_kernel<nt, vq, true>), grid, block, 0, st, a);
+      }))
+    return -1;
   return (int)hipGetLastError();
 }
 
@@ -69,18 +61,10 @@ int launch_yw_lwr(const YwArgs& a, int m_pad, hipStream_t st) {
   if (tuning(4 /* HMV_TUNE_YW_FORM */) == 3) return launch_yw_lwr2(a, m_pad, st);
   if (tuning(4) == 4) return launch_yw_lwr_legacy(a, m_pad, st);
   const dim3 grid((unsigned)a.n_items), block(256);
-  const bool vq = (a.Vq_logdet != nullptr);
-  switch (m_pad) {
-    case 16: if (vq) hipLaunchKernelGGL((yw_lwr_kernel<1, true>), grid, block, 0, st, a);
-             else hipLaunchKernelGGL((yw_lwr_kernel<1, false>), grid, block, 0, st, a); break;
-    case 32: if (vq) hipLaunchKernelGGL((yw_lwr_kernel<2, true>), grid, block, 0, st, a);
-             else hipLaunchKernelGGL((yw_lwr_kernel<2, false>), grid, block, 0, st, a); break;
-    case 48: if (vq) hipLaunchKernelGGL((yw_lwr_kernel<3, true>), grid, block, 0, st, a);
-             else hipLaunchKernelGGL((yw_lwr_kernel<3, false>), grid, block, 0, st, a); break;
-    case 64: if (vq) hipLaunchKernelGGL((yw_lwr_kernel<4, true>), grid, block, 0, st, a);
-             else hipLaunchKernelGGL((yw_lwr_kernel<4, false>), grid, block, 0, st, a); break;
-    default: return -1;
-  }
+  if (for_nt(m_pad, a.Vq_logdet != nullptr, [&](auto nt, auto vq) {
+        hipLaunchKernelGGL((yw_lwr_kernel<nt, vq>), grid, block, 0, st, a);
+      }))
+    return -1;
   return (int)hipGetLastError();
 }
 
@@ -90,13 +74,8 @@ int yw_lwr_occupancy(int m_pad) {
   if (tuning(4 /* HMV_TUNE_YW_FORM */) == 3 || tuning(4) == 4) return 0;
   int occ = 0;
   hipError_t e = hipErrorInvalidValue;
-  switch (m_pad) {
-    case 16: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, yw_lwr_kernel<1, false>, 256, 0); break;
-    case 32: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, yw_lwr_kernel<2, false>, 256, 0); break;
-    case 48: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, yw_lwr_kernel<3, false>, 256, 0); break;
-    case 64: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, yw_lwr_kernel<4, false>, 256, 0); break;
-    default: return 0;
-  }
+  if (for_nt(m_pad, [&](auto nt) { e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, yw_lwr_kernel<nt, false>, 256, 0); }))
+    return 0;
   return (e == hipSuccess && occ > 0) ? occ : 0;
 }
 

@@ -412,18 +412,10 @@ __global__ void __launch_bounds__(256, 3) yw_lwr2_kernel(YwArgs a) {
 int launch_yw_lwr2(const YwArgs& a, int m_pad, hipStream_t st) {
   if (a.n_items == 0) return 0;
   const dim3 grid((unsigned)a.n_items), block(256);
-  const bool vq = (a.Vq_logdet != nullptr);
-  switch (m_pad) {
-    case 16: if (vq) hipLaunchKernelGGL((yw_lwr2_kernel<1, true>), grid, block, 0, st, a);
-             else hipLaunchKernelGGL((yw_lwr2_kernel<1, false>), grid, block, 0, st, a); break;
-    case 32: if (vq) hipLaunchKernelGGL((yw_lwr2_kernel<2, true>), grid, block, 0, st, a);
-             else hipLaunchKernelGGL((yw_lwr2_kernel<2, false>), grid, block, 0, st, a); break;
-    case 48: if (vq) hipLaunchKernelGGL((yw_lwr2_kernel<3, true>), grid, block, 0, st, a);
-             else hipLaunchKernelGGL((yw_lwr2_kernel<3, false>), grid, block, 0, st, a); break;
-    case 64: if (vq) hipLaunchKernelGGL((yw_lwr2_kernel<4, true>), grid, block, 0, st, a);
-             else hipLaunchKernelGGL((yw_lwr2_kernel<4, false>), grid, block, 0, st, a); break;
-    default: return -1;
-  }
+  if (for_nt(m_pad, a.Vq_logdet != nullptr, [&](auto nt, auto vq) {
+        hipLaunchKernelGGL((yw_lwr2_kernel<nt, vq>), grid, block, 0, st, a);
+      }))
+    return -1;
   return (int)hipGetLastError();
 }
 

@@ -406,13 +406,7 @@ int launch_yw_guarded(const YwArgs& a_in, int m_pad, hipStream_t st) {
   a.Vq_logdet = nullptr;
   if (a.n_items == 0) return 0;
   const dim3 grid((unsigned)a.n_items), block(256);
-  switch (m_pad) {
-    case 16: hipLaunchKernelGGL((yw_window_kernel<1, false>), grid, block, 0, st, a, 0); break;
-    case 32: hipLaunchKernelGGL((yw_window_kernel<2, false>), grid, block, 0, st, a, 0); break;
-    case 48: hipLaunchKernelGGL((yw_window_kernel<3, false>), grid, block, 0, st, a, 0); break;
-    case 64: hipLaunchKernelGGL((yw_window_kernel<4, false>), grid, block, 0, st, a, 0); break;
-    default: return -1;
-  }
+  if (for_nt(m_pad, [&](auto nt) { hipLaunchKernelGGL((yw_window_kernel<nt, false>), grid, block, 0, st, a, 0); })) return -1;
   return (int)hipGetLastError();
 }
 
@@ -437,28 +431,16 @@ static int launch_yw_unpivoted(const YwArgs& a_in, int m_pad, hipStream_t st) {
     if (!a.only_guarded)
       if (const hipError_t e = hipMemsetAsync(a.info, 0, sizeof(int) * a.n_items, st)) return (int)e;
     const dim3 grid((unsigned)a.n_items), block(256);
-    const bool vq = (a.Vq_logdet != nullptr);
-    switch (m_pad) {
-      case 16: if (vq) hipLaunchKernelGGL((yw_window_kernel<1, true>), grid, block, 0, st, a, 0);
-               else hipLaunchKernelGGL((yw_window_kernel<1, false>), grid, block, 0, st, a, 0); break;
-      case 32: if (vq) hipLaunchKernelGGL((yw_window_kernel<2, true>), grid, block, 0, st, a, 0);
-               else hipLaunchKernelGGL((yw_window_kernel<2, false>), grid, block, 0, st, a, 0); break;
-      case 48: if (vq) hipLaunchKernelGGL((yw_window_kernel<3, true>), grid, block, 0, st, a, 0);
-               else hipLaunchKernelGGL((yw_window_kernel<3, false>), grid, block, 0, st, a, 0); break;
-      case 64: if (vq) hipLaunchKernelGGL((yw_window_kernel<4, true>), grid, block, 0, st, a, 0);
-               else hipLaunchKernelGGL((yw_window_kernel<4, false>), grid, block, 0, st, a, 0); break;
-      default: return -1;
-    }
+    if (for_nt(m_pad, a.Vq_logdet != nullptr, [&](auto nt, auto vq) {
+          hipLaunchKernelGGL((yw_window_kernel<nt, vq>), grid, block, 0, st, a, 0);
+        }))
+      return -1;
     return (int)hipGetLastError();
   }
   if (a.order) return -1;                     // a per-window order exists in the one-launch form only
-  switch (m_pad) {
-    case 16: return launch_yw_nt<1>(a, st);
-    case 32: return launch_yw_nt<2>(a, st);
-    case 48: return launch_yw_nt<3>(a, st);
-    case 64: return launch_yw_nt<4>(a, st);
-    default: return -1;
-  }
+  int rc = 0;
+  if (for_nt(m_pad, [&](auto nt) { rc = launch_yw_nt<nt>(a, st); })) return -1;
+  return rc;
 }
 
 // The solver the caller's form and HMV_TUNE_YW_FORM choose, then (YwArgs::pivoted) the pivoted LU over the windows it

@@ -42,10 +42,6 @@ class SingularMatrixError(np.linalg.LinAlgError):
     """Raised where the reference's np.linalg.solve / np.linalg.inv raise LinAlgError('Singular matrix')."""
 
 
-def _ptr(t):
-    return 0 if t is None else t.data_ptr()
-
-
 def validate_items(x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, p: int):
     """Refuse window descriptors the kernels would read out of bounds with, BEFORE anything is launched: wrong
     dtype / device, a recording index outside x, a window that does not lie inside its recording (one tiny
@@ -292,6 +288,12 @@ class Engine:
     def stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
+    def _call(self, entry, *args):
+        """The C entry `entry` on the engine's device (`_lib.call`: tensors as their pointers, None as null; raises on a status
+        other than 0).  The stream is an argument like any other."""
+        with torch.cuda.device(self.device):
+            _lib.call(self.lib, entry, *args)
+
     def to_device(self, a, dtype=torch.float64):
         if isinstance(a, torch.Tensor):
             return a.to(device=self.device, dtype=dtype).contiguous()
@@ -347,11 +349,8 @@ class Engine:
         self.check_items(x, item_rec, item_start, n, p)
         n_items = int(item_rec.numel())
         R = self.empty(n_items, p + 1, mp, mp)
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_lagcov_f64(x.data_ptr(), x.stride(0), x.stride(1), item_rec.data_ptr(),
-                                         item_start.data_ptr(), n_items, m, int(n), int(p), R.data_ptr(),
-                                         self.stream())
-        _lib.check(rc, "hmv_lagcov_f64")
+        self._call("hmv_lagcov_f64", x, x.stride(0), x.stride(1), item_rec, item_start, n_items, m, int(n), int(p), R,
+                   self.stream())
         return R
 
     def lagcov_regular(self, x: torch.Tensor, first: int, hop: int, n_win: int, n: int, p: int):
@@ -366,19 +365,15 @@ class Engine:
             raise ValueError("the window must be a whole number of hops")
         ws = self.empty(max(nws, 1))
         R = self.empty(n_win, p + 1, mp, mp)
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_lagcov_regular_f64(x.data_ptr(), x.stride(0), T, int(first), int(hop), int(n_win), m, int(n),
-                                                 int(p), R.data_ptr(), ws.data_ptr(), self.stream())
-        _lib.check(rc, "hmv_lagcov_regular_f64")
+        self._call("hmv_lagcov_regular_f64", x, x.stride(0), T, int(first), int(hop), int(n_win), m, int(n), int(p), R, ws,
+                   self.stream())
         return R
 
     def trial_mean(self, R: torch.Tensor, m: int):
         """(trials, p+1, MP, MP) -> (1, p+1, MP, MP): count_corr's average over trials (mtmvar.py:78-85)."""
         trials, p1, mp, _ = R.shape
         out = self.empty(1, p1, mp, mp)
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_trial_mean_f64(R.data_ptr(), trials, m, p1 - 1, out.data_ptr(), self.stream())
-        _lib.check(rc, "hmv_trial_mean_f64")
+        self._call("hmv_trial_mean_f64", R, trials, m, p1 - 1, out, self.stream())
         return out
 
     # ------------------------------------------------------------------ K2
@@ -396,10 +391,7 @@ class Engine:
         V = self.empty(n_items, mp, mp)
         info = self.empty(n_items, dtype=torch.int32)
         logdet = self.empty(n_items, p) if want_logdet else None
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_yw_solve_f64(R.data_ptr(), n_items, m, p, ws.data_ptr(), ar.data_ptr(), V.data_ptr(),
-                                           _ptr(logdet), info.data_ptr(), int(flags), self.stream())
-        _lib.check(rc, "hmv_yw_solve_f64")
+        self._call("hmv_yw_solve_f64", R, n_items, m, p, ws, ar, V, logdet, info, int(flags), self.stream())
         if return_route:
             return ar, V, logdet, info, self.yw_routes(ws, n_items, m, p)
         return ar, V, logdet, info
@@ -421,9 +413,7 @@ class Engine:
         """The route words of a K2 workspace (`hmv_yw_routes_i32`): int32 per item, 0 recursion, 1 LDL^T, 2 LU."""
         route = self.empty(n_items, dtype=torch.int32)
         if n_items:
-            with torch.cuda.device(self.device):
-                rc = self.lib.hmv_yw_routes_i32(ws.data_ptr(), n_items, int(m), int(p), route.data_ptr(), self.stream())
-            _lib.check(rc, "hmv_yw_routes_i32")
+            self._call("hmv_yw_routes_i32", ws, n_items, int(m), int(p), route, self.stream())
         return route
 
     def yw_solve_auto(self, R: torch.Tensor, m: int, n: int, crit_type: str = "AIC"):
@@ -439,20 +429,19 @@ class Engine:
         orders = self.empty(n_items, dtype=torch.int32)
         curve = self.empty(n_items, pmax)
         info = self.empty(n_items, dtype=torch.int32)
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_yw_solve_auto_f64(_ptr(R), n_items, m, pmax, int(n), crit, ws.data_ptr(), _ptr(ar), _ptr(V),
-                                                _ptr(orders), _ptr(curve), 0, _ptr(info), 0, self.stream())
-        if n_items:
-            _lib.check(rc, "hmv_yw_solve_auto_f64")
+        try:
+            self._call("hmv_yw_solve_auto_f64", R, n_items, m, pmax, int(n), crit, ws, ar, V, orders, curve, None, info, 0,
+                       self.stream())
+        except (ValueError, RuntimeError):
+            if n_items:         # the status of an empty batch is not looked at: its tensors have null pointers, which the
+                raise           # entry refuses, and there is nothing it could have solved
         return ar, V, orders, curve, info
 
     # ------------------------------------------------------------------ K3 (+K4/K5 layout kernels)
     def twiddles(self, freqs, fs: float, p: int):
         f = self.to_device(np.asarray(freqs, dtype=np.float64))
         tw = self.empty(f.numel(), p, 2)
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_twiddles_f64(f.data_ptr(), f.numel(), float(fs), p, tw.data_ptr(), self.stream())
-        _lib.check(rc, "hmv_twiddles_f64")
+        self._call("hmv_twiddles_f64", f, f.numel(), float(fs), p, tw, self.stream())
         return tw
 
     def transfer(self, ar: torch.Tensor, m: int, tw: torch.Tensor, want_P=True, want_H=False, want_A=False):
@@ -466,11 +455,7 @@ class Engine:
         A = self.empty(n_items, F, mp, mp, 2) if want_A else None
         info = self.empty(n_items * F, dtype=torch.int32)
         ws = self.empty(max(1, int(self.lib.hmv_tf_workspace_doubles(n_items, m, p))))
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_tf_f64(ar.data_ptr(), n_items, m, p, tw.data_ptr(), F, _ptr(P), _ptr(rowsum),
-                                     _ptr(H), _ptr(A), info.data_ptr(), self.pivot_tau, ws.data_ptr(),
-                                     self.stream())
-        _lib.check(rc, "hmv_tf_f64")
+        self._call("hmv_tf_f64", ar, n_items, m, p, tw, F, P, rowsum, H, A, info, self.pivot_tau, ws, self.stream())
         out.update(P=P, rowsum=rowsum, H=H, A=A, info=info)
         return out
 
@@ -478,27 +463,20 @@ class Engine:
         n_items, F, mp, _ = P.shape
         den = self.empty(n_items, mp)
         out = self.empty(n_items, m, m, F)
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_ffdtf_norm_f64(P.data_ptr(), _ptr(rowsum), den.data_ptr(), out.data_ptr(), n_items,
-                                             F, m, 1 if normalise else 0, self.stream())
-        _lib.check(rc, "hmv_ffdtf_norm_f64")
+        self._call("hmv_ffdtf_norm_f64", P, rowsum, den, out, n_items, F, m, 1 if normalise else 0, self.stream())
         return out, den
 
     def to_mmf_complex(self, Z: torch.Tensor, m: int):
         """(items, F, MP, MP, 2) -> complex128 (items, m, m, F), the reference's H / A / spectra layout."""
         n_items, F, mp, _, _ = Z.shape
         out = self.empty(n_items, m, m, F, 2)
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_transpose_c128(Z.data_ptr(), out.data_ptr(), n_items, F, m, self.stream())
-        _lib.check(rc, "hmv_transpose_c128")
+        self._call("hmv_transpose_c128", Z, out, n_items, F, m, self.stream())
         return torch.view_as_complex(out)
 
     def spectra(self, H: torch.Tensor, V: torch.Tensor, m: int):
         n_items, F, mp, _, _ = H.shape
         S = self.empty(n_items, F, mp, mp, 2)
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_spectra_f64(H.data_ptr(), V.data_ptr(), S.data_ptr(), n_items, m, F, self.stream())
-        _lib.check(rc, "hmv_spectra_f64")
+        self._call("hmv_spectra_f64", H, V, S, n_items, m, F, self.stream())
         return S
 
     # ------------------------------------------------------------------ measures on top of K3 / K5
@@ -508,9 +486,7 @@ class Engine:
         mp = self.pad(m)
         zin = torch.view_as_real(Z.contiguous())
         out = self.empty(n_items, F, mp, mp, 2)
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_pack_c128(zin.data_ptr(), out.data_ptr(), n_items, F, m, self.stream())
-        _lib.check(rc, "hmv_pack_c128")
+        self._call("hmv_pack_c128", zin, out, n_items, F, m, self.stream())
         return out
 
     def complex_inverse(self, Z: torch.Tensor, m: int):
@@ -519,10 +495,7 @@ class Engine:
         Zi = self.empty(n_items, F, mp, mp, 2)
         detph = self.empty(n_items * F, 2)
         info = self.empty(n_items * F, dtype=torch.int32)
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_cinv_c128(Z.data_ptr(), n_items, m, F, Zi.data_ptr(), detph.data_ptr(), info.data_ptr(),
-                                        1.0, self.stream())
-        _lib.check(rc, "hmv_cinv_c128")
+        self._call("hmv_cinv_c128", Z, n_items, m, F, Zi, detph, info, 1.0, self.stream())
         return Zi, detph, info
 
     def partial_coherence(self, S: torch.Tensor, m: int):
@@ -530,10 +503,7 @@ class Engine:
         n_items, F, mp, _, _ = S.shape
         Si, detph, info = self.complex_inverse(S, m)
         kap = self.empty(n_items, F, mp, mp, 2)
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_partial_coherence_c128(Si.data_ptr(), detph.data_ptr(), kap.data_ptr(), n_items, m, F,
-                                                     self.stream())
-        _lib.check(rc, "hmv_partial_coherence_c128")
+        self._call("hmv_partial_coherence_c128", Si, detph, kap, n_items, m, F, self.stream())
         return self.to_mmf_complex(kap, m), info
 
     def ddtf(self, ff: torch.Tensor, kappa: torch.Tensor):
@@ -542,9 +512,7 @@ class Engine:
         ff = ff.contiguous()
         kr = torch.view_as_real(kappa.contiguous())
         out = self.empty(n_items, m, m, F)
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_ddtf_f64(ff.data_ptr(), kr.data_ptr(), out.data_ptr(), n_items, m, F, self.stream())
-        _lib.check(rc, "hmv_ddtf_f64")
+        self._call("hmv_ddtf_f64", ff, kr, out, n_items, m, F, self.stream())
         return out
 
     def band_tables(self, bin_lo, bin_hi, F: int):
@@ -575,19 +543,14 @@ class Engine:
         nb = int(lo.numel())
         rows = ff.numel() // F if F else 0
         out = self.empty(*ff.shape[:-1], nb)
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_band_sums_f64(ff.data_ptr(), rows, F, lo.data_ptr(), hi.data_ptr(), nb, out.data_ptr(),
-                                            self.stream())
-        _lib.check(rc, "hmv_band_sums_f64")
+        self._call("hmv_band_sums_f64", ff, rows, F, lo, hi, nb, out, self.stream())
         return out
 
     def gpdc(self, A: torch.Tensor, V: torch.Tensor, m: int):
         """A (items, F, MP, MP, 2) from `transfer(want_A=True)`, V (items, MP, MP) -> GPDC (items, m, m, F)."""
         n_items, F, mp, _, _ = A.shape
         G = self.empty(n_items, F, mp, mp)
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_gpdc_f64(A.data_ptr(), V.data_ptr(), G.data_ptr(), n_items, m, F, self.stream())
-        _lib.check(rc, "hmv_gpdc_f64")
+        self._call("hmv_gpdc_f64", A, V, G, n_items, m, F, self.stream())
         out, _ = self.normalise(G, None, m, normalise=False)
         return out
 
@@ -620,7 +583,7 @@ class Engine:
 
     # The routes: what is particular to one fused C entry, written down once each.  `_sliding_call` is all they share.
     # `_route` and `_ensemble_route` follow; `_mix_route`, `_pairs_route`, `_block_route` and `_block_pairs_route` stand in
-    # front of the entries they serve.  A route's `call` reads the driver's pointers by name (`a.out`, `a.info_yw`, ...);
+    # front of the entries they serve.  A route's `call` reads the driver's buffers by name (`a.out`, `a.info_yw`, ...);
     # an output or info array the route does not list in `more` / `infos` reads as a null pointer (`_ABSENT`).
     def _window_grid(self, x, items, n_items, grid, compare):
         """grid = (hop, first, n_win) of the single-trial routes -> the three grid arguments of the C call."""
@@ -727,14 +690,13 @@ class Engine:
             err.args = (err.args[0], err.args[1] + f" (group {int(err.groups[0])}, window at offset {int(err.offsets[0])})")
 
         def call(a):
-            front = (code, *a.x, a.T, trial_rec.data_ptr(), trial_start.data_ptr(), group_ptr.data_ptr(), n_groups, *a.items,
+            front = (code, *a.x, a.T, trial_rec, trial_start, group_ptr, n_groups, *a.items,
                      a.n_items, a.m, n, p, a.f, a.F, a.fs, a.out, a.lo, a.hi, a.nb, a.S, a.ar, a.V, a.info_yw, a.info_tf, a.ws,
                      a.nbytes, a.chunk, a.tau, a.flags)
             if shuffle is None:
                 return "hmv_sliding_ensemble_f64", (*front, *a.grid, a.stream, a.aux)
             rec_b, start_b, split, R_base, item_base = shuffle
-            return "hmv_sliding_ensemble_split_f64", (*front, rec_b.data_ptr(), start_b.data_ptr(), int(split), _ptr(R_base),
-                                                      _ptr(item_base), a.stream, a.aux)
+            return "hmv_sliding_ensemble_split_f64", (*front, rec_b, start_b, int(split), R_base, item_base, a.stream, a.aux)
         return _Route(
             name="sliding_ensemble", measure=measure, p=p, order_text=f"n={n}, p={p}", more=(_SPECTRA,) if spectra else (),
             blame=blame, infos=_measure_infos(measure, "ar_coeff (Yule-Walker solve of the trial-averaged covariances; a negative "
@@ -825,18 +787,15 @@ class Engine:
         ws = self._workspace(nbytes)
         more, ar, V, orders, curve, infos = buffers()
         ptrs = dict(_ABSENT)
-        ptrs.update((mo.name, buf.data_ptr()) for mo, buf in zip(rt.more, more) if mo is not None)
-        ptrs.update(("info_" + i.name, buf.data_ptr()) for i, buf in zip(rt.infos, infos) if i is not None)
+        ptrs.update((mo.name, buf) for mo, buf in zip(rt.more, more) if mo is not None)
+        ptrs.update(("info_" + i.name, buf) for i, buf in zip(rt.infos, infos) if i is not None)
         a = types.SimpleNamespace(
-            **ptrs, x=(x.data_ptr(), x.stride(0), x.stride(1)), T=T, items=(items[0].data_ptr(), items[1].data_ptr()),
-            n_items=n_items, m=m, f=_ptr(f), F=F, fs=float(fs), out=_ptr(res), nb=knb, lo=b_lo.data_ptr() if knb else 0,
-            hi=b_hi.data_ptr() if knb else 0, ar=_ptr(ar), V=_ptr(V), orders=_ptr(orders), curve=_ptr(curve), ws=ws.data_ptr(),
+            **ptrs, x=(x, x.stride(0), x.stride(1)), T=T, items=tuple(items), n_items=n_items, m=m, f=f, F=F, fs=float(fs),
+            out=res, nb=knb, lo=b_lo if knb else None, hi=b_hi if knb else None, ar=ar, V=V, orders=orders, curve=curve, ws=ws,
             nbytes=nbytes, chunk=chunk, tau=self.pivot_tau, flags=int(flags), grid=g,
             k3=tuple(k3_events) if k3_events else (0, 0), stream=self.stream(), aux=self.aux_stream().cuda_stream if overlap else 0)
         entry, args = rt.call(a)
-        with torch.cuda.device(self.device):
-            rc = getattr(self.lib, entry)(*args)
-        _lib.check(rc, entry)
+        self._call(entry, *args)
         if two_step:
             res = self.band_sums(res, bands[0], bands[1])
             if out is not None:
@@ -954,11 +913,8 @@ class Engine:
             if nbytes < 0:
                 raise ValueError(f"block_granger: bad sizes (m={m}, p={p}, split={split}, F={F})")
             ws = self._workspace(nbytes)
-            with torch.cuda.device(self.device):
-                rc = self.lib.hmv_block_gc_f64(ar.data_ptr(), V.data_ptr(), n_items, m, p, split, f.data_ptr(), F, float(fs),
-                                               out.data_ptr(), info_v.data_ptr(), info_gc.data_ptr(), ws.data_ptr(), nbytes,
-                                               self.stream())
-            _lib.check(rc, "hmv_block_gc_f64")
+            self._call("hmv_block_gc_f64", ar, V, n_items, m, p, split, f, F, float(fs), out, info_v, info_gc, ws, nbytes,
+                       self.stream())
         if not check:
             return out, info_v, info_gc
         self.raise_on_info(info_v, "block_granger (residual covariance not positive definite)")
@@ -1030,12 +986,8 @@ class Engine:
         if nws < 0:
             raise ValueError(f"lagcov_ensemble: bad sizes (m={m}, n={n}, p={p})")
         ws = self.empty(max(nws, 1))
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_lagcov_ensemble_f64(
-                x.data_ptr(), x.stride(0), x.stride(1), T, trial_rec.data_ptr(), trial_start.data_ptr(), group_ptr.data_ptr(),
-                n_groups, item_group.data_ptr(), item_offset.data_ptr(), n_items, m, int(n), int(p), R.data_ptr(),
-                ws.data_ptr(), nws, g_hop, g_nwin, int(flags), self.stream())
-        _lib.check(rc, "hmv_lagcov_ensemble_f64")
+        self._call("hmv_lagcov_ensemble_f64", x, x.stride(0), x.stride(1), T, trial_rec, trial_start, group_ptr, n_groups,
+                   item_group, item_offset, n_items, m, int(n), int(p), R, ws, nws, g_hop, g_nwin, int(flags), self.stream())
         return R
 
     def sliding_ensemble(self, x: torch.Tensor, trial_rec: torch.Tensor, trial_start: torch.Tensor, group_ptr: torch.Tensor,
@@ -1107,12 +1059,9 @@ class Engine:
         R = self.empty(n_items, int(p) + 1, mp, mp)
         if n_items == 0:
             return R
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_lagcov_ensemble_split_f64(
-                x.data_ptr(), x.stride(0), x.stride(1), T, trial_rec.data_ptr(), trial_start.data_ptr(), group_ptr.data_ptr(),
-                n_groups, item_group.data_ptr(), item_offset.data_ptr(), n_items, m, int(n), int(p), R.data_ptr(),
-                trial_rec_b.data_ptr(), trial_start_b.data_ptr(), int(split), _ptr(R_base), _ptr(item_base), 0, self.stream())
-        _lib.check(rc, "hmv_lagcov_ensemble_split_f64")
+        self._call("hmv_lagcov_ensemble_split_f64", x, x.stride(0), x.stride(1), T, trial_rec, trial_start, group_ptr,
+                   n_groups, item_group, item_offset, n_items, m, int(n), int(p), R, trial_rec_b, trial_start_b, int(split),
+                   R_base, item_base, 0, self.stream())
         return R
 
     def ensemble_significance_chunk(self, measure: str, m: int, n: int, p: int, F: int, nb: int) -> int:
@@ -1183,10 +1132,7 @@ class Engine:
             if E == 0 and R.numel():
                 raise ValueError("lagcov_mix needs at least one trial")
             return R
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_lagcov_mix_f64(Rt.data_ptr(), E, n_win, W.data_ptr(), _ptr(scale), rows, int(m), p1 - 1,
-                                             R.data_ptr(), self.stream())
-        _lib.check(rc, "hmv_lagcov_mix_f64")
+        self._call("hmv_lagcov_mix_f64", Rt, E, n_win, W, scale, rows, int(m), p1 - 1, R, self.stream())
         return R
 
     def _mix_route(self, measure, n, m, Rt, W, scale, spectra=False):
@@ -1203,7 +1149,7 @@ class Engine:
 
         def call(a):
             return "hmv_sliding_mix_f64", (
-                code, a.x[0], E, n_win, W.data_ptr(), _ptr(scale), rows, a.m, n, p, a.f, a.F, a.fs, a.out, a.lo, a.hi, a.nb, a.S,
+                code, a.x[0], E, n_win, W, scale, rows, a.m, n, p, a.f, a.F, a.fs, a.out, a.lo, a.hi, a.nb, a.S,
                 a.ar, a.V, a.info_yw, a.info_tf, a.ws, a.nbytes, a.chunk, a.tau, a.flags, a.stream, a.aux)
         return _Route(
             name="sliding_mix", measure=measure, p=p, order_text=f"n={n}, p={p}", more=(_SPECTRA,) if spectra else (),
@@ -1325,11 +1271,8 @@ class Engine:
         assert R.is_contiguous() and R.dtype == torch.float64 and tuple(R.shape) == (n_items, int(p) + 1, mp, mp)
         if n_items == 0:
             return R
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_lagcov_pairs_f64(
-                x.data_ptr(), x.stride(0), x.stride(1), T, rec_a.data_ptr(), rec_b.data_ptr(), item_start.data_ptr(), n_items,
-                m, int(n), int(p), int(split), R.data_ptr(), _ptr(R_base), _ptr(base_a), _ptr(base_b), 0, self.stream())
-        _lib.check(rc, "hmv_lagcov_pairs_f64")
+        self._call("hmv_lagcov_pairs_f64", x, x.stride(0), x.stride(1), T, rec_a, rec_b, item_start, n_items, m, int(n),
+                   int(p), int(split), R, R_base, base_a, base_b, 0, self.stream())
         return R
 
     @staticmethod
@@ -1351,9 +1294,9 @@ class Engine:
 
         def call(a):
             return "hmv_sliding_pairs_f64", (
-                code, *a.x, a.T, a.items[0], rec_b.data_ptr(), a.items[1], a.n_items, a.m, n, p, a.f, a.F, a.fs, a.out, a.lo,
+                code, *a.x, a.T, a.items[0], rec_b, a.items[1], a.n_items, a.m, n, p, a.f, a.F, a.fs, a.out, a.lo,
                 a.hi, a.nb, a.S, a.ar, a.V, a.info_yw, a.info_tf, a.ws, a.nbytes, a.chunk, a.tau, a.flags, int(split),
-                _ptr(R_base), _ptr(base_a), _ptr(base_b), a.stream, a.aux)
+                R_base, base_a, base_b, a.stream, a.aux)
         return _Route(
             name="sliding_pairs", measure=measure, p=p, order_text=f"n={n}, p={p}", blame=blame,
             infos=_measure_infos(measure, _YW_TEXT),
@@ -1408,13 +1351,13 @@ class Engine:
         validation and the blame of `_pairs_route` and no grid.  Of `spectral` (spec) and `time` (timed) the one not asked
         for is None, with its info array; `red` comes out behind them on request, and the looked-up fits ride along."""
         lib, n, code = self.lib, int(n), (1 if spec else 0) | (2 if timed else 0)
-        red_in = (0, 0) if red_base is None else (red_base[0].data_ptr(), red_base[1].data_ptr())
+        red_in = (None, None) if red_base is None else tuple(red_base)
 
         def call(a):
             return "hmv_sliding_block_gc_pairs_f64", (
-                *a.x, a.T, a.items[0], rec_b.data_ptr(), a.items[1], a.n_items, a.m, n, p, split, a.f, a.F, a.fs, a.out, a.lo, a.hi,
-                a.nb, a.time, a.ar, a.V, a.info_yw, a.info_red, a.info_gc, a.ws, a.nbytes, a.chunk, a.flags, _ptr(R_base),
-                _ptr(base_a), _ptr(base_b), code, a.red, *red_in, a.stream)
+                *a.x, a.T, a.items[0], rec_b, a.items[1], a.n_items, a.m, n, p, split, a.f, a.F, a.fs, a.out, a.lo, a.hi,
+                a.nb, a.time, a.ar, a.V, a.info_yw, a.info_red, a.info_gc, a.ws, a.nbytes, a.chunk, a.flags, R_base, base_a,
+                base_b, code, a.red, *red_in, a.stream)
         return _Route(
             name="sliding_block_granger_pairs", measure="block_gc", p=p, order_text=f"n={n}, p={p}, split={split}", row=(2,),
             more=(_BLOCK_TIME if timed else None,) + ((_BLOCK_RED,) if return_red else ()), zero_infos=True,
@@ -1529,11 +1472,8 @@ class Engine:
         x = x if x.stride(2) == 1 else x.contiguous()
         Sb, W = int(shift.shape[0]), int(item_rec.numel())
         out = self.empty(Sb * W, m, int(n)) if out is None else out
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_surrogate_shift_f64(x.data_ptr(), x.stride(0), x.stride(1), T, item_rec.data_ptr(),
-                                                  item_start.data_ptr(), W, shift.data_ptr(), n_rec, Sb, m, int(n), int(split),
-                                                  out.data_ptr(), self.stream())
-        _lib.check(rc, "hmv_surrogate_shift_f64")
+        self._call("hmv_surrogate_shift_f64", x, x.stride(0), x.stride(1), T, item_rec, item_start, W, shift, n_rec, Sb, m,
+                   int(n), int(split), out, self.stream())
         return out
 
     def window_spectra(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int):
@@ -1547,10 +1487,7 @@ class Engine:
         Sb = int(phi.shape[0])
         sr = torch.view_as_real(spec.contiguous())
         out = self.empty(Sb * W, m, nf, 2)
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_surrogate_phase_c128(sr.data_ptr(), W, phi.data_ptr(), Sb, m, int(n), out.data_ptr(),
-                                                   self.stream())
-        _lib.check(rc, "hmv_surrogate_phase_c128")
+        self._call("hmv_surrogate_phase_c128", sr, W, phi, Sb, m, int(n), out, self.stream())
         return torch.view_as_complex(out)
 
     def surrogate_phase(self, spec: torch.Tensor, phi: torch.Tensor, n: int):
@@ -1566,13 +1503,9 @@ class Engine:
         W, m, _, nb = observed.shape
         bad8 = bad.to(torch.uint8).contiguous()
         M = self.empty(n_surr * W, nb)
-        fin = [state[k].data_ptr() for k in ("p", "p_fwe", "null_mean", "null_std")] if finalize else [0] * 4
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_null_accumulate_f64(
-                observed.data_ptr(), surr.data_ptr(), bad8.data_ptr(), tested.data_ptr(), W, int(n_surr), m, nb, M.data_ptr(),
-                state["n_valid"].data_ptr(), state["count"].data_ptr(), state["count_fwe"].data_ptr(),
-                state["n_cell"].data_ptr(), state["mean"].data_ptr(), state["m2"].data_ptr(), *fin, self.stream())
-        _lib.check(rc, "hmv_null_accumulate_f64")
+        fin = [state[k] for k in ("p", "p_fwe", "null_mean", "null_std")] if finalize else [None] * 4
+        self._call("hmv_null_accumulate_f64", observed, surr, bad8, tested, W, int(n_surr), m, nb, M, state["n_valid"],
+                   state["count"], state["count_fwe"], state["n_cell"], state["mean"], state["m2"], *fin, self.stream())
         return M
 
     def null_state(self, W: int, m: int, nb: int):
@@ -1828,16 +1761,10 @@ class Engine:
         o["crit"] = self.empty(S, P) if int(order) == 0 else None
         o["ar"] = self.empty(S, P)
         o["noise_variance"] = self.empty(S)
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_fad_f64(
-                x.data_ptr(), x.stride(0), x.stride(1), item_rec.data_ptr(), item_start.data_ptr(), n_items, m, int(n),
-                P, int(order), int(crit), float(fs), float(imag_tol), int(bool(pair_conjugates)),
-                o["order"].data_ptr(), _ptr(o["crit"]), o["ar"].data_ptr(), o["noise_variance"].data_ptr(),
-                o["poles"].data_ptr(), o["C"].data_ptr(), o["alpha"].data_ptr(), o["freq_hz"].data_ptr(),
-                o["beta"].data_ptr(), o["bandwidth_hz"].data_ptr(), o["phi"].data_ptr(), o["B"].data_ptr(),
-                o["osc_mask"].data_ptr(), o["paired_index"].data_ptr(), o["n_paired"].data_ptr(), o["info"].data_ptr(),
-                self.stream())
-        _lib.check(rc, "hmv_fad_f64")
+        self._call("hmv_fad_f64", x, x.stride(0), x.stride(1), item_rec, item_start, n_items, m, int(n), P, int(order),
+                   int(crit), float(fs), float(imag_tol), int(bool(pair_conjugates)), o["order"], o["crit"], o["ar"],
+                   o["noise_variance"], o["poles"], o["C"], o["alpha"], o["freq_hz"], o["beta"], o["bandwidth_hz"], o["phi"],
+                   o["B"], o["osc_mask"], o["paired_index"], o["n_paired"], o["info"], self.stream())
         return self._fad_finish(o)
 
     def fad_decompose(self, ar: torch.Tensor, fs: float, imag_tol: float = 1e-8, pair_conjugates: bool = True):
@@ -1847,14 +1774,9 @@ class Engine:
         assert ar.dim() == 2
         S, p = ar.shape
         o = self._fad_outputs(S, p)
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_fad_decompose_f64(
-                ar.data_ptr(), S, p, float(fs), float(imag_tol), int(bool(pair_conjugates)),
-                o["poles"].data_ptr(), o["C"].data_ptr(), o["alpha"].data_ptr(), o["freq_hz"].data_ptr(),
-                o["beta"].data_ptr(), o["bandwidth_hz"].data_ptr(), o["phi"].data_ptr(), o["B"].data_ptr(),
-                o["osc_mask"].data_ptr(), o["paired_index"].data_ptr(), o["n_paired"].data_ptr(), o["info"].data_ptr(),
-                self.stream())
-        _lib.check(rc, "hmv_fad_decompose_f64")
+        self._call("hmv_fad_decompose_f64", ar, S, p, float(fs), float(imag_tol), int(bool(pair_conjugates)), o["poles"],
+                   o["C"], o["alpha"], o["freq_hz"], o["beta"], o["bandwidth_hz"], o["phi"], o["B"], o["osc_mask"],
+                   o["paired_index"], o["n_paired"], o["info"], self.stream())
         return self._fad_finish(o)
 
     # ------------------------------------------------------------------ model validation (csrc/validate.hip)
@@ -1887,11 +1809,8 @@ class Engine:
         per_item = int(self.lib.hmv_residuals_workspace_bytes(1, m, p))
         nbytes = per_item * self._chunk(n_items, per_item, self.max_workspace_bytes)
         ws = self._workspace(nbytes)
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_residuals_f64(x.data_ptr(), x.stride(0), x.stride(1), item_rec.data_ptr(),
-                                            item_start.data_ptr(), n_items, m, int(n), p, ar.data_ptr(), E.data_ptr(), N,
-                                            ws.data_ptr(), nbytes, self.stream())
-        _lib.check(rc, "hmv_residuals_f64")
+        self._call("hmv_residuals_f64", x, x.stride(0), x.stride(1), item_rec, item_start, n_items, m, int(n), p, ar, E, N,
+                   ws, nbytes, self.stream())
         return E
 
     def whiteness(self, C: torch.Tensor, m: int, N: int, acf_thr: float):
@@ -1903,11 +1822,8 @@ class Engine:
                  acf_count=self.empty(n_items, dtype=torch.int32), info=self.empty(n_items, dtype=torch.int32))
         if n_items == 0:
             return o
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_whiteness_f64(C.data_ptr(), n_items, int(m), int(N), h, float(acf_thr), o["s"].data_ptr(),
-                                            o["q"].data_ptr(), o["q_channel"].data_ptr(), o["acf_count"].data_ptr(),
-                                            o["info"].data_ptr(), self.stream())
-        _lib.check(rc, "hmv_whiteness_f64")
+        self._call("hmv_whiteness_f64", C, n_items, int(m), int(N), h, float(acf_thr), o["s"], o["q"], o["q_channel"],
+                   o["acf_count"], o["info"], self.stream())
         return o
 
     def model_validation(self, x: torch.Tensor, item_rec: torch.Tensor, item_start: torch.Tensor, n: int, ar: torch.Tensor,
@@ -1948,13 +1864,9 @@ class Engine:
         if nbytes < 0:
             raise ValueError(f"model_validation: bad sizes (m={m}, n={n}, p={p}, max_lag={h}, chunk={chunk})")
         ws = self._workspace(nbytes)
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_model_validation_f64(
-                x.data_ptr(), x.stride(0), x.stride(1), item_rec.data_ptr(), item_start.data_ptr(), n_items, m, int(n), p,
-                ar.data_ptr(), h, float(acf_z) / float(np.sqrt(N)), o["s"].data_ptr(), o["q"].data_ptr(),
-                o["q_channel"].data_ptr(), o["acf_count"].data_ptr(), o["info"].data_ptr(), cov.data_ptr(), _ptr(E), N,
-                ws.data_ptr(), nbytes, chunk, self.stream())
-        _lib.check(rc, "hmv_model_validation_f64")
+        self._call("hmv_model_validation_f64", x, x.stride(0), x.stride(1), item_rec, item_start, n_items, m, int(n), p, ar,
+                   h, float(acf_z) / float(np.sqrt(N)), o["s"], o["q"], o["q_channel"], o["acf_count"], o["info"], cov, E, N,
+                   ws, nbytes, chunk, self.stream())
         return o
 
     # ------------------------------------------------------------------ FIR decimation (decimate.hip)
@@ -1994,10 +1906,8 @@ class Engine:
                     or tuple(y3.shape) != (n_rec, m, T_out) or (n_rec > 0 and (y3.stride(2) != 1 or y3.stride(1) < T_out))):
                 raise ValueError(f"decimate: out must be a float64 tensor of shape {(*x.shape[:-1], T_out)} on {self.device}, "
                                  "unit stride along time")
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_decimate_fir_f64(x3.data_ptr(), x3.stride(0), x3.stride(1), T, n_rec, m, q, h.data_ptr(),
-                                               int(h.numel()), y3.data_ptr(), y3.stride(0), y3.stride(1), self.stream())
-        _lib.check(rc, "hmv_decimate_fir_f64")
+        self._call("hmv_decimate_fir_f64", x3, x3.stride(0), x3.stride(1), T, n_rec, m, q, h, int(h.numel()), y3,
+                   y3.stride(0), y3.stride(1), self.stream())
         return (y3[0] if x.dim() == 2 else y3) if out is None else out
 
     # ------------------------------------------------------------------ phase synchrony (phase_sync.hip)
@@ -2046,11 +1956,8 @@ class Engine:
             out["lagged"] = self.empty(n_items, m, m)
         if coherency:
             out["coherency"] = self.empty(n_items, 2, m, m)
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_phase_sync_c128(z.data_ptr(), z.stride(0), z.stride(1), T, n_rec, m, item_rec.data_ptr(),
-                                              item_start.data_ptr(), n_items, int(n), int(mode), _ptr(out.get("coherency")),
-                                              _ptr(out.get("mag")), _ptr(out.get("lagged")), info.data_ptr(), self.stream())
-        _lib.check(rc, "hmv_phase_sync_c128")
+        self._call("hmv_phase_sync_c128", z, z.stride(0), z.stride(1), T, n_rec, m, item_rec, item_start, n_items, int(n),
+                   int(mode), out.get("coherency"), out.get("mag"), out.get("lagged"), info, self.stream())
         out["info"] = info
         return out
 
@@ -2069,12 +1976,9 @@ class Engine:
         n_rec, m, T = z.shape
         n_items = int(rec_a.numel())
         info = torch.empty(n_items, dtype=torch.int32, device=self.device) if info is None else info
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_phase_sync_pairs_c128(z.data_ptr(), z.stride(0), z.stride(1), T, n_rec, m, int(split),
-                                                    rec_a.data_ptr(), rec_b.data_ptr(), item_start.data_ptr(), _ptr(shift_b),
-                                                    n_items, int(n), int(mode), values.data_ptr(), int(values.shape[-1]),
-                                                    int(cols[0]), int(cols[1]), info.data_ptr(), self.stream())
-        _lib.check(rc, "hmv_phase_sync_pairs_c128")
+        self._call("hmv_phase_sync_pairs_c128", z, z.stride(0), z.stride(1), T, n_rec, m, int(split), rec_a, rec_b,
+                   item_start, shift_b, n_items, int(n), int(mode), values, int(values.shape[-1]), int(cols[0]),
+                   int(cols[1]), info, self.stream())
         return values, info
 
     def phase_sync_pairs(self, z: torch.Tensor, rec_a: torch.Tensor, rec_b: torch.Tensor, item_start: torch.Tensor, n: int,
@@ -2163,11 +2067,8 @@ class Engine:
         n_items = int(item_rec.numel())
         info = torch.empty(n_items, dtype=torch.int32, device=self.device)
         out = {q: self.empty(n_items, m, m) for q in want}
-        with torch.cuda.device(self.device):
-            rc = self.lib.hmv_phase_lag_c128(z.data_ptr(), z.stride(0), z.stride(1), T, n_rec, m, int(split),
-                                             item_rec.data_ptr(), item_start.data_ptr(), n_items, int(n), _ptr(out.get("pli")),
-                                             _ptr(out.get("wpli")), _ptr(out.get("dwpli")), info.data_ptr(), self.stream())
-        _lib.check(rc, "hmv_phase_lag_c128")
+        self._call("hmv_phase_lag_c128", z, z.stride(0), z.stride(1), T, n_rec, m, int(split), item_rec, item_start, n_items,
+                   int(n), out.get("pli"), out.get("wpli"), out.get("dwpli"), info, self.stream())
         out["info"] = info
         return out
 

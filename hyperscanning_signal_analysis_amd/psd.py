@@ -16,7 +16,6 @@ import tempfile
 import numpy as np
 import torch
 
-from . import _lib
 from .engine import default_engine
 
 __all__ = ["compute_psd_multitaper", "compute_psd_multitaper_device", "average_psd_across_conditions", "dpss_device"]
@@ -39,10 +38,8 @@ def dpss_device(n_times: int, half_nbw: float, k_max: int, sym: bool = False, en
     ws = torch.empty(nbytes, dtype=torch.uint8, device=eng.device)
     tapers = eng.empty(int(k_max), int(n_times))
     ratios = eng.empty(int(k_max))
-    with torch.cuda.device(eng.device):
-        rc = eng.lib.hmv_dpss_f64(int(n_times), float(half_nbw), int(k_max), int(bool(sym)), tapers.data_ptr(), ratios.data_ptr(),
-                                  ws.data_ptr(), nbytes, eng.stream())
-    _lib.check(rc, "hmv_dpss_f64")
+    eng._call("hmv_dpss_f64", int(n_times), float(half_nbw), int(k_max), int(bool(sym)), tapers, ratios, ws, nbytes,
+              eng.stream())
     return tapers, ratios
 
 
@@ -114,10 +111,8 @@ def compute_psd_multitaper_device(xd: torch.Tensor, sfreq, fmin, fmax, bandwidth
     nbytes = int(eng.lib.hmv_psd_workspace_bytes(ch_chunk, n_times, K))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=eng.device)
     out = eng.empty(n_ch, hi - lo + 1)
-    with torch.cuda.device(eng.device):
-        rc = eng.lib.hmv_psd_multitaper_f64(xd.data_ptr(), n_ch, n_times, xd.stride(0), td.data_ptr(), wd.data_ptr(), K,
-                                            lo, hi, out.data_ptr(), ws.data_ptr(), nbytes, ch_chunk, eng.stream())
-    _lib.check(rc, "hmv_psd_multitaper_f64")
+    eng._call("hmv_psd_multitaper_f64", xd, n_ch, n_times, xd.stride(0), td, wd, K, lo, hi, out, ws, nbytes, ch_chunk,
+              eng.stream())
     ws.record_stream(torch.cuda.current_stream(eng.device))
     return freqs[lo:hi + 1], out
 
@@ -143,10 +138,8 @@ def compute_psd_multitaper(data, sfreq, fmin, fmax, bandwidth, max_workspace_byt
     ws = torch.empty(nbytes, dtype=torch.uint8, device=eng.device)
     xd = eng.to_device(x)
     out = eng.empty(n_ch, hi - lo + 1)
-    with torch.cuda.device(eng.device):
-        rc = eng.lib.hmv_psd_multitaper_f64(xd.data_ptr(), n_ch, n_times, n_times, td.data_ptr(), wd.data_ptr(), K,
-                                            lo, hi, out.data_ptr(), ws.data_ptr(), nbytes, ch_chunk, eng.stream())
-    _lib.check(rc, "hmv_psd_multitaper_f64")
+    eng._call("hmv_psd_multitaper_f64", xd, n_ch, n_times, n_times, td, wd, K, lo, hi, out, ws, nbytes, ch_chunk,
+              eng.stream())
     return freqs[lo:hi + 1], out.cpu().numpy()
 
 

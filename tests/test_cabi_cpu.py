@@ -36,6 +36,94 @@ def test_header_symbols_all_exported(lib):
     assert lib.hmv_version() == int(re.search(r"#define HMV_VERSION (\d+)", hdr).group(1))
 
 
+def test_signatures_keep_the_types_of_the_hand_written_table():
+    """`_lib.SIGNATURES` is read from include/hypermvar.h.  tests/golden/cabi_signatures.json is the table as it was written
+    by hand before that ({name: [restype.__name__, [argtype.__name__, ...]]}, 81 entries): every entry in it still binds with
+    the same return type and the same argument types, in number and order.  An entry that is not in the file is free: it is
+    declared in the header only."""
+    import json
+    from hyperscanning_signal_analysis_amd import _lib
+    with open(os.path.join(ROOT, "tests", "golden", "cabi_signatures.json")) as fh:
+        want = json.load(fh)
+    assert len(want) == 81
+    for name, (res, args) in want.items():
+        assert name in _lib.SIGNATURES, name
+        got_res, got_args = _lib.SIGNATURES[name]
+        assert (got_res.__name__, [a.__name__ for a in got_args]) == (res, args), name
+
+
+def test_header_parser_reads_what_it_should_and_refuses_the_rest(monkeypatch, tmp_path):
+    from ctypes import c_char_p, c_double, c_int, c_int32, c_int64, c_void_p
+    from hyperscanning_signal_analysis_amd import _lib
+    parse, refused = _lib.signatures_from_header, _lib.HypermvarLibraryError
+    # comments and preprocessor lines are not declarations
+    text = """/* int hmv_in_a_comment(int a);
+               * int hmv_in_its_second_line(int a); */
+              // int hmv_behind_slashes(int a);
+              #define HMV_CALL(x) hmv_in_a_macro(x)
+              int hmv_real(int a);   // int hmv_behind_code(int a);
+              int hmv_other(int64_t n /* int hmv_inside(int a); */, double x);"""
+    assert parse(text) == {"hmv_real": (c_int, [c_int]), "hmv_other": (c_int, [c_int64, c_double])}
+    # a declaration spread over four lines
+    assert parse("""int64_t
+                    hmv_spread(const double* x,
+                               int64_t n_items, int32_t k,
+                               void* stream);""") == {"hmv_spread": (c_int64, [c_void_p, c_int64, c_int32, c_void_p])}
+    assert parse("int hmv_none(void);\nint hmv_nothing();") == {"hmv_none": (c_int, []), "hmv_nothing": (c_int, [])}
+    assert parse("int hmv_p(const int64_t* a, int32_t* info, const int n);") == {"hmv_p": (c_int, [c_void_p, c_void_p, c_int])}
+    assert parse("const char* hmv_text(void);\nconst char *hmv_text2(const char* s);") == {
+        "hmv_text": (c_char_p, []), "hmv_text2": (c_char_p, [c_void_p])}
+    assert parse("double* hmv_ptr(void);") == {"hmv_ptr": (c_void_p, [])}
+    assert parse("") == {}
+    # nothing is guessed: a type that is none of the four scalars, or a parameter without a name
+    for bad, names in [("int hmv_f(float x);", "float x"), ("int hmv_u(unsigned n);", "unsigned n"),
+                       ("int hmv_ui(int a, unsigned int n);", "unsigned int n"), ("int hmv_s(size_t n);", "size_t n"),
+                       ("size_t hmv_r(int n);", "size_t"), ("int hmv_st(struct hmv_args a);", "struct hmv_args a"),
+                       ("int hmv_un(int);", "int"), ("int hmv_un2(int a, int64_t);", "int64_t")]:
+        with pytest.raises(refused, match=names) as err:
+            parse(bad)
+        assert re.search(r"hmv_\w+\(", str(err.value)), "the declaration is named"
+    # nothing is skipped: an occurrence of `hmv_name(` that is no readable prototype
+    for bad in ["int hmv_ok(int a);\nint hmv_cb(int (*f)(int), int n);", "int hmv_ok(int a);\nHMV_API(int, hmv_wrapped(int a));",
+                "int hmv_ok(int a);\nint hmv_unfinished(int a", "int hmv_twice(int a);\nint hmv_twice(int a);"]:
+        with pytest.raises(refused, match="occurs"):
+            parse(bad)
+    # a missing header fails as loudly as a missing library, and names the path
+    monkeypatch.setattr(_lib, "HEADER", str(tmp_path / "nope.h"))
+    with pytest.raises(ImportError, match="nope.h"):
+        _lib._header_text()
+
+
+def test_call_helper_passes_pointers_and_raises_on_a_status(lib):
+    """`_lib.call`: tensors as their data pointers, None as a null pointer, a status other than 0 as the exception `check`
+    words.  On the real library only calls that are refused before anything is dereferenced or launched."""
+    import torch
+    from hyperscanning_signal_analysis_amd import _lib
+    with pytest.raises(ValueError, match=r"hmv_lagcov_f64: .*channel count.*\(code -1\)"):
+        _lib.call(lib, "hmv_lagcov_f64", None, 0, 0, None, None, 1, 65, 100, 4, None, None)
+    with pytest.raises(ValueError, match=r"\(code -2\)"):
+        _lib.call(lib, "hmv_lagcov_f64", None, 0, 0, None, None, 1, 8, 100, 40, None, 0)
+    assert _lib.call(lib, "hmv_set_tuning", _lib.TUNE_NORM_LAG, lib.hmv_get_tuning(_lib.TUNE_NORM_LAG)) is None
+    seen = []
+
+    class Fake:
+        @staticmethod
+        def hmv_recorded(*args):
+            seen.append(args)
+            return 0
+
+        @staticmethod
+        def hmv_hip_error(*args):
+            return 7
+    t = torch.arange(6, dtype=torch.float64)
+    _lib.call(Fake, "hmv_recorded", None, t, t[2:], 5, 2.5, None)
+    assert seen == [(0, t.data_ptr(), t.data_ptr() + 16, 5, 2.5, 0)] and t.data_ptr() != 0
+    with pytest.raises(RuntimeError, match="hmv_hip_error: HIP error 7"):
+        _lib.call(Fake, "hmv_hip_error", None)
+    with pytest.raises(AttributeError):
+        _lib.call(Fake, "hmv_missing")
+
+
 def test_argument_checks_without_gpu(lib):
     assert lib.hmv_pad(3) == 16 and lib.hmv_pad(16) == 16 and lib.hmv_pad(19) == 32 and lib.hmv_pad(64) == 64
     assert lib.hmv_pad(0) == -1 and lib.hmv_pad(65) == -1
